@@ -7,15 +7,18 @@ batch of synthetic walkers already resident in HBM: kinetic energy (forward-Lapl
 that replaces the reference's pmean (train.py:78-80).  Walkers shard across ranks with no other
 communication ("scaling": "weak": every rank keeps `--batch` walkers).
 
-    python bench.py [--gpus N --steps K --warmup W] [--scaling weak|strong]
+    python bench.py [--gpus N --steps K --warmup W] [--scaling weak|strong] [--dump-outputs DIR] [--full]
         N > 1: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`, or
         -- when no launcher environment is present -- bench.py re-executes itself under that launcher.
         weak (default): every rank keeps --batch walkers; strong: --batch is the global batch, split over the
         ranks like process.py:72-77 (4096 global -> 512 per GPU at N = 8).
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, HIP-event timed inside the
-library over the timed region) and `cpu_baseline` (the oracle's reference-algorithm restatement,
-timed on this box's host cores; N = 1 only).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times exactly --steps steps and prints the headline
+(`value`, `ms_per_step`, the batch energy of the last step).  --dump-outputs DIR writes what the last timed step returned
+(loss and the per-walker energies of AuxiliaryLossData) as DIR/<name>.npy; the inputs are seeded, so two builds can be
+compared output for output.  --full adds everything else: `roofline` (dominant kernel, HIP-event timed inside the
+library over the timed region), the per-kernel breakdown, the opt-in int8 layer, the Metropolis sub-benchmark, the other
+scaling mode (N > 1) and `cpu_baseline` (the oracle's reference-algorithm restatement on the host cores; N = 1 only).
 """
 import argparse
 import json
@@ -98,6 +101,46 @@ def log(msg):
     print(f'[bench {time.strftime("%H:%M:%S")}] {msg}', file=sys.stderr, flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, loss, aux):
+    """What the timed path returned in its last step, as DIR/<name>.npy: the scalar loss and every field of
+    AuxiliaryLossData, complex arrays as (..., 2) real / imaginary pairs, float32 or float64 as computed.  Above 64 MB the
+    per-walker arrays keep a fixed, seeded sample of walkers, whose indices go to walker_index.npy."""
+    arrays = {'loss': loss}
+    arrays.update(aux._asdict())
+    out = {}
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach()
+        if t.is_complex():
+            t = torch.view_as_real(t)
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.to(torch.float64)
+        out[name] = t.cpu().numpy()
+    n_walkers = out['local_energy'].shape[0]
+    per_walker = [k for k, v in out.items() if v.ndim >= 1 and v.shape[0] == n_walkers]
+    walker_bytes = sum(out[k].nbytes for k in per_walker) / max(n_walkers, 1)
+    if sum(v.nbytes for v in out.values()) > DUMP_LIMIT_BYTES:
+        keep = int((DUMP_LIMIT_BYTES - (1 << 20)) // (walker_bytes + 8))
+        idx = np.sort(np.random.default_rng(0).choice(n_walkers, keep, replace=False))
+        for k in per_walker:
+            out[k] = out[k][idx]
+        out['walker_index'] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + '.npy'), a)
+    log(f'outputs of the last timed step -> {path}: ' + ', '.join(f'{k}{list(v.shape)}' for k, v in out.items()))
+
+
+def host_cpus():
+    """CPUs this process may use: its affinity set, capped by OMP_NUM_THREADS where the host sets a thread budget
+    (os.cpu_count() counts the whole machine)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
+    omp = os.environ.get('OMP_NUM_THREADS', '')
+    return max(1, min(n, int(omp))) if omp.isdigit() and int(omp) > 0 else n
+
+
 def cpu_model():
     try:
         for line in open('/proc/cpuinfo'):
@@ -138,7 +181,7 @@ def cpu_all_cores(system, net_kw, params_np, xs_np, t_dir_single, value_single, 
     import pickle
     import subprocess
     import tempfile
-    n = max(1, min(max_procs, (os.cpu_count() or 1) // threads))
+    n = max(1, min(max_procs, host_cpus() // threads))
     if n < 2:
         return None
     procs, path = [], None
@@ -189,7 +232,7 @@ def cpu_baseline(cell, klist, net_kw, params_np, x_np, e_gpu, seconds=20.0, walk
     from oracle import network as onet
     # 16 threads: the contractions of one walker are small (<= 832 x 256); on the 256-thread host of the GPU box torch's
     # intra-op pool at full width is ~30x SLOWER than at 16 threads (measured: 46 s vs 1.5 s per loop iteration)
-    cores = min(os.cpu_count() or 1, 16)
+    cores = min(host_cpus(), 16)
     torch.set_num_threads(cores)
     net = onet.make_solid_fermi_net(klist=klist, simulation_cell=cell, method_name='eval_logdet', **net_kw)
     p = onet.params_to_torch(params_np)
@@ -303,8 +346,15 @@ def main():
     ap.add_argument('--single-scaling', action='store_true', help='N > 1: measure only --scaling, not the other mode beside it')
     ap.add_argument('--dry-run', action='store_true',
                     help='launcher / reduction plumbing only (no GPU work): every rank reports in, rank 0 prints the JSON line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the loss and per-walker energies of the last timed step as DIR/<name>.npy (rank 0)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline does not need: roofline and per-kernel figures, the int8 layer, the '
+                         'Metropolis sub-benchmark, the other scaling mode and the CPU baseline (the --no-* switches still apply)')
     ap.add_argument('--cpu-worker', default=None, help=argparse.SUPPRESS)       # child process of the all-cores CPU baseline
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.cpu_worker:
         import pickle
@@ -377,10 +427,42 @@ def main():
             dt_ = float(t.item())
         return dt_, loss, aux
 
-    log(f'system {args.system}: N={sum(cell.nelec)} batch/GPU={args.batch} world={world}; warm-up')
-    dt, loss, aux = timed(x, args.steps, args.warmup, True)
+    def report_in():
+        """-> how many ranks ran the timed region (one all-reduce over the process group)."""
+        if not use_dist:
+            return 1
+        seen = torch.zeros(world, dtype=torch.float64, device=dev)
+        seen[rank] = 1.0
+        dist.all_reduce(seen)
+        return int(seen.sum().item())
+
+    n_e = sum(cell.nelec)
+    log(f'system {args.system}: N={n_e} batch/GPU={args.batch} world={world}; warm-up')
+    # the in-library kernel events of the roofline figures run inside the timed region with --full only
+    dt, loss, aux = timed(x, args.steps, args.warmup, args.full)
     gpu_ms_main = getattr(timed, 'gpu_ms', None)
     log('timed region done')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, aux)
+    out = {
+        'metric': 'local-energy evals/sec', 'value': world * args.batch * args.steps / dt,
+        'unit': 'local-energy evals/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True, 'scaling': args.scaling, 'vs_baseline': None,
+        'dtype': args.dtype, 'data': 'synthetic',
+        'config': {'workload': f'{args.system} {n_e} e- ({cell.nelec[0]},{cell.nelec[1]}), total_energy primal '
+                               f'(E_kin forward-Laplacian + Ewald), default detnet ((256,32),)*3, 8 dets',
+                   'batch_per_gpu': args.batch, 'global_batch': global_batch, 'parallelism': f'walker-dp{world}'},
+        'energy_mean_ha': float(loss), 'energy_imag_ha': float(aux.imaginary), 'variance': float(aux.variance),
+        # HIP-event time of the timed region: evidence of GPU work that does not depend on an smi sample
+        'gpu_ms_timed_region': gpu_ms_main, 'full': args.full,
+    }
+    if not args.full:
+        out['ranks_seen'] = report_in()
+        if rank == 0:
+            print(json.dumps(out))
+        if use_dist:
+            dist.destroy_process_group()
+        return
     prof = sysd.profile_read()
     clk_cycles, clk_ticks, clk_ghz = sysd.profile_clock()
     # the other scaling mode in the same invocation (N > 1): BASELINE configs 4 / 5 split ONE global batch over the GPUs
@@ -469,17 +551,11 @@ def main():
         mcmc = {'ms_per_mcmc_step': ms, 'moves': 20, 'width': 0.02, 'pmove': float(pm), 'logpsi_forward_ms': e0.elapsed_time(e1) / reps,
                 'walker_moves_per_s': world * args.batch * 20 / (ms * 1e-3)}
         log(f"mcmc_step (20 moves, {args.batch} walkers): {ms:.1f} ms, log-psi forward {mcmc['logpsi_forward_ms']:.2f} ms, pmove {float(pm):.3f}")
-    ranks_seen = 1
-    if use_dist:
-        seen = torch.zeros(world, dtype=torch.float64, device=dev)
-        seen[rank] = 1.0
-        dist.all_reduce(seen)                               # every rank that ran the timed region reports in
-        ranks_seen = int(seen.sum().item())
+    ranks_seen = report_in()                                # every rank that ran the timed region reports in
     if rank != 0:
         dist.destroy_process_group()
         return
 
-    n_e = sum(cell.nelec)
     h1 = net_kw['hidden_dims'][0][0]
     h2 = net_kw['hidden_dims'][0][1]
     nch = 2 if cell.nelec[1] else 1
@@ -596,26 +672,17 @@ def main():
         mcmc['roofline'] = {'bound': 'mfma', 'achieved': f_fwd * args.batch / (mcmc['logpsi_forward_ms'] * 1e-3) / 1e12, 'peak': peak,
                             'unit': 'TFLOP/s'}
         mcmc['roofline']['frac'] = mcmc['roofline']['achieved'] / peak
-    out = {
-        'metric': 'local-energy evals/sec', 'value': world * args.batch * args.steps / dt,
-        'unit': 'local-energy evals/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-        'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True, 'scaling': args.scaling, 'vs_baseline': None,
-        'dtype': args.dtype, 'data': 'synthetic',
-        'config': {'workload': f'{args.system} {n_e} e- ({cell.nelec[0]},{cell.nelec[1]}), total_energy primal '
-                               f'(E_kin forward-Laplacian + Ewald), default detnet ((256,32),)*3, 8 dets',
-                   'batch_per_gpu': args.batch, 'global_batch': global_batch, 'parallelism': f'walker-dp{world}'},
+    out.update({
         'ranks_seen': ranks_seen,
-        'energy_mean_ha': float(loss), 'energy_imag_ha': float(aux.imaginary), 'variance': float(aux.variance),
         'roofline': roofline,
         'roofline_other_kernels': dict(({'orbital_head': orbital_obj} if dominant == 'single_hidden' else {'hidden_layers': hidden_obj}),
                                        **({'lowrank_layer': lr_obj} if lr_obj else {})),
         'kernel_ms_per_step': kms,     # from one extra untimed step
-        # evidence of GPU work that does not depend on an smi sample: HIP-event time of the timed region and the kernel sum of a step
-        'gpu_ms_timed_region': gpu_ms_main, 'kernel_ms_sum_per_step': sum(kms.values()),
+        'kernel_ms_sum_per_step': sum(kms.values()),
         'mcmc': mcmc,
         # the default IS strict float64 since round 6; the opt-in int8 hidden layer beside it
         'strict_f64': True, 'int8_split': i8blk,
-    }
+    })
     if other:
         out['other_scaling'] = other
     tr = pmc_traffic('ds::' + hidden_name.split(' ')[0].replace(',', ', '), args.system, args.dtype, hidden_obj['avg_launch_ms'])

@@ -35,7 +35,7 @@ def test_bench_strong_and_weak_lines_over_rccl(n):
     if NGPU < n:
         pytest.skip(f'needs {n} GPUs, this box has {NGPU}')
     r = _torchrun(n, [os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--system', 'bcc_li', '--batch', '4096', '--scaling', 'strong',
-                      '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-mcmc'], 29541 + n)
+                      '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-mcmc'], 29541 + n)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith('{')]
     assert len(line) == 1
@@ -137,7 +137,7 @@ def test_bench_two_ranks_on_one_gpu():
     if NGPU < 1:
         pytest.skip('needs a GPU')
     r = _torchrun(2, [os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--system', 'lih', '--batch', '512', '--scaling', 'strong',
-                      '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-mcmc', '--backend', 'gloo', '--shared-gpu'], 29573)
+                      '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-mcmc', '--backend', 'gloo', '--shared-gpu'], 29573)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][0])
     assert d['n_gpus'] == 2 and d['ranks_seen'] == 2 and d['scaling'] == 'strong'

@@ -327,6 +327,37 @@ def test_bench_under_torchrun_with_rccl_one_rank():
     assert d['n_gpus'] == 1 and d['ranks_seen'] == 1 and d['value'] > 0
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run prints the headline only, times exactly --steps steps (the HIP-event time of the timed region is
+    --steps times ms_per_step, not one or two steps' worth), and --dump-outputs writes what the last timed step returned: the
+    per-walker energies, whose mean is the printed batch energy."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--system', 'lih', '--batch', '512', '--steps', '6',
+           '--warmup', '1', '--dump-outputs', str(tmp_path)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    line = [l for l in r.stdout.splitlines() if l.startswith('{')]
+    assert len(line) == 1
+    d = json.loads(line[0])
+    assert d['metric'] == 'local-energy evals/sec' and d['unit'] == 'local-energy evals/s' and d['higher_is_better'] is True
+    assert d['dtype'] == 'f64' and d['steps'] == 6 and d['full'] is False
+    assert d['ms_per_step'] > 0 and d['value'] == pytest.approx(512 * 1e3 / d['ms_per_step'], rel=1e-9)
+    timed_ms = d['steps'] * d['ms_per_step']                      # wall time of the timed region, synchronize included
+    assert timed_ms / 1.5 < d['gpu_ms_timed_region'] <= timed_ms * 1.01
+    assert 'roofline' not in d and 'cpu_baseline' not in d and 'mcmc' not in d
+    e_l = np.load(tmp_path / 'local_energy.npy')
+    assert e_l.shape == (512, 2) and e_l.dtype == np.float64 and np.isfinite(e_l).all()
+    np.testing.assert_allclose(e_l, np.load(tmp_path / 'kinetic.npy') + np.stack([np.load(tmp_path / 'ewald.npy'), 0 * e_l[:, 1]], 1),
+                               rtol=0, atol=1e-12)
+    assert float(np.load(tmp_path / 'loss.npy')) == pytest.approx(d['energy_mean_ha'], abs=1e-12)
+    assert float(np.load(tmp_path / 'loss.npy')) == pytest.approx(e_l[:, 0].mean(), rel=1e-12)
+
+
 @pytest.mark.parametrize('name', ['lih', 'bcc_li'])
 def test_fused_one_electron_sampler(name):
     """`ds_mcmc_step_one_electron` (make_mcmc_step(one_electron_moves=True), qmc.py:227-287,355-358): with explicit noise it

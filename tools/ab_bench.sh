@@ -2,6 +2,7 @@
 # A/B of one environment switch on the bench step: tools/ab_bench.sh VAR valueA valueB [bench args]
 # ("default" = unset).  Prints ms_per_step and the per-kernel breakdown of each side; JSON lines under gpurun_out/.
 VAR=$1; A=$2; B=$3; shift 3
+set -- --full "$@"          # kernel_ms_per_step is one of the --full figures
 mkdir -p gpurun_out
 for v in "$A" "$B"; do
   if [ "$v" = default ]; then unset $VAR; else export $VAR=$v; fi

@@ -9,6 +9,6 @@ mkdir -p $F
 bash tools/pmc_traffic.sh ${TAG}c > $F/pmc_traffic.txt 2>&1
 cp gpurun_out/pmc_${TAG}c/summary.json profiles/${TAG}_pmc_traffic.json
 cp gpurun_out/pmc_${TAG}c/summary.json $F/${TAG}_pmc_traffic.json
-python bench.py > $F/bench.json 2> $F/bench.err
+python bench.py --full > $F/bench.json 2> $F/bench.err
 bash tools/profile_bench.sh ${TAG}_bench > $F/prof.txt 2>&1
 tail -c 400 $F/bench.json
