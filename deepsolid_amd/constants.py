@@ -50,3 +50,13 @@ def pmean_packed(*scalars):
         dist.all_reduce(packed, op=dist.ReduceOp.SUM)
         packed = packed / world_size()
     return tuple(packed.unbind(0))
+
+
+def pmean_vector(vec):
+    """Mean over ranks of a 1-D float64 tensor in ONE all-reduce (estimator.py's pmeans of <rho>, <|rho|^2> and the
+    polarization travel together); the identity at world size 1."""
+    if world_size() == 1:
+        return vec
+    packed = vec.to(torch.float64).contiguous().clone()
+    dist.all_reduce(packed, op=dist.ReduceOp.SUM)
+    return packed / world_size()

@@ -16,6 +16,7 @@
 #include "ds_grad.h"
 #include "ds_tiles.h"
 #include "ds_mcmc.h"
+#include "ds_obs.h"
 #include "ds_i8.h"
 
 // the per-slot-tile-count kernel instances live in ds_tiles_inst.hip (five slot-tile ranges x two element types)
@@ -1533,7 +1534,26 @@ int check_arch(const ds_system_desc* d) {
 
 }  // namespace
 
+// observables (ds_obs.h): one kernel instance per number of q points per lane
+namespace {
+template <typename T, int QJ>
+void launch_obs_partial(const ds::ObsArgs& A, const void* x, int64_t B, int N, int G, double* part, hipStream_t st) {
+    hipLaunchKernelGGL((ds::k_obs_partial<T, QJ>), dim3(G), dim3(64), 0, st, A, (const T*)x, (long long)B, N, part);
+}
+
+template <typename T>
+void obs_partial(const ds::ObsArgs& A, const void* x, int64_t B, int N, int G, double* part, hipStream_t st) {
+    switch ((A.n_q + 63) / 64) {    // points per lane
+        case 0: case 1: launch_obs_partial<T, 1>(A, x, B, N, G, part, st); break;
+        case 2: launch_obs_partial<T, 2>(A, x, B, N, G, part, st); break;
+        case 3: case 4: launch_obs_partial<T, 4>(A, x, B, N, G, part, st); break;
+        default: launch_obs_partial<T, 8>(A, x, B, N, G, part, st); break;
+    }
+}
+}  // namespace
+
 // =============================================================================== C ABI
+
 extern "C" {
 
 const char* ds_last_error(void) { return g_err.c_str(); }
@@ -1786,6 +1806,52 @@ int ds_enforce_pbc(const double* latvec, int dtype, const void* x, int64_t n_ele
     } else {
         return fail("dtype must be 0 or 1");
     }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int64_t ds_observables_workspace_bytes(int64_t B, int n_q) {
+    if (B < 1 || n_q < 0 || n_q > ds::OBS_MAX_Q) return -1;
+    return (int64_t)ds::obs_groups(B) * (2 + 3 * n_q) * (int64_t)sizeof(double);
+}
+
+int ds_observables(const double* recvec, int dtype, const void* x, int64_t B, int64_t n_elec, const int32_t* q_int, int n_q,
+                   int pol_direction, double* out_sums, void* ws, int64_t ws_bytes, void* stream) {
+    if (!recvec || !x || !out_sums || !ws) return fail("null argument");
+    if (dtype != 0 && dtype != 1) return fail("dtype must be 0 or 1");
+    if (B < 1) return fail("B must be >= 1 (got %lld)", (long long)B);
+    if (n_elec < 1 || n_elec > ds::OBS_MAX_N) return fail("n_elec must be in 1..%d (got %lld)", ds::OBS_MAX_N, (long long)n_elec);
+    if (n_q < 0 || n_q > ds::OBS_MAX_Q) return fail("n_q must be in 0..%d (got %d)", ds::OBS_MAX_Q, n_q);
+    if (n_q > 0 && !q_int) return fail("null q_int with n_q = %d", n_q);
+    if (pol_direction < -1 || pol_direction > 2) return fail("pol_direction must be -1, 0, 1 or 2 (got %d)", pol_direction);
+    const int64_t need = ds_observables_workspace_bytes(B, n_q);
+    if (ws_bytes < need) return fail("workspace too small for ds_observables: %lld bytes < %lld", (long long)ws_bytes, (long long)need);
+    ds::ObsArgs A;
+    for (int i = 0; i < 9; ++i) {
+        if (!std::isfinite(recvec[i])) return fail("recvec[%d] is not finite", i);
+        A.g[i] = recvec[i];
+    }
+    A.n_q = n_q;
+    A.pol = pol_direction;
+    int pmax = 0;
+    for (int k = 0; k < 3 * n_q; ++k) {
+        const int32_t n = q_int[k];
+        if (n < 0 || n >= ds::OBS_MAX_POW)
+            return fail("q point %d: lattice coordinate %d is outside 0..%d", k / 3, (int)n, ds::OBS_MAX_POW - 1);
+        A.qn[k] = (signed char)n;
+        pmax = std::max(pmax, (int)n);
+    }
+    for (int k = 3 * n_q; k < 3 * ds::OBS_MAX_Q; ++k) A.qn[k] = 0;
+    A.n_pow = pmax + 1;
+    hipStream_t st = (hipStream_t)stream;
+    const int G = ds::obs_groups(B), K = 2 + 3 * n_q;
+    double* part = (double*)ws;
+    if (dtype == 0)
+        obs_partial<double>(A, x, B, (int)n_elec, G, part, st);
+    else
+        obs_partial<float>(A, x, B, (int)n_elec, G, part, st);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(ds::k_obs_final, dim3((K + 255) / 256), dim3(256), 0, st, (const double*)part, G, K, out_sums);
     HIP_OK(hipGetLastError());
     return 0;
 }

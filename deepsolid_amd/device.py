@@ -616,3 +616,31 @@ class DeviceSystem:
         if n < 0:
             raise RuntimeError(f'ds_debug_stage({stage}): {self.lib.ds_last_error().decode()}')
         return out[:n]
+
+
+def observable_sums(recvec, x, q_int, pol_direction):
+    """Batch sums of the walker observables of estimator.py (`ds_observables`, csrc/ds_obs.h); needs no handle.
+    recvec (3, 3): the simulation cell's reciprocal vectors (rows g_j); x (B, 3N) float64 / float32 device tensor;
+    q_int (Q, 3) integer lattice coordinates in 0..7 (Q may be 0); pol_direction 0..2 or -1 (no polarization).
+    -> float64 device tensor [sum Re P, sum Im P, sum Re rho(q_k), sum Im rho(q_k), sum |rho(q_k)|^2] of 2 + 3Q values."""
+    _require_gpu()
+    if not x.is_cuda:
+        raise RuntimeError('observable_sums: walkers must live on the ROCm device (no CPU path)')
+    if x.dtype not in _DTYPES:
+        raise TypeError(f'observable_sums: walkers must be float64 or float32, got {x.dtype}')
+    if x.dim() != 2 or x.shape[1] % 3:
+        raise ValueError(f'observable_sums: walkers must have shape (B, 3N), got {tuple(x.shape)}')
+    if x.shape[0] < 1:
+        raise ValueError('observable_sums: empty walker batch (the observables are batch means)')
+    lib = _lib.load()
+    x = x.contiguous()
+    rv = np.ascontiguousarray(np.asarray(recvec, dtype=np.float64).reshape(3, 3))
+    q = np.ascontiguousarray(np.asarray(q_int, dtype=np.int32).reshape(-1, 3))
+    B, n_q = x.shape[0], q.shape[0]
+    need = lib.ds_observables_workspace_bytes(B, n_q)
+    ws = torch.empty(max(int(need), 8) // 8, dtype=torch.float64, device=x.device)
+    out = torch.empty(2 + 3 * n_q, dtype=torch.float64, device=x.device)
+    _lib.check(lib.ds_observables(_pd(rv), _DTYPES[x.dtype], _ptr(x), B, x.shape[1] // 3,
+                                  q.ctypes.data_as(C.POINTER(C.c_int32)), n_q, int(pol_direction), _ptr(out), _ptr(ws),
+                                  ws.numel() * 8, _stream()), 'ds_observables')
+    return out

@@ -57,12 +57,49 @@ def _rank_generator(key, device, t_init=0):
     return torch.Generator(device=device).manual_seed(seed)
 
 
+def _observables(simulation_cell, complex_polarization, structure_factor, structure_factor_nq, save_path):
+    """cfg.log.complex_polarization / cfg.log.structure_factor (base_config.py:94-95, process.py:277-283): -> (schema, f) with
+    f(data) -> dict of the observables for the returned row (and the CSV column), appending the S(k) row to
+    <save_path>/structure_factor.csv on every call (process.py:339-342); f is None when both switches are off."""
+    schema = list(TRAIN_SCHEMA)
+    if not (complex_polarization or structure_factor):
+        return schema, None
+    from . import estimator
+    if complex_polarization:
+        schema.append('complex_polarization')                            # process.py:277-278
+    obs = estimator.make_observables(simulation_cell, polarization_direction=0 if complex_polarization else None,
+                                     nq=structure_factor_nq if structure_factor else None)
+    sk_path = os.path.join(save_path, 'structure_factor.csv') if save_path else None
+
+    def evaluate(data):
+        pol, sk = obs(data)
+        out = {}
+        if pol is not None:
+            out['complex_polarization'] = np.asarray(pol.cpu().numpy())  # process.py:362
+        if sk is not None:
+            out['structure_factor'] = sk.cpu().numpy()
+            if sk_path:
+                estimator.append_structure_factor_row(sk_path, out['structure_factor'])
+        return out
+    return schema, evaluate
+
+
+def _csv_row(row, schema):
+    """The keys of a returned row that are CSV columns (S(k) has a file of its own)."""
+    return {k: v for k, v in row.items() if k in schema}
+
+
 def run_inference(slog_net, logdet_net, params, data, simulation_cell, iterations, key=0, move_width=0.02,
                   mcmc_steps=20, burn_in=100, adapt_frequency=100, stats_frequency=1, save_path=None,
-                  stats_file_name='train_stats', laplacian_mode='for', partition_number=3):
+                  stats_file_name='train_stats', laplacian_mode='for', partition_number=3, complex_polarization=False,
+                  structure_factor=False, structure_factor_nq=4):
     """Returns (data, mcmc_width, rows).  `slog_net` / `logdet_net` are the objects returned by
     ``make_solid_fermi_net(method_name='eval_slogdet' | 'eval_logdet')``; `data` is (B, 3N) on the device.
-    Energies are reported per primitive cell like process.py:330-334 (divided by ``simulation_cell.scale``)."""
+    Energies are reported per primitive cell like process.py:330-334 (divided by ``simulation_cell.scale``).
+    `complex_polarization` / `structure_factor` (cfg.log switches, base_config.py:94-95): evaluate the observables of
+    `deepsolid_amd.estimator` on the walkers after every step; rows carry 'complex_polarization' (also a CSV column) and
+    'structure_factor' (the nq^3 values, `structure_factor_nq` = nq, one row per iteration in
+    <save_path>/structure_factor.csv)."""
     gen = _rank_generator(key, data.device)
     batch = data.shape[0]
     mcmc_step = qmc.make_mcmc_step(slog_net.apply, batch, latvec=simulation_cell.a, steps=mcmc_steps)
@@ -74,7 +111,8 @@ def run_inference(slog_net, logdet_net, params, data, simulation_cell, iteration
     scale = float(getattr(simulation_cell, 'scale', 1))
     pmoves = np.zeros(adapt_frequency)
     rows = []
-    writer = Writer(stats_file_name, TRAIN_SCHEMA, save_path) if save_path else None
+    schema, observe = _observables(simulation_cell, complex_polarization, structure_factor, structure_factor_nq, save_path)
+    writer = Writer(stats_file_name, schema, save_path) if save_path else None
     if writer:
         writer.__enter__()
     try:
@@ -88,10 +126,12 @@ def run_inference(slog_net, logdet_net, params, data, simulation_cell, iteration
                    'imaginary': float(aux.imaginary) / scale,
                    'kinetic': complex(aux.kinetic.mean().item()) / scale,
                    'ewald': float(aux.ewald.mean()) / scale}
+            if observe:                                                  # process.py:337-342
+                row.update(observe(data))
             if t % stats_frequency == 0:
                 rows.append(row)
                 if writer:
-                    writer.write(t, **row)
+                    writer.write(t, **_csv_row(row, schema))
             if t > 0 and t % adapt_frequency == 0:                       # :368-373
                 if np.mean(pmoves) > 0.55:
                     width *= 1.1
@@ -113,7 +153,8 @@ def learning_rate_schedule(rate=5e-2, decay=1.0, delay=10000.0):
 def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations, key=0, move_width=0.02, mcmc_steps=10,
                  burn_in=100, adapt_frequency=100, learning_rate=None, clip_local_energy=5.0, clip_type='real',
                  save_path=None, save_every=None, stats_file_name='train_stats', laplacian_mode='for',
-                 partition_number=3, t_init=0, opt_state=None, check_nan=True, max_rejected=20):
+                 partition_number=3, t_init=0, opt_state=None, check_nan=True, max_rejected=20, complex_polarization=False,
+                 structure_factor=False, structure_factor_nq=4):
     """The `optimizer='adam'` branch of the reference driver (process.py:204-219, 256-383): burn-in, then per iteration
     ``mcmc_step -> value_and_grad(total_energy) -> gradient pmean -> Adam -> CSV row -> width adaptation``, with
     checkpoints in the reference's layout (`deepsolid_amd.checkpoint.save`) every `save_every` iterations.
@@ -126,7 +167,10 @@ def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations
     after `max_rejected` (default 20) rejections IN A ROW the loop writes the state it is stuck in (walkers, parameters, optimiser
     state: nothing of a rejected step was kept) as `aborted_ckpt_<t>.npz` -- a name `find_last_checkpoint` does not pick up, so a
     restart resumes from the last regular checkpoint -- and raises instead of running to the end doing nothing;
-    `max_rejected=None` is the reference's behaviour: log and go on (process.py:303-318)."""
+    `max_rejected=None` is the reference's behaviour: log and go on (process.py:303-318).
+    `complex_polarization` / `structure_factor` / `structure_factor_nq`: as in `run_inference`; the observables are evaluated on
+    the walkers the step returns, rejected steps included (their rows carry them too), and the S(k) row is written for a
+    rejected step as well, since the reference writes it before its `loss is not None` gate (process.py:339-345)."""
     from . import checkpoint
     gen = _rank_generator(key, data.device, t_init)
     batch = data.shape[0]
@@ -144,7 +188,8 @@ def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations
     scale = float(getattr(simulation_cell, 'scale', 1))
     pmoves = np.zeros(adapt_frequency)
     rows = []
-    writer = Writer(stats_file_name, TRAIN_SCHEMA, save_path) if save_path else None
+    schema, observe = _observables(simulation_cell, complex_polarization, structure_factor, structure_factor_nq, save_path)
+    writer = Writer(stats_file_name, schema, save_path) if save_path else None
     if writer:
         writer.__enter__()
     t_last = t_init + iterations - 1
@@ -152,8 +197,9 @@ def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations
     try:
         for t in range(t_init, t_init + iterations):
             data, params, opt_state, loss, aux, pmove, _ = step(t, data, params, opt_state, gen, width)
+            observed = observe(data) if observe else {}                  # process.py:337-342
             if loss is None:                                             # rejected step: nothing was updated, no CSV row
-                rows.append({'step': t, 'rejected': True, 'pmove': float(pmove)})
+                rows.append({'step': t, 'rejected': True, 'pmove': float(pmove), **observed})
                 n_rejected += 1
                 logging.warning('step %d: non-finite local energy / loss / gradient, step discarded (%d in a row)', t, n_rejected)
                 if max_rejected is not None and n_rejected >= max_rejected:
@@ -167,10 +213,11 @@ def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations
                 row = {'step': t, 'energy': float(loss) / scale, 'variance': float(aux.variance) / scale ** 2,
                        'pmove': float(pmove), 'imaginary': float(aux.imaginary) / scale,
                        'kinetic': complex(aux.kinetic.mean().item()) / scale, 'ewald': float(aux.ewald.mean()) / scale}
+                row.update(observed)
                 n_rejected = 0
                 rows.append(row)
                 if writer:
-                    writer.write(t, **row)
+                    writer.write(t, **_csv_row(row, schema))
             if t > 0 and t % adapt_frequency == 0:                       # process.py:368-373
                 if np.mean(pmoves) > 0.55:
                     width *= 1.1

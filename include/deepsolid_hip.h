@@ -184,6 +184,19 @@ int ds_local_energy(ds_system* sys, const void* params, const void* x, int64_t B
 int ds_enforce_pbc(const double* latvec, int dtype, const void* x, int64_t n_elec, void* out_x,
                    void* out_wrap, void* stream);
 
+/* Walker observables of estimator.py (complex polarization :15-42, structure factor :44-84) as float64 sums over the batch;
+ * needs no handle.  recvec: HOST pointer to the simulation cell's reciprocal vectors (3x3, row j = g_j = 2 pi inv(a)^T row j);
+ * dtype 0 = f64, 1 = f32; x: (B, 3 n_elec) device array, 1 <= n_elec <= 128, B >= 1;
+ * q_int: HOST pointer to n_q (0..512) integer points (n1, n2, n3), 0 <= n_j <= 7, q = n1 g_1 + n2 g_2 + n3 g_3;
+ * pol_direction: 0..2, or -1 for no polarization.  out_sums: device array of 2 + 3 n_q doubles,
+ *   [sum_b Re P_b, sum_b Im P_b, sum_b Re rho_b(q_k) (k < n_q), sum_b Im rho_b(q_k) (k < n_q), sum_b |rho_b(q_k)|^2 (k < n_q)]
+ * with P_b = exp(i sum_e g_dir . r_be), rho_b(q) = sum_e exp(i q . r_be); the polarization pair is 0 when pol_direction = -1.
+ * ws: device workspace of at least ds_observables_workspace_bytes(B, n_q) bytes.  Fixed reduction order, no atomics:
+ * the same input gives bit-identical sums. */
+int64_t ds_observables_workspace_bytes(int64_t B, int n_q);
+int ds_observables(const double* recvec, int dtype, const void* x, int64_t B, int64_t n_elec, const int32_t* q_int, int n_q,
+                   int pol_direction, double* out_sums, void* ws, int64_t ws_bytes, void* stream);
+
 /* qmc.mh_update symmetric branch (qmc.py:190-196, 217-222) split around the network call:
  *   propose: x2 = wrap(x1 + width * normal)
  *   accept : cond = (lp2 - lp1) > log(uniform); x1,lp1 <- select; n_accept[0] += sum(cond)
