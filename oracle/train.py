@@ -7,12 +7,13 @@ with clip_diff treated as a constant.  The derivative of log psi comes from torc
 autograd over the restated forward (oracle/network.py), the same role jax.jvp
 plays at train.py:131.
 """
+import contextlib
 from types import SimpleNamespace
 
 import torch
 
 from . import hamiltonian
-from .network import params_to_torch
+from .network import params_to_torch, working_dtype
 
 
 def clip_difference(diff, clip_local_energy, clip_type):
@@ -35,9 +36,20 @@ def clip_difference(diff, clip_local_energy, clip_type):
     raise ValueError('Unrecognized clip type.')
 
 
-def logpsi_vjp(network, params, data, cot):
+def logpsi_vjp(network, params, data, cot, dtype=None):
     """Gradient w.r.t. every parameter leaf of sum_b Re(conj(cot_b) * network(params, x_b)),
-    network = eval_logdet (log|psi| + i arg psi).  -> tree shaped like params."""
+    network = eval_logdet (log|psi| + i arg psi).  -> tree shaped like params.
+    dtype (e.g. torch.float32): parameters, walkers and cotangents in that dtype and the restatement under
+    network.working_dtype(dtype) -- what a straight evaluation in that precision gives; build `network` under the
+    same context.  None (the default) is the float64 computation."""
+    with (working_dtype(dtype) if dtype is not None else contextlib.nullcontext()):
+        if dtype is not None:
+            data = torch.as_tensor(data).to(dtype)
+            cot = torch.as_tensor(cot).to(torch.complex128 if dtype == torch.float64 else torch.complex64)
+        return _logpsi_vjp(network, params_to_torch(params, dtype), data, cot)
+
+
+def _logpsi_vjp(network, params, data, cot):
     leaves = []
 
     def req(o):
@@ -48,7 +60,7 @@ def logpsi_vjp(network, params, data, cot):
         t = o.clone().detach().requires_grad_(True)
         leaves.append(t)
         return t
-    p = req(params_to_torch(params))
+    p = req(params)
     tot = 0.0
     for x, c in zip(data, cot):
         lp = network(p, x)

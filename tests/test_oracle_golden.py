@@ -165,6 +165,58 @@ def test_oracle_parameter_gradient_vs_reference_finite_differences(name):
             assert abs(dot(g, v) - float(fx[key][b])) < 2e-7 * max(1.0, abs(float(fx[key][b])))
 
 
+def test_oracle_parameter_gradient_dtype():
+    """oracle.train.logpsi_vjp(dtype=...): the default is the float64 computation, bit for bit -- the same leaves as
+    dtype=torch.float64 and as torch autograd written out here over the float64 restatement; dtype=torch.float32 runs in float32
+    (float32 leaves that differ from the float64 gradient at the same float32-rounded inputs by more than float64 round-off,
+    less than 1e-3 of a leaf's largest entry)."""
+    from oracle import train as otrain
+    fx, cell, klist, net_kw, params = load_case('lih')
+    x = tt(fx['x'][:2])
+    cot = torch.complex(tt([0.7, -1.3]), tt([0.4, 0.9]))
+    net = oracle_net(cell, klist, net_kw, 'eval_logdet')
+    g = otrain.logpsi_vjp(net.apply, params, x, cot)
+    g64 = otrain.logpsi_vjp(net.apply, params, x, cot, dtype=torch.float64)
+    p = onet.params_to_torch(params)
+    flat = []
+
+    def req(o):
+        if isinstance(o, dict):
+            return {k: req(v) for k, v in o.items()}
+        if isinstance(o, (list, tuple)):
+            return [req(v) for v in o]
+        flat.append(o.clone().requires_grad_(True))
+        return flat[-1]
+    pr = req(p)
+    tot = sum((torch.conj(c) * net.apply(pr, xx)).real for xx, c in zip(x, cot))
+    by_hand = torch.autograd.grad(tot, flat, allow_unused=True)
+
+    def leaves_of(o):
+        if isinstance(o, dict):
+            return [t for k in o for t in leaves_of(o[k])]
+        if isinstance(o, (list, tuple)):
+            return [t for v in o for t in leaves_of(v)]
+        return [o]
+    lg, l64 = leaves_of(g), leaves_of(g64)
+    assert len(lg) == len(l64) == len(by_hand)
+    for a, b, h in zip(lg, l64, by_hand):
+        assert a.dtype == torch.float64 and torch.equal(a, b)
+        assert torch.equal(a, torch.zeros_like(a) if h is None else h)
+    with onet.working_dtype(torch.float32):
+        net32 = oracle_net(cell, klist, net_kw, 'eval_logdet')
+    g32 = leaves_of(otrain.logpsi_vjp(net32.apply, params, x.float(), cot.to(torch.complex64), dtype=torch.float32))
+    p32 = {k: [{kk: np.asarray(vv, dtype=np.float32).astype(np.float64) for kk, vv in d.items()} for d in v] for k, v in params.items()}
+    r = leaves_of(otrain.logpsi_vjp(net.apply, p32, x.float().double(), cot.to(torch.complex64).to(torch.complex128)))
+    worst = 0.0
+    for a, b in zip(g32, r):
+        assert a.dtype == torch.float32
+        scale = float(b.abs().max())
+        d = float((a.double() - b).abs().max()) / max(scale, 1e-30)
+        assert d < 1e-3, d
+        worst = max(worst, d)
+    assert worst > 1e-9          # float32 round-off, not float64
+
+
 # ----------------------------------------------------------------------------------------------
 # The reference's OWN hamiltonian.py / train.py, executed over its own network.py under the
 # torch-backed `jax` stand-in (tools/jax_torch_standin.py, tools/make_golden.py): ke_ref / grad_ref.
