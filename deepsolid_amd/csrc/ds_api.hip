@@ -414,29 +414,15 @@ int copy_out(DumpReq<T>* dr, const T* src, size_t n, hipStream_t st) {
     return 0;
 }
 
-// Static part of two dispatch decisions of the chain (the dims of sd and sf are the same):
-// the first hidden layer on the low-rank form of the layer-0 output (k_layer1_lr; off for stage dumps) ...
-inline bool lowrank_possible(const ds_system* s, int ST) {
+// A dense residual hidden layer l with the shape of the int8 split (ds_i8.h: float64, 256 features from K = 320 rows).  The slot axis and
+// the switch are the caller's: the energy chain (plan_chain: 5 slot tiles) ...
+inline bool i8_shape(const ds_system* s, int l) {
     const ds::SysDev<double>& S = s->sd;
-    const int K0loc = S.h1[0] + S.nch * S.h2[0], K0sh = S.nch * S.h1[0];
-    const int lr_nc = std::max(2, (K0loc + K0sh + 4 + 15) / 16);      // column tiles of the per-electron weights C (instances: 2, 3, 4)
-    // (worth it when the weights C cost fewer products than the rows they replace: Kh / 4 k-steps of NB x NC tiles against
-    //  (Kh - K0 - 4) / 4 k-steps of NB x ST -- not for the one- or two-tile cells, N <= 10)
-    return s->use_lr && S.n_layers >= 2 && !s->res1[0] && lr_nc <= 4 && S.h1[1] % 16 == 0 && (S.nch * S.h2[1]) % 4 == 0 &&
-           3 * (K0loc + K0sh + 4) <= S.h1[1] && lr_nc * S.h1[1] < (S.h1[1] - K0loc - K0sh - 4) * ST;
+    return s->dtype == 0 && l >= 1 && s->res1[l] && S.h1[l + 1] == ds::i8::NOUT && S.h1[l] + S.nch * S.h2[l] == 320;
 }
-// ... and a dense residual hidden layer l with its per-electron contraction as an int8 split (ds_i8.h: float64, 5 slot tiles, 256 features)
-inline bool int8_layer(const ds_system* s, int l) {
-    const ds::SysDev<double>& S = s->sd;
-    const int Kloc = S.h1[l] + S.nch * S.h2[l];
-    return s->dtype == 0 && s->use_i8 && l >= 1 && s->res1[l] && S.P == ds::i8::P && S.h1[l + 1] == ds::i8::NOUT && Kloc == 320;
-}
-// (the value chain's column axis is 80 walkers whatever the electron count: any float64 cell with such a layer)
-inline bool int8_value_layer(const ds_system* s, int l) {
-    const ds::SysDev<double>& S = s->sd;
-    const int Kloc = S.h1[l] + S.nch * S.h2[l];
-    return s->dtype == 0 && s->use_i8_val && l >= 1 && s->res1[l] && ds::PV == ds::i8::P && S.h1[l + 1] == ds::i8::NOUT && Kloc == 320;
-}
+// ... and the value chain (its column axis is 80 walkers whatever the electron count: any float64 cell with such a layer; whether a
+// call takes it depends on its batch)
+inline bool int8_value_layer(const ds_system* s, int l) { return s->use_i8_val && ds::PV == ds::i8::P && i8_shape(s, l); }
 
 // digit planes + column scales of layer l's per-electron weights: prepared by the first launch of a C-ABI call that needs them (the
 // 20 forwards of an mcmc_step, the chunks of a local-energy batch and the value / energy chains of one call share them)
@@ -450,7 +436,214 @@ inline void i8_prepare(ds_system* s, int l, const double* Wloc, int Kloc, int No
     }
 }
 
-// The forward-Laplacian chain on a chunk of Bc walkers.
+// ---------------------------------------------------------------- the plan of the forward-Laplacian chain
+// Which kernel variant every stage of run_chain launches.  All dispatch predicates of the chain live in plan_chain; run_chain executes
+// the plan, and the producer and the consumer of a buffer read the same entry of it.
+enum class LayerKind {
+    Dense,            // k_jet_gemm EPI 1 (+ k_layer_res_add behind it when res_sep)
+    DenseRes,         // k_jet_gemm EPI 2: the residual inside the GEMM
+    L0Stats,          // layer 0 in front of the low-rank layer 1 as one kernel: k_layer0_stats
+    L0Epi9Means,      // ... as two: k_jet_gemm EPI 9 (output dropped), then k_layer0_means per slot chunk
+    LowRank1,         // k_layer1_lr: the first hidden layer on the low-rank form of the layer-0 output
+    Int8              // i8::k_layer_i8: the per-electron contraction as an int8 split
+};
+struct PairPlan {     // pair-stream layer l (l < n_double)
+    bool res, res_sep;                        // residual inside the kernel / added by k_pair_res_add behind it
+    bool expand;                              // k_two_layer_expand: the layer writes the pair-mean rows of one-electron layer l + 1 itself
+    bool write_out;                           // the output itself has a reader (another pair layer, or the orbital head's pair means)
+    unsigned xz; int EW, NW; size_t xlds;     // k_two_layer_expand: feature splits, electrons and waves per workgroup, LDS bytes
+};
+struct LayerPlan {    // one-electron layer l
+    LayerKind kind;
+    bool res_sep;         // k_layer_res_add follows
+    bool wide;            // the chunked form of the kind's kernel (ds_wide.h)
+    bool pm_mask;         // the layer sets oe.pm_*: its kernel skips the structurally zero slot tiles of the pair-mean rows
+    bool pm_unwritten;    // ... and never reads them: the producer of the rows may leave those tiles unwritten
+    int prof_kind;
+    PairPlan pair;
+};
+enum class OrbKind { Orb3, Wide, Ldsb, Gemm };
+template <typename T> struct ChainPlan {
+    const ds::TileOps<T>* to;     // the kernels instantiated per jet-slot tile count (ds_tiles.h)
+    bool lr_on;                   // layers 0 and 1 run as L0Stats / L0Epi9Means + LowRank1
+    int lr_nc;                    // column tiles of the low-rank layer's per-electron weights C (instances: 2, 3, 4)
+    int g4;                       // > 0: DenseRes layers and the orbital head multiply the last slot tile as g4 groups of four columns
+    LayerPlan layer[DS_MAX_LAYERS];
+    OrbKind orb[2];               // orbital head per spin
+    int count(LayerKind k, int n_layers) const {
+        int n = 0;
+        for (int l = 0; l < n_layers; ++l) n += layer[l].kind == k ? 1 : 0;
+        return n;
+    }
+};
+
+// dump: a stage dump shows the dense path's buffers (no low-rank layer, no fused pair expansion, every tile written)
+template <typename T>
+int plan_chain(const ds_system* s, bool dump, ChainPlan<T>* p) {
+    const ds::SysDev<double>& S = s->sd;      // (the dims of sd and sf are the same)
+    const ds::TileOps<T>* to = p->to = ds::tile_ops<T>(S.P / 16);
+    if (!to) return fail("no kernel instance for %d slot tiles (N = %d electrons)", S.P / 16, S.N);
+    const int ST = to->ST;
+    // wide slot ranges: 64-feature x 4/5-tile wave tiles in slot chunks (ds_wide.h), where they are the faster form (or everywhere)
+    const bool wide = s->use_wide && to->gemm_wide != nullptr;
+    auto gemm_wide = [&](int epi) { return wide && (s->wide_all || ds::gemm_wide_faster<T>(epi)); };
+    // Low-rank first hidden layer (k_layer1_lr): layer 0 reads its input tiles from their own buffer XL (layer 1 needs them again
+    // while it overwrites G[0]) and does not write its dense output -- k_layer0_stats leaves (y, oL) per electron and the spin means
+    // of the output (the input of layer 1's shared term), layer 1 recomputes its residual rows from the layer-0 input.
+    const int K0loc = S.h1[0] + S.nch * S.h2[0], K0sh = S.nch * S.h1[0];
+    p->lr_nc = std::max(2, (K0loc + K0sh + 4 + 15) / 16);
+    // (worth it when the weights C cost fewer products than the rows they replace: Kh / 4 k-steps of NB x NC tiles against
+    //  (Kh - K0 - 4) / 4 k-steps of NB x ST -- not for the one- or two-tile cells, N <= 10)
+    p->lr_on = !dump && s->use_lr && S.n_layers >= 2 && !s->res1[0] && p->lr_nc <= 4 && S.h1[1] % 16 == 0 && (S.nch * S.h2[1]) % 4 == 0 &&
+               3 * (K0loc + K0sh + 4) <= S.h1[1] && p->lr_nc * S.h1[1] < (S.h1[1] - K0loc - K0sh - 4) * ST;
+    // the last slot tile as 4-column groups where at most 12 of its 16 columns are jets (instances: three groups on five tiles -- 73 .. 76
+    // jets, 24 electrons --, one group on ten tiles -- 48 electrons: two jets on the tenth tile)
+    const int used = S.D - 16 * (ST - 1);
+    p->g4 = !s->use_g4 ? 0 : (ST == 5 && used > 8 && used <= 12) ? 3 : (ST == 10 && used <= 4) ? 1 : 0;
+    for (int l = 0; l < S.n_layers; ++l) {
+        const int Kh = S.h1[l], K2 = S.h2[l], Nout = S.h1[l + 1], Kloc = Kh + S.nch * K2;
+        LayerPlan& lp = p->layer[l];
+        lp = LayerPlan{};
+        if (Nout % 64 || Nout > 1024) return fail("hidden_single must be a multiple of 64 and <= 1024 (got %d)", Nout);
+        if (l < S.n_double) {
+            PairPlan& pp = lp.pair;
+            const int K2o = S.h2[l + 1];
+            if (K2o != 32 && K2o != 16) return fail("hidden_double must be 16 or 32 (got %d)", K2o);
+            if (K2 % 4) return fail("pair-stream width %d is not a multiple of 4", K2);
+            // (a first pair layer as wide as the pair features: its residual is added by k_pair_res_add behind the layer)
+            pp.res_sep = s->res2[l] && l == 0;
+            pp.res = s->res2[l] && !pp.res_sep;
+            pp.xz = (!pp.res && K2o == 32) ? 2 : 1;       // (a residual layer keeps its operands: all features in one workgroup)
+            pp.write_out = l + 1 < S.n_double || s->use_last;
+            // two electrons per workgroup where the output is written and a single electron's pairs would end in the middle of a 128-byte line
+            pp.EW = (pp.write_out && S.N % 16 == 8 && pp.xz == 2) ? 2 : 1;
+            pp.NW = (pp.EW * S.N + 15) / 16;
+            pp.xlds = ((size_t)(K2o / pp.xz) * 5 * pp.EW * S.N + (size_t)pp.EW * S.nch * (K2o / pp.xz) * 5) * sizeof(T);
+            // the layer and the spin means of its output in one kernel (a workgroup per electron) when the output jets of an electron's
+            // pairs fit the LDS: the next level's rows land in the buffer the one-electron layer below writes its output to
+            pp.expand = !dump && s->use_pair_expand && !pp.res_sep && l + 1 < S.n_layers && pp.NW <= 8 && pp.xlds <= 150 * 1024;
+        }
+        const bool res = s->res1[l];
+        // a first layer as wide as its input features: the residual is added by k_layer_res_add behind the layer (see there)
+        lp.res_sep = res && l == 0 && (Kloc % 16 != 0 || S.nf * S.A != Nout);
+        if (res && !lp.res_sep && Kloc % 16) return fail("residual layer with K = %d: the GEMM's operand ring needs K %% 16 == 0", Kloc);
+        if (p->lr_on && l == 1) {
+            lp.kind = LayerKind::LowRank1;
+            lp.wide = wide && (s->wide_all || ds::lr_wide_faster<T>(p->lr_nc));
+        } else if (p->lr_on && l == 0) {
+            const bool one_kernel = to->layer0_stats && ds::layer0_stats_instance(ST, K0loc / 4);
+            lp.kind = one_kernel ? LayerKind::L0Stats : LayerKind::L0Epi9Means;
+            lp.wide = !one_kernel && gemm_wide(9);
+        } else if (s->use_i8 && S.P == ds::i8::P && i8_shape(s, l)) {
+            lp.kind = LayerKind::Int8;      // (float64, 5 slot tiles)
+        } else if (res && !lp.res_sep) {
+            lp.kind = LayerKind::DenseRes;
+            lp.wide = gemm_wide(2);
+        } else {
+            lp.kind = LayerKind::Dense;
+            lp.wide = gemm_wide(1);
+        }
+        lp.prof_kind = l == 0 ? DS_PROF_SINGLE_FIRST : (lp.kind == LayerKind::LowRank1 ? DS_PROF_SINGLE_LR : DS_PROF_SINGLE_HIDDEN);
+        // Pair-mean rows: layer 0 (EPI 1 / 9: own-feature rows, then the pair-mean rows per partner spin) and the residual hidden layers
+        // (EPI 2: whole rounds of four k-steps per partner spin) run them under tile masks.
+        // (first finding: every layer-0 kind gets the mask fields, a DenseRes layer 0 with K2 % 16 != 0 included)
+        lp.pm_mask = s->use_pm_skip && (l == 0 || (lp.kind == LayerKind::DenseRes && Kh % 16 == 0 && K2 % 16 == 0));
+        // The masked tiles of a hidden layer's rows stay unwritten when its kernel never reads them: the low-rank layer 1 (it skips them by
+        // itself) and the float64 masked instances.  The chunked kernels of ds_wide.h have no masks: they read every slot.
+        lp.pm_unwritten = !dump && l >= 1 && !lp.wide &&
+                          (lp.kind == LayerKind::LowRank1 ? s->use_pm_skip : (lp.pm_mask && ds::pm_instance<T>(ST)));
+    }
+    // orbital head
+    const int Korb = S.h1[S.n_layers] + (s->use_last ? S.nch * S.h2[S.n_layers] : 0);
+    if (Korb % 16) return fail("orbital head with K = %d: the GEMM's operand ring needs K %% 16 == 0", Korb);
+    for (int sp = 0; sp < S.nch; ++sp) {
+        const int OC = S.ocols[sp];
+        // 192 columns (n_s*K = 96) would give 3 waves of 64 columns per workgroup and leave SIMDs with a single wave;
+        // 48-column waves give 4 balanced waves (the MFMA pipe needs >= 2 waves per SIMD, profiles/r01_mfma_f64_probe.json)
+        if (to->gemm_orb3 && OC % 256 != 0 && OC % 192 == 0) p->orb[sp] = OrbKind::Orb3;
+        else if (gemm_wide(5)) p->orb[sp] = OrbKind::Wide;
+        else if (to->orbital_lb && s->use_ldsb && OC % 64 == 0) p->orb[sp] = OrbKind::Ldsb;      // float32 wide cells: jet rows staged in LDS (ds_ldsb.h)
+        else p->orb[sp] = OrbKind::Gemm;
+    }
+    return 0;
+}
+
+// Inverse + determinant of the orbital matrices of determinant channel ch: in-place Gauss-Jordan with one lane per matrix row where an
+// instance exists (k_det_inv_wave), else the LDS Gauss-Jordan kernel; value = slot 0 of slot tile 0
+template <typename T>
+void launch_det_inverse(const ds_system* s, const ds::SysDev<T>& S, const Carve<T>& c, int ch, int64_t Bc, hipStream_t st) {
+    const WsLayout& L = s->ws;
+    const int n = S.det_n[ch];
+    const size_t sh = (size_t)n * 2 * n * sizeof(ds::Cx<T>) + 16;
+    if (s->no_lu_wave || !ds::launch_det_inv_wave<T>(n, dim3(S.K, (unsigned)Bc), st, S, c.MOUT, L.MOUT, L.mout_off[ch], ch, 16, c.MINV, L.MINV,
+                                                     L.minv_off[ch], c.DETS, L.DETS, L.dets_off[ch], S.P))
+        hipLaunchKernelGGL((ds::k_det_inverse<T>), dim3(S.K, (unsigned)Bc), dim3(64), sh, st, S, c.MOUT, L.MOUT, L.mout_off[ch], ch,
+                           c.MINV, L.MINV, L.minv_off[ch], c.DETS, L.DETS, L.dets_off[ch], S.P, 16, 1, 1);
+}
+
+// tr(Y_d), sum Y_d Y_d^T of Y_d = d_d M . M^-1 for determinant channel ch: the instance by matrix size n
+template <typename T>
+int launch_det_trace(const ds_system* s, const ds::SysDev<T>& S, const Carve<T>& c, int ch, int64_t Bc, hipStream_t st) {
+    const WsLayout& L = s->ws;
+    const int n = S.det_n[ch];
+    const dim3 grid(S.K, (unsigned)Bc);
+    unsigned long long* const clk = (s->dbg & 32) ? s->clk_dev + 2 : (unsigned long long*)nullptr;
+#define DS_TR_ARGS S, c.MOUT, L.MOUT, L.mout_off[ch], ch, c.MINV, L.MINV, L.minv_off[ch], c.TR, L.TR, L.tr_off[ch], c.DETS, L.DETS, L.dets_off[ch]
+    // matrix-core version when the real expansion (2n) is a whole number of k-steps and a slot tile (or half of one) of Y fits LDS
+    const int nt = (2 * n + 15) / 16;
+    // (nt >= 3: 8-wave workgroups, one per CU at these sizes; their [512] reduction buffer is counted for all)
+    const size_t ybytes16 = (size_t)n * 2 * n * 16 * sizeof(T) + 512 * sizeof(ds::Cx<T>);
+    const size_t ybytes8 = (size_t)n * 2 * n * 8 * sizeof(T) + 512 * sizeof(ds::Cx<T>);
+    const bool sw8 = ybytes16 > 160 * 1024;
+    const size_t ybytes = sw8 ? ybytes8 : ybytes16;
+    if ((2 * n) % 4 == 0 && ybytes <= 160 * 1024 && nt <= 6 && !s->det_valu) {
+#define DS_TRMF(NTV, SWV, NWV, NF) hipLaunchKernelGGL((ds::k_det_trace_mfma<T, NTV, SWV, NWV, NF>), grid, dim3(64 * NWV), ybytes, st, DS_TR_ARGS, clk)
+#define DS_TRM(NTV, SWV, NWV) hipLaunchKernelGGL((ds::k_det_trace_mfma<T, NTV, SWV, NWV>), grid, dim3(64 * NWV), ybytes, st, DS_TR_ARGS)
+        if (sw8 && (n == 32 || n == 48)) {
+            // row-split mode: half the rows of a full slot tile in LDS, nothing computed twice
+            // (4 waves: the A fragments + three operand sets need the 512-register budget; 8 waves with one set less
+            //  measured slower, 71.3 vs 68.7 ms per diamond step)
+            constexpr int NWS = 4;
+            const size_t sbytes = (size_t)(n / 2) * 2 * n * 16 * sizeof(T) + 512 * sizeof(ds::Cx<T>);
+#define DS_TRS(NTV) hipLaunchKernelGGL((ds::k_det_trace_mfma_split<T, NTV, NWS, (NTV <= 4 || sizeof(T) == 4 ? 2 : 1)>), grid, dim3(64 * NWS), sbytes, st, DS_TR_ARGS, clk)
+            if (n == 32) DS_TRS(4); else DS_TRS(6);        // 2n = 16 NT exactly
+#undef DS_TRS
+        } else if (sw8) { if (nt <= 4) DS_TRM(4, 8, 4); else DS_TRM(6, 8, 4); }
+        else if (n == 12) {
+            // (pair table in LDS, one operand tile: 37.2 KB -- Y + the table -- and < 128 registers: four workgroups per CU)
+            const size_t tbytes = (size_t)n * 2 * n * 16 * sizeof(T) + 512;      // Y + the pair table (78 x 4 bytes)
+            hipLaunchKernelGGL((ds::k_det_trace_mfma<T, 2, 16, 4, 12>), grid, dim3(256), tbytes, st, DS_TR_ARGS, clk);
+        } else if (n == 24) DS_TRMF(3, 16, 8, 24);      // (compile-time n: see the kernel)
+        else if (nt == 1) DS_TRM(1, 16, 4); else if (nt == 2) DS_TRM(2, 16, 4); else if (nt == 3) DS_TRM(3, 16, 8); else if (nt == 4) DS_TRM(4, 16, 8);
+        else DS_TRM(6, 16, 4);
+#undef DS_TRM
+#undef DS_TRMF
+    } else if (n > 16 && n <= 64 && !s->det_valu) {
+        // any other size (odd n, or a slot tile of Y beyond the LDS): blocks of 16 electrons, two blocks of Y at a time
+        const size_t bbytes = (size_t)2 * 16 * 32 * 16 * sizeof(T) + (size_t)(S.P + 256) * sizeof(ds::Cx<T>);
+#define DS_TRB(KSMV) hipLaunchKernelGGL((ds::k_det_trace_blocked<T, KSMV>), grid, dim3(256), bbytes, st, DS_TR_ARGS)
+        if (n <= 48) DS_TRB(24); else if (n <= 56) DS_TRB(28); else DS_TRB(32);
+#undef DS_TRB
+    } else {
+        // VALU kernel
+#define DS_TRACE(NMAX, SP)                                                                                                    \
+    do {                                                                                                                      \
+        const int rp = ((n * SP + 63) / 64 * 64) / SP;            /* rows per pass: whole waves, >= n when it fits */        \
+        const int nthr = std::min(256, rp * SP);                                                                               \
+        const size_t sh = ((size_t)n * n + (size_t)SP * (n * n + 1) + nthr) * sizeof(ds::Cx<T>);                               \
+        hipLaunchKernelGGL((ds::k_det_trace<T, NMAX, SP>), grid, dim3(nthr), sh, st, DS_TR_ARGS);                              \
+    } while (0)
+        if (n <= 16) DS_TRACE(16, 16);
+        else if (n <= 32) DS_TRACE(32, 8);
+        else if (n <= 64) DS_TRACE(64, 2);      // LDS: (1 + SP) n^2 complex must stay below 160 KiB
+        else return fail("n_s = %d > 64 electrons per spin is not supported", n);
+#undef DS_TRACE
+    }
+#undef DS_TR_ARGS
+    return 0;
+}
+
+// The forward-Laplacian chain on a chunk of Bc walkers: executes plan_chain's plan.
 template <typename T>
 int run_chain(ds_system* s, const T* params, const T* x, int64_t Bc, void* ws, hipStream_t st, T* out_ke, T* out_logabs,
               T* out_phase, DumpReq<T>* dr, T* out_grad = nullptr) {
@@ -459,20 +652,12 @@ int run_chain(ds_system* s, const T* params, const T* x, int64_t Bc, void* ws, h
     Carve<T> c = carve<T>(s, ws, Bc);
     auto blk = [&](int i) { return params + s->blocks[i].offset; };
     const int stop = dr ? dr->stop : STOP_NONE;
-    // the kernels instantiated per jet-slot tile count (ds_tiles.h)
-    const ds::TileOps<T>* to = ds::tile_ops<T>(S.P / 16);
-    if (!to) return fail("no kernel instance for %d slot tiles (N = %d electrons)", S.P / 16, S.N);
-    const int NB = to->NB, ST = to->ST;
-    const bool wide = s->use_wide && to->gemm_wide != nullptr;      // wide slot ranges: 64-feature x 4/5-tile wave tiles in slot chunks (ds_wide.h)
-    // Low-rank first hidden layer (k_layer1_lr): layer 0 reads its input tiles from their own buffer XL (layer 1 needs them again
-    // while it overwrites G[0]) and does not write its dense output -- k_layer0_stats leaves (y, oL) per electron and the spin means
-    // of the output (the input of layer 1's shared term), layer 1 recomputes its residual rows from the layer-0 input.  Off for the
-    // stage dumps, which show the dense path's buffers.
+    ChainPlan<T> plan;
+    if (int rc = plan_chain<T>(s, dr != nullptr, &plan)) return rc;
+    const ds::TileOps<T>* to = plan.to;
+    const int NB = to->NB, ST = to->ST, lr_nc = plan.lr_nc;
+    const bool lr_on = plan.lr_on;
     const int K0loc = S.h1[0] + S.nch * S.h2[0], K0sh = S.nch * S.h1[0];
-    const int lr_nc = std::max(2, (K0loc + K0sh + 4 + 15) / 16);      // column tiles of the per-electron weights C (instances: 2, 3, 4)
-    // (worth it when the weights C cost fewer products than the rows they replace: Kh / 4 k-steps of NB x NC tiles against
-    //  (Kh - K0 - 4) / 4 k-steps of NB x ST -- not for the one- or two-tile cells, N <= 10)
-    const bool lr_on = !dr && lowrank_possible(s, ST);
     // 1. features
     {
         ProfScope ps(s, DS_PROF_FEATURES, st);
@@ -488,86 +673,58 @@ int run_chain(ds_system* s, const T* params, const T* x, int64_t Bc, void* ws, h
     if (stop == STOP_MEAN0) return copy_out(dr, c.MEAN[0], (size_t)S.nch * S.h1[0] * S.P * Bc, st);
     if (stop == STOP_H2_0) return copy_out(dr, c.H2[0], (size_t)S.h2[0] * 5 * S.NP * Bc, st);
     if (stop == STOP_Q) return copy_out(dr, c.Q, L.Q * Bc, st);
-    int gi = 0, hi = 0, mi = 0;       // current G / H2 / MEAN buffer
-    bool expanded = false;            // the pair-mean rows of the coming layer were written by the pair layer behind them (k_two_layer_expand)
+    int gi = 0, hi = 0;               // current G / H2 buffer
     for (int l = 0; l < S.n_layers; ++l) {
+        const LayerPlan& lp = plan.layer[l];
         const int Kh = S.h1[l], K2 = S.h2[l], Nout = S.h1[l + 1];
-        if (Nout % 64 || Nout > 1024) return fail("hidden_single must be a multiple of 64 and <= 1024 (got %d)", Nout);
-        // spin means of the pair stream -> rows [Kh, Kh + nch*K2) of the layer input
-        // the structurally zero slot tiles of the rows are left unwritten when the layer's kernel never uses them: the low-rank
-        // layer 1 and the float64 dense layers (every pair-mean k-step under the tile masks)
-        auto pm_skip_of = [&](int ll) {
-            if (dr || !s->use_pm_skip || ll < 1) return 0;
-            const int Kh_l = S.h1[ll], K2_l = S.h2[ll], Kloc_l = Kh_l + S.nch * K2_l;
-            // (the chunked kernels of ds_wide.h have no masks: what they take over keeps every slot)
-            const bool wide_lr = wide && (s->wide_all || (sizeof(T) == 8 && lr_nc <= 2)), wide_gemm = wide && (s->wide_all || sizeof(T) == 8);
-            if (lr_on && ll == 1) return wide_lr ? 0 : 1;
-            return (s->res1[ll] && Kloc_l % 16 == 0 && Kh_l % 16 == 0 && K2_l % 16 == 0 && !int8_layer(s, ll) && !wide_gemm && ds::pm_instance<T>(ST)) ? 1 : 0;
-        };
-        if (!expanded) {
+        // spin means of the pair stream -> rows [Kh, Kh + nch*K2) of the layer input, unless the pair layer behind them wrote them
+        if (!(l > 0 && plan.layer[l - 1].pair.expand)) {
             ProfScope ps(s, DS_PROF_M2_EXPAND, st);
             const bool xl = lr_on && l == 0;
             hipLaunchKernelGGL((ds::k_m2_expand<T>), dim3(S.N, (unsigned)Bc, m2_split<T>(K2, S.N)), dim3(256), (size_t)(K2 * 5 * S.N + S.nch * K2 * 5) / m2_split<T>(K2, S.N) * sizeof(T), st, S,
-                               c.H2[hi], K2, xl ? c.XL : c.G[gi], Kh, xl ? K0loc : S.ldk, pm_skip_of(l));
+                               c.H2[hi], K2, xl ? c.XL : c.G[gi], Kh, xl ? K0loc : S.ldk, lp.pm_unwritten ? 1 : 0);
         }
-        expanded = false;
         if (stop == STOP_G0 + l) return copy_out(dr, c.G[gi], L.G * Bc, st);
         // pair stream layer
         if (l < S.n_double) {
+            const PairPlan& pp = lp.pair;
             const int K2o = S.h2[l + 1];
-            if (K2o != 32 && K2o != 16) return fail("hidden_double must be 16 or 32 (got %d)", K2o);
-            if (K2 % 4) return fail("pair-stream width %d is not a multiple of 4", K2);
-            dim3 grid((S.NP / 16 + 3) / 4, (unsigned)Bc);
-            // (a first pair layer as wide as the pair features: its residual is added by k_pair_res_add behind the layer)
-            const bool res_sep = s->res2[l] && l == 0;
-            const bool res = s->res2[l] && !res_sep;
             const T* W2 = blk(s->i_w2[l]); const T* b2 = blk(s->i_b2[l]);
             ProfScope ps(s, DS_PROF_TWO_LAYER, st);
-            // the layer and the spin means of its output in one kernel (k_two_layer_expand: a workgroup per electron) when the output jets
-            // of an electron's pairs fit the LDS: the next level's rows land in the buffer the one-electron layer below writes its output to
-            const unsigned xz = (!res && K2o == 32) ? 2 : 1;       // feature splits (a residual layer keeps its operands: all features in one workgroup)
-            // (the output itself has a reader only if another pair layer or the orbital head's pair means follow)
-            T* Hnext = (l + 1 < S.n_double || s->use_last) ? c.H2[hi ^ 1] : nullptr;
-            // electrons per workgroup: two where the output is written and a single electron's pairs would end in the middle of a 128-byte line
-            const int EW = (Hnext && S.N % 16 == 8 && xz == 2) ? 2 : 1, NW = (EW * S.N + 15) / 16;
-            const size_t xlds = ((size_t)(K2o / xz) * 5 * EW * S.N + (size_t)EW * S.nch * (K2o / xz) * 5) * sizeof(T);
-            if (!dr && s->use_pair_expand && !res_sep && l + 1 < S.n_layers && NW <= 8 && xlds <= 150 * 1024) {
-#define DS_TWOX(NT2, RES) hipLaunchKernelGGL((ds::k_two_layer_expand<T, NT2, RES>), dim3(S.N / EW, (unsigned)Bc, xz), dim3(64 * NW), xlds, st, S, c.H2[hi], K2, W2, b2, Hnext, \
-                                             c.G[gi ^ 1], S.h1[l + 1], S.ldk, pm_skip_of(l + 1), EW)
-                if (K2o == 32 && res) DS_TWOX(2, true);
-                else if (res) DS_TWOX(1, true);
+            if (pp.expand) {
+                // (the rows of level l + 1 land in the buffer the one-electron layer below writes its output to)
+#define DS_TWOX(NT2, RES) hipLaunchKernelGGL((ds::k_two_layer_expand<T, NT2, RES>), dim3(S.N / pp.EW, (unsigned)Bc, pp.xz), dim3(64 * pp.NW), pp.xlds, st, S, c.H2[hi], K2, W2, b2, \
+                                             pp.write_out ? c.H2[hi ^ 1] : (T*)nullptr, c.G[gi ^ 1], S.h1[l + 1], S.ldk, plan.layer[l + 1].pm_unwritten ? 1 : 0, pp.EW)
+                if (K2o == 32 && pp.res) DS_TWOX(2, true);
+                else if (pp.res) DS_TWOX(1, true);
                 else DS_TWOX(1, false);
 #undef DS_TWOX
-                expanded = true;
             } else {
+                const dim3 grid((S.NP / 16 + 3) / 4, (unsigned)Bc);
 #define DS_TWO(NT2, RES) hipLaunchKernelGGL((ds::k_two_layer<T, NT2, RES, false>), grid, dim3(256), 0, st, S, c.H2[hi], K2, W2, b2, c.H2[hi ^ 1])
-            if (K2o == 32) { if (res) DS_TWO(2, true); else DS_TWO(2, false); }
-            else { if (res) DS_TWO(1, true); else DS_TWO(1, false); }
+                if (K2o == 32) { if (pp.res) DS_TWO(2, true); else DS_TWO(2, false); }
+                else { if (pp.res) DS_TWO(1, true); else DS_TWO(1, false); }
 #undef DS_TWO
             }
-            if (res_sep)
+            if (pp.res_sep)
                 hipLaunchKernelGGL((ds::k_pair_res_add<T>), dim3((unsigned)(((size_t)K2o * 5 * S.NP + 255) / 256), (unsigned)Bc), dim3(256), 0, st, c.H2[hi], K2, c.H2[hi ^ 1], K2o,
                                    S.nf, S.NP);
         }
         // one-electron stream layer: GEMM over the N electron tiles + the shared spin-mean tile, then epilogue
-        const int hin = hi;                                // the layer reads the pair stream of its own level (hi flips below)
         const int Kloc = Kh + S.nch * K2, Ksh = S.nch * Kh;
-        const bool res = s->res1[l];
-        // a first layer as wide as its input features: the residual is added by k_layer_res_add behind the layer (see there)
-        const bool res_sep = res && l == 0 && (Kloc % 16 != 0 || S.nf * S.A != Nout);
-        if (res && !res_sep && Kloc % 16) return fail("residual layer with K = %d: the GEMM's operand ring needs K %% 16 == 0", Kloc);
         {
             dim3 block; unsigned gz;
             gemm_geom(Nout, NB, &block, &gz, ST);
             dim3 wblock; unsigned wgz;                     // geometry of the wide kernels (NB = 4, four waves)
             gemm_geom(Nout, 4, &wblock, &wgz, 6);
             const size_t gws = (size_t)S.N * S.ldk * S.P, gts = (size_t)S.ldk * S.P;
-            T* Sl = (lr_on && l == 1) ? c.ZB + (size_t)Bc * S.h1[1] * S.P : c.ZB;      // this layer's shared term
+            const bool lr1 = lp.kind == LayerKind::LowRank1;
+            T* Sl = lr1 ? c.ZB + (size_t)Bc * S.h1[1] * S.P : c.ZB;      // this layer's shared term
             {
                 // shared spin-mean term S (one tile per walker): layer 0 from the MEAN buffer of k_features,
                 // hidden layers straight from the electron rows of G (means formed on the fly)
                 ProfScope ps(s, DS_PROF_SHARED_TERM, st);
-                if (l == 0 || (lr_on && l == 1)) {
+                if (l == 0 || lr1) {
                     // a plain product on ready spin means: those of the input features (MEAN[0], k_features), or -- in front of the
                     // low-rank layer 1 -- those of the layer-0 output (MEAN[1], k_layer0_stats); S of layer 0 stays in front of S of layer 1
                     const ds::GemmArgs<T> ga{nullptr, 0, 0, nullptr, 0, l == 0 ? c.MEAN[0] : c.MEAN[1], (size_t)Ksh * S.P, blk(s->i_wsh[l]), Ksh, 0,
@@ -582,42 +739,43 @@ int run_chain(ds_system* s, const T* params, const T* x, int64_t Bc, void* ws, h
                                     blk(s->i_b[l]), 0);
                 }
             }
-            {
             // ... then the N electron tiles with the fused epilogue
-            ProfScope ps(s, l == 0 ? DS_PROF_SINGLE_FIRST : ((lr_on && l == 1) ? DS_PROF_SINGLE_LR : DS_PROF_SINGLE_HIDDEN), st);
+            ProfScope ps(s, lp.prof_kind, st);
             // layer input tiles: G[gi], or (layer 0 in front of the low-rank layer 1) the XL buffer
             const T* Xin = (lr_on && l == 0) ? c.XL : c.G[gi];
             const size_t xws = (lr_on && l == 0) ? (size_t)S.N * K0loc * S.P : gws, xts = (lr_on && l == 0) ? (size_t)K0loc * S.P : gts;
             const dim3 lgrid(S.N * gz, (unsigned)Bc, 1), wgrid(S.N * wgz, (unsigned)Bc, 1);
             auto layer_gemm = [&](int epi, const ds::GemmArgs<T>& g) {
-                if (!(wide && to->gemm_wide(epi, s->wide_all, wgrid, wblock, st, g))) to->gemm(epi, lgrid, block, st, g);
+                if (lp.wide) to->gemm_wide(epi, wgrid, wblock, st, g); else to->gemm(epi, lgrid, block, st, g);
             };
             ds::GemmArgs<T> ga{Xin, xws, xts, blk(s->i_wloc[l]), Kloc, nullptr, 0, nullptr, 0, S.N, c.G[gi ^ 1], gws, gts, Nout, S.P, c.ZB, blk(s->i_b[l]),
                                ds::OrbEpi<T>{}};
-            // layer 0 (EPI 1 / 9): own-feature rows, then the pair-mean rows per partner spin -- structurally zero slot tiles are skipped
-            if (l == 0 && s->use_pm_skip) { ga.oe.pm_k0 = S.h1[0] / 4; ga.oe.pm_ks = S.h2[0] / 4; ga.oe.pm_nup = S.n_up; ga.oe.pm_nch = S.nch; }
-            if (lr_on && l == 1) {
+            if (lp.pm_mask) { ga.oe.pm_k0 = Kh / 4; ga.oe.pm_ks = K2 / 4; ga.oe.pm_nup = S.n_up; ga.oe.pm_nch = S.nch; }
+            switch (lp.kind) {
+            case LayerKind::LowRank1: {
                 // first hidden layer on the low-rank form of the layer-0 output (ds_gemm.h: k_layer1_lr)
                 const ds::LrArgs<T> la{c.XL, (size_t)S.N * K0loc * S.P, (size_t)K0loc * S.P, c.MEAN[0], (size_t)K0sh * S.P, K0loc, K0sh,
                                        (const T*)s->lr_w0t, c.G[gi], gws, gts, blk(s->i_wloc[l]), Kh, S.nch * K2, c.G[gi ^ 1], gws, gts, Sl,
                                        Nout, S.P, S.N, c.YO, L.YO, blk(s->i_wloc[0]), c.ZB, s->dbg >> 8, S.n_up, S.nch};
-                if (!(wide && to->layer1_lr_wide(lr_nc, res, s->wide_all, wgrid, wblock, st, la))) to->layer1_lr(lr_nc, res, lgrid, block, st, la);
-            } else if (lr_on && l == 0) {
-                // layer 0 without its dense output: (y, oL) per electron + the spin means of the output (ds_gemm.h).  One kernel when
-                // a wave holds all slot tiles of 16 features (k_layer0_stats) ...
-                const bool one_kernel = to->layer0_stats &&
-                    to->layer0_stats(K0loc / 4, dim3(S.nch * (unsigned)((Nout + 63) / 64), (unsigned)Bc), st, S, c.XL, (size_t)S.N * K0loc * S.P,
-                                     (size_t)K0loc * S.P, blk(s->i_wloc[0]), c.ZB, Nout, S.P, c.YO, c.MEAN[1]);
-                if (!one_kernel) {
-                    // ... otherwise (y, oL) from the layer kernel with the output dropped (EPI 9), then the means per slot chunk (k_layer0_means)
-                    ga.Z = c.YO; ga.zws = L.YO; ga.zts = (size_t)2 * Nout;
-                    layer_gemm(9, ga);
-                    constexpr int STC = 5;
-                    const unsigned nfb = (unsigned)((Nout + 63) / 64), nck = (unsigned)((S.P / 16 + STC - 1) / STC);
-                    hipLaunchKernelGGL((ds::k_layer0_means<T, STC>), dim3(S.nch * nfb * nck, (unsigned)Bc), dim3(256), 0, st, S, c.XL,
-                                       (size_t)S.N * K0loc * S.P, (size_t)K0loc * S.P, blk(s->i_wloc[0]), K0loc, c.ZB, Nout, S.P, c.YO, c.MEAN[1]);
-                }
-            } else if (int8_layer(s, l)) {
+                if (lp.wide) to->layer1_lr_wide(lr_nc, s->res1[l], wgrid, wblock, st, la); else to->layer1_lr(lr_nc, s->res1[l], lgrid, block, st, la);
+                break;
+            }
+            case LayerKind::L0Stats:
+                // layer 0 without its dense output: (y, oL) per electron + the spin means of the output (ds_gemm.h), in one kernel
+                to->layer0_stats(K0loc / 4, dim3(S.nch * (unsigned)((Nout + 63) / 64), (unsigned)Bc), st, S, c.XL, (size_t)S.N * K0loc * S.P,
+                                 (size_t)K0loc * S.P, blk(s->i_wloc[0]), c.ZB, Nout, S.P, c.YO, c.MEAN[1]);
+                break;
+            case LayerKind::L0Epi9Means: {
+                // ... or (y, oL) from the layer kernel with the output dropped (EPI 9), then the means per slot chunk (k_layer0_means)
+                ga.Z = c.YO; ga.zws = L.YO; ga.zts = (size_t)2 * Nout;
+                layer_gemm(9, ga);
+                constexpr int STC = 5;
+                const unsigned nfb = (unsigned)((Nout + 63) / 64), nck = (unsigned)((S.P / 16 + STC - 1) / STC);
+                hipLaunchKernelGGL((ds::k_layer0_means<T, STC>), dim3(S.nch * nfb * nck, (unsigned)Bc), dim3(256), 0, st, S, c.XL,
+                                   (size_t)S.N * K0loc * S.P, (size_t)K0loc * S.P, blk(s->i_wloc[0]), K0loc, c.ZB, Nout, S.P, c.YO, c.MEAN[1]);
+                break;
+            }
+            case LayerKind::Int8: {
                 // dense residual layer of the 5-slot-tile float64 cells: the per-electron contraction as a 47-bit fixed-point split on the
                 // int8 matrix pipe (ds_i8.h); float64 in, float64 out, same shared term, same epilogue
                 uint8_t* wp; double* sw;
@@ -626,23 +784,19 @@ int run_chain(ds_system* s, const T* params, const T* x, int64_t Bc, void* ws, h
                 const dim3 igrid((unsigned)std::min<int64_t>(ntiles, s->n_cu));
                 hipLaunchKernelGGL((ds::i8::k_layer_i8<5, 2>), igrid, dim3(512), ds::i8::lds_bytes(), st, (const double*)c.G[gi], gts, (const uint4*)wp,
                                    (const double*)sw, (const double*)Sl, S.N, (double*)c.G[gi ^ 1], ntiles);
-            } else if (res && !res_sep) {
+                break;
+            }
+            case LayerKind::DenseRes:
                 ga.oe.dbg = s->dbg & 3;                 // (timing experiments: 1 = no epilogue, 2 = accumulators start at zero)
-                // pair-mean rows of a hidden layer: structurally zero slot tiles are skipped (whole rounds of four k-steps per partner spin)
-                if (l > 0 && s->use_pm_skip && Kh % 16 == 0 && K2 % 16 == 0) { ga.oe.pm_k0 = Kh / 4; ga.oe.pm_ks = K2 / 4; ga.oe.pm_nup = S.n_up; ga.oe.pm_nch = S.nch; }
-                // 73 .. 76 jets on five slot tiles (24 electrons): the last tile as three groups of four columns
-                if (s->use_g4) {
-                    const int used = S.D - 16 * (ST - 1);
-                    if (ST == 5 && used > 8 && used <= 12) ga.oe.g4 = 3;
-                    if (ST == 10 && used <= 4) ga.oe.g4 = 1;          // (48 electrons: two jets on the tenth tile)
-                }
+                ga.oe.g4 = plan.g4;
                 if (l > 0 && s->prof_on && (s->prof_only < 0 || s->prof_only == DS_PROF_SINGLE_HIDDEN)) { ga.oe.clk = s->clk_dev; ga.oe.dbg = s->dbg; }
                 layer_gemm(2, ga);
-            } else {
+                break;
+            case LayerKind::Dense:
                 layer_gemm(1, ga);
-                if (res_sep)
+                if (lp.res_sep)
                     hipLaunchKernelGGL((ds::k_layer_res_add<T>), dim3(S.N, (unsigned)Bc), dim3(256), 0, st, Xin, xws, xts, c.G[gi ^ 1], gws, gts, S.nf * S.A, Nout, S.P);
-            }
+                break;
             }
         }
         gi ^= 1;
@@ -662,120 +816,48 @@ int run_chain(ds_system* s, const T* params, const T* x, int64_t Bc, void* ws, h
     for (int sp = 0; sp < S.nch; ++sp) {
         const int ns = sp == 0 ? S.n_up : S.n_dn, i0 = sp == 0 ? 0 : S.n_up, OC = S.ocols[sp];
         const int Korb = Kl + (s->use_last ? S.nch * K2l : 0);
-        if (Korb % 16) return fail("orbital head with K = %d: the GEMM's operand ring needs K %% 16 == 0", Korb);
-        {
-            dim3 block; unsigned gz;
-            gemm_geom(OC, NB, &block, &gz, ST);
-            if (s->use_last) {
-                ProfScope ps(s, DS_PROF_SHARED_TERM, st);
-                to->shared_term(dim3(1, (unsigned)Bc, gz), block, 2 * 16 * S.P * sizeof(T), st, S, c.G[gi], blk(s->i_wsh_orb[sp]), Kl, c.ZB, OC, S.P,
-                                (const T*)nullptr, 0);
-            }
-            ProfScope ps(s, DS_PROF_ORBITAL, st);
-            const int ch = S.mat_ch[sp];
-            ds::OrbEpi<T> oe{c.Q, c.MOUT, L.MOUT, L.mout_off[ch], S.N, i0, S.nparam[sp], S.nparam_max, S.norb[sp], S.det_n[ch],
-                             S.row_off[sp], S.bias_orb ? blk(s->i_borb[sp]) : (const T*)nullptr, nullptr};
-            // the last slot tile as 4-column groups where at most 12 of its 16 columns are jets (instances: three groups on five tiles -- 24
-            // electrons, the 48-column waves --, one group on ten tiles -- 48 electrons; the launchers fall back to 16-column products)
-            if (s->use_g4) {
-                const int used = S.D - 16 * (ST - 1);
-                if (ST == 5 && used > 8 && used <= 12) oe.g4 = 3;
-                if (ST == 10 && used <= 4) oe.g4 = 1;
-            }
-            const ds::GemmArgs<T> ga{c.G[gi] + (size_t)i0 * S.ldk * S.P, (size_t)S.N * S.ldk * S.P, (size_t)S.ldk * S.P, blk(s->i_worb[sp]), Korb,
-                                     nullptr, 0, nullptr, 0, ns, nullptr, 0, 0, OC, S.P, s->use_last ? (const T*)c.ZB : (const T*)nullptr, nullptr, oe};
-            // 192 columns (n_s*K = 96) would give 3 waves of 64 columns per workgroup and leave SIMDs with a single wave;
-            // 48-column waves give 4 balanced waves (the MFMA pipe needs >= 2 waves per SIMD, profiles/r01_mfma_f64_probe.json)
-            if (to->gemm_orb3 && OC % 256 != 0 && OC % 192 == 0) {
-                dim3 b3; unsigned gz3;
-                gemm_geom(OC, 3, &b3, &gz3);
-                to->gemm_orb3(dim3(ns * gz3, (unsigned)Bc, 1), b3, st, ga);
-            } else {
-                dim3 wb; unsigned wz;
-                gemm_geom(OC, 4, &wb, &wz, 6);
-                if (wide && to->gemm_wide(5, s->wide_all, dim3(ns * wz, (unsigned)Bc, 1), wb, st, ga)) {
-                } else if (to->orbital_lb && s->use_ldsb && OC % 64 == 0 && ga.K % 16 == 0)    // float32 wide cells: jet rows staged in LDS (ds_ldsb.h)
-                    to->orbital_lb(dim3(ns * (unsigned)(OC / 64), (unsigned)Bc, 1), st, ga);
-                else
-                    to->gemm(5, dim3(ns * gz, (unsigned)Bc, 1), block, st, ga);
-            }
+        dim3 block; unsigned gz;
+        gemm_geom(OC, NB, &block, &gz, ST);
+        if (s->use_last) {
+            ProfScope ps(s, DS_PROF_SHARED_TERM, st);
+            to->shared_term(dim3(1, (unsigned)Bc, gz), block, 2 * 16 * S.P * sizeof(T), st, S, c.G[gi], blk(s->i_wsh_orb[sp]), Kl, c.ZB, OC, S.P,
+                            (const T*)nullptr, 0);
+        }
+        ProfScope ps(s, DS_PROF_ORBITAL, st);
+        const int ch = S.mat_ch[sp];
+        ds::OrbEpi<T> oe{c.Q, c.MOUT, L.MOUT, L.mout_off[ch], S.N, i0, S.nparam[sp], S.nparam_max, S.norb[sp], S.det_n[ch],
+                         S.row_off[sp], S.bias_orb ? blk(s->i_borb[sp]) : (const T*)nullptr, nullptr};
+        oe.g4 = plan.g4;      // (the launchers fall back to 16-column products where they have no such instance)
+        const ds::GemmArgs<T> ga{c.G[gi] + (size_t)i0 * S.ldk * S.P, (size_t)S.N * S.ldk * S.P, (size_t)S.ldk * S.P, blk(s->i_worb[sp]), Korb,
+                                 nullptr, 0, nullptr, 0, ns, nullptr, 0, 0, OC, S.P, s->use_last ? (const T*)c.ZB : (const T*)nullptr, nullptr, oe};
+        dim3 ob; unsigned oz;      // geometry of the 48-column waves / of the wide kernel
+        switch (plan.orb[sp]) {
+        case OrbKind::Orb3:
+            gemm_geom(OC, 3, &ob, &oz);
+            to->gemm_orb3(dim3(ns * oz, (unsigned)Bc, 1), ob, st, ga);
+            break;
+        case OrbKind::Wide:
+            gemm_geom(OC, 4, &ob, &oz, 6);
+            to->gemm_wide(5, dim3(ns * oz, (unsigned)Bc, 1), ob, st, ga);
+            break;
+        case OrbKind::Ldsb:
+            to->orbital_lb(dim3(ns * (unsigned)(OC / 64), (unsigned)Bc, 1), st, ga);
+            break;
+        case OrbKind::Gemm:
+            to->gemm(5, dim3(ns * gz, (unsigned)Bc, 1), block, st, ga);
+            break;
         }
     }
     if (stop == STOP_MOUT) return copy_out(dr, c.MOUT, L.MOUT * Bc, st);
-    // determinants
-    for (int sp = 0; sp < S.n_detch; ++sp) {          // sp = determinant channel from here on
-        const int n = S.det_n[sp];
-        size_t sh = (size_t)n * 2 * n * sizeof(ds::Cx<T>) + 16;
+    // determinants (ch = determinant channel)
+    for (int ch = 0; ch < S.n_detch; ++ch) {
         ProfScope ps(s, DS_PROF_DET_INVERSE, st);
-        // in-place Gauss-Jordan with one lane per matrix row where an instance exists (k_det_inv_wave; value = slot 0 of slot tile 0),
-        // else the LDS Gauss-Jordan kernel
-        if (s->no_lu_wave || !ds::launch_det_inv_wave<T>(n, dim3(S.K, (unsigned)Bc), st, S, c.MOUT, L.MOUT, L.mout_off[sp], sp, 16, c.MINV, L.MINV,
-                                                         L.minv_off[sp], c.DETS, L.DETS, L.dets_off[sp], S.P))
-        hipLaunchKernelGGL((ds::k_det_inverse<T>), dim3(S.K, (unsigned)Bc), dim3(64), sh, st, S, c.MOUT, L.MOUT, L.mout_off[sp], sp,
-                           c.MINV, L.MINV, L.minv_off[sp], c.DETS, L.DETS, L.dets_off[sp], S.P, 16, 1, 1);   // value = slot 0 of slot tile 0
+        launch_det_inverse<T>(s, S, c, ch, Bc, st);
     }
     if (stop == STOP_MINV) return copy_out(dr, c.MINV, L.MINV * Bc, st);
-    for (int sp = 0; sp < S.n_detch; ++sp) {
-        const int n = S.det_n[sp];
+    for (int ch = 0; ch < S.n_detch; ++ch) {
         ProfScope ps(s, DS_PROF_DET_TRACE, st);
-#define DS_TRACE(NMAX, SP)                                                                                                    \
-    do {                                                                                                                      \
-        const int rp = ((n * SP + 63) / 64 * 64) / SP;            /* rows per pass: whole waves, >= n when it fits */        \
-        const int nthr = std::min(256, rp * SP);                                                                               \
-        size_t sh = ((size_t)n * n + (size_t)SP * (n * n + 1) + nthr) * sizeof(ds::Cx<T>);                                            \
-        hipLaunchKernelGGL((ds::k_det_trace<T, NMAX, SP>), dim3(S.K, (unsigned)Bc), dim3(nthr), sh, st, S, c.MOUT, L.MOUT,     \
-                           L.mout_off[sp], sp, c.MINV, L.MINV, L.minv_off[sp], c.TR, L.TR, L.tr_off[sp], c.DETS, L.DETS,        \
-                           L.dets_off[sp]);                                                                                    \
-    } while (0)
-        // matrix-core version when the real expansion (2n) is a whole number of k-steps and a slot tile (or half of one) of Y fits LDS
-        const int nt = (2 * n + 15) / 16;
-        // (nt >= 3: 8-wave workgroups, one per CU at these sizes; their [512] reduction buffer is counted for all)
-        const size_t ybytes16 = (size_t)n * 2 * n * 16 * sizeof(T) + 512 * sizeof(ds::Cx<T>);
-        const size_t ybytes8 = (size_t)n * 2 * n * 8 * sizeof(T) + 512 * sizeof(ds::Cx<T>);
-        const bool sw8 = ybytes16 > 160 * 1024;
-        const size_t ybytes = sw8 ? ybytes8 : ybytes16;
-        if ((2 * n) % 4 == 0 && ybytes <= 160 * 1024 && nt <= 6 && !s->det_valu) {
-#define DS_TRMF(NTV, SWV, NWV, NF) hipLaunchKernelGGL((ds::k_det_trace_mfma<T, NTV, SWV, NWV, NF>), dim3(S.K, (unsigned)Bc), dim3(64 * NWV), ybytes, st, S, c.MOUT, L.MOUT,  \
-                                            L.mout_off[sp], sp, c.MINV, L.MINV, L.minv_off[sp], c.TR, L.TR, L.tr_off[sp], c.DETS, L.DETS,     \
-                                            L.dets_off[sp], (s->dbg & 32) ? s->clk_dev + 2 : (unsigned long long*)nullptr)
-#define DS_TRM(NTV, SWV, NWV) hipLaunchKernelGGL((ds::k_det_trace_mfma<T, NTV, SWV, NWV>), dim3(S.K, (unsigned)Bc), dim3(64 * NWV), ybytes, st, S, c.MOUT, L.MOUT,  \
-                                            L.mout_off[sp], sp, c.MINV, L.MINV, L.minv_off[sp], c.TR, L.TR, L.tr_off[sp], c.DETS, L.DETS,     \
-                                            L.dets_off[sp])
-            if (sw8 && (n == 32 || n == 48)) {
-                // row-split mode: half the rows of a full slot tile in LDS, nothing computed twice
-                // (4 waves: the A fragments + three operand sets need the 512-register budget; 8 waves with one set less
-                //  measured slower, 71.3 vs 68.7 ms per diamond step)
-                constexpr int NWS = 4;
-                const size_t sbytes = (size_t)(n / 2) * 2 * n * 16 * sizeof(T) + 512 * sizeof(ds::Cx<T>);
-#define DS_TRS(NTV) hipLaunchKernelGGL((ds::k_det_trace_mfma_split<T, NTV, NWS, (NTV <= 4 || sizeof(T) == 4 ? 2 : 1)>), dim3(S.K, (unsigned)Bc), dim3(64 * NWS), sbytes, st, S, c.MOUT, L.MOUT,  \
-                                       L.mout_off[sp], sp, c.MINV, L.MINV, L.minv_off[sp], c.TR, L.TR, L.tr_off[sp], c.DETS, L.DETS, L.dets_off[sp], \
-                                       (s->dbg & 32) ? s->clk_dev + 2 : (unsigned long long*)nullptr)
-                if (n == 32) DS_TRS(4); else DS_TRS(6);        // 2n = 16 NT exactly
-#undef DS_TRS
-            } else if (sw8) { if (nt <= 4) DS_TRM(4, 8, 4); else DS_TRM(6, 8, 4); }
-            else if (n == 12) {
-                // (pair table in LDS, one operand tile: 37.2 KB -- Y + the table -- and < 128 registers: four workgroups per CU)
-                const size_t tbytes = (size_t)n * 2 * n * 16 * sizeof(T) + 512;      // Y + the pair table (78 x 4 bytes)
-                hipLaunchKernelGGL((ds::k_det_trace_mfma<T, 2, 16, 4, 12>), dim3(S.K, (unsigned)Bc), dim3(256), tbytes, st, S, c.MOUT, L.MOUT, L.mout_off[sp], sp, c.MINV, L.MINV,
-                                   L.minv_off[sp], c.TR, L.TR, L.tr_off[sp], c.DETS, L.DETS, L.dets_off[sp], (s->dbg & 32) ? s->clk_dev + 2 : (unsigned long long*)nullptr);
-            } else if (n == 24) DS_TRMF(3, 16, 8, 24);      // (compile-time n: see the kernel)
-            else if (nt == 1) DS_TRM(1, 16, 4); else if (nt == 2) DS_TRM(2, 16, 4); else if (nt == 3) DS_TRM(3, 16, 8); else if (nt == 4) DS_TRM(4, 16, 8);
-            else DS_TRM(6, 16, 4);
-#undef DS_TRM
-#undef DS_TRMF
-        } else if (n > 16 && n <= 64 && !s->det_valu) {
-            // any other size (odd n, or a slot tile of Y beyond the LDS): blocks of 16 electrons, two blocks of Y at a time
-            const size_t bbytes = (size_t)2 * 16 * 32 * 16 * sizeof(T) + (size_t)(S.P + 256) * sizeof(ds::Cx<T>);
-#define DS_TRB(KSMV) hipLaunchKernelGGL((ds::k_det_trace_blocked<T, KSMV>), dim3(S.K, (unsigned)Bc), dim3(256), bbytes, st, S, c.MOUT, L.MOUT, L.mout_off[sp], sp, \
-                                        c.MINV, L.MINV, L.minv_off[sp], c.TR, L.TR, L.tr_off[sp], c.DETS, L.DETS, L.dets_off[sp])
-            if (n <= 48) DS_TRB(24); else if (n <= 56) DS_TRB(28); else DS_TRB(32);
-#undef DS_TRB
-        } else
-        if (n <= 16) DS_TRACE(16, 16);
-        else if (n <= 32) DS_TRACE(32, 8);
-        else if (n <= 64) DS_TRACE(64, 2);      // LDS: (1 + SP) n^2 complex must stay below 160 KiB
-        else return fail("n_s = %d > 64 electrons per spin is not supported", n);
-#undef DS_TRACE
+        if (int rc = launch_det_trace<T>(s, S, c, ch, Bc, st)) return rc;
     }
     if (stop == STOP_DETS) return copy_out(dr, c.DETS, L.DETS * Bc, st);
     if (stop == STOP_TR) return copy_out(dr, c.TR, L.TR * Bc, st);
@@ -895,7 +977,7 @@ int run_value_chain(ds_system* s, const T* params, const T* x, int64_t Bc, const
         }
         if (Nout % 64 || Nout > 1024) return fail("hidden_single must be a multiple of 64 and <= 1024 (got %d)", Nout);
         const int Kloc = Kh + S.nch * K2, Ksh = S.nch * Kh;
-        const bool res_sep = s->res1[l] && l == 0 && (Kloc % 16 != 0 || S.nf * S.A != Nout);      // (see run_chain)
+        const bool res_sep = s->res1[l] && l == 0 && (Kloc % 16 != 0 || S.nf * S.A != Nout);      // (see plan_chain)
         if (s->res1[l] && !res_sep && Kloc % 16) return fail("residual layer with K = %d: the GEMM's operand ring needs K %% 16 == 0", Kloc);
         dim3 block; unsigned gz;
         gemm_geom(Nout, 4, &block, &gz);
@@ -1655,9 +1737,11 @@ int ds_system_create(const ds_system_desc* ref_desc, ds_system** out) {
     s->use_wide = getenv("DS_NO_WIDE") == nullptr;
     s->wide_all = getenv("DS_WIDE_ALL") != nullptr;
     {
-        // digit planes of the int8 layers' weights: only for a handle some layer of which can run as an int8 split
-        bool need = false;
-        for (int l = 1; l < s->sd.n_layers; ++l) need = need || int8_layer(s, l) || int8_value_layer(s, l);
+        // digit planes of the int8 layers' weights: only for a handle some layer of which can run as an int8 split (the energy chain has
+        // the most such layers in a stage dump: no low-rank layer 1)
+        ChainPlan<double> plan;
+        bool need = plan_chain<double>(s, true, &plan) == 0 && plan.count(LayerKind::Int8, s->sd.n_layers) > 0;
+        for (int l = 1; l < s->sd.n_layers; ++l) need = need || int8_value_layer(s, l);
         if (need && hipMalloc(&s->i8_wp, (size_t)DS_MAX_LAYERS * (ds::i8::wp_bytes(64 * 5) + ds::i8::NOUT * sizeof(double))) != hipSuccess) {
             ds_system_destroy(s);
             return fail("hipMalloc of the int8 layer's weight planes failed");
@@ -1683,11 +1767,8 @@ int64_t ds_param_count(const ds_system* s) { return s ? s->nparams : -1; }
 
 int ds_int8_layers(const ds_system* s) {
     if (!s) return -1;
-    const ds::TileOps<double>* to = ds::tile_ops<double>(s->sd.P / 16);
-    const bool lr = to && lowrank_possible(s, to->ST);
-    int n = 0;
-    for (int l = 1; l < s->sd.n_layers; ++l) n += (int8_layer(s, l) && !(lr && l == 1)) ? 1 : 0;
-    return n;
+    ChainPlan<double> plan;
+    return plan_chain<double>(s, false, &plan) == 0 ? plan.count(LayerKind::Int8, s->sd.n_layers) : 0;
 }
 
 int ds_param_layout(const ds_system* s, ds_param_block* blocks, int max_blocks) {

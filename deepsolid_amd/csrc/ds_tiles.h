@@ -25,17 +25,15 @@ template <typename T> struct TileOps {
                         int Nout, int P, const T* bias, int bias_all_slots);
     // k_layer1_lr<T, NB, ST, nc, res> (nc = 2, 3, 4)
     void (*layer1_lr)(int nc, bool res, dim3 grid, dim3 block, hipStream_t st, const LrArgs<T>& a);
-    // k_layer0_stats<T, ST, nks> (ST <= 5, nks = 2, 3, 4): returns false when there is no such instance; or null
-    bool (*layer0_stats)(int nks, dim3 grid, hipStream_t st, const SysDev<T>& S, const T* XL, size_t xl_ws, size_t xl_ts, const T* W0,
+    // k_layer0_stats<T, ST, nks> where layer0_stats_instance(ST, nks); null for ST > 5
+    void (*layer0_stats)(int nks, dim3 grid, hipStream_t st, const SysDev<T>& S, const T* XL, size_t xl_ws, size_t xl_ts, const T* W0,
                          const T* S0, int Nout, int P, T* YO, T* MEAN1);
     // wide slot ranges (ST > 10; ds_wide.h): the same products with 64-feature x <= 5-tile wave tiles walking the slot range in chunks,
     // two waves per SIMD -- k_jet_gemm_wide<T, STC, epi> for epi = 1, 2, 5, 9 (grid / block for NB = 4: gemm_geom(Nout, 4, .., 5)) and
-    // k_layer1_lr_wide<T, STC, nc, res>; null for ST <= 10
-    // Both return false (nothing launched) when the chunked form is not the faster one for that kernel and element type -- measured:
-    // float64 all but the low-rank layer with three or more column tiles of C (its LDS block then leaves one workgroup per CU);
-    // float32 only layer 0 -- unless force is set (DS_WIDE_ALL=1: tests, A/B runs).
-    bool (*gemm_wide)(int epi, bool force, dim3 grid, dim3 block, hipStream_t st, const GemmArgs<T>& a);
-    bool (*layer1_lr_wide)(int nc, bool res, bool force, dim3 grid, dim3 block, hipStream_t st, const LrArgs<T>& a);
+    // k_layer1_lr_wide<T, STC, nc, res>; null for ST <= 10.  Whether the chunked form is the one to launch: gemm_wide_faster /
+    // lr_wide_faster below.
+    void (*gemm_wide)(int epi, dim3 grid, dim3 block, hipStream_t st, const GemmArgs<T>& a);
+    void (*layer1_lr_wide)(int nc, bool res, dim3 grid, dim3 block, hipStream_t st, const LrArgs<T>& a);
     // float32, ST > 10 (ds_ldsb.h): k_jet_gemm_lb<float, ST, 5, 4>, the orbital head with four 16-feature waves per workgroup and the
     // tile's jet rows staged in LDS; grid = (n_tiles x Nout / 64, walkers), block 256.  Null otherwise.
     void (*orbital_lb)(dim3 grid, hipStream_t st, const GemmArgs<T>& a);
@@ -43,6 +41,15 @@ template <typename T> struct TileOps {
 
 constexpr int DS_MAX_TILES = 25;
 constexpr int tile_nb(int st, int elem_bytes) { return st <= 5 ? 4 : (st <= 10 ? 2 : (elem_bytes == 4 ? 2 : 1)); }
+
+// Which instance the host code launches (ds_api.hip: plan_chain) -- the launchers above do not decide.
+// k_layer0_stats: a wave holds all slot tiles of 16 features (ST <= 5), nks = K0 / 4 k-steps unrolled
+constexpr bool layer0_stats_instance(int st, int nks) { return st <= 5 && nks >= 2 && nks <= 4; }
+// The chunked form of a layer / orbital GEMM (epi = 1, 2, 5, 9) and of the low-rank layer 1 is the faster one -- measured: float64 all
+// but the low-rank layer with three or more column tiles of C (its LDS block then leaves one workgroup per CU); float32 only layer 0
+// (epi 1 / 9).  DS_WIDE_ALL=1 (tests, A/B runs) takes the chunked form wherever it exists.
+template <typename T> constexpr bool gemm_wide_faster(int epi) { return sizeof(T) == 8 || epi == 1 || epi == 9; }
+template <typename T> constexpr bool lr_wide_faster(int nc) { return sizeof(T) == 8 && nc <= 2; }
 
 // the table entry of a slot-tile count, or null (ds_api.hip; the parts are defined in ds_tiles_inst.hip)
 template <typename T> const TileOps<T>* tile_ops(int st_tiles);

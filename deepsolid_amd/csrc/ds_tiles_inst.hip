@@ -104,46 +104,40 @@ template <typename T, int NB, int ST> struct TileImpl {
         else { if (res) DS_LR(4, true); else DS_LR(4, false); }
 #undef DS_LR
     }
-    static bool layer0_stats(int nks, dim3 grid, hipStream_t st, const SysDev<T>& S, const T* XL, size_t xl_ws, size_t xl_ts, const T* W0,
+    static void layer0_stats(int nks, dim3 grid, hipStream_t st, const SysDev<T>& S, const T* XL, size_t xl_ws, size_t xl_ts, const T* W0,
                              const T* S0, int Nout, int P, T* YO, T* MEAN1) {
         if constexpr (ST <= 5) {
 #define DS_L0S(NKSV) hipLaunchKernelGGL((k_layer0_stats<T, ST, NKSV>), grid, dim3(256), 0, st, S, XL, xl_ws, xl_ts, W0, S0, Nout, P, YO, MEAN1)
-            if (nks == 2) { DS_L0S(2); return true; }
-            if (nks == 3) { DS_L0S(3); return true; }
-            if (nks == 4) { DS_L0S(4); return true; }
+            if (nks == 2) DS_L0S(2);
+            else if (nks == 3) DS_L0S(3);
+            else if (nks == 4) DS_L0S(4);
 #undef DS_L0S
         }
-        return false;
     }
     // chunk width of the wide kernels: 5 slot tiles in float32 (7 for the orbital head), 4 in float64 (five spill there)
     static constexpr int STCW = sizeof(T) == 4 ? 5 : 4, STCO = sizeof(T) == 4 ? 7 : 4;
-    static bool gemm_wide(int epi, bool force, dim3 grid, dim3 block, hipStream_t st, const GemmArgs<T>& a) {
+    static void gemm_wide(int epi, dim3 grid, dim3 block, hipStream_t st, const GemmArgs<T>& a) {
         if constexpr (ST > 10) {
-            if (!force && sizeof(T) == 4 && epi != 1 && epi != 9) return false;
 #define DS_GW(STCV, E, LDS) hipLaunchKernelGGL((k_jet_gemm_wide<T, STCV, E>), grid, block, (LDS), st, a.X, a.xws, a.xts, a.W, a.K, a.n_tiles, a.Z, a.zws, a.zts, \
                                                a.Nout, a.P, a.Sb, a.oe)
             switch (epi) {
-                case 1: DS_GW(STCW, 1, 0); return true;
-                case 2: DS_GW(STCW, 2, (wide_stash_bytes<T, STCW>(block.x))); return true;
-                case 5: DS_GW(STCO, 5, 0); return true;
-                case 9: DS_GW(STCW, 9, 0); return true;
-                default: return false;
+                case 1: DS_GW(STCW, 1, 0); break;
+                case 2: DS_GW(STCW, 2, (wide_stash_bytes<T, STCW>(block.x))); break;
+                case 5: DS_GW(STCO, 5, 0); break;
+                case 9: DS_GW(STCW, 9, 0); break;
+                default: break;
             }
 #undef DS_GW
         }
-        return false;
     }
-    static bool layer1_lr_wide(int nc, bool res, bool force, dim3 grid, dim3 block, hipStream_t st, const LrArgs<T>& a) {
+    static void layer1_lr_wide(int nc, bool res, dim3 grid, dim3 block, hipStream_t st, const LrArgs<T>& a) {
         if constexpr (ST > 10) {
-            if (!force && (sizeof(T) == 4 || nc > 2)) return false;
 #define DS_LRW(NCV, RESV) hipLaunchKernelGGL((k_layer1_lr_wide<T, STCW, NCV, RESV>), grid, block, (lr_lds_bytes<T, 4, NCV>(block.x, a.Kh)), st, a)
             if (nc <= 2) { if (res) DS_LRW(2, true); else DS_LRW(2, false); }
             else if (nc == 3) { if (res) DS_LRW(3, true); else DS_LRW(3, false); }
             else { if (res) DS_LRW(4, true); else DS_LRW(4, false); }
 #undef DS_LRW
-            return true;
         }
-        return false;
     }
     static void orbital_lb(dim3 grid, hipStream_t st, const GemmArgs<T>& a) {
         if constexpr (ST > 10 && sizeof(T) == 4)
