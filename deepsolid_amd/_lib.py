@@ -52,6 +52,8 @@ SIGNATURES = {
     'ds_logpsi_grad': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     'ds_vjp_workspace_bytes': (C.c_int64, [_VP, C.c_int64]),
     'ds_logpsi_vjp': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    'ds_pretrain_workspace_bytes': (C.c_int64, [_VP, C.c_int64]),
+    'ds_pretrain_loss_vjp': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     'ds_orbitals': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP]),
     'ds_ewald': (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP]),
     'ds_local_energy': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),

@@ -880,6 +880,8 @@ template <typename T> struct ValBufs {
     T* PHI[2];              // orbital GEMM output per spin channel (the plain pass reuses ZB for both)
     T* SORB[2];             // use_last_layer: shared term of the orbital head
     T* MINV;                // optional inverses, laid out like MOUT (walker-interleaved)
+    bool keep;              // gradient passes: every layer's activations and the raw orbital products PHI stay in memory
+                            // (MOUT may then be null: the orbital matrices themselves are not formed, ds_pretrain_loss_vjp)
 };
 
 template <typename T>
@@ -933,7 +935,7 @@ int run_value_chain(ds_system* s, const T* params, const T* x, int64_t Bc, const
     // kernel instance, no residual on the first pair layer (its input has another width anyway) and the segment sums as the only
     // consumer of the pair stream.  The sums of layer l go to PARTM (l = 0) and into the second H2 buffer, which this path leaves
     // unused (a PARTM block is 3/16 of an H2 buffer).
-    bool fuse_pairs = fuse_means && !vb.MINV && s->use_pair_fuse && S.n_double >= 1 && S.n_double <= ds::PS_MAX_LAYERS && !s->res2[0] &&
+    bool fuse_pairs = fuse_means && !vb.keep && s->use_pair_fuse && S.n_double >= 1 && S.n_double <= ds::PS_MAX_LAYERS && !s->res2[0] &&
                       S.h2[0] % 4 == 0 && (S.h2[1] == 16 || S.h2[1] == 32) && (size_t)(S.n_double - 1) * L.PARTM <= L.H2;
     for (int l = 1; l < S.n_double; ++l) fuse_pairs = fuse_pairs && S.h2[l + 1] == S.h2[1];
     auto pm_of = [&](int l) -> T* { return (!fuse_pairs || l == 0) ? vb.PARTM : vb.H2l[1] + (size_t)(l - 1) * L.PARTM * ng; };
@@ -965,7 +967,7 @@ int run_value_chain(ds_system* s, const T* params, const T* x, int64_t Bc, const
             const T* W2 = blk(s->i_w2[l]); const T* b2 = blk(s->i_b2[l]);
             // the last pair layer's output is only needed as means unless the activations are kept (gradient pass) or the
             // orbital head / a later layer reads H2 again without a pair layer in between
-            T* Hnext = (fuse_means && !vb.MINV && l + 1 == S.n_double) ? (T*)nullptr : vb.H2l[l + 1];
+            T* Hnext = (fuse_means && !vb.keep && l + 1 == S.n_double) ? (T*)nullptr : vb.H2l[l + 1];
             T* pmv = fuse_means ? vb.PARTM : (T*)nullptr;
 #define DS_TWO(NT2, RES) hipLaunchKernelGGL((ds::k_two_layer<T, NT2, RES, true>), grid, dim3(256), 0, st, S, Hin, K2, W2, b2, Hnext, pmv)
             if (K2o == 32) { if (res) DS_TWO(2, true); else DS_TWO(2, false); }
@@ -1043,14 +1045,15 @@ int run_value_chain(ds_system* s, const T* params, const T* x, int64_t Bc, const
         if (s->use_last)
             hipLaunchKernelGGL((ds::k_shared_term<T, 4, 5>), dim3(1, (unsigned)ng, ogz), oblock, 2 * 16 * PV * sizeof(T), st, S, Gl,
                                blk(s->i_wsh_orb[sp]), Kl, Sorb, OC, PV, (const T*)nullptr, 0);
-        if (vb.MINV) {
+        if (vb.keep) {
             // gradient pass: the raw products PHI are kept (k_orbital_bwd reads them), the product with q is its own kernel
             hipLaunchKernelGGL((ds::k_jet_gemm<T, 4, 5, 0>), dim3(ns, (unsigned)ng, ogz), oblock, 0, st, Gl + (size_t)i0 * S.ldk * PV,
                                gws, gts, blk(s->i_worb[sp]), Korb, (const T*)nullptr, (size_t)0, (const T*)nullptr, 0, ns, vb.PHI[sp], (size_t)ns * OC * PV, (size_t)0,
                                OC, PV, (const T*)nullptr, (const T*)nullptr, ds::OrbEpi<T>{});
-            hipLaunchKernelGGL((ds::k_orbital_epilogue_val<T>), dim3(ns, (unsigned)ng), dim3(256), 0, st, S, vb.PHI[sp], (size_t)ns * OC * PV, Q, MOUT, sp,
-                               L.MOUT, L.mout_off[S.mat_ch[sp]], S.bias_orb ? blk(s->i_borb[sp]) : (const T*)nullptr,
-                               s->use_last ? (const T*)Sorb : (const T*)nullptr);
+            if (MOUT)
+                hipLaunchKernelGGL((ds::k_orbital_epilogue_val<T>), dim3(ns, (unsigned)ng), dim3(256), 0, st, S, vb.PHI[sp], (size_t)ns * OC * PV, Q, MOUT, sp,
+                                   L.MOUT, L.mout_off[S.mat_ch[sp]], S.bias_orb ? blk(s->i_borb[sp]) : (const T*)nullptr,
+                                   s->use_last ? (const T*)Sorb : (const T*)nullptr);
             continue;
         }
         // log psi only: the product with the envelope x phase factor q is the GEMM's epilogue (EPI 8): no PHI buffer, no second kernel
@@ -1241,22 +1244,63 @@ int grad_plan(const ds_system* s, GradPlan* gp) {
     return 0;
 }
 
+// A gradient pass has three parts, shared by its two entry points (ds_logpsi_vjp, ds_pretrain_loss_vjp):
+//   1. run_value_chain with every activation kept (buffers: carve_grad),
+//   2. a seed that fills PHIBAR / QBAR (seed_logdet: cotangent of log psi; seed_mse: residual of the orbital-matching loss),
+//   3. sweep_from_seed: PHIBAR / QBAR -> every parameter's partial sums -> grad.
+template <typename T> struct GradBufs {
+    ValBufs<T> vb;
+    T *MEANL, *MEANBAR, *MEANBAR2, *QBAR, *PB[2], *CW, *GBAR, *HB[2], *ZBAR, *SBAR, *H2BAR[2], *Z2BAR, *PART, *W2S;
+};
+
 template <typename T>
-int logpsi_vjp_impl(ds_system* s, const void* params_, const void* x_, int64_t B, const void* cot_, void* grad_, void* out_logabs,
-                    void* out_phase, void* ws, int64_t ws_bytes, hipStream_t st) {
+GradBufs<T> carve_grad(ds_system* s, const GradPlan& gp, T* p, int64_t ng) {
     const ds::SysDev<T>& S = dev<T>(s);
-    const int PV = ds::PV;
-    GradPlan gp;
-    if (int rc = grad_plan(s, &gp)) return rc;
-    const T* params = (const T*)params_;
-    const T* cot = (const T*)cot_;
-    T* grad = (T*)grad_;
-    const int64_t avail = ws_bytes / (int64_t)sizeof(T) - (int64_t)gp.wt_total;
-    const int64_t cg = avail / (int64_t)gp.per_group;
-    if (cg < 1) return fail("workspace too small for the parameter gradient: %lld bytes", (long long)ws_bytes);
+    const WsLayout& V = s->wsv;
+    const int PV = ds::PV, L = S.n_layers;
+    const size_t np = (size_t)s->nparams;
+    GradBufs<T> b{};
+    ValBufs<T>& vb = b.vb;
+    vb.keep = true;
+    for (int l = 0; l <= L; ++l) { vb.Gl[l] = p; p += V.G * ng; }
+    for (int l = 0; l <= S.n_double; ++l) { vb.H2l[l] = p; p += gp.h2 * ng; }
+    for (int l = S.n_double + 1; l <= L; ++l) vb.H2l[l] = vb.H2l[S.n_double];
+    vb.MEAN0 = p; p += V.MEAN * ng;
+    b.MEANL = p; p += V.MEAN * ng;
+    vb.MEANS = b.MEANL;                       // forward scratch; the reverse sweep refills it layer by layer
+    b.MEANBAR = p; p += V.MEAN * ng;
+    vb.ZB = p; p += V.ZB * ng;
+    vb.Q = p; p += V.Q * ng;
+    b.QBAR = p; p += V.Q * ng;
+    vb.MOUT = p; p += V.MOUT * ng;
+    vb.MINV = p; p += V.MOUT * ng;
+    vb.DETS = p; p += V.DETS * ng;
+    vb.PARTM = p; p += V.PARTM * ng;
+    for (int c = 0; c < S.nch; ++c) { vb.PHI[c] = p + gp.phi_off[c] * ng; vb.SORB[c] = nullptr; }
+    p += gp.phi_total * ng;
+    for (int c = 0; c < S.nch; ++c) b.PB[c] = p + gp.phi_off[c] * ng;
+    p += gp.phi_total * ng;
+    b.CW = p; p += (size_t)S.K * 2 * PV * ng;
+    b.GBAR = p; p += gp.gbar * ng;
+    b.HB[0] = p; p += gp.hb * ng; b.HB[1] = p; p += gp.hb * ng;
+    b.ZBAR = p; p += gp.hb * ng;
+    b.SBAR = p; p += gp.sbar * ng;
+    b.H2BAR[0] = p; p += gp.h2 * ng; b.H2BAR[1] = p; p += gp.h2 * ng;
+    b.Z2BAR = p; p += gp.h2 * ng;
+    b.PART = p; p += np * ng;
+    b.W2S = p; p += gp.w2s * ng;       // split partials of the pair-stream weight gradients
+    if (s->use_last) {
+        b.MEANBAR2 = p; p += V.MEAN * ng;
+        for (int c = 0; c < S.nch; ++c) { vb.SORB[c] = p; p += (size_t)S.ocols[c] * PV * ng; }
+    }
+    return b;
+}
+
+// transposed, zero-padded weights for the W * ZBAR products of the sweep, shared by all groups
+template <typename T>
+void grad_transposes(ds_system* s, const GradPlan& gp, const T* params, T* WT, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
     auto blk = [&](int i) { return params + s->blocks[i].offset; };
-    auto boff = [&](int i) { return (size_t)s->blocks[i].offset; };
-    T* WT = (T*)ws;
     const int L = S.n_layers, Kl = S.h1[L];
     auto transpose = [&](const T* W, int rows, int cols, T* out, int ldt) {
         const size_t n = (size_t)cols * ldt;
@@ -1271,58 +1315,73 @@ int logpsi_vjp_impl(ds_system* s, const void* params_, const void* x_, int64_t B
         transpose(blk(s->i_worb[c]), gp.korb, S.ocols[c], WT + gp.worbT[c], gp.korb_pad);
         if (s->use_last) transpose(blk(s->i_wsh_orb[c]), S.nch * Kl, S.ocols[c], WT + gp.wshorbT[c], S.nch * Kl);
     }
-    const size_t np = (size_t)s->nparams;
+}
+
+// Seed of the log-psi VJP: determinants -> orbital head.  `cot`: (Bc, 2) cotangents of this chunk's walkers
+template <typename T>
+int seed_logdet(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, const T* params, const T* cot, int64_t Bc, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
     const WsLayout& V = s->wsv;
-    int h1max = 0;
-    for (int l = 0; l <= L; ++l) h1max = std::max(h1max, S.h1[l]);
-    bool first = true;
-    for (int64_t b0 = 0; b0 < B; b0 += cg * PV) {
-        const int64_t Bc = std::min<int64_t>(cg * PV, B - b0), ng = (Bc + PV - 1) / PV;
-        const T* x = (const T*)x_ + b0 * 3 * S.N;
-        // ---- carve
-        T* p = WT + gp.wt_total;
-        ValBufs<T> vb{};
-        for (int l = 0; l <= L; ++l) { vb.Gl[l] = p; p += V.G * ng; }
-        for (int l = 0; l <= S.n_double; ++l) { vb.H2l[l] = p; p += gp.h2 * ng; }
-        for (int l = S.n_double + 1; l <= L; ++l) vb.H2l[l] = vb.H2l[S.n_double];
-        vb.MEAN0 = p; p += V.MEAN * ng;
-        T* MEANL = p; p += V.MEAN * ng;
-        vb.MEANS = MEANL;                         // forward scratch; the reverse sweep refills it layer by layer
-        T* MEANBAR = p; p += V.MEAN * ng;
-        vb.ZB = p; p += V.ZB * ng;
-        vb.Q = p; p += V.Q * ng;
-        T* QBAR = p; p += V.Q * ng;
-        vb.MOUT = p; p += V.MOUT * ng;
-        vb.MINV = p; p += V.MOUT * ng;
-        vb.DETS = p; p += V.DETS * ng;
-        vb.PARTM = p; p += V.PARTM * ng;
-        T* PB[2] = {nullptr, nullptr};
-        for (int c = 0; c < S.nch; ++c) { vb.PHI[c] = p + gp.phi_off[c] * ng; vb.SORB[c] = nullptr; }
-        p += gp.phi_total * ng;
-        for (int c = 0; c < S.nch; ++c) PB[c] = p + gp.phi_off[c] * ng;
-        p += gp.phi_total * ng;
-        T* CW = p; p += (size_t)S.K * 2 * PV * ng;
-        T* GBAR = p; p += gp.gbar * ng;
-        T* HB[2]; HB[0] = p; p += gp.hb * ng; HB[1] = p; p += gp.hb * ng;
-        T* ZBAR = p; p += gp.hb * ng;
-        T* SBAR = p; p += gp.sbar * ng;
-        T* H2BAR[2]; H2BAR[0] = p; p += gp.h2 * ng; H2BAR[1] = p; p += gp.h2 * ng;
-        T* Z2BAR = p; p += gp.h2 * ng;
-        T* PART = p; p += np * ng;
-        T* W2S = p; p += gp.w2s * ng;       // split partials of the pair-stream weight gradients
-        T* MEANBAR2 = nullptr;
-        if (s->use_last) {
-            MEANBAR2 = p; p += V.MEAN * ng;
-            for (int c = 0; c < S.nch; ++c) { vb.SORB[c] = p; p += (size_t)S.ocols[c] * PV * ng; }
-        }
-        // ---- forward with every activation kept
-        int rc = run_value_chain<T>(s, params, x, Bc, vb, st, out_logabs ? (T*)out_logabs + b0 : nullptr,
-                                    out_phase ? (T*)out_phase + 2 * b0 : nullptr);
-        if (rc) return rc;
+    const int PV = ds::PV;
+    const int64_t ng = (Bc + PV - 1) / PV;
+    const ValBufs<T>& vb = gb.vb;
+    auto blk = [&](int i) { return params + s->blocks[i].offset; };
+    hipLaunchKernelGGL((ds::k_det_weights<T>), dim3((unsigned)((ng * PV + 63) / 64)), dim3(64), 0, st, S, vb.DETS, s->ws.DETS,
+                       s->ws.dets_off[1], cot, (long)Bc, gb.CW);
+    for (int sp = 0; sp < S.nch; ++sp) {
+        const int ns = sp == 0 ? S.n_up : S.n_dn;
+        const size_t pgs = (size_t)ns * S.ocols[sp] * PV;
+        HIP_OK(hipMemsetAsync(gb.PB[sp], 0, pgs * ng * sizeof(T), st));
+        hipLaunchKernelGGL((ds::k_orbital_bwd<T>), dim3(ns, (unsigned)ng), dim3(256), 0, st, S, vb.PHI[sp], pgs, vb.Q, vb.MINV, V.MOUT,
+                           V.mout_off[S.mat_ch[sp]], gb.CW, sp, (long)Bc, S.bias_orb ? blk(s->i_borb[sp]) : (const T*)nullptr,
+                           s->use_last ? (const T*)vb.SORB[sp] : (const T*)nullptr, gb.PB[sp], gb.QBAR);
+    }
+    return 0;
+}
+
+// Seed of the orbital-matching loss (reference pretrain.py:70-94), ds_grad.h: k_orbital_bwd_mse.  `tgt[sp]`: this chunk's
+// walkers of the spin's target; `B_total`: walkers of the whole call (the mean runs over all of them); LPART: N * ng loss
+// partials, added to out_loss[0] (overwritten when `first`)
+template <typename T>
+int seed_mse(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, const T* params, const T* const tgt[2], int64_t Bc,
+             int64_t B_total, T* LPART, bool first, double* out_loss, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const int PV = ds::PV;
+    const int64_t ng = (Bc + PV - 1) / PV;
+    const ValBufs<T>& vb = gb.vb;
+    auto blk = [&](int i) { return params + s->blocks[i].offset; };
+    // the reference's list has one entry per active spin (mean over the entries), or the one dense matrix with full_det
+    const double c_s = 1.0 / (double)S.n_detch;
+    for (int sp = 0; sp < S.nch; ++sp) {
+        const int ns = sp == 0 ? S.n_up : S.n_dn, n = S.det_n[S.mat_ch[sp]];
+        const size_t pgs = (size_t)ns * S.ocols[sp] * PV;
+        const double w = c_s / ((double)B_total * S.K * n * n);
+        HIP_OK(hipMemsetAsync(gb.PB[sp], 0, pgs * ng * sizeof(T), st));
+        hipLaunchKernelGGL((ds::k_orbital_bwd_mse<T>), dim3(ns, (unsigned)ng), dim3(256), 0, st, S, vb.PHI[sp], pgs, vb.Q, tgt[sp], sp,
+                           (long)Bc, S.bias_orb ? blk(s->i_borb[sp]) : (const T*)nullptr,
+                           s->use_last ? (const T*)vb.SORB[sp] : (const T*)nullptr, (T)(2.0 * w), (T)w, gb.PB[sp], gb.QBAR, LPART);
+    }
+    hipLaunchKernelGGL((ds::k_loss_final<T>), dim3(1), dim3(256), 0, st, LPART, (long)(S.N * ng), first ? 0 : 1, out_loss);
+    return 0;
+}
+
+// PHIBAR / QBAR of a chunk -> parameter gradient: grad = (first ? 0 : grad) + this chunk's sums
+template <typename T>
+int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, const T* params, const T* WT, const T* x, int64_t Bc,
+                    bool first, T* grad, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const int PV = ds::PV;
+    const int64_t ng = (Bc + PV - 1) / PV;
+    const size_t np = (size_t)s->nparams;
+    const int L = S.n_layers, Kl = S.h1[L];
+    auto blk = [&](int i) { return params + s->blocks[i].offset; };
+    auto boff = [&](int i) { return (size_t)s->blocks[i].offset; };
+    const ValBufs<T>& vb = gb.vb;
+    T* const* PB = gb.PB; T* const* HB = gb.HB; T* const* H2BAR = gb.H2BAR;
+    T *MEANL = gb.MEANL, *MEANBAR = gb.MEANBAR, *MEANBAR2 = gb.MEANBAR2, *QBAR = gb.QBAR, *GBAR = gb.GBAR, *ZBAR = gb.ZBAR, *SBAR = gb.SBAR,
+      *Z2BAR = gb.Z2BAR, *PART = gb.PART, *W2S = gb.W2S;
+    {
         HIP_OK(hipMemsetAsync(PART, 0, np * ng * sizeof(T), st));
-        // ---- determinants -> orbital head
-        hipLaunchKernelGGL((ds::k_det_weights<T>), dim3((unsigned)((ng * PV + 63) / 64)), dim3(64), 0, st, S, vb.DETS, s->ws.DETS,
-                           s->ws.dets_off[1], cot + 2 * b0, (long)Bc, CW);
         const size_t gws = (size_t)S.N * S.ldk * PV, gts = (size_t)S.ldk * PV;
         auto outer = [&](const T* X, size_t xg, size_t xt, int ldx, const T* Z, size_t zg, size_t zt, int ldz, int nt, int J, int K,
                          int Nc, size_t off, int nsplit = 1) {
@@ -1337,10 +1396,6 @@ int logpsi_vjp_impl(ds_system* s, const void* params_, const void* x_, int64_t B
         for (int sp = 0; sp < S.nch; ++sp) {
             const int ns = sp == 0 ? S.n_up : S.n_dn, i0 = sp == 0 ? 0 : S.n_up, OC = S.ocols[sp];
             const size_t pgs = (size_t)ns * OC * PV;
-            HIP_OK(hipMemsetAsync(PB[sp], 0, pgs * ng * sizeof(T), st));
-            hipLaunchKernelGGL((ds::k_orbital_bwd<T>), dim3(ns, (unsigned)ng), dim3(256), 0, st, S, vb.PHI[sp], pgs, vb.Q, vb.MINV, V.MOUT,
-                               V.mout_off[S.mat_ch[sp]], CW, sp, (long)Bc, S.bias_orb ? blk(s->i_borb[sp]) : (const T*)nullptr,
-                               s->use_last ? (const T*)vb.SORB[sp] : (const T*)nullptr, PB[sp], QBAR);
             outer(vb.Gl[L] + (size_t)i0 * S.ldk * PV, gws, gts, PV, PB[sp], pgs, (size_t)OC * PV, PV, ns, PV, gp.korb, OC, boff(s->i_worb[sp]));
             if (S.bias_orb)
                 hipLaunchKernelGGL((ds::k_orb_bias_grad<T>), dim3(2 * S.nparam[sp], (unsigned)ng), dim3(256), 0, st, PB[sp], pgs, ns, OC,
@@ -1442,6 +1497,78 @@ int logpsi_vjp_impl(ds_system* s, const void* params_, const void* x_, int64_t B
         }
         hipLaunchKernelGGL((ds::k_reduce_partials<T>), dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, PART, np, (long)ng, (long)np,
                            first ? 0 : 1, grad);
+    }
+    return 0;
+}
+
+// workspace of a gradient pass: [transposed weights | cg groups of GradPlan::per_group] -> groups per chunk
+template <typename T>
+int grad_chunk_groups(const GradPlan& gp, int64_t ws_bytes, int64_t* cg) {
+    *cg = (ws_bytes / (int64_t)sizeof(T) - (int64_t)gp.wt_total) / (int64_t)gp.per_group;
+    if (*cg < 1) return fail("workspace too small for the parameter gradient: %lld bytes", (long long)ws_bytes);
+    return 0;
+}
+
+template <typename T>
+int logpsi_vjp_impl(ds_system* s, const void* params_, const void* x_, int64_t B, const void* cot_, void* grad_, void* out_logabs,
+                    void* out_phase, void* ws, int64_t ws_bytes, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const int PV = ds::PV;
+    GradPlan gp;
+    if (int rc = grad_plan(s, &gp)) return rc;
+    int64_t cg;
+    if (int rc = grad_chunk_groups<T>(gp, ws_bytes, &cg)) return rc;
+    const T* params = (const T*)params_;
+    T* WT = (T*)ws;
+    grad_transposes<T>(s, gp, params, WT, st);
+    bool first = true;
+    for (int64_t b0 = 0; b0 < B; b0 += cg * PV) {
+        const int64_t Bc = std::min<int64_t>(cg * PV, B - b0);
+        const T* x = (const T*)x_ + b0 * 3 * S.N;
+        const GradBufs<T> gb = carve_grad<T>(s, gp, WT + gp.wt_total, (Bc + PV - 1) / PV);
+        if (int rc = run_value_chain<T>(s, params, x, Bc, gb.vb, st, out_logabs ? (T*)out_logabs + b0 : nullptr,
+                                        out_phase ? (T*)out_phase + 2 * b0 : nullptr)) return rc;
+        if (int rc = seed_logdet<T>(s, gp, gb, params, (const T*)cot_ + 2 * b0, Bc, st)) return rc;
+        if (int rc = sweep_from_seed<T>(s, gp, gb, params, WT, x, Bc, first, (T*)grad_, st)) return rc;
+        first = false;
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// Loss and gradient of the orbital-matching pretraining (reference pretrain.py:70-94): the forward stops behind the orbital
+// head (no orbital matrices, LU, inverses or determinant weights), the seed is the residual against the target
+template <typename T>
+int pretrain_loss_vjp_impl(ds_system* s, const void* params_, const void* x_, int64_t B, const void* target_up, const void* target_dn,
+                           void* out_loss, void* grad_, void* ws, int64_t ws_bytes, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const int PV = ds::PV;
+    GradPlan gp;
+    if (int rc = grad_plan(s, &gp)) return rc;
+    int64_t cg;
+    if (int rc = grad_chunk_groups<T>(gp, ws_bytes, &cg)) return rc;
+    if (B > 0 && (!target_up || (S.n_dn > 0 && !target_dn))) return fail("ds_pretrain_loss_vjp: a target is needed for every spin with electrons");
+    if ((size_t)S.N > s->wsv.MOUT) return fail("ds_pretrain_loss_vjp: internal: no room for the loss partials");
+    if (B <= 0) {                                       // the empty batch: zero loss, zero gradient
+        HIP_OK(hipMemsetAsync(out_loss, 0, sizeof(double), st));
+        HIP_OK(hipMemsetAsync(grad_, 0, (size_t)s->nparams * sizeof(T), st));
+        return 0;
+    }
+    const T* params = (const T*)params_;
+    T* WT = (T*)ws;
+    grad_transposes<T>(s, gp, params, WT, st);
+    bool first = true;
+    for (int64_t b0 = 0; b0 < B; b0 += cg * PV) {
+        const int64_t Bc = std::min<int64_t>(cg * PV, B - b0);
+        const T* x = (const T*)x_ + b0 * 3 * S.N;
+        GradBufs<T> gb = carve_grad<T>(s, gp, WT + gp.wt_total, (Bc + PV - 1) / PV);
+        T* LPART = gb.vb.MINV;                          // the determinant buffers are idle in this pass
+        gb.vb.MOUT = nullptr; gb.vb.MINV = nullptr;
+        if (int rc = run_value_chain<T>(s, params, x, Bc, gb.vb, st, nullptr, nullptr)) return rc;
+        const T* tgt[2] = {(const T*)target_up + (size_t)b0 * S.n_up * S.n_up * 2,
+                           target_dn ? (const T*)target_dn + (size_t)b0 * S.n_dn * S.n_dn * 2 : nullptr};
+        if (int rc = seed_mse<T>(s, gp, gb, params, tgt, Bc, B, LPART, first, (double*)out_loss, st)) return rc;
+        if (int rc = sweep_from_seed<T>(s, gp, gb, params, WT, x, Bc, first, (T*)grad_, st)) return rc;
         first = false;
     }
     HIP_OK(hipGetLastError());
@@ -1850,6 +1977,17 @@ int ds_logpsi_vjp(ds_system* s, const void* params, const void* x, int64_t B, co
     }
     return s->dtype == 0 ? logpsi_vjp_impl<double>(s, params, x, B, cot, grad, out_logabs, out_phase, ws, ws_bytes, st)
                          : logpsi_vjp_impl<float>(s, params, x, B, cot, grad, out_logabs, out_phase, ws, ws_bytes, st);
+}
+
+int64_t ds_pretrain_workspace_bytes(const ds_system* s, int64_t B) { return ds_vjp_workspace_bytes(s, B); }
+
+int ds_pretrain_loss_vjp(ds_system* s, const void* params, const void* x, int64_t B, const void* target_up, const void* target_dn,
+                         void* out_loss, void* grad, void* ws, int64_t ws_bytes, void* stream) {
+    if (s) ++s->call_seq;
+    if (!s || !params || !out_loss || !grad || !ws || (B > 0 && !x)) return fail("null argument");
+    hipStream_t st = (hipStream_t)stream;
+    return s->dtype == 0 ? pretrain_loss_vjp_impl<double>(s, params, x, B, target_up, target_dn, out_loss, grad, ws, ws_bytes, st)
+                         : pretrain_loss_vjp_impl<float>(s, params, x, B, target_up, target_dn, out_loss, grad, ws, ws_bytes, st);
 }
 
 int ds_ewald(ds_system* s, const void* x, int64_t B, void* out, void* stream) {

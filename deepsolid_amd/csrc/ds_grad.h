@@ -104,6 +104,80 @@ __global__ void __launch_bounds__(256) k_orbital_bwd(SysDev<T> S, const T* __res
     }
 }
 
+// Second seed of the sweep: the orbital-matching loss of reference pretrain.py:70-94,
+//   L = sum_s (c_s / cnt_s) sum_{b,k,i,m} |M_s[b,k,i,m] - T_s[b,i,m]|^2,   M = (phi + shared term + bias) * q
+// recomputed here from the kept PHI / SORB / bias / Q exactly as k_orbital_bwd reads them.  With r = M - T the seed is
+// A = 2 (c_s / cnt_s) conj(r)  (dL = Re sum A dM), written as PHIBAR / QBAR in the layouts of k_orbital_bwd.
+//   TGT: this spin's target (walkers of the chunk, n_s, n_s, [re, im]) in the caller's layout; with full_det the orbital
+//        index runs over all N orbitals and the block-diagonal target is implied: outside the spin's own block T = 0.
+//        (A lane's walker stride in TGT is a whole matrix: the 2 n_s values of a row are fetched once per cache line and
+//         reused from the cache over the determinants; the kernel is a few per cent of the sweep's traffic.)
+//   LPART[group * N + electron] = lscale * sum |r|^2 of the workgroup, summed in a fixed order (strided per thread, then an
+//        LDS tree); k_loss_final adds the entries in index order: two calls give the same bits.
+// Walkers beyond the batch in the last group seed exact zeros and add nothing to the loss.  grid (n_s, groups), block 256
+template <typename T>
+__global__ void __launch_bounds__(256) k_orbital_bwd_mse(SysDev<T> S, const T* __restrict__ PHI, size_t phi_group_stride,
+                                                         const T* __restrict__ Q, const T* __restrict__ TGT, int sp, long Bc,
+                                                         const T* __restrict__ bias, const T* __restrict__ Sb, T scale, T lscale,
+                                                         T* __restrict__ PHIBAR, T* __restrict__ QBAR, T* __restrict__ LPART) {
+    __shared__ T red[256];
+    const int ii = blockIdx.x, g = blockIdx.y, N = S.N, OC = S.ocols[sp];
+    const int i0 = sp == 0 ? 0 : S.n_up, ns = sp == 0 ? S.n_up : S.n_dn, nparam = S.nparam[sp], i = i0 + ii;
+    const int norb = S.norb[sp], m0 = S.full_det ? i0 : 0;          // first orbital of the spin's own target block
+    const T* Pw = PHI + (size_t)g * phi_group_stride + (size_t)ii * OC * PV;
+    const T* Qw = Q + ((size_t)(g * N + i) * S.nparam_max) * 2 * PV;
+    T* Pb = PHIBAR + (size_t)g * phi_group_stride + (size_t)ii * OC * PV;
+    T* Qb = QBAR + ((size_t)(g * N + i) * S.nparam_max) * 2 * PV;
+    T loss = 0;
+    for (int idx = threadIdx.x; idx < nparam * PV; idx += blockDim.x) {
+        const int c = idx % PV, p = idx / PV;
+        const int cr = orb_col<T>(p, 0), ci = orb_col<T>(p, 1);
+        Cx<T> a(0, 0), qb(0, 0);
+        if ((long)g * PV + c < Bc) {
+            const int ml = p % norb - m0;
+            Cx<T> phi(Pw[(size_t)cr * PV + c], Pw[(size_t)ci * PV + c]);
+            if (Sb) { phi.re += Sb[((size_t)g * OC + cr) * PV + c]; phi.im += Sb[((size_t)g * OC + ci) * PV + c]; }   // use_last_layer
+            if (bias) { phi.re += bias[p]; phi.im += bias[nparam + p]; }
+            const Cx<T> q(Qw[(size_t)(p * 2) * PV + c], Qw[(size_t)(p * 2 + 1) * PV + c]);
+            Cx<T> r = phi * q;
+            if (ml >= 0 && ml < ns) {
+                const T* t = TGT + ((((size_t)g * PV + c) * ns + ii) * ns + ml) * 2;
+                r.re -= t[0]; r.im -= t[1];
+            }
+            loss += r.re * r.re + r.im * r.im;
+            const Cx<T> A(scale * r.re, -scale * r.im);
+            a = A * q;
+            qb = A * phi;
+        }
+        Pb[(size_t)cr * PV + c] = a.re;
+        Pb[(size_t)ci * PV + c] = -a.im;
+        Qb[(size_t)(p * 2) * PV + c] = qb.re;
+        Qb[(size_t)(p * 2 + 1) * PV + c] = qb.im;
+    }
+    red[threadIdx.x] = loss;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) LPART[(size_t)g * N + i] = lscale * red[0];
+}
+
+// out[0] = (accumulate ? out[0] : 0) + sum_j part[j], in float64 and in a fixed order (strided per thread, LDS tree).  One block of 256
+template <typename T>
+__global__ void __launch_bounds__(256) k_loss_final(const T* __restrict__ part, long n, int accumulate, double* __restrict__ out) {
+    __shared__ double red[256];
+    double v = 0;
+    for (long j = threadIdx.x; j < n; j += blockDim.x) v += (double)part[j];
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = (accumulate ? out[0] : 0.0) + red[0];
+}
+
 // Envelope parameters (network.py:335-364): q = e * exp(i k.x), e = sum_a pi[a,p] exp(-r_a),
 //   isotropic r = |sd sigma[a,p]|;  diagonal r = |(sigma[a,m,p] rel_m)_m|;  full r = |(sum_k sigma[k,m,a,p] rel_k)_m|
 //   d pi[a,p] = sum_{i,b} ge exp(-r),   d sigma = sum_{i,b} ge pi exp(-r) (-dr/dsigma),   ge = Re(QBAR * exp(i k.x)).

@@ -408,6 +408,46 @@ class DeviceSystem:
                                           ws.numel(), _stream()), 'ds_logpsi_vjp')
         return grad, la, torch.view_as_complex(ph)
 
+    def pretrain_loss_vjp(self, params, x, targets, max_bytes=None):
+        """Orbital-matching loss of pretrain.py:70-94 and its packed parameter gradient (`ds_pretrain_loss_vjp`).
+        `targets`: the reference's list, one complex (B, n_s, n_s) tensor [walker, electron, orbital] per spin with
+        electrons (what `hf.SCF.eval_orb_mat` returns, empty spins dropped); real (B, n_s, n_s, 2) is taken as well.  With
+        `full_det` the block-diagonal target is formed inside the kernel.  The means run over THIS call's walkers.
+        -> (loss: 0-d float64 device tensor, flat grad (param_count,)); `unpack_grad` gives the parameter tree."""
+        x = self._check_x(x)
+        B = x.shape[0]
+        sizes = [n for n in self.nelec if n > 0]        # (a spin-down-only cell runs mirrored: its one target is `up` here)
+        targets = list(targets)
+        if len(targets) != len(sizes):
+            raise ValueError(f'targets must hold one matrix per spin with electrons ({len(sizes)}), got {len(targets)}')
+        tg = []
+        for t, n in zip(targets, sizes):
+            if not isinstance(t, torch.Tensor):
+                t = torch.as_tensor(np.asarray(t))
+            if t.is_complex():
+                t = torch.view_as_real(t.resolve_conj())
+            if tuple(t.shape) != (B, n, n, 2):
+                raise ValueError(f'target must be ({B}, {n}, {n}) complex, got {tuple(t.shape)}')
+            tg.append(t.to(device=self.device, dtype=self.dtype).contiguous())
+        p = self.pack_params(params)
+        if B == 0:
+            return (torch.zeros((), dtype=torch.float64, device=self.device),
+                    torch.zeros(self.param_count, dtype=self.dtype, device=self.device))
+        need = int(self.lib.ds_pretrain_workspace_bytes(self.handle, int(B)))
+        if need < 0:
+            _lib.check(1, 'ds_pretrain_workspace_bytes')
+        if max_bytes is not None:
+            need = min(need, int(max_bytes))      # fewer walker groups per pass (the library chunks the batch)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._ws[:need]
+        loss = torch.empty(1, dtype=torch.float64, device=self.device)
+        grad = torch.empty(self.param_count, dtype=self.dtype, device=self.device)
+        _lib.check(self.lib.ds_pretrain_loss_vjp(self.handle, _ptr(p), _ptr(x), B, _ptr(tg[0]), _ptr(tg[1] if len(tg) > 1 else None),
+                                                 _ptr(loss), _ptr(grad), _ptr(ws), ws.numel(), _stream()), 'ds_pretrain_loss_vjp')
+        return loss[0], grad
+
     def _grad_index(self, params):
         """For every leaf of the parameter tree: positions of its entries in the packed buffer (the packing
         is a gather with zero padding, so its transpose is one index_select per leaf).  Found by packing a

@@ -162,6 +162,21 @@ int64_t ds_vjp_workspace_bytes(const ds_system* sys, int64_t B);
 int ds_logpsi_vjp(ds_system* sys, const void* params, const void* x, int64_t B, const void* cot, void* grad,
                   void* out_logabs, void* out_phase, void* ws, int64_t ws_bytes, void* stream);
 
+/* Orbital-matching pretraining (pretrain.py:70-94, make_pretrain_step's loss_fn and its jax.value_and_grad):
+ *   loss = mean over the spin channels with electrons of  mean_{b,k,i,m} |target_s[b,i,m] - M_s[b,k,i,m]|^2,
+ * M = the orbital matrices of ds_orbitals.  target_up (B, n_up, n_up, 2), target_dn (B, n_dn, n_dn, 2) in the layout of
+ * hf.SCF.eval_orb_mat, [walker, electron, orbital] complex as (Re, Im) pairs; target_dn is NULL when n_dn = 0.  With full_det
+ * the single dense target is blockdiag(target_up, target_dn) (pretrain.py:79-86); the zero blocks are implied, never passed.
+ * The means run over the B walkers of THIS call (per-device jnp.mean; the caller averages loss and gradient over ranks).
+ * out_loss (1,) float64 on the device for both dtypes (a float32 system sums |r|^2 per workgroup in float32; the per-workgroup
+ * partials are added in float64); grad (ds_param_count(),) packed like ds_logpsi_vjp's, overwritten,
+ * padding entries zero.  The batch is processed in chunks that fit ws; loss and gradient are summed in a fixed order (no
+ * atomics): two calls give the same bits.  The forward stops behind the orbital head: no determinant work is launched.
+ * Nothing is allocated or synchronised.  B = 0: zero loss, zero gradient.  Every network option of ds_system_desc is supported. */
+int64_t ds_pretrain_workspace_bytes(const ds_system* sys, int64_t B);
+int ds_pretrain_loss_vjp(ds_system* sys, const void* params, const void* x, int64_t B, const void* target_up,
+                         const void* target_dn, void* out_loss, void* grad, void* ws, int64_t ws_bytes, void* stream);
+
 /* network.eval_func method 'eval_mats' (network.py:601): out_up (B, n_det, n_up, n_up, 2),
  * out_dn (B, n_det, n_dn, n_dn, 2), complex as (Re, Im) pairs. */
 int ds_orbitals(ds_system* sys, const void* params, const void* x, int64_t B,
