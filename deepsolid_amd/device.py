@@ -205,7 +205,8 @@ class DeviceSystem:
         if self._ws is None or self._ws.numel() < need:
             self._ws = None
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+        # a cap holds even when an earlier, larger call left a bigger buffer behind: the library sizes its chunks by what it is given
+        return self._ws if max_bytes is None else self._ws[:need]
 
     def pack_params(self, params):
         """Reference parameter tree (network.py:135-186) -> the flat device buffer of
@@ -363,12 +364,13 @@ class DeviceSystem:
                                       _stream()), 'ds_logpsi')
         return la, ph
 
-    def logpsi_grad(self, params, x):
-        """-> (log|psi| (B,), grad (B, 3N) complex: Re = grad log|psi|, Im = grad arg psi)."""
+    def logpsi_grad(self, params, x, ws_bytes=None):
+        """-> (log|psi| (B,), grad (B, 3N) complex: Re = grad log|psi|, Im = grad arg psi).  `ws_bytes` caps the workspace: the
+        library then walks the batch in chunks, as `logpsi` and `local_energy` do."""
         x = self._check_x(x)
         B = x.shape[0]
         p = self.pack_params(params)
-        ws = self.workspace(B)
+        ws = self.workspace(B, ws_bytes)
         la = torch.empty(B, dtype=self.dtype, device=self.device)
         gr = torch.empty(B, 3 * self.n, 2, dtype=self.dtype, device=self.device)
         if B:

@@ -112,6 +112,74 @@ def test_philox_known_answers_and_moments():
     assert abs(u2.mean() - 0.5) < 0.01
 
 
+def test_numpy_philox_model_matches_library():
+    """The numpy model of the in-kernel noise (tests/sampler_helpers.py), which the GPU sampler tests replay chains with, against
+    `ds_philox_host` word for word: random and edge (seed, offset, step, index, stream) tuples, with bits above 2^32 in the index
+    and in offset + step, a sum that wraps past 2^64, and offsets whose two top bits are set (the kernel masks them off: they
+    would otherwise select another stream).  Then the maps from words to deviates on known words."""
+    import ctypes as C
+    from deepsolid_amd import _lib
+    import sampler_helpers as sh
+    lib = _lib.load()
+    rng = np.random.default_rng(2024)
+    r64 = lambda n: [int(v) for v in rng.integers(0, 2 ** 64, size=n, dtype=np.uint64)]
+    n = 300
+    seeds, offs, steps, idxs = r64(n), r64(n), [int(v) for v in rng.integers(0, 2 ** 20, size=n)], r64(n)
+    streams = [int(v) for v in rng.integers(0, 3, size=n)]
+    edges = [(0, 0, 0, 0, 0), (1, 2 ** 32 - 1, 1, 2 ** 32, 1), (2 ** 64 - 1, 2 ** 64 - 1, 2, 2 ** 64 - 1, 2),       # wraps to 1
+             (7, 3 << 62, 5, 70 * 96 + 3, 0), (7, (3 << 62) | (1 << 40), 2 ** 33, 2 ** 40 + 9, 2), (7, 1 << 62, 0, 5, 1),
+             (2 ** 63 + 11, 2 ** 32 - 2, 3, 2 ** 31, 2), (5, 7, 3, 11, 0), (5, 10, 0, 11, 0)]
+    for e in edges:
+        for lst, v in zip((seeds, offs, steps, idxs, streams), e):
+            lst.append(v)
+    assert any(i >> 32 for i in idxs) and any(((o + s) % 2 ** 64) >> 32 for o, s in zip(offs, steps)) and any(o >> 62 == 3 for o in offs)
+    got = sh.philox_block(seeds, offs, steps, idxs, np.asarray(streams))
+    out = (C.c_uint32 * 4)()
+    for j in range(len(seeds)):
+        lib.ds_philox_host(seeds[j], offs[j], steps[j], idxs[j], streams[j], out)
+        assert [int(v) for v in got[:, j]] == [int(v) for v in out], (j, seeds[j], offs[j], steps[j], idxs[j], streams[j])
+    # the top bits of the offset are dropped, they do not leak into the stream number
+    assert np.array_equal(sh.philox_block(7, 3 << 62, 5, 9, 0), sh.philox_block(7, 0, 5, 9, 0))
+    assert not np.array_equal(sh.philox_block(7, 0, 5, 9, 0), sh.philox_block(7, 0, 5, 9, 1))
+    # words -> uniforms: the 53 bits are a's low 32 bits shifted up by 21, xor b's high 21 bits
+    w = lambda v: np.asarray([v], dtype=np.uint64)
+    assert sh.u53_co(w(0), w(0))[0] == 0.0 and sh.u53_oc(w(0), w(0))[0] == 2.0 ** -53
+    assert sh.u53_co(w(2 ** 32 - 1), w(2 ** 32 - 1))[0] == 1.0 - 2.0 ** -53 and sh.u53_oc(w(2 ** 32 - 1), w(2 ** 32 - 1))[0] == 1.0
+    assert sh.u53_co(w(1), w(0))[0] == 2.0 ** -32 and sh.u53_co(w(0), w(1 << 11))[0] == 2.0 ** -53
+    assert sh.u53_co(w(0), w(2 ** 11 - 1))[0] == 0.0                    # b's low 11 bits are dropped
+    # noise(): shapes, the electron index walker * N + electron, streams 0 / 1 / 2 and the offset + step rule
+    B, N = 5, 3
+    nz, un = sh.noise(99, 4, 3, B, N)
+    assert nz.shape == (3, B, 3 * N) and un.shape == (3, B) and nz.dtype == np.float64
+    a = sh.philox_block(99, 4, 2, 4 * N + 1, 0)
+    b = sh.philox_block(99, 4, 2, 4 * N + 1, 1)
+    ra, rb = np.sqrt(-2 * np.log(sh.u53_oc(a[0], a[1]))), np.sqrt(-2 * np.log(sh.u53_oc(b[0], b[1])))
+    ta, tb = 2 * np.pi * sh.u53_co(a[2], a[3]), 2 * np.pi * sh.u53_co(b[2], b[3])
+    assert np.array_equal(nz[2, 4, 3:6], np.asarray([ra * np.cos(ta), ra * np.sin(ta), rb * np.cos(tb)]).reshape(3))
+    c = sh.philox_block(99, 4, 2, 4, 2)
+    assert un[2, 4] == sh.u53_co(c[0], c[1]) and 0 <= un.min() and un.max() < 1
+    nz2, un2 = sh.noise(99, 6, 1, B, N)
+    assert np.array_equal(nz2[0], nz[2]) and np.array_equal(un2[0], un[2])
+    n1, u1 = sh.noise(99, 4, 3, B, N, one_electron=True, first_electron=2)
+    assert n1.shape == (3, B, 3) and np.array_equal(u1, un)
+    for i in range(3):
+        e = (2 + i) % N
+        assert np.array_equal(n1[i], nz[i].reshape(B, N, 3)[:, e])
+    assert len(np.unique(nz)) == nz.size                                # no two electrons share a deviate
+    assert abs(nz.mean()) < 0.5 and 0.5 < nz.std() < 1.5
+
+
+def test_sampler_test_seeds_meet_the_oracle_conditions():
+    """The seeds and widths of the GPU sampler tests (sampler_helpers.CHAINS / SINGLE_MOVES), checked in the oracle alone: every
+    Metropolis decision is decidable (|ratio - log u| above the tolerance on lp), every test holds an acceptance and a rejection,
+    and a proposed electron crosses a cell face."""
+    import sampler_helpers as sh
+    for (name, kind), (seed, width, steps) in sh.CHAINS.items():
+        sh.assert_conditions(sh.chain_reference(name, kind, seed, width, sh.CHAIN_BATCH, steps)['cond3'])
+    for (name, f32, kind), (seed, width, B, i) in sh.SINGLE_MOVES.items():
+        sh.assert_conditions(sh.single_move_reference(name, kind, seed, width, B, i, f32)['cond3'])
+
+
 def test_shape_limits_are_rejected_at_create():
     """Every shape the kernels cannot run is refused by ds_system_create itself (check_arch runs before any device
     allocation, so this needs no GPU): a handle that was created never fails at its first launch.  The supported set is
