@@ -36,6 +36,12 @@ class ParamBlock(C.Structure):
     _fields_ = [('offset', C.c_int64), ('rows', C.c_int32), ('cols', C.c_int32)]
 
 
+class KfacBlock(C.Structure):
+    _fields_ = [('kind', C.c_int32), ('index', C.c_int32), ('n_param_blocks', C.c_int32), ('param_blocks', C.c_int32 * 3),
+                ('has_bias', C.c_int32), ('d_in', C.c_int32), ('d_out', C.c_int32), ('repeats', C.c_int32),
+                ('a_offset', C.c_int64), ('g_offset', C.c_int64)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/deepsolid_hip.h
 _VP = C.c_void_p
 SIGNATURES = {
@@ -54,6 +60,10 @@ SIGNATURES = {
     'ds_logpsi_vjp': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     'ds_pretrain_workspace_bytes': (C.c_int64, [_VP, C.c_int64]),
     'ds_pretrain_loss_vjp': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    'ds_kfac_block_count': (C.c_int, [_VP]),
+    'ds_kfac_layout': (C.c_int, [_VP, C.POINTER(KfacBlock), C.c_int]),
+    'ds_kfac_workspace_bytes': (C.c_int64, [_VP, C.c_int64]),
+    'ds_kfac_factors': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP]),
     'ds_orbitals': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP]),
     'ds_ewald': (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP]),
     'ds_local_energy': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),

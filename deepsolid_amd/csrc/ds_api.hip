@@ -14,6 +14,7 @@
 
 #include "../../include/deepsolid_hip.h"
 #include "ds_grad.h"
+#include "ds_kfac.h"
 #include "ds_tiles.h"
 #include "ds_mcmc.h"
 #include "ds_obs.h"
@@ -1365,10 +1366,136 @@ int seed_mse(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, const T* p
     return 0;
 }
 
+// ------------------------------------------------------------------ KFAC factor pass (ds_kfac.h), hooks of sweep_from_seed
+// One entry per `repeated_dense` block of the reference (network.py:430-446), in the order single[0..], double[0..], orbital[0..]
+struct KfacBlockPlan {
+    ds_kfac_block pub;               // what ds_kfac_layout reports
+    ds::KfacRows rows;               // reference rows against padded rows
+    int dout_pad, omap, nparam;      // rows of the cotangent in memory; orbital column packing (ds_gemm.h: orb_col)
+};
+struct KfacPlan {
+    std::vector<KfacBlockPlan> blocks;
+    int64_t total = 0;               // elements of `factors`
+    size_t p1 = 0, p2 = 0, p3 = 0, aux = 0, per_group = 0;   // per group of PV walkers: partials of P1 / P2 / G and the operand v
+    int nsplit2 = ds::PV / 5;        // pair layers: waves per 32 x 32 block (one per 5-walker tile, as their weight gradient)
+};
+
+int kfac_plan(const ds_system* s, KfacPlan* kp) {
+    const ds::SysDev<double>& S = s->sd;
+    const int L = S.n_layers, nf_in = S.nf * S.A;
+    auto add = [&](int kind, int index, ds::KfacRows R, int d_out, int dout_pad, int repeats, int omap, int nparam, int nsplit,
+                   std::initializer_list<int> pbs) {
+        KfacBlockPlan b{};
+        R.d_in = R.kh + R.nmean * R.kh + R.npm * R.k2 + R.bias;
+        b.rows = R; b.dout_pad = dout_pad; b.omap = omap; b.nparam = nparam;
+        b.pub.kind = kind; b.pub.index = index; b.pub.has_bias = R.bias; b.pub.d_in = R.d_in; b.pub.d_out = d_out; b.pub.repeats = repeats;
+        for (int i = 0; i < 3; ++i) b.pub.param_blocks[i] = -1;
+        for (int pb : pbs) if (pb >= 0) b.pub.param_blocks[b.pub.n_param_blocks++] = pb;
+        b.pub.a_offset = kp->total; kp->total += (int64_t)R.d_in * R.d_in;
+        b.pub.g_offset = kp->total; kp->total += (int64_t)d_out * d_out;
+        const size_t Kloc = (size_t)R.Kh + (size_t)R.npm * R.K2, K2t = Kloc + (size_t)R.nmean * R.Kh + 1;
+        kp->p1 = std::max(kp->p1, (size_t)nsplit * (Kloc + 1) * (Kloc + 1));
+        if (R.nmean) { kp->p2 = std::max(kp->p2, K2t * K2t); kp->aux = std::max(kp->aux, (K2t - 1) * ds::PV); }
+        kp->p3 = std::max(kp->p3, (size_t)nsplit * dout_pad * dout_pad);
+        kp->blocks.push_back(b);
+    };
+    for (int l = 0; l < L; ++l)
+        add(0, l, ds::KfacRows{l == 0 ? nf_in : s->ref_single[l - 1], S.h1[l], S.nch, l == 0 ? S.nf : s->ref_double[l - 1], S.h2[l], S.nch, 1, 0},
+            s->ref_single[l], S.h1[l + 1], S.N, 0, 0, 1, {s->i_wloc[l], s->i_wsh[l], s->i_b[l]});
+    for (int l = 0; l < S.n_double; ++l)
+        add(1, l, ds::KfacRows{l == 0 ? S.nf : s->ref_double[l - 1], S.h2[l], 0, 0, 0, 0, 1, 0}, s->ref_double[l], S.h2[l + 1], S.N * S.N, 0, 0,
+            kp->nsplit2, {s->i_w2[l], s->i_b2[l]});
+    for (int c = 0; c < S.nch; ++c) {
+        const int nm = s->use_last ? S.nch : 0;
+        add(2, c, ds::KfacRows{s->ref_single[L - 1], S.h1[L], nm, s->ref_double[L - 1], S.h2[L], nm, S.bias_orb ? 1 : 0, 0}, 2 * S.nparam[c],
+            S.ocols[c], c == 0 ? S.n_up : S.n_dn, 1, S.nparam[c], 1,
+            {s->i_worb[c], s->use_last ? s->i_wsh_orb[c] : -1, S.bias_orb ? s->i_borb[c] : -1});
+    }
+    auto r4 = [](size_t v) { return (v + 3) / 4 * 4; };       // (the operands are read as 4-element vectors)
+    kp->p1 = r4(kp->p1); kp->p2 = r4(kp->p2); kp->p3 = r4(kp->p3); kp->aux = r4(kp->aux);
+    kp->per_group = kp->p1 + kp->p2 + kp->p3 + kp->aux;
+    return 0;
+}
+
+template <typename T> struct KfacSink {
+    const KfacPlan* kp;
+    T *P1, *P2, *P3, *AUX;           // ng groups each
+    T* factors;
+    int64_t B_total;
+    bool first;
+};
+
+// K rows of one operand of k_syrk in its tile layout (ds_kfac.h): where the rows live and which columns count
+template <typename T> struct SyrkTiles {
+    const T* base = nullptr;
+    size_t group_stride = 0, tile_stride = 0;
+    int ld = 0, n_tiles = 0;         // row stride, tiles per group
+    int J = 0, JP = 0;               // columns of a tile, columns per walker of the tile
+    int qfix = -1, tw = 0;           // valid columns per walker (-1: the walkers inside the batch), walkers per tile step
+};
+
+// [tile = electron][row][PV]: one column per walker of the group
+template <typename T>
+SyrkTiles<T> walker_tiles(const T* base, size_t group_stride, size_t tile_stride, int n_tiles) {
+    SyrkTiles<T> t;
+    t.base = base; t.group_stride = group_stride; t.tile_stride = tile_stride; t.n_tiles = n_tiles;
+    t.ld = t.J = t.JP = ds::PV;
+    return t;
+}
+
+// [tile = 5-walker block][row][5][NP]: the pair axis of k_two_bwd, N^2 of its NP columns per walker are pairs
+template <typename T>
+SyrkTiles<T> pair_tiles(const T* base, int rows, int N, int NP) {
+    SyrkTiles<T> t;
+    t.J = t.ld = 5 * NP; t.JP = NP; t.qfix = N * N; t.tw = 5; t.n_tiles = ds::PV / 5;
+    t.base = base; t.tile_stride = (size_t)rows * t.J; t.group_stride = t.tile_stride * t.n_tiles;
+    return t;
+}
+
+// the operands of a block: X (input rows) and Z (cotangent of the output); Gaux is the G buffer the spin means and the sums
+// over the electrons e0 .. e0 + ne - 1 are taken from (one-electron layers, orbital head with use_last_layer), else null
+template <typename T> struct KfacOperands {
+    SyrkTiles<T> X, Z;
+    const T* Gaux = nullptr;
+    int e0 = 0, ne = 0;
+};
+
+template <typename T>
+void kfac_emit(ds_system* s, const KfacSink<T>& ks, const KfacBlockPlan& b, const KfacOperands<T>& o, int nsplit, int64_t Bc,
+               hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const int PV = ds::PV;
+    const int64_t ng = (Bc + PV - 1) / PV;
+    const ds::KfacRows& R = b.rows;
+    const int Kloc = R.Kh + R.npm * R.K2, K2t = Kloc + R.nmean * R.Kh + 1;
+    // part[group][split] = the upper blocks of x x^T over K rows of x (and a virtual row of ones)
+    auto syrk = [&](const SyrkTiles<T>& x, int K, bool ones, T* part, int nsp) {
+        const int Kt = K + (ones ? 1 : 0), nb = (Kt + 31) / 32, nblk = nb * (nb + 1) / 2 * nsp;
+        hipLaunchKernelGGL((ds::k_syrk<T>), dim3((unsigned)((nblk + 3) / 4), (unsigned)ng), dim3(256), 0, st, x.base, x.group_stride,
+                           x.tile_stride, x.ld, x.n_tiles, x.J, K, ones ? 1 : 0, x.JP, x.qfix, x.tw, (long)Bc, part, (size_t)Kt * Kt, nsp);
+    };
+    syrk(o.X, Kloc, true, ks.P1, nsplit);
+    if (R.nmean) {
+        const int rows = K2t - 1;
+        hipLaunchKernelGGL((ds::k_kfac_aux<T>), dim3((unsigned)((rows * PV + 255) / 256), (unsigned)ng), dim3(256), 0, st, S, o.Gaux, Kloc, R.Kh,
+                           R.nmean, o.e0, o.ne, (long)Bc, ks.AUX);
+        syrk(walker_tiles<T>(ks.AUX, (size_t)rows * PV, 0, 1), rows, true, ks.P2, 1);
+    }
+    syrk(o.Z, b.dout_pad, false, ks.P3, nsplit);
+    const T scale = (T)(1.0 / ((double)ks.B_total * b.pub.repeats));
+    const long na = (long)R.d_in * R.d_in, ngo = (long)b.pub.d_out * b.pub.d_out;
+    hipLaunchKernelGGL((ds::k_kfac_assemble<T>), dim3((unsigned)((na + 255) / 256)), dim3(256), 0, st, R, (const T*)ks.P1, (long)(ng * nsplit),
+                       (const T*)ks.P2, (long)ng, (T)b.pub.repeats, scale, ks.first ? 1 : 0, ks.factors + b.pub.a_offset);
+    hipLaunchKernelGGL((ds::k_kfac_assemble_g<T>), dim3((unsigned)((ngo + 255) / 256)), dim3(256), 0, st, b.pub.d_out, b.dout_pad, b.omap,
+                       b.nparam, (const T*)ks.P3, (long)(ng * nsplit), scale, ks.first ? 1 : 0, ks.factors + b.pub.g_offset);
+}
+
 // PHIBAR / QBAR of a chunk -> parameter gradient: grad = (first ? 0 : grad) + this chunk's sums
 template <typename T>
 int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, const T* params, const T* WT, const T* x, int64_t Bc,
-                    bool first, T* grad, hipStream_t st) {
+                    bool first, T* grad, hipStream_t st, const KfacSink<T>* ks = nullptr) {
+    // ks: the KFAC factor pass (ds_kfac_factors) -- every tagged layer's A and G from the operands of its weight gradient;
+    // grad may then be null (no packed gradient wanted)
     const ds::SysDev<T>& S = dev<T>(s);
     const int PV = ds::PV;
     const int64_t ng = (Bc + PV - 1) / PV;
@@ -1397,6 +1524,13 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
             const int ns = sp == 0 ? S.n_up : S.n_dn, i0 = sp == 0 ? 0 : S.n_up, OC = S.ocols[sp];
             const size_t pgs = (size_t)ns * OC * PV;
             outer(vb.Gl[L] + (size_t)i0 * S.ldk * PV, gws, gts, PV, PB[sp], pgs, (size_t)OC * PV, PV, ns, PV, gp.korb, OC, boff(s->i_worb[sp]));
+            if (ks) {
+                KfacOperands<T> o;
+                o.X = walker_tiles<T>(vb.Gl[L] + (size_t)i0 * S.ldk * PV, gws, gts, ns);
+                o.Z = walker_tiles<T>(PB[sp], pgs, (size_t)OC * PV, ns);
+                o.Gaux = vb.Gl[L]; o.e0 = i0; o.ne = ns;
+                kfac_emit<T>(s, *ks, ks->kp->blocks[L + S.n_double + sp], o, 1, Bc, st);
+            }
             if (S.bias_orb)
                 hipLaunchKernelGGL((ds::k_orb_bias_grad<T>), dim3(2 * S.nparam[sp], (unsigned)ng), dim3(256), 0, st, PB[sp], pgs, ns, OC,
                                    S.nparam[sp], PART + boff(s->i_borb[sp]), np);
@@ -1442,6 +1576,13 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
                 hipLaunchKernelGGL((ds::k_layer_bwd_prep<T, false>), dim3(Nout / 4, (unsigned)ng), dim3(4 * PV), 0, st, S, D1, ld1, MB, MB2, CARRY,
                                    vb.Gl[l + 1], vb.Gl[l], Nout, HBc, ZBAR, SBAR, PART + boff(s->i_b[l]), np);
             outer(vb.Gl[l], gws, gts, PV, ZBAR, (size_t)S.N * Nout * PV, (size_t)Nout * PV, PV, S.N, PV, Kloc, Nout, boff(s->i_wloc[l]));
+            if (ks) {
+                KfacOperands<T> o;
+                o.X = walker_tiles<T>(vb.Gl[l], gws, gts, S.N);
+                o.Z = walker_tiles<T>(ZBAR, (size_t)S.N * Nout * PV, (size_t)Nout * PV, S.N);
+                o.Gaux = vb.Gl[l]; o.e0 = 0; o.ne = S.N;
+                kfac_emit<T>(s, *ks, ks->kp->blocks[l], o, 1, Bc, st);
+            }
             const T* MEANl = vb.MEAN0;
             if (l > 0) {
                 hipLaunchKernelGGL((ds::k_spin_mean<T>), dim3((unsigned)((S.nch * Kh * PV + 255) / 256), (unsigned)ng), dim3(256), 0, st, S,
@@ -1488,6 +1629,12 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
                 const int J = 5 * S.NP;
                 outer(vb.H2l[l], (size_t)(PV / 5) * K2 * J, (size_t)K2 * J, J, Z2BAR, (size_t)(PV / 5) * K2o * J, (size_t)K2o * J, J, PV / 5,
                       J, K2, K2o, boff(s->i_w2[l]), PV / 5);
+                if (ks) {
+                    KfacOperands<T> o;
+                    o.X = pair_tiles<T>(vb.H2l[l], K2, S.N, S.NP);
+                    o.Z = pair_tiles<T>(Z2BAR, K2o, S.N, S.NP);
+                    kfac_emit<T>(s, *ks, ks->kp->blocks[L + l], o, ks->kp->nsplit2, Bc, st);
+                }
                 hipLaunchKernelGGL((ds::k_row_sums<T>), dim3(K2o, (unsigned)ng), dim3(256), 0, st, Z2BAR, (size_t)(PV / 5) * K2o * J,
                                    (size_t)K2o * J, J, PV / 5, J, PART + boff(s->i_b2[l]), np);
                 h2i ^= 1;
@@ -1495,8 +1642,9 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
             D1 = GBAR; ld1 = Kpad; MB = MEANBAR; MB2 = nullptr; CARRY = res ? HBc : nullptr;
             hbi ^= 1;
         }
-        hipLaunchKernelGGL((ds::k_reduce_partials<T>), dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, PART, np, (long)ng, (long)np,
-                           first ? 0 : 1, grad);
+        if (grad)
+            hipLaunchKernelGGL((ds::k_reduce_partials<T>), dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, PART, np, (long)ng, (long)np,
+                               first ? 0 : 1, grad);
     }
     return 0;
 }
@@ -1530,6 +1678,46 @@ int logpsi_vjp_impl(ds_system* s, const void* params_, const void* x_, int64_t B
                                         out_phase ? (T*)out_phase + 2 * b0 : nullptr)) return rc;
         if (int rc = seed_logdet<T>(s, gp, gb, params, (const T*)cot_ + 2 * b0, Bc, st)) return rc;
         if (int rc = sweep_from_seed<T>(s, gp, gb, params, WT, x, Bc, first, (T*)grad_, st)) return rc;
+        first = false;
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// KFAC factor pass: the value chain, the seed (sqrt2, 0) on every walker, one reverse sweep.
+// workspace: [transposed weights | cg groups of (GradPlan::per_group + KfacPlan::per_group + 2 PV seed entries)]
+template <typename T>
+int kfac_factors_impl(ds_system* s, const void* params_, const void* x_, int64_t B, void* factors_, void* grad_, void* ws, int64_t ws_bytes,
+                      hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const int PV = ds::PV;
+    GradPlan gp;
+    if (int rc = grad_plan(s, &gp)) return rc;
+    KfacPlan kp;
+    if (int rc = kfac_plan(s, &kp)) return rc;
+    const int64_t per_group = (int64_t)gp.per_group + (int64_t)kp.per_group + 2 * PV;
+    const int64_t cg = (ws_bytes / (int64_t)sizeof(T) - (int64_t)gp.wt_total - 4) / per_group;     // (4: alignment of the partials)
+    if (cg < 1) return fail("workspace too small for the KFAC factor pass: %lld bytes", (long long)ws_bytes);
+    const T* params = (const T*)params_;
+    T* WT = (T*)ws;
+    grad_transposes<T>(s, gp, params, WT, st);
+    bool first = true;
+    for (int64_t b0 = 0; b0 < B; b0 += cg * PV) {
+        const int64_t Bc = std::min<int64_t>(cg * PV, B - b0), ng = (Bc + PV - 1) / PV;
+        const T* x = (const T*)x_ + b0 * 3 * S.N;
+        T* base = WT + gp.wt_total;
+        const GradBufs<T> gb = carve_grad<T>(s, gp, base, ng);
+        T* p = WT + (gp.wt_total + gp.per_group * ng + 3) / 4 * 4;       // k_syrk reads its operands as 4-element vectors
+        KfacSink<T> ks{&kp, nullptr, nullptr, nullptr, nullptr, (T*)factors_, B, first};
+        ks.P1 = p; p += kp.p1 * ng;
+        ks.P2 = p; p += kp.p2 * ng;
+        ks.P3 = p; p += kp.p3 * ng;
+        ks.AUX = p; p += kp.aux * ng;
+        T* cot = p;
+        hipLaunchKernelGGL((ds::k_kfac_seed<T>), dim3((unsigned)((Bc + 255) / 256)), dim3(256), 0, st, cot, (long)Bc);
+        if (int rc = run_value_chain<T>(s, params, x, Bc, gb.vb, st, nullptr, nullptr)) return rc;
+        if (int rc = seed_logdet<T>(s, gp, gb, params, cot, Bc, st)) return rc;
+        if (int rc = sweep_from_seed<T>(s, gp, gb, params, WT, x, Bc, first, (T*)grad_, st, &ks)) return rc;
         first = false;
     }
     HIP_OK(hipGetLastError());
@@ -1977,6 +2165,52 @@ int ds_logpsi_vjp(ds_system* s, const void* params, const void* x, int64_t B, co
     }
     return s->dtype == 0 ? logpsi_vjp_impl<double>(s, params, x, B, cot, grad, out_logabs, out_phase, ws, ws_bytes, st)
                          : logpsi_vjp_impl<float>(s, params, x, B, cot, grad, out_logabs, out_phase, ws, ws_bytes, st);
+}
+
+int ds_kfac_block_count(const ds_system* s) {
+    if (!s) return -1;
+    KfacPlan kp;
+    return kfac_plan(s, &kp) ? -1 : (int)kp.blocks.size();
+}
+
+int ds_kfac_layout(const ds_system* s, ds_kfac_block* blocks, int max_blocks) {
+    if (!s) return -1;
+    KfacPlan kp;
+    if (kfac_plan(s, &kp)) return -1;
+    const int n = (int)kp.blocks.size();
+    for (int i = 0; i < n && i < max_blocks; ++i) blocks[i] = kp.blocks[i].pub;
+    return n;
+}
+
+int64_t ds_kfac_workspace_bytes(const ds_system* s, int64_t B) {
+    if (!s) return -1;
+    GradPlan gp;
+    KfacPlan kp;
+    if (grad_plan(s, &gp) || kfac_plan(s, &kp)) return -1;
+    const int64_t esz = s->dtype == 0 ? 8 : 4;
+    const int64_t budget = (int64_t)32 << 30, per_group = (int64_t)gp.per_group + (int64_t)kp.per_group + 2 * ds::PV;
+    int64_t groups = std::min<int64_t>((std::max<int64_t>(B, 1) + ds::PV - 1) / ds::PV, 64);
+    groups = std::max<int64_t>(1, std::min<int64_t>(groups, budget / (per_group * esz)));
+    return ((int64_t)gp.wt_total + per_group * groups) * esz + 256;
+}
+
+int ds_kfac_factors(ds_system* s, const void* params, const void* x, int64_t B, void* factors, void* grad_seed, void* ws, int64_t ws_bytes,
+                    void* stream) {
+    if (s) ++s->call_seq;
+    if (!s || !params || !factors || (B > 0 && (!x || !ws))) return fail("null argument");      // (the empty batch needs no workspace)
+    if (s->sd.env_type == 2)
+        return fail("ds_kfac_factors: envelope_type 'full' is not supported (its sigma is the tagged block qmc1, network.py:358-362)");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t esz = s->dtype == 0 ? 8 : 4;
+    if (B <= 0) {                                       // the empty batch: zero factors, zero gradient
+        KfacPlan kp;
+        if (int rc = kfac_plan(s, &kp)) return rc;
+        HIP_OK(hipMemsetAsync(factors, 0, (size_t)kp.total * esz, st));
+        if (grad_seed) HIP_OK(hipMemsetAsync(grad_seed, 0, (size_t)s->nparams * esz, st));
+        return 0;
+    }
+    return s->dtype == 0 ? kfac_factors_impl<double>(s, params, x, B, factors, grad_seed, ws, ws_bytes, st)
+                         : kfac_factors_impl<float>(s, params, x, B, factors, grad_seed, ws, ws_bytes, st);
 }
 
 int64_t ds_pretrain_workspace_bytes(const ds_system* s, int64_t B) { return ds_vjp_workspace_bytes(s, B); }

@@ -450,6 +450,51 @@ class DeviceSystem:
                                                  _ptr(loss), _ptr(grad), _ptr(ws), ws.numel(), _stream()), 'ds_pretrain_loss_vjp')
         return loss[0], grad
 
+    def kfac_layout(self):
+        """The KFAC blocks of the network (`ds_kfac_layout`): one dict per `repeated_dense` layer of the reference, in the
+        order single[0..], double[0..], orbital[0..], with the keys kind ('single' | 'double' | 'orbital'), index,
+        param_blocks (indices into `self.blocks`), has_bias, d_in (bias row included), d_out, repeats, a_offset, g_offset."""
+        n = int(self.lib.ds_kfac_block_count(self.handle))
+        if n < 0:
+            _lib.check(1, 'ds_kfac_block_count')
+        raw = (_lib.KfacBlock * n)()
+        if int(self.lib.ds_kfac_layout(self.handle, raw, n)) != n:
+            _lib.check(1, 'ds_kfac_layout')
+        kinds = ('single', 'double', 'orbital')
+        return [dict(kind=kinds[b.kind], index=int(b.index), param_blocks=[int(v) for v in b.param_blocks[:b.n_param_blocks]],
+                     has_bias=bool(b.has_bias), d_in=int(b.d_in), d_out=int(b.d_out), repeats=int(b.repeats),
+                     a_offset=int(b.a_offset), g_offset=int(b.g_offset)) for b in raw]
+
+    def kfac_factors(self, params, x, want_grad=True, max_bytes=None):
+        """Kronecker factors of every tagged layer at walkers x (`ds_kfac_factors`): one value chain and one reverse sweep with
+        the seed sqrt2 on every walker.  -> (factors: [(A (d_in, d_in), G (d_out, d_out))] views in the order of `kfac_layout`,
+        already divided by B * repeats; grad_seed: packed gradient of sum_b sqrt2 log|psi_b|, or None without `want_grad`).
+        `max_bytes` caps the workspace (the library then walks the batch in chunks)."""
+        if self.net_kw.get('envelope_type') == 'full':
+            raise NotImplementedError("KFAC with envelope_type='full' is not supported: the reference tags its sigma as a "
+                                      "curvature block of its own (qmc1, network.py:358-362), which has no factor kernel here")
+        x = self._check_x(x)
+        B = x.shape[0]
+        p = self.pack_params(params)
+        layout = self.kfac_layout()
+        total = layout[-1]['g_offset'] + layout[-1]['d_out'] ** 2
+        need = int(self.lib.ds_kfac_workspace_bytes(self.handle, int(B)))
+        if need < 0:
+            _lib.check(1, 'ds_kfac_workspace_bytes')
+        if max_bytes is not None:
+            need = min(need, int(max_bytes))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._ws[:need]
+        flat = torch.empty(total, dtype=self.dtype, device=self.device)
+        grad = torch.empty(self.param_count, dtype=self.dtype, device=self.device) if want_grad else None
+        _lib.check(self.lib.ds_kfac_factors(self.handle, _ptr(p), _ptr(x), B, _ptr(flat), _ptr(grad), _ptr(ws), ws.numel(),
+                                            _stream()), 'ds_kfac_factors')
+        out = [(flat[b['a_offset']:b['a_offset'] + b['d_in'] ** 2].view(b['d_in'], b['d_in']),
+                flat[b['g_offset']:b['g_offset'] + b['d_out'] ** 2].view(b['d_out'], b['d_out'])) for b in layout]
+        return out, grad
+
     def _grad_index(self, params):
         """For every leaf of the parameter tree: positions of its entries in the packed buffer (the packing
         is a gather with zero padding, so its transpose is one index_select per leaf).  Found by packing a

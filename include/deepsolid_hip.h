@@ -177,6 +177,40 @@ int64_t ds_pretrain_workspace_bytes(const ds_system* sys, int64_t B);
 int ds_pretrain_loss_vjp(ds_system* sys, const void* params, const void* x, int64_t B, const void* target_up,
                          const void* target_dn, void* out_loss, void* grad, void* ws, int64_t ws_bytes, void* stream);
 
+/* KFAC factor pass: the curvature statistics of the reference's default optimizer (process.py:209-228,
+ * kfac_ferminet_alpha.Optimizer with estimation_mode = 'fisher_exact' on the normal predictive distribution train.py:133 registers).
+ * Every linear layer is a `repeated_dense` block (network.py:430-446; curvature_blocks.py:158-281).  With x the layer's input
+ * rows -- one per walker and repeat --, x~ = [x | 1] when the layer has a bias, and dy = sqrt2 * d log|psi_b| / d (layer output)
+ * (the one extra reverse sweep of 'fisher_exact': seed 1 / sqrt(variance 0.5) on every walker, independent of E_L),
+ *   A = x~^T x~ / (B R)  (d_in x d_in),   G = dy^T dy / (B R)  (d_out x d_out).
+ * ds_kfac_layout describes the blocks, in the order single[0..], double[0..], orbital[0..]:
+ *   kind / index      0 one-electron layer l (R = N), 1 pair layer l (R = N^2), 2 orbital head of spin channel s (R = n_s)
+ *   param_blocks      the n_param_blocks entries of ds_param_layout the block covers: W_loc [, W_sh] [, b]
+ *   d_in, d_out       the REFERENCE's unpadded sizes, d_in including the bias row when has_bias; rows of A in the reference's
+ *                     order [h | mean_up h | mean_dn h | pair-mean_up | pair-mean_dn | 1] (empty spin channels dropped,
+ *                     network.py:327-328), columns of G in the order of the reference's weight columns (orbital head: Re | Im)
+ *   a_offset, g_offset  element offsets of A and G in `factors` (row-major); the last block's g_offset + d_out^2 is its length
+ * ds_kfac_factors runs the value chain and ONE reverse sweep with cotangent (sqrt2, 0) on every walker (the buffers and kernels
+ * of ds_logpsi_vjp) and overwrites `factors` with every block's A and G, already divided by B R, exactly symmetric.  The
+ * contractions over (repeat, walker) run as symmetric rank-k updates on the MFMA pipe (csrc/ds_kfac.h), upper triangle only;
+ * padded rows and walkers beyond the batch never reach the output.  grad_seed (ds_param_count(),), may be NULL: the packed
+ * gradient of the same seed, sum_b sqrt2 log|psi_b| (the untagged envelope parameters take their diagonal curvature from it,
+ * curvature_blocks.py:111-154).  The batch is processed in the chunks that fit ws; all sums run in a fixed order without atomics:
+ * two calls give the same bits.  Nothing is allocated or synchronised.  B = 0: zeros.  envelope_type 'full' is not supported
+ * (its sigma is a tagged block of its own, `qmc1`, network.py:358-362): the call returns an error. */
+typedef struct ds_kfac_block {
+    int32_t kind, index;
+    int32_t n_param_blocks;
+    int32_t param_blocks[3];
+    int32_t has_bias, d_in, d_out, repeats;
+    int64_t a_offset, g_offset;
+} ds_kfac_block;
+int ds_kfac_block_count(const ds_system* sys);
+int ds_kfac_layout(const ds_system* sys, ds_kfac_block* blocks, int max_blocks);
+int64_t ds_kfac_workspace_bytes(const ds_system* sys, int64_t B);
+int ds_kfac_factors(ds_system* sys, const void* params, const void* x, int64_t B, void* factors, void* grad_seed, void* ws,
+                    int64_t ws_bytes, void* stream);
+
 /* network.eval_func method 'eval_mats' (network.py:601): out_up (B, n_det, n_up, n_up, 2),
  * out_dn (B, n_det, n_dn, n_dn, 2), complex as (Re, Im) pairs. */
 int ds_orbitals(ds_system* sys, const void* params, const void* x, int64_t B,
