@@ -64,6 +64,12 @@ SIGNATURES = {
     'ds_kfac_layout': (C.c_int, [_VP, C.POINTER(KfacBlock), C.c_int]),
     'ds_kfac_workspace_bytes': (C.c_int64, [_VP, C.c_int64]),
     'ds_kfac_factors': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP]),
+    'ds_kfac_step_workspace_bytes': (C.c_int64, [_VP]),
+    'ds_kfac_inverses': (C.c_int, [_VP, _VP, C.c_double, C.c_double, _VP, _VP, C.c_int64, _VP]),
+    'ds_kfac_precondition': (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    'ds_kfac_inverses_sized_workspace_bytes': (C.c_int64, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    'ds_kfac_inverses_sized': (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _VP,
+                                        C.c_double, C.c_double, _VP, _VP, C.c_int64, _VP]),
     'ds_orbitals': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP]),
     'ds_ewald': (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP]),
     'ds_local_energy': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),

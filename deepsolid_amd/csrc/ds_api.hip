@@ -1951,6 +1951,113 @@ void obs_partial(const ds::ObsArgs& A, const void* x, int64_t B, int N, int G, d
 
 // =============================================================================== C ABI
 
+// ------------------------------------------------------------------ KFAC step (ds_kfac.h): damped inverses, preconditioner
+namespace {
+struct KfacStepPlan {
+    ds::KfacMats M;
+    int64_t total = 0, rows = 0, vtotal = 0;      // elements of factors / inverses; rows of all matrices; elements of v / out
+    int nmax = 0, tiles_max = 0;                  // largest order; most 32 x 32 output tiles of one block
+    // workspace, in doubles: work copy | damped matrix, then refined inverse | residual | traces | pivot inverses |
+    // saved column panels | T = A^- V | tile partials
+    int64_t o_w = 0, o_m = 0, o_r = 0, o_tr = 0, o_p = 0, o_c = 0, o_t = 0, o_part = 0, doubles = 0;
+};
+
+int kfac_step_plan_sized(int nb, const int32_t* d_in, const int32_t* d_out, const int32_t* rep, KfacStepPlan* sp) {
+    if (nb < 1 || nb > DS_KFAC_MAX_BLOCKS) return fail("KFAC step: between 1 and 18 blocks");
+    ds::KfacMats& M = sp->M;
+    std::memset(&M, 0, sizeof(M));
+    M.nb = nb;
+    for (int b = 0; b < nb; ++b) {
+        if (d_in[b] < 1 || d_out[b] < 1 || rep[b] < 1) return fail("KFAC step: block sizes and repeats must be positive");
+        const int n2[2] = {d_in[b], d_out[b]};
+        for (int h = 0; h < 2; ++h) {
+            const int m = 2 * b + h;
+            M.n[m] = n2[h]; M.off[m] = (long)sp->total; M.rs[m] = (long)sp->rows;
+            sp->total += (int64_t)n2[h] * n2[h]; sp->rows += n2[h];
+            sp->nmax = std::max(sp->nmax, n2[h]);
+        }
+        M.rep[b] = rep[b];
+        M.voff[b] = (long)sp->vtotal; sp->vtotal += (int64_t)d_in[b] * d_out[b];
+        const int tiles = ((d_in[b] + 31) / 32) * ((d_out[b] + 31) / 32);
+        M.toff[b + 1] = M.toff[b] + tiles;
+        sp->tiles_max = std::max(sp->tiles_max, tiles);
+    }
+    auto r8 = [](int64_t v) { return (v + 7) / 8 * 8; };
+    sp->o_w = 0;
+    sp->o_m = sp->o_w + r8(sp->total);
+    sp->o_r = sp->o_m + r8(sp->total);
+    sp->o_tr = sp->o_r + r8(sp->total);
+    sp->o_p = sp->o_tr + r8(2 * nb);
+    sp->o_c = sp->o_p + (int64_t)2 * nb * 1024;
+    sp->o_t = sp->o_c + sp->rows * 32;
+    sp->o_part = sp->o_t + r8(sp->vtotal);
+    sp->doubles = sp->o_part + r8(M.toff[nb]);
+    return 0;
+}
+
+int kfac_step_plan(const ds_system* s, KfacStepPlan* sp, bool refuse_scalar) {
+    if (s->sd.env_type == 2)
+        return fail("KFAC step: envelope_type 'full' is not supported (its sigma is the tagged block qmc1, network.py:358-362)");
+    KfacPlan kp;
+    if (int rc = kfac_plan(s, &kp)) return rc;
+    const int nb = (int)kp.blocks.size();
+    if (nb > DS_KFAC_MAX_BLOCKS) return fail("KFAC step: more than 18 blocks");
+    int32_t di[DS_KFAC_MAX_BLOCKS], dout[DS_KFAC_MAX_BLOCKS], rep[DS_KFAC_MAX_BLOCKS];
+    for (int b = 0; b < nb; ++b) {
+        di[b] = kp.blocks[b].pub.d_in; dout[b] = kp.blocks[b].pub.d_out; rep[b] = kp.blocks[b].pub.repeats;
+        if (refuse_scalar && (di[b] == 1 || dout[b] == 1))
+            return fail("KFAC step: a block with d_in == 1 or d_out == 1 is not supported (pi_adjusted_inverse treats it specially, "
+                        "utils.py:179-191)");
+    }
+    return kfac_step_plan_sized(nb, di, dout, rep, sp);
+}
+
+template <typename T>
+int kfac_inverses_run(const KfacStepPlan& sp, const void* factors, double w, double damping, void* inverses, void* ws, int64_t ws_bytes,
+                      hipStream_t st) {
+    if (ws_bytes < sp.doubles * 8) return fail("ds_kfac_inverses: workspace too small (ds_kfac_step_workspace_bytes)");
+    if (!(w > 0.0)) return fail("ds_kfac_inverses: ema_weight must be positive");
+    if (!(damping > 0.0)) return fail("ds_kfac_inverses: damping must be positive");
+    double* base = (double*)ws;
+    double *W = base + sp.o_w, *M0 = base + sp.o_m, *R = base + sp.o_r, *tr = base + sp.o_tr, *P = base + sp.o_p, *C = base + sp.o_c;
+    const unsigned nm = 2u * (unsigned)sp.M.nb;
+    const unsigned ge = (unsigned)(((int64_t)sp.nmax * sp.nmax + 255) / 256);
+    const int nbmax = (sp.nmax + 31) / 32;
+    hipLaunchKernelGGL((ds::k_kinv_trace<T>), dim3(nm), dim3(256), 0, st, sp.M, (const T*)factors, w, tr);
+    hipLaunchKernelGGL((ds::k_kinv_prep<T>), dim3(ge, nm), dim3(256), 0, st, sp.M, (const T*)factors, w, damping, (const double*)tr, W, M0);
+    for (int k = 0; k < nbmax; ++k) {
+        hipLaunchKernelGGL(ds::k_kinv_diag, dim3(nm), dim3(256), 0, st, sp.M, (const double*)W, P, k);
+        if (nbmax > 1)
+            hipLaunchKernelGGL(ds::k_kinv_panel, dim3((unsigned)((nbmax + 3) / 4), nm), dim3(256), 0, st, sp.M, W, (const double*)P, C, k);
+        hipLaunchKernelGGL(ds::k_kinv_update, dim3((unsigned)((nbmax * nbmax + 3) / 4), nm), dim3(256), 0, st, sp.M, W, (const double*)P,
+                           (const double*)C, k);
+    }
+    // one Newton step: R = I - M0 W, then M0 <- W + W R (M0 is free once R exists)
+    const dim3 gr((unsigned)((nbmax * nbmax + 3) / 4), nm);
+    hipLaunchKernelGGL((ds::k_kinv_refine<1>), gr, dim3(256), 0, st, sp.M, (const double*)M0, (const double*)W, R);
+    hipLaunchKernelGGL((ds::k_kinv_refine<2>), gr, dim3(256), 0, st, sp.M, (const double*)W, (const double*)R, M0);
+    hipLaunchKernelGGL((ds::k_kinv_finish<T>), dim3(ge, nm), dim3(256), 0, st, sp.M, (const double*)M0, damping, (const double*)tr,
+                       (T*)inverses);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+template <typename T>
+int kfac_precondition_run(const KfacStepPlan& sp, const void* inverses, const void* v, void* out, double* sq, void* ws, int64_t ws_bytes,
+                          hipStream_t st) {
+    if (ws_bytes < sp.doubles * 8) return fail("ds_kfac_precondition: workspace too small (ds_kfac_step_workspace_bytes)");
+    double* base = (double*)ws;
+    T* Tm = (T*)(base + sp.o_t);
+    double* part = base + sp.o_part;
+    const dim3 grid((unsigned)((sp.tiles_max + 3) / 4), (unsigned)sp.M.nb);
+    hipLaunchKernelGGL((ds::k_kprec_gemm<T, 1>), grid, dim3(256), 0, st, sp.M, (const T*)inverses, (const T*)v, Tm, (const T*)v, part);
+    hipLaunchKernelGGL((ds::k_kprec_gemm<T, 2>), grid, dim3(256), 0, st, sp.M, (const T*)inverses, (const T*)Tm, (T*)out, (const T*)v, part);
+    hipLaunchKernelGGL(ds::k_kprec_final, dim3((unsigned)sp.M.nb), dim3(64), 0, st, sp.M, (const double*)part, sq);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+}  // namespace
+
 extern "C" {
 
 const char* ds_last_error(void) { return g_err.c_str(); }
@@ -2211,6 +2318,50 @@ int ds_kfac_factors(ds_system* s, const void* params, const void* x, int64_t B, 
     }
     return s->dtype == 0 ? kfac_factors_impl<double>(s, params, x, B, factors, grad_seed, ws, ws_bytes, st)
                          : kfac_factors_impl<float>(s, params, x, B, factors, grad_seed, ws, ws_bytes, st);
+}
+
+int64_t ds_kfac_step_workspace_bytes(const ds_system* s) {
+    if (!s) return -1;
+    KfacStepPlan sp;
+    if (kfac_step_plan(s, &sp, false)) return -1;
+    return sp.doubles * 8;
+}
+
+int ds_kfac_inverses(ds_system* s, const void* factors, double ema_weight, double damping, void* inverses, void* ws, int64_t ws_bytes,
+                     void* stream) {
+    if (!s || !factors || !inverses || !ws) return fail("null argument");
+    KfacStepPlan sp;
+    if (int rc = kfac_step_plan(s, &sp, true)) return rc;
+    return s->dtype == 0 ? kfac_inverses_run<double>(sp, factors, ema_weight, damping, inverses, ws, ws_bytes, (hipStream_t)stream)
+                         : kfac_inverses_run<float>(sp, factors, ema_weight, damping, inverses, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int ds_kfac_precondition(ds_system* s, const void* inverses, const void* v, void* out, double* sq_norm, void* ws, int64_t ws_bytes,
+                         void* stream) {
+    if (!s || !inverses || !v || !out || !sq_norm || !ws) return fail("null argument");
+    KfacStepPlan sp;
+    if (int rc = kfac_step_plan(s, &sp, true)) return rc;
+    return s->dtype == 0 ? kfac_precondition_run<double>(sp, inverses, v, out, sq_norm, ws, ws_bytes, (hipStream_t)stream)
+                         : kfac_precondition_run<float>(sp, inverses, v, out, sq_norm, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int64_t ds_kfac_inverses_sized_workspace_bytes(int n_blocks, const int32_t* d_in, const int32_t* d_out) {
+    if (!d_in || !d_out) return -1;
+    int32_t rep[DS_KFAC_MAX_BLOCKS];
+    for (int b = 0; b < DS_KFAC_MAX_BLOCKS; ++b) rep[b] = 1;
+    KfacStepPlan sp;
+    if (kfac_step_plan_sized(n_blocks, d_in, d_out, rep, &sp)) return -1;
+    return sp.doubles * 8;
+}
+
+int ds_kfac_inverses_sized(int dtype, int n_blocks, const int32_t* d_in, const int32_t* d_out, const int32_t* repeats, const void* factors,
+                           double ema_weight, double damping, void* inverses, void* ws, int64_t ws_bytes, void* stream) {
+    if (!d_in || !d_out || !repeats || !factors || !inverses || !ws) return fail("null argument");
+    if (dtype != 0 && dtype != 1) return fail("ds_kfac_inverses_sized: dtype must be 0 (float64) or 1 (float32)");
+    KfacStepPlan sp;
+    if (int rc = kfac_step_plan_sized(n_blocks, d_in, d_out, repeats, &sp)) return rc;
+    return dtype == 0 ? kfac_inverses_run<double>(sp, factors, ema_weight, damping, inverses, ws, ws_bytes, (hipStream_t)stream)
+                      : kfac_inverses_run<float>(sp, factors, ema_weight, damping, inverses, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int64_t ds_pretrain_workspace_bytes(const ds_system* s, int64_t B) { return ds_vjp_workspace_bytes(s, B); }

@@ -195,4 +195,285 @@ __global__ void __launch_bounds__(256) k_kfac_assemble_g(int d_out, int Kp, int 
     G[idx] = (first ? T(0) : G[idx]) + scale * v;
 }
 
+// ------------------------------------------------------------------ KFAC step: damped factor inverses and the preconditioner
+// (reference utils.py:130-218 pi_adjusted_inverse / psd_inv_cholesky, curvature_blocks.py:233-281).  Matrix m = 2 b is the A
+// (d_in x d_in), m = 2 b + 1 the G (d_out x d_out) of block b; all of them share every launch: a grid dimension runs over the
+// matrices and a matrix (a tile) beyond its own size exits at once.  The descriptor travels by value (no table on the device).
+#define DS_KFAC_MAX_BLOCKS 18          // DS_MAX_LAYERS one-electron + DS_MAX_LAYERS pair layers + two orbital heads
+struct KfacMats {
+    int nb;                                 // blocks
+    int n[2 * DS_KFAC_MAX_BLOCKS];          // order of matrix m
+    long off[2 * DS_KFAC_MAX_BLOCKS];       // its first element in factors / inverses / the float64 work copy
+    long rs[2 * DS_KFAC_MAX_BLOCKS];        // rows of the matrices before it (the saved column panel is [rs + row][32])
+    int rep[DS_KFAC_MAX_BLOCKS];            // R
+    long voff[DS_KFAC_MAX_BLOCKS];          // first element of the block's d_in x d_out matrix in v / out
+    int toff[DS_KFAC_MAX_BLOCKS + 1];       // first 32 x 32 output tile of the block among the partials of <out, v>
+};
+
+// tr[m] = trace(F_m) / w, summed in a fixed order.  grid (2 nb), block 256
+template <typename T>
+__global__ void __launch_bounds__(256) k_kinv_trace(KfacMats M, const T* __restrict__ F, double w, double* __restrict__ tr) {
+    __shared__ double red[256];
+    const int m = blockIdx.x, n = M.n[m];
+    const T* A = F + M.off[m];
+    double v = 0;
+    for (int i = threadIdx.x; i < n; i += 256) v += (double)A[(size_t)i * n + i];
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) tr[m] = red[0] / w;
+}
+
+// the pi-adjusted damping of matrix m (utils.py:193-201): false when the block takes the zero branch (s > 0 fails, NaN included)
+__device__ __forceinline__ bool kinv_terms(const KfacMats& M, int m, const double* tr, double damping, double* norm, double* damp,
+                                           double* s_out, double* lam_out) {
+    const int b = m >> 1;
+    const double n0 = tr[2 * b], n1 = tr[2 * b + 1], s = n0 * n1, lam = damping / (double)M.rep[b];
+    const double d_in = (double)M.n[2 * b], d_out = (double)M.n[2 * b + 1];
+    *s_out = s; *lam_out = lam;
+    if (!(s > 0.0)) return false;
+    *norm = (m & 1) ? n1 : n0;
+    *damp = (m & 1) ? sqrt(lam * d_in / (s * d_out)) : sqrt(lam * d_out / (s * d_in));
+    return true;
+}
+
+// W_m = M0_m = F_m / w / norm + damp I in float64 (the identity on the zero branch, so the elimination below stays harmless).
+// grid (ceil(nmax^2 / 256), 2 nb), block 256
+template <typename T>
+__global__ void __launch_bounds__(256) k_kinv_prep(KfacMats M, const T* __restrict__ F, double w, double damping,
+                                                   const double* __restrict__ tr, double* __restrict__ W, double* __restrict__ M0) {
+    const int m = blockIdx.y, n = M.n[m];
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)n * n) return;
+    const int r = (int)(idx / n), c = (int)(idx % n);
+    double norm, damp, s, lam;
+    const bool reg = kinv_terms(M, m, tr, damping, &norm, &damp, &s, &lam);
+    const size_t o = (size_t)M.off[m] + (size_t)idx;
+    const double v = reg ? (double)F[o] / w / norm + (r == c ? damp : 0.0) : (r == c ? 1.0 : 0.0);
+    W[o] = v;
+    M0[o] = v;           // kept for the refinement step (k_kinv_refine)
+}
+
+// Block step k of the in-place Gauss-Jordan inverse without pivoting (sound for SPD input), pivot rows K = [32 k, 32 k + kb):
+//   k_kinv_diag    P = W[K][K]^-1 in LDS, one workgroup per matrix                                  -> P (32 x 32 per matrix)
+//   k_kinv_panel   C[i] = W[i][K] (saved: the update below overwrites it),  W[K][j] = P W[K][j]     for the blocks i, j != k
+//   k_kinv_update  W[i][j] -= C[i] W[K][j],  W[i][K] = -C[i] P,  W[K][K] = P                       for i != k
+// After the last step W is the inverse.  Edge blocks are handled by index: nothing beyond row / column n is read or written.
+// grid (2 nb), block 256
+__global__ void __launch_bounds__(256) k_kinv_diag(KfacMats M, const double* __restrict__ W, double* __restrict__ P, int k) {
+    __shared__ double S[32][33];
+    const int m = blockIdx.x, n = M.n[m], k0 = 32 * k;
+    if (k0 >= n) return;
+    const int kb = n - k0 < 32 ? n - k0 : 32;
+    const double* A = W + M.off[m];
+    for (int e = threadIdx.x; e < 1024; e += 256) {
+        const int r = e >> 5, c = e & 31;
+        S[r][c] = (r < kb && c < kb) ? A[(size_t)(k0 + r) * n + k0 + c] : (r == c ? 1.0 : 0.0);
+    }
+    __syncthreads();
+    for (int p = 0; p < kb; ++p) {
+        double nv[4];
+        const double piv = 1.0 / S[p][p];
+        for (int q = 0; q < 4; ++q) {
+            const int e = threadIdx.x + 256 * q, r = e >> 5, c = e & 31;
+            const double rp = S[r][p], pc = S[p][c], rc = S[r][c];
+            nv[q] = r == p ? (c == p ? piv : pc * piv) : (c == p ? -rp * piv : rc - rp * piv * pc);
+        }
+        __syncthreads();
+        for (int q = 0; q < 4; ++q) {
+            const int e = threadIdx.x + 256 * q;
+            S[e >> 5][e & 31] = nv[q];
+        }
+        __syncthreads();
+    }
+    double* Pm = P + (size_t)m * 1024;
+    for (int e = threadIdx.x; e < 1024; e += 256) Pm[e] = S[e >> 5][e & 31];
+}
+
+// acc (32 x 32) = A (32 x kb) B (kb x 32) on one wave: A[r][k] = Ap[r * lda + k] for r < ra, B[k][c] = Bp[k * ldb + c] for c < cb
+__device__ __forceinline__ void kinv_mma(const double* Ap, size_t lda, int ra, const double* Bp, size_t ldb, int cb, int kb,
+                                         Acc4<double>::type acc[2][2]) {
+    const int lane = threadIdx.x & 63, lr = lane & 15, lq = lane >> 4;
+    for (int a = 0; a < 2; ++a)
+        for (int b = 0; b < 2; ++b) acc[a][b] = Acc4<double>::type{0, 0, 0, 0};
+    for (int k0 = 0; k0 < kb; k0 += 4) {
+        const int kk = k0 + lq;
+        double av[2], bv[2];
+        for (int a = 0; a < 2; ++a) {
+            av[a] = (16 * a + lr < ra && kk < kb) ? Ap[(size_t)(16 * a + lr) * lda + kk] : 0.0;
+            bv[a] = (16 * a + lr < cb && kk < kb) ? Bp[(size_t)kk * ldb + 16 * a + lr] : 0.0;
+        }
+        for (int a = 0; a < 2; ++a)
+            for (int b = 0; b < 2; ++b) acc[a][b] = mfma16(av[a], bv[b], acc[a][b]);
+    }
+}
+
+// grid (ceil(nbmax / 4), 2 nb), block 256: a wave per 32-wide block j of the pivot row panel
+__global__ void __launch_bounds__(256) k_kinv_panel(KfacMats M, double* __restrict__ W, const double* __restrict__ P,
+                                                    double* __restrict__ Cs, int k) {
+    const int m = blockIdx.y, n = M.n[m], k0 = 32 * k, nbm = (n + 31) / 32;
+    const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, lr = lane & 15;
+    if (k0 >= n || j >= nbm || j == k) return;
+    const int kb = n - k0 < 32 ? n - k0 : 32, j0 = 32 * j, jb = n - j0 < 32 ? n - j0 : 32;
+    double* A = W + M.off[m];
+    double* C = Cs + (size_t)M.rs[m] * 32;
+    for (int e = lane; e < 1024; e += 64) {
+        const int r = e >> 5, c = e & 31;
+        if (r < jb) C[(size_t)(j0 + r) * 32 + c] = c < kb ? A[(size_t)(j0 + r) * n + k0 + c] : 0.0;
+    }
+    Acc4<double>::type acc[2][2];
+    kinv_mma(P + (size_t)m * 1024, 32, kb, A + (size_t)k0 * n + j0, (size_t)n, jb, kb, acc);
+    for (int a = 0; a < 2; ++a)
+        for (int r = 0; r < 4; ++r) {
+            const int row = 16 * a + acc_row<double>(lane, r);
+            if (row >= kb) continue;
+            for (int b = 0; b < 2; ++b)
+                if (16 * b + lr < jb) A[(size_t)(k0 + row) * n + j0 + 16 * b + lr] = acc[a][b][r];
+        }
+}
+
+// grid (ceil(nbmax^2 / 4), 2 nb), block 256: a wave per 32 x 32 block (i, j)
+__global__ void __launch_bounds__(256) k_kinv_update(KfacMats M, double* __restrict__ W, const double* __restrict__ P,
+                                                     const double* __restrict__ Cs, int k) {
+    const int m = blockIdx.y, n = M.n[m], k0 = 32 * k, nbm = (n + 31) / 32;
+    const int wt = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, lr = lane & 15;
+    if (k0 >= n || wt >= nbm * nbm) return;
+    const int i = wt / nbm, j = wt % nbm;
+    const int kb = n - k0 < 32 ? n - k0 : 32, i0 = 32 * i, ib = n - i0 < 32 ? n - i0 : 32, j0 = 32 * j, jb = n - j0 < 32 ? n - j0 : 32;
+    double* A = W + M.off[m];
+    const double* Pm = P + (size_t)m * 1024;
+    if (i == k) {
+        if (j == k)
+            for (int e = lane; e < 1024; e += 64) {
+                const int r = e >> 5, c = e & 31;
+                if (r < kb && c < kb) A[(size_t)(k0 + r) * n + k0 + c] = Pm[e];
+            }
+        return;
+    }
+    const double* C = Cs + ((size_t)M.rs[m] + i0) * 32;
+    Acc4<double>::type acc[2][2];
+    if (j == k) kinv_mma(C, 32, ib, Pm, 32, kb, kb, acc);
+    else kinv_mma(C, 32, ib, A + (size_t)k0 * n + j0, (size_t)n, jb, kb, acc);
+    for (int a = 0; a < 2; ++a)
+        for (int r = 0; r < 4; ++r) {
+            const int row = 16 * a + acc_row<double>(lane, r);
+            if (row >= ib) continue;
+            for (int b = 0; b < 2; ++b) {
+                const int col = 16 * b + lr;
+                if (col >= jb) continue;
+                double* dst = A + (size_t)(i0 + row) * n + j0 + col;
+                *dst = j == k ? -acc[a][b][r] : *dst - acc[a][b][r];
+            }
+        }
+}
+
+// One Newton step on the eliminated inverse X of M0:  STAGE 1: Out = I - M0 X,  STAGE 2: Out = X + X R.
+// The elimination keeps A_SS^-1 A_SU in place, whose entries grow with the square root of the condition number, and so loses
+// more than a factorisation does (about 1e-9 of the largest entry at condition 1e5); one step of X (2 I - M0 X) brings the
+// result to the rounding of the two products.  A wave per 32 x 32 tile, K = n.  grid as k_kinv_update
+template <int STAGE>
+__global__ void __launch_bounds__(256) k_kinv_refine(KfacMats M, const double* __restrict__ A, const double* __restrict__ B,
+                                                     double* __restrict__ Out) {
+    const int m = blockIdx.y, n = M.n[m], nbm = (n + 31) / 32;
+    const int wt = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, lr = lane & 15;
+    if (wt >= nbm * nbm) return;
+    const int i0 = 32 * (wt / nbm), j0 = 32 * (wt % nbm);
+    const int ib = n - i0 < 32 ? n - i0 : 32, jb = n - j0 < 32 ? n - j0 : 32;
+    const size_t o = (size_t)M.off[m];
+    Acc4<double>::type acc[2][2];
+    kinv_mma(A + o + (size_t)i0 * n, (size_t)n, ib, B + o + j0, (size_t)n, jb, n, acc);
+    for (int a = 0; a < 2; ++a)
+        for (int r = 0; r < 4; ++r) {
+            const int row = 16 * a + acc_row<double>(lane, r);
+            if (row >= ib) continue;
+            for (int b = 0; b < 2; ++b) {
+                const int col = 16 * b + lr;
+                if (col >= jb) continue;
+                const size_t e = o + (size_t)(i0 + row) * n + j0 + col;
+                Out[e] = STAGE == 1 ? (i0 + row == j0 + col ? 1.0 : 0.0) - acc[a][b][r] : A[e] + acc[a][b][r];
+            }
+        }
+}
+
+// out_m = W_m / sqrt(s) (I / sqrt(lambda) on the zero branch), both triangles from the upper one.  grid as k_kinv_prep
+template <typename T>
+__global__ void __launch_bounds__(256) k_kinv_finish(KfacMats M, const double* __restrict__ W, double damping,
+                                                     const double* __restrict__ tr, T* __restrict__ out) {
+    const int m = blockIdx.y, n = M.n[m];
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long)n * n) return;
+    int r = (int)(idx / n), c = (int)(idx % n);
+    if (r > c) { const int t = r; r = c; c = t; }
+    double norm, damp, s, lam;
+    const bool reg = kinv_terms(M, m, tr, damping, &norm, &damp, &s, &lam);
+    const double v = reg ? W[(size_t)M.off[m] + (size_t)r * n + c] / sqrt(s) : (r == c ? 1.0 / sqrt(lam) : 0.0);
+    out[(size_t)M.off[m] + (size_t)idx] = (T)v;
+}
+
+// One product of the preconditioner P_b = A^-_b V_b G^-_b / R_b, a wave per 32 x 32 output tile of block b = blockIdx.y:
+//   STAGE 1: Y_b = A^-_b X_b  (the symmetric A^- is read transposed: sixteen lanes read sixteen consecutive elements)
+//   STAGE 2: Y_b = X_b G^-_b / R_b, and part[toff[b] + tile] = sum over the tile of Y o V in float64 (fixed order: registers,
+//            then a butterfly over the lanes)
+// grid (ceil(max tiles / 4), nb), block 256
+template <typename T, int STAGE>
+__global__ void __launch_bounds__(256) k_kprec_gemm(KfacMats M, const T* __restrict__ inv, const T* __restrict__ X, T* __restrict__ Y,
+                                                    const T* __restrict__ V, double* __restrict__ part) {
+    typedef typename Acc4<T>::type acc_t;
+    const int b = blockIdx.y, rows = M.n[2 * b], cols = M.n[2 * b + 1], tn = (cols + 31) / 32, tm = (rows + 31) / 32;
+    const int wt = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, lr = lane & 15, lq = lane >> 4;
+    if (wt >= tm * tn) return;
+    const int i0 = 32 * (wt / tn), j0 = 32 * (wt % tn);
+    const int K = STAGE == 1 ? rows : cols;
+    const T* Ap = STAGE == 1 ? inv + M.off[2 * b] : X + M.voff[b];
+    const T* Bp = STAGE == 1 ? X + M.voff[b] : inv + M.off[2 * b + 1];
+    const size_t sar = STAGE == 1 ? 1 : (size_t)cols, sak = STAGE == 1 ? (size_t)rows : 1;
+    acc_t acc[2][2];
+    for (int a = 0; a < 2; ++a)
+        for (int c = 0; c < 2; ++c) acc[a][c] = acc_t{0, 0, 0, 0};
+    for (int k0 = 0; k0 < K; k0 += 4) {
+        const int kk = k0 + lq;
+        T av[2], bv[2];
+        for (int a = 0; a < 2; ++a) {
+            const int row = i0 + 16 * a + lr, col = j0 + 16 * a + lr;
+            av[a] = (row < rows && kk < K) ? Ap[(size_t)row * sar + (size_t)kk * sak] : T(0);
+            bv[a] = (col < cols && kk < K) ? Bp[(size_t)kk * cols + col] : T(0);
+        }
+        for (int a = 0; a < 2; ++a)
+            for (int c = 0; c < 2; ++c) acc[a][c] = mfma16(av[a], bv[c], acc[a][c]);
+    }
+    T* Yb = Y + M.voff[b];
+    const T* Vb = V + M.voff[b];
+    const T rep = (T)M.rep[b];
+    double dot = 0;
+    for (int a = 0; a < 2; ++a)
+        for (int r = 0; r < 4; ++r) {
+            const int row = i0 + 16 * a + acc_row<T>(lane, r);
+            if (row >= rows) continue;
+            for (int c = 0; c < 2; ++c) {
+                const int col = j0 + 16 * c + lr;
+                if (col >= cols) continue;
+                const size_t o = (size_t)row * cols + col;
+                const T y = STAGE == 1 ? acc[a][c][r] : acc[a][c][r] / rep;
+                Yb[o] = y;
+                if (STAGE == 2) dot += (double)y * (double)Vb[o];
+            }
+        }
+    if (STAGE == 2) {
+        for (int s = 32; s > 0; s >>= 1) dot += __shfl_xor(dot, s, 64);
+        if (lane == 0) part[M.toff[b] + wt] = dot;
+    }
+}
+
+// sq[b] = the block's tile partials added in index order.  grid (nb), block 64
+__global__ void k_kprec_final(KfacMats M, const double* __restrict__ part, double* __restrict__ sq) {
+    if (threadIdx.x != 0) return;
+    const int b = blockIdx.x;
+    double v = 0;
+    for (int t = M.toff[b]; t < M.toff[b + 1]; ++t) v += part[t];
+    sq[b] = v;
+}
+
 }  // namespace ds

@@ -465,11 +465,13 @@ class DeviceSystem:
                      has_bias=bool(b.has_bias), d_in=int(b.d_in), d_out=int(b.d_out), repeats=int(b.repeats),
                      a_offset=int(b.a_offset), g_offset=int(b.g_offset)) for b in raw]
 
-    def kfac_factors(self, params, x, want_grad=True, max_bytes=None):
+    def kfac_factors(self, params, x, want_grad=True, max_bytes=None, flat=False):
         """Kronecker factors of every tagged layer at walkers x (`ds_kfac_factors`): one value chain and one reverse sweep with
         the seed sqrt2 on every walker.  -> (factors: [(A (d_in, d_in), G (d_out, d_out))] views in the order of `kfac_layout`,
         already divided by B * repeats; grad_seed: packed gradient of sum_b sqrt2 log|psi_b|, or None without `want_grad`).
-        `max_bytes` caps the workspace (the library then walks the batch in chunks)."""
+        `max_bytes` caps the workspace (the library then walks the batch in chunks).  `flat=True`: the flat factor buffer itself
+        (the layout of `kfac_layout`: what `kfac_inverses` reads) in place of the list of views."""
+        flat_out = bool(flat)
         if self.net_kw.get('envelope_type') == 'full':
             raise NotImplementedError("KFAC with envelope_type='full' is not supported: the reference tags its sigma as a "
                                       "curvature block of its own (qmc1, network.py:358-362), which has no factor kernel here")
@@ -491,9 +493,106 @@ class DeviceSystem:
         grad = torch.empty(self.param_count, dtype=self.dtype, device=self.device) if want_grad else None
         _lib.check(self.lib.ds_kfac_factors(self.handle, _ptr(p), _ptr(x), B, _ptr(flat), _ptr(grad), _ptr(ws), ws.numel(),
                                             _stream()), 'ds_kfac_factors')
-        out = [(flat[b['a_offset']:b['a_offset'] + b['d_in'] ** 2].view(b['d_in'], b['d_in']),
-                flat[b['g_offset']:b['g_offset'] + b['d_out'] ** 2].view(b['d_out'], b['d_out'])) for b in layout]
-        return out, grad
+        if flat_out:
+            return flat, grad
+        return self.kfac_views(flat, layout), grad
+
+    def kfac_views(self, flat, layout=None):
+        """[(A, G)] views of a flat factor (or inverse) buffer, in the order of `kfac_layout`."""
+        layout = layout or self.kfac_layout()
+        return [(flat[b['a_offset']:b['a_offset'] + b['d_in'] ** 2].view(b['d_in'], b['d_in']),
+                 flat[b['g_offset']:b['g_offset'] + b['d_out'] ** 2].view(b['d_out'], b['d_out'])) for b in layout]
+
+    def _kfac_step_ws(self):
+        need = int(self.lib.ds_kfac_step_workspace_bytes(self.handle))
+        if need < 0:
+            _lib.check(1, 'ds_kfac_step_workspace_bytes')
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws[:need]
+
+    def kfac_inverses(self, factors_flat, ema_weight, damping):
+        """Damped inverses of every block's factors (`ds_kfac_inverses`, reference utils.py:155-218): `factors_flat` holds the raw
+        moving-average arrays in the flat layout of `kfac_factors(flat=True)`, their value is array / `ema_weight`; `damping` is
+        l2_reg + damping.  -> the inverses in the same flat layout (`kfac_views` cuts it up), exactly symmetric."""
+        layout = self.kfac_layout()
+        total = layout[-1]['g_offset'] + layout[-1]['d_out'] ** 2
+        f = factors_flat.to(device=self.device, dtype=self.dtype).contiguous()
+        if f.numel() != total:
+            raise ValueError(f'factors must hold {total} elements, got {f.numel()}')
+        ws = self._kfac_step_ws()
+        out = torch.empty(total, dtype=self.dtype, device=self.device)
+        _lib.check(self.lib.ds_kfac_inverses(self.handle, _ptr(f), float(ema_weight), float(damping), _ptr(out), _ptr(ws), ws.numel(),
+                                             _stream()), 'ds_kfac_inverses')
+        return out
+
+    def kfac_precondition(self, inverses_flat, v_flat):
+        """`ds_kfac_precondition`: v_flat holds one row-major d_in x d_out matrix per block in layout order (`kfac_index` maps the
+        packed gradient onto it).  -> (out_flat with out_b = A^-_b v_b G^-_b / R_b, sq_norm (n_blocks,) float64 = <out_b, v_b>)."""
+        layout = self.kfac_layout()
+        total = layout[-1]['g_offset'] + layout[-1]['d_out'] ** 2
+        nv = sum(b['d_in'] * b['d_out'] for b in layout)
+        inv = inverses_flat.to(device=self.device, dtype=self.dtype).contiguous()
+        v = v_flat.to(device=self.device, dtype=self.dtype).contiguous()
+        if inv.numel() != total or v.numel() != nv:
+            raise ValueError(f'inverses / v must hold {total} / {nv} elements, got {inv.numel()} / {v.numel()}')
+        ws = self._kfac_step_ws()
+        out = torch.empty(nv, dtype=self.dtype, device=self.device)
+        sq = torch.empty(len(layout), dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.ds_kfac_precondition(self.handle, _ptr(inv), _ptr(v), _ptr(out), _ptr(sq), _ptr(ws), ws.numel(), _stream()),
+                   'ds_kfac_precondition')
+        return out, sq
+
+    def kfac_index(self, params):
+        """Index maps of the KFAC step for a parameter tree of this shape, built once (the leaf numbering of `_grad_index`):
+        -> dict(v_src, diag_src: positions in the PACKED buffer of every entry of v (all blocks' d_in x d_out matrices in layout
+        order, rows in the reference's order w.reshape(-1, d_out) then b) and of the untagged leaves (envelope pi, sigma);
+        v_tree, diag_tree: the same entries as positions in the tree-flat vector (leaves in sorted-key order, row-major);
+        leaf_sizes: entries per leaf of that vector).  Packing is `packed.index_select(0, v_src)`, unpacking one `index_copy_`."""
+        pos = self._grad_index(params)
+        if getattr(self, '_kidx_key', None) == self._gidx_key:
+            return self._kidx
+        if bool((pos < 0).any()):
+            raise RuntimeError('parameter entries without a place in the packed buffer')
+        starts, sizes, off = {}, [], [0]
+
+        def walk(o, path):
+            if isinstance(o, dict):
+                for k in sorted(o):
+                    walk(o[k], path + (k,))
+            elif isinstance(o, (list, tuple)):
+                for i, v in enumerate(o):
+                    walk(v, path + (i,))
+            else:
+                t = torch.as_tensor(np.asarray(o)) if not isinstance(o, torch.Tensor) else o
+                starts[path] = (off[0], tuple(t.shape))
+                sizes.append(t.numel())
+                off[0] += t.numel()
+        walk(params, ())
+        tagged, v_tree = set(), []
+        for b in self.kfac_layout():
+            w0, wshape = starts[(b['kind'], b['index'], 'w')]
+            d_out = wshape[-1]
+            nw = int(np.prod(wshape))
+            rows = nw // d_out + (1 if b['has_bias'] else 0)
+            if d_out != b['d_out'] or rows != b['d_in']:
+                raise ValueError(f"{b['kind']}[{b['index']}]: the tree holds a {rows} x {d_out} block, the layout {b['d_in']} x {b['d_out']}")
+            v_tree.append(torch.arange(w0, w0 + nw))
+            tagged.add((b['kind'], b['index'], 'w'))
+            if b['has_bias']:
+                b0, bshape = starts[(b['kind'], b['index'], 'b')]
+                if int(np.prod(bshape)) != d_out:
+                    raise ValueError(f"{b['kind']}[{b['index']}]['b'] does not have {d_out} entries")
+                v_tree.append(torch.arange(b0, b0 + d_out))
+                tagged.add((b['kind'], b['index'], 'b'))
+        diag_tree = [torch.arange(s, s + int(np.prod(shp))) for path, (s, shp) in starts.items() if path not in tagged]
+        v_tree = torch.cat(v_tree).to(self.device)
+        diag_tree = (torch.cat(diag_tree) if diag_tree else torch.zeros(0, dtype=torch.int64)).to(self.device)
+        self._kidx = dict(v_src=pos[v_tree], diag_src=pos[diag_tree], v_tree=v_tree, diag_tree=diag_tree, leaf_sizes=sizes,
+                          diag_paths=[p for p in starts if p not in tagged])
+        self._kidx_key = self._gidx_key
+        return self._kidx
 
     def _grad_index(self, params):
         """For every leaf of the parameter tree: positions of its entries in the packed buffer (the packing

@@ -154,7 +154,8 @@ def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations
                  burn_in=100, adapt_frequency=100, learning_rate=None, clip_local_energy=5.0, clip_type='real',
                  save_path=None, save_every=None, stats_file_name='train_stats', laplacian_mode='for',
                  partition_number=3, t_init=0, opt_state=None, check_nan=True, max_rejected=20, complex_polarization=False,
-                 structure_factor=False, structure_factor_nq=4, pretrain_iterations=0, pretrain_lr=5e-3, scf_approx=None):
+                 structure_factor=False, structure_factor_nq=4, pretrain_iterations=0, pretrain_lr=5e-3, scf_approx=None,
+                 optimizer='adam', kfac=None):
     """The `optimizer='adam'` branch of the reference driver (process.py:204-219, 256-383): burn-in, then per iteration
     ``mcmc_step -> value_and_grad(total_energy) -> gradient pmean -> Adam -> CSV row -> width adaptation``, with
     checkpoints in the reference's layout (`deepsolid_amd.checkpoint.save`) every `save_every` iterations.
@@ -173,8 +174,17 @@ def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations
     rejected step as well, since the reference writes it before its `loss is not None` gate (process.py:339-345).
     `pretrain_iterations` > 0 on a fresh start (`t_init == 0`): the orbital-matching stage of process.py:148-179 runs first
     (`deepsolid_amd.pretrain.pretrain_hartree_fock`, Adam with `pretrain_lr`, base_config.py:149-154) against `scf_approx`
-    (any object with `eval_orb_mat`; None: the plane waves of the network's own `klist`).  0 (default): no such stage."""
+    (any object with `eval_orb_mat`; None: the plane waves of the network's own `klist`).  0 (default): no such stage.
+    `optimizer='kfac'`: the reference's default optimizer instead (process.py:209-228; `deepsolid_amd.kfac`): the factor pass, the
+    damped inverses and the preconditioner run on the GPU every iteration.  `kfac`: dict of the keys of base_config.py:62-75
+    (invert_every, damping, cov_ema_decay, norm_constraint, l2_reg; momentum must be 0, register_only_generic False); `learning_rate`
+    is then the schedule of the optimizer's own step count.  `opt_state` of a resumed run is the dict `checkpoint.restore` returns
+    (through `checkpoint.opt_state_to_single_device`)."""
     from . import checkpoint
+    if optimizer not in ('adam', 'kfac'):
+        raise ValueError(f"optimizer must be 'adam' or 'kfac', got {optimizer!r}")
+    if kfac is not None and optimizer != 'kfac':
+        raise ValueError("the `kfac` settings need optimizer='kfac'")
     if pretrain_iterations > 0 and t_init == 0:
         from . import pretrain
         from .network import NetworkApply
@@ -188,10 +198,30 @@ def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations
     mcmc_step = qmc.make_mcmc_step(slog_net.apply, batch, latvec=simulation_cell.a, steps=mcmc_steps)
     total_energy = train.make_loss(logdet_net.apply, None, simulation_cell, clip_local_energy=clip_local_energy,
                                    clip_type=clip_type, mode=laplacian_mode, partition_number=partition_number)
-    opt_init, opt_update = train.adam(learning_rate if learning_rate is not None else learning_rate_schedule())
-    if opt_state is None:
-        opt_state = opt_init(params)
-    step = train.make_training_step(mcmc_step, total_energy, opt_update, check_nan=check_nan)
+    schedule = learning_rate if learning_rate is not None else learning_rate_schedule()
+    if optimizer == 'kfac':
+        from . import kfac as kfac_mod
+        cfg = dict(kfac or {})
+        known = {'invert_every': 1, 'cov_update_every': 1, 'damping': 1e-3, 'cov_ema_decay': 0.95, 'momentum': 0.0,
+                 'momentum_type': 'regular', 'min_damping': 1e-4, 'norm_constraint': 1e-3, 'mean_center': True, 'l2_reg': 0.0,
+                 'register_only_generic': False}
+        unknown = sorted(set(cfg) - set(known))
+        if unknown:
+            raise ValueError(f'unknown kfac settings {unknown} (base_config.py:62-75)')
+        cfg = {**known, **cfg}
+        if cfg['cov_update_every'] != 1:
+            raise NotImplementedError('kfac: cov_update_every != 1 is not supported (process.py never passes it on)')
+        kfac_opt = kfac_mod.kfac(schedule, damping=cfg['damping'], l2_reg=cfg['l2_reg'], norm_constraint=cfg['norm_constraint'],
+                                 cov_ema_decay=cfg['cov_ema_decay'], invert_every=cfg['invert_every'], momentum=cfg['momentum'],
+                                 register_only_generic=cfg['register_only_generic'])
+        if opt_state is None:
+            opt_state = kfac_opt[0](params)
+        step = kfac_mod.make_kfac_training_step(mcmc_step, total_energy, kfac_opt, check_nan=check_nan)
+    else:
+        opt_init, opt_update = train.adam(schedule)
+        if opt_state is None:
+            opt_state = opt_init(params)
+        step = train.make_training_step(mcmc_step, total_energy, opt_update, check_nan=check_nan)
     width = float(move_width)
     if t_init == 0:                                                      # process.py:256: burn-in only on a fresh start
         for _ in range(burn_in):

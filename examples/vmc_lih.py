@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """End-to-end example on one MI355X: variational Monte Carlo of the 4-electron LiH cell with the reference's default
-network -- a few Adam iterations (train.py / process.py Adam branch), then an energy evaluation of the result
+network -- a few Adam (or KFAC) iterations (train.py / process.py), then an energy evaluation of the result
 (process.py `optimizer='none'`).  Synthetic start (random parameters, uniform walkers): the numbers are not physics,
-the point is the call sequence.  usage: python examples/vmc_lih.py [iterations] [batch] [--pretrain N]   (N iterations of orbital-matching pretraining against
-the plane waves of the network's own k list first, process.py:148-177)"""
+the point is the call sequence.  usage: python examples/vmc_lih.py [iterations] [batch] [--pretrain N] [--optimizer adam|kfac]   (N iterations of orbital-matching pretraining against
+the plane waves of the network's own k list first, process.py:148-177; --optimizer kfac: the reference's default optimizer,
+process.py:209-228, with the learning-rate schedule of base_config.py:46-51)"""
 import os
 import sys
 
@@ -17,6 +18,11 @@ if '--pretrain' in sys.argv:
     i = sys.argv.index('--pretrain')
     n_pre = int(sys.argv[i + 1])
     del sys.argv[i:i + 2]
+optimizer = 'adam'
+if '--optimizer' in sys.argv:
+    i = sys.argv.index('--optimizer')
+    optimizer = sys.argv[i + 1]
+    del sys.argv[i:i + 2]
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 batch = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
 cell, klist = systems.build('lih')
@@ -26,7 +32,8 @@ slogdet = network.make_solid_fermi_net(klist=klist, simulation_cell=cell, method
 params = logdet.init(0)
 data = torch.as_tensor(systems.synthetic_walkers(cell, batch), device='cuda')
 data, params, state, width, rows = inference.run_training(slogdet, logdet, params, data, cell, iterations=iters, burn_in=20,
-                                                          learning_rate=2e-3, move_width=0.1, pretrain_iterations=n_pre)
+                                                          learning_rate=2e-3 if optimizer == 'adam' else None, move_width=0.1,
+                                                          pretrain_iterations=n_pre, optimizer=optimizer)
 print('training:   E[0] = %.4f  ->  E[%d] = %.4f Ha   (pmove %.2f)' % (rows[0]['energy'], iters - 1, rows[-1]['energy'], rows[-1]['pmove']))
 data, width, rows = inference.run_inference(slogdet, logdet, params, data, cell, iterations=10, burn_in=10, move_width=width)
 print('evaluation: E = %.4f +- %.4f Ha over 10 x %d walkers' % (sum(r['energy'] for r in rows) / len(rows),

@@ -211,6 +211,32 @@ int64_t ds_kfac_workspace_bytes(const ds_system* sys, int64_t B);
 int ds_kfac_factors(ds_system* sys, const void* params, const void* x, int64_t B, void* factors, void* grad_seed, void* ws,
                     int64_t ws_bytes, void* stream);
 
+/* KFAC step, device part (csrc/ds_kfac.h; reference utils.py:130-218, curvature_blocks.py:233-281).  Both calls work on the
+ * blocks of ds_kfac_layout, enqueue on `stream`, allocate nothing, read nothing back and use no atomics: two calls give the
+ * same bits.  ws: ds_kfac_step_workspace_bytes() bytes, shared by the two calls.
+ * ds_kfac_inverses: `factors` holds the raw moving-average arrays in the flat layout of ds_kfac_factors; their value is
+ *   array / ema_weight.  With lambda = damping / R (damping = l2_reg + damping of the optimizer), n0 = tr A, n1 = tr G, s = n0 n1,
+ *     s > 0:  A^- = (A / n0 + sqrt(lambda d_out / (s d_in)) I)^-1 / sqrt(s),  G^- = (G / n1 + sqrt(lambda d_in / (s d_out)) I)^-1 / sqrt(s)
+ *     else:   both I / sqrt(lambda)
+ *   is written to `inverses` in the same layout, exactly symmetric.  Traces, the branch and the damping terms are computed on
+ *   the device.  The elimination (blocked Gauss-Jordan without pivoting, block 32, trailing update on the f64 MFMA, then one
+ *   Newton step X (2 I - M X)) runs in float64 for both dtypes.  A block with d_in == 1 or d_out == 1 is refused (the reference treats it specially).
+ * ds_kfac_precondition: v and out hold one dense row-major d_in x d_out matrix per block in layout order (block b starts at
+ *   element sum_{j<b} d_in_j d_out_j); out_b = A^-_b v_b G^-_b / R_b and sq_norm[b] = sum(out_b o v_b), accumulated in float64
+ *   in a fixed order (sq_norm: n_blocks float64 values on the device).
+ * ds_kfac_inverses_sized: the same inverse kernels on blocks of explicit sizes, without a system handle (n_blocks <= 18;
+ *   dtype 0 float64, 1 float32; flat layout A_0, G_0, A_1, ...): the general formula above for ANY size, 1 included.  For tests
+ *   of the block arithmetic at sizes the network layouts do not reach. */
+int64_t ds_kfac_step_workspace_bytes(const ds_system* sys);
+int ds_kfac_inverses(ds_system* sys, const void* factors, double ema_weight, double damping, void* inverses, void* ws,
+                     int64_t ws_bytes, void* stream);
+int ds_kfac_precondition(ds_system* sys, const void* inverses, const void* v, void* out, double* sq_norm, void* ws,
+                         int64_t ws_bytes, void* stream);
+int64_t ds_kfac_inverses_sized_workspace_bytes(int n_blocks, const int32_t* d_in, const int32_t* d_out);
+int ds_kfac_inverses_sized(int dtype, int n_blocks, const int32_t* d_in, const int32_t* d_out, const int32_t* repeats,
+                           const void* factors, double ema_weight, double damping, void* inverses, void* ws, int64_t ws_bytes,
+                           void* stream);
+
 /* network.eval_func method 'eval_mats' (network.py:601): out_up (B, n_det, n_up, n_up, 2),
  * out_dn (B, n_det, n_dn, n_dn, 2), complex as (Re, Im) pairs. */
 int ds_orbitals(ds_system* sys, const void* params, const void* x, int64_t B,
