@@ -42,6 +42,16 @@ class KfacBlock(C.Structure):
                 ('a_offset', C.c_int64), ('g_offset', C.c_int64)]
 
 
+class HfDesc(C.Structure):
+    _PI = C.POINTER(C.c_int32)
+    _fields_ = [
+        ('a', C.c_double * 9), ('n_atoms', C.c_int32), ('atoms', _PD), ('n_shells', C.c_int32), ('shell_atom', _PI),
+        ('shell_l', _PI), ('shell_nprim', _PI), ('exps', _PD), ('coefs', _PD), ('n_k', C.c_int32), ('kpts', _PD),
+        ('n_images', C.c_int32), ('images', _PD), ('n_up', C.c_int32), ('n_dn', C.c_int32), ('nocc_up', _PI), ('nocc_dn', _PI),
+        ('mo_up', _PD), ('mo_dn', _PD),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/deepsolid_hip.h
 _VP = C.c_void_p
 SIGNATURES = {
@@ -99,6 +109,9 @@ SIGNATURES = {
     'ds_debug_timeline': (C.c_int, [_VP, C.POINTER(C.c_uint64), C.c_int]),
     'ds_calib_copy': (C.c_int, [_VP, _VP, C.c_int64, _VP]),
     'ds_mfma_f64_peak': (C.c_int64, [C.c_int64, C.c_int, C.c_int, _VP, _VP]),
+    'ds_hf_create': (C.c_int, [C.POINTER(HfDesc), C.POINTER(_VP)]),
+    'ds_hf_destroy': (None, [_VP]),
+    'ds_hf_orbitals': (C.c_int, [_VP, C.c_int, _VP, C.c_int64, _VP, _VP, _VP]),
 }
 
 PROF_KINDS = ('features', 'm2_expand', 'two_layer', 'single_first', 'single_hidden', 'orbital', 'det_inverse',

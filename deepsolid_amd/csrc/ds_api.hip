@@ -2058,6 +2058,11 @@ int kfac_precondition_run(const KfacStepPlan& sp, const void* inverses, const vo
 }
 }  // namespace
 
+// the message slot of ds_last_error for the entry points compiled in other objects (ds_hf.hip)
+namespace ds {
+void set_last_error(const char* msg) { g_err = msg; }
+}  // namespace ds
+
 extern "C" {
 
 const char* ds_last_error(void) { return g_err.c_str(); }

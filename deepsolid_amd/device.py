@@ -830,3 +830,61 @@ def observable_sums(recvec, x, q_int, pol_direction):
                                   q.ctypes.data_as(C.POINTER(C.c_int32)), n_q, int(pol_direction), _ptr(out), _ptr(ws),
                                   ws.numel() * 8, _stream()), 'ds_observables')
     return out
+
+
+class HfOrbitalTables:
+    """The device tables of one `hf.GaussianOrbitals` (`ds_hf_create`, csrc/ds_hf.h); needs no DeviceSystem.  The arrays are
+    the fields of `ds_hf_desc` (include/deepsolid_hip.h); `mo` is the pair of (nao, n_s) complex128 coefficient matrices."""
+
+    def __init__(self, a, atoms, shell_atom, shell_l, shell_nprim, exps, coefs, kpts, images, nocc, mo, device=None):
+        _require_gpu()
+        self.lib = _lib.load()
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        f8 = lambda v, shape: np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(shape))
+        i4 = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.int32).reshape(-1))
+        pi = lambda v: v.ctypes.data_as(C.POINTER(C.c_int32))
+        a, atoms, kpts, images = f8(a, (3, 3)), f8(atoms, (-1, 3)), f8(kpts, (-1, 3)), f8(images, (-1, 3))
+        shell_atom, shell_l, shell_nprim = i4(shell_atom), i4(shell_l), i4(shell_nprim)
+        exps, coefs = f8(exps, -1), f8(coefs, -1)
+        nocc = [i4(n) for n in nocc]
+        mo = [np.ascontiguousarray(np.asarray(m, dtype=np.complex128)) for m in mo]
+        self.nelec = tuple(int(m.shape[1]) for m in mo)
+        d = _lib.HfDesc()
+        d.a[:] = a.reshape(-1).tolist()
+        d.n_atoms, d.atoms = atoms.shape[0], _pd(atoms)
+        d.n_shells, d.shell_atom, d.shell_l, d.shell_nprim = shell_l.shape[0], pi(shell_atom), pi(shell_l), pi(shell_nprim)
+        d.exps, d.coefs = _pd(exps), _pd(coefs)
+        d.n_k, d.kpts = kpts.shape[0], _pd(kpts)
+        d.n_images, d.images = images.shape[0], _pd(images)
+        d.n_up, d.n_dn = self.nelec
+        d.nocc_up, d.nocc_dn = pi(nocc[0]), pi(nocc[1])
+        d.mo_up, d.mo_dn = (m.view(np.float64).ctypes.data_as(C.POINTER(C.c_double)) if m.size else None for m in mo)
+        self.handle = C.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.ds_hf_create(C.byref(d), C.byref(self.handle)), 'ds_hf_create')
+
+    def __del__(self):
+        h, self.handle = getattr(self, 'handle', None), None
+        if h:
+            try:
+                self.lib.ds_hf_destroy(h)
+            except Exception:
+                pass
+
+    def orbitals(self, x):
+        """x (B, 3N) float64 / float32 device tensor -> [up (B, n_up, n_up), dn (B, n_dn, n_dn)] complex128 (`ds_hf_orbitals`)."""
+        if not x.is_cuda or x.device != self.device:
+            raise RuntimeError(f'HfOrbitalTables.orbitals: walkers must live on {self.device} (no CPU path)')
+        if x.dtype not in _DTYPES:
+            raise TypeError(f'HfOrbitalTables.orbitals: walkers must be float64 or float32, got {x.dtype}')
+        n = sum(self.nelec)
+        if x.dim() != 2 or x.shape[1] != 3 * n:
+            raise ValueError(f'HfOrbitalTables.orbitals: walkers must have shape (B, {3 * n}), got {tuple(x.shape)}')
+        x = x.contiguous()
+        B = x.shape[0]
+        outs = [torch.empty(B, ns, ns, 2, dtype=torch.float64, device=x.device) for ns in self.nelec]
+        if B:
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.ds_hf_orbitals(self.handle, _DTYPES[x.dtype], _ptr(x), B, _ptr(outs[0] if self.nelec[0] else None),
+                                                   _ptr(outs[1] if self.nelec[1] else None), _stream()), 'ds_hf_orbitals')
+        return [torch.view_as_complex(o) for o in outs]

@@ -155,7 +155,7 @@ def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations
                  save_path=None, save_every=None, stats_file_name='train_stats', laplacian_mode='for',
                  partition_number=3, t_init=0, opt_state=None, check_nan=True, max_rejected=20, complex_polarization=False,
                  structure_factor=False, structure_factor_nq=4, pretrain_iterations=0, pretrain_lr=5e-3, scf_approx=None,
-                 optimizer='adam', kfac=None):
+                 optimizer='adam', kfac=None, pretrain_method='net', pretrain_steps=1):
     """The `optimizer='adam'` branch of the reference driver (process.py:204-219, 256-383): burn-in, then per iteration
     ``mcmc_step -> value_and_grad(total_energy) -> gradient pmean -> Adam -> CSV row -> width adaptation``, with
     checkpoints in the reference's layout (`deepsolid_amd.checkpoint.save`) every `save_every` iterations.
@@ -175,6 +175,10 @@ def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations
     `pretrain_iterations` > 0 on a fresh start (`t_init == 0`): the orbital-matching stage of process.py:148-179 runs first
     (`deepsolid_amd.pretrain.pretrain_hartree_fock`, Adam with `pretrain_lr`, base_config.py:149-154) against `scf_approx`
     (any object with `eval_orb_mat`; None: the plane waves of the network's own `klist`).  0 (default): no such stage.
+    `pretrain_method` (cfg.pretrain.method, process.py:148,164): 'net' moves the walkers on the network's density, 'hf' on the
+    Hartree-Fock density of `scf_approx` (`pretrain_hartree_fock_usingHF`, `pretrain_steps` = cfg.pretrain.steps moves per
+    iteration); 'hf' needs a `scf_approx` with `eval_slogdet` (`deepsolid_amd.hf.GaussianOrbitals`): plane waves are singular
+    as a density.
     `optimizer='kfac'`: the reference's default optimizer instead (process.py:209-228; `deepsolid_amd.kfac`): the factor pass, the
     damped inverses and the preconditioner run on the GPU every iteration.  `kfac`: dict of the keys of base_config.py:62-75
     (invert_every, damping, cov_ema_decay, norm_constraint, l2_reg; momentum must be 0, register_only_generic False); `learning_rate`
@@ -185,14 +189,25 @@ def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations
         raise ValueError(f"optimizer must be 'adam' or 'kfac', got {optimizer!r}")
     if kfac is not None and optimizer != 'kfac':
         raise ValueError("the `kfac` settings need optimizer='kfac'")
+    if pretrain_method not in ('net', 'hf'):
+        raise ValueError(f"pretrain_method must be 'net' or 'hf', got {pretrain_method!r}")
+    if pretrain_method == 'hf' and scf_approx is None:
+        raise ValueError("pretrain_method='hf' samples the Hartree-Fock density and needs scf_approx (deepsolid_amd.hf."
+                         "GaussianOrbitals); the plane-wave stand-in is singular as a density")
     if pretrain_iterations > 0 and t_init == 0:
         from . import pretrain
         from .network import NetworkApply
         net = slog_net.apply
         orbitals = NetworkApply(net.simulation_cell, net.klist, net.net_kw, 'eval_mats', net.dtype)
-        params, data = pretrain.pretrain_hartree_fock(
-            params, data, net, orbitals, key, simulation_cell, scf_approx or pretrain.PlaneWaveOrbitals(net.klist),
-            full_det=bool(net.net_kw.get('full_det', False)), iterations=pretrain_iterations, learning_rate=pretrain_lr)
+        full_det = bool(net.net_kw.get('full_det', False))
+        if pretrain_method == 'hf':
+            params, data = pretrain.pretrain_hartree_fock_usingHF(
+                params, data, orbitals, key, simulation_cell, scf_approx, iterations=pretrain_iterations,
+                learning_rate=pretrain_lr, nsteps=pretrain_steps, full_det=full_det)
+        else:
+            params, data = pretrain.pretrain_hartree_fock(
+                params, data, net, orbitals, key, simulation_cell, scf_approx or pretrain.PlaneWaveOrbitals(net.klist),
+                full_det=full_det, iterations=pretrain_iterations, learning_rate=pretrain_lr)
     gen = _rank_generator(key, data.device, t_init)
     batch = data.shape[0]
     mcmc_step = qmc.make_mcmc_step(slog_net.apply, batch, latvec=simulation_cell.a, steps=mcmc_steps)

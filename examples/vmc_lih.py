@@ -4,7 +4,10 @@ network -- a few Adam (or KFAC) iterations (train.py / process.py), then an ener
 (process.py `optimizer='none'`).  Synthetic start (random parameters, uniform walkers): the numbers are not physics,
 the point is the call sequence.  usage: python examples/vmc_lih.py [iterations] [batch] [--pretrain N] [--optimizer adam|kfac]   (N iterations of orbital-matching pretraining against
 the plane waves of the network's own k list first, process.py:148-177; --optimizer kfac: the reference's default optimizer,
-process.py:209-228, with the learning-rate schedule of base_config.py:46-51)"""
+process.py:209-228, with the learning-rate schedule of base_config.py:46-51;
+--hf FILE.npz: pretrain against the Hartree-Fock orbitals dumped into FILE.npz (deepsolid_amd.hf.GaussianOrbitals, INTEGRATION.md:
+a calculation of THIS 4-electron cell) instead of plane waves, the network taking the file's k list; --pretrain-method net|hf:
+move the pretraining walkers on the network's density or on the Hartree-Fock density, process.py:148,164; hf needs --hf)"""
 import os
 import sys
 
@@ -23,9 +26,23 @@ if '--optimizer' in sys.argv:
     i = sys.argv.index('--optimizer')
     optimizer = sys.argv[i + 1]
     del sys.argv[i:i + 2]
+scf_approx, pretrain_method = None, 'net'
+if '--hf' in sys.argv:
+    from deepsolid_amd import hf
+    i = sys.argv.index('--hf')
+    scf_approx = hf.GaussianOrbitals.load(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
+if '--pretrain-method' in sys.argv:
+    i = sys.argv.index('--pretrain-method')
+    pretrain_method = sys.argv[i + 1]
+    del sys.argv[i:i + 2]
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 batch = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
 cell, klist = systems.build('lih')
+if scf_approx is not None:
+    if scf_approx.nelec != tuple(cell.nelec):
+        sys.exit(f'--hf: the file holds nelec = {scf_approx.nelec}, this cell has {tuple(cell.nelec)}')
+    klist = scf_approx.klist
 kw = dict(systems.DETNET_DEFAULTS)
 logdet = network.make_solid_fermi_net(klist=klist, simulation_cell=cell, method_name='eval_logdet', **kw)
 slogdet = network.make_solid_fermi_net(klist=klist, simulation_cell=cell, method_name='eval_slogdet', **kw)
@@ -33,7 +50,8 @@ params = logdet.init(0)
 data = torch.as_tensor(systems.synthetic_walkers(cell, batch), device='cuda')
 data, params, state, width, rows = inference.run_training(slogdet, logdet, params, data, cell, iterations=iters, burn_in=20,
                                                           learning_rate=2e-3 if optimizer == 'adam' else None, move_width=0.1,
-                                                          pretrain_iterations=n_pre, optimizer=optimizer)
+                                                          pretrain_iterations=n_pre, optimizer=optimizer, scf_approx=scf_approx,
+                                                          pretrain_method=pretrain_method)
 print('training:   E[0] = %.4f  ->  E[%d] = %.4f Ha   (pmove %.2f)' % (rows[0]['energy'], iters - 1, rows[-1]['energy'], rows[-1]['pmove']))
 data, width, rows = inference.run_inference(slogdet, logdet, params, data, cell, iterations=10, burn_in=10, move_width=width)
 print('evaluation: E = %.4f +- %.4f Ha over 10 x %d walkers' % (sum(r['energy'] for r in rows) / len(rows),

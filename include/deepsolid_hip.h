@@ -392,6 +392,46 @@ int ds_calib_copy(const void* src, void* dst, int64_t n_elems, void* stream);
  * `blocks_per_cu` waves resident per SIMD; returns the FLOPs executed (caller times with HIP events). */
 int64_t ds_mfma_f64_peak(int64_t iters, int blocks_per_cu, int n_acc, void* scratch, void* stream);
 
+/* Hartree-Fock crystalline orbitals of a Gaussian basis (hf.py:84-153 without PySCF; csrc/ds_hf.h); needs no
+ * ds_system.  Every pointer of the descriptor is a HOST array that ds_hf_create copies; conventions of PySCF's PBCGTOval_sph:
+ *   ao_k,mu(r) = sum_L exp(i k.L) R_mu(|d|) S_lm(d),  d = r - R_atom(mu) - L,  R = sum_p coefs_p exp(-exps_p |d|^2),
+ *   S_lm orthonormal real solid harmonics, l = 1: x, y, z; l = 2: xy, yz, z^2, xz, x^2-y^2; AO index: shells in order, m inside.
+ * a: primitive cell (rows = lattice vectors, Bohr); atoms (n_atoms, 3); shell_atom / shell_l (0..2) / shell_nprim (n_shells),
+ * exps / coefs: the primitives of all shells back to back, coefficients as applied (normalised); sum (2l+1) <= 128 AOs;
+ * kpts (n_k <= 64, 3); images (n_images, 3): the lattice translations L to sum over, in summation order;
+ * n_up, n_dn <= 64 electrons per spin; nocc_up / nocc_dn (n_k): occupied bands per k point, summing to n_up / n_dn;
+ * mo_up / mo_dn: (nao, n_s) complex128 as (re, im) pairs, row-major, columns ordered by k point and then band. */
+typedef struct ds_hf ds_hf;
+typedef struct ds_hf_desc {
+    double a[9];
+    int32_t n_atoms;
+    const double* atoms;
+    int32_t n_shells;
+    const int32_t* shell_atom;
+    const int32_t* shell_l;
+    const int32_t* shell_nprim;
+    const double* exps;
+    const double* coefs;
+    int32_t n_k;
+    const double* kpts;
+    int32_t n_images;
+    const double* images;
+    int32_t n_up, n_dn;
+    const int32_t* nocc_up;
+    const int32_t* nocc_dn;
+    const double* mo_up;
+    const double* mo_dn;
+} ds_hf_desc;
+/* Copies the tables to the device once and precomputes the (n_k, n_images) table of exp(i k.L); no allocation afterwards. */
+int ds_hf_create(const ds_hf_desc* desc, ds_hf** out);
+void ds_hf_destroy(ds_hf* hf);
+/* Orbital matrices at B walkers: x (B, 3N) device array, dtype 0 = f64, 1 = f32 (widened on load; all arithmetic is float64);
+ * out_up (B, n_up, n_up), out_dn (B, n_dn, n_dn) complex128 device arrays [walker, electron, orbital] (NULL for a spin without
+ * electrons).  The walker is wrapped into the primitive cell and the wrap phase exp(i k.(wrap a)) applied (hf.py:113-120).
+ * Needs no workspace; no atomics and a fixed summation order: a walker's rows have the same bits wherever it sits in the batch.
+ * A chunk of 64 images (32 beyond 64 AOs) is skipped when alpha_min |d|^2 > 90 for each of its images and every atom. */
+int ds_hf_orbitals(ds_hf* hf, int dtype, const void* x, int64_t B, void* out_up, void* out_dn, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
