@@ -87,6 +87,8 @@ SIGNATURES = {
     'ds_observables_workspace_bytes': (C.c_int64, [C.c_int64, C.c_int]),
     'ds_observables': (C.c_int, [_PD, C.c_int, _VP, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.c_int, C.c_int, _VP, _VP,
                                  C.c_int64, _VP]),
+    'ds_realspace_counts': (C.c_int, [_PD, C.POINTER(C.c_int32), _PD, _PD, C.c_double, C.c_int, C.c_int, _VP, C.c_int64, C.c_int64,
+                                      C.c_int64, _VP, _VP, _VP]),
     'ds_mh_propose': (C.c_int, [_VP, _VP, _VP, C.c_double, C.c_int64, _VP, _VP]),
     'ds_mh_accept': (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP, _VP]),
     'ds_mh_propose_ex': (C.c_int, [_VP, C.c_int, _VP, _VP, C.c_double, _VP, C.c_int, C.c_int64, _VP, _VP, _VP]),

@@ -18,6 +18,7 @@
 #include "ds_tiles.h"
 #include "ds_mcmc.h"
 #include "ds_obs.h"
+#include "ds_realspace.h"
 #include "ds_i8.h"
 
 // the per-slot-tile-count kernel instances live in ds_tiles_inst.hip (five slot-tile ranges x two element types)
@@ -2462,6 +2463,63 @@ int ds_observables(const double* recvec, int dtype, const void* x, int64_t B, in
     HIP_OK(hipGetLastError());
     hipLaunchKernelGGL(ds::k_obs_final, dim3((K + 255) / 256), dim3(256), 0, st, (const double*)part, G, K, out_sums);
     HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int ds_realspace_counts(const double* fold_inv, const int32_t* grid, const double* latvec, const double* latvec_inv, double r_max,
+                        int n_r, int dtype, const void* x, int64_t B, int64_t n_elec, int64_t n_up, int64_t* dens, int64_t* pair,
+                        void* stream) {
+    if (!x) return fail("null argument");
+    if (!dens && !pair) return fail("ds_realspace_counts: dens and pair are both null, nothing to count");
+    if (dtype != 0 && dtype != 1) return fail("dtype must be 0 or 1");
+    if (B < 1) return fail("B must be >= 1 (got %lld)", (long long)B);
+    if (n_elec < 1 || n_elec > ds::RS_MAX_N) return fail("n_elec must be in 1..%d (got %lld)", ds::RS_MAX_N, (long long)n_elec);
+    if (n_up < 0 || n_up > n_elec) return fail("n_up must be in 0..n_elec = %lld (got %lld)", (long long)n_elec, (long long)n_up);
+    ds::RealSpaceArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.n_up = (int)n_up;
+    A.do_dens = dens != nullptr;
+    A.do_pair = pair != nullptr;
+    if (dens) {
+        if (!fold_inv || !grid) return fail("ds_realspace_counts: the density needs fold_inv and grid");
+        long long cells = 1;
+        for (int j = 0; j < 3; ++j) {
+            if (grid[j] < 1 || grid[j] > ds::RS_MAX_G) return fail("grid[%d] must be in 1..%d (got %d)", j, ds::RS_MAX_G, (int)grid[j]);
+            A.g[j] = grid[j];
+            cells *= grid[j];
+        }
+        if (cells > ds::RS_MAX_BINS) return fail("grid has %lld points, at most %lld are supported", cells, ds::RS_MAX_BINS);
+        for (int i = 0; i < 9; ++i) {
+            if (!std::isfinite(fold_inv[i])) return fail("fold_inv[%d] is not finite", i);
+            A.fold_inv[i] = fold_inv[i];
+        }
+    }
+    if (pair) {
+        if (!latvec || !latvec_inv) return fail("ds_realspace_counts: the pair counts need latvec and latvec_inv");
+        if (n_r < 1 || n_r > ds::RS_MAX_NR) return fail("n_r must be in 1..%d (got %d)", ds::RS_MAX_NR, n_r);
+        if (!(r_max > 0.0) || !std::isfinite(r_max)) return fail("r_max must be positive and finite (got %g)", r_max);
+        for (int i = 0; i < 9; ++i) {
+            if (!std::isfinite(latvec[i]) || !std::isfinite(latvec_inv[i])) return fail("latvec / latvec_inv [%d] is not finite", i);
+            A.a[i] = latvec[i];
+            A.a_inv[i] = latvec_inv[i];
+        }
+        A.n_r = n_r;
+        A.r_max = r_max;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    // pieces of at most RS_MAX_LAUNCH_WALKERS walkers: the bound behind the uint32 LDS bins (ds_realspace.h)
+    for (int64_t b0 = 0; b0 < B; b0 += ds::RS_MAX_LAUNCH_WALKERS) {
+        const long long nb = (long long)std::min<int64_t>(B - b0, ds::RS_MAX_LAUNCH_WALKERS);
+        const dim3 grid_dim((unsigned)ds::rs_groups(nb)), block(ds::RS_THREADS);
+        const size_t off = (size_t)b0 * 3 * (size_t)n_elec;
+        if (dtype == 0)
+            hipLaunchKernelGGL((ds::k_realspace_counts<double>), grid_dim, block, 0, st, A, (const double*)x + off, nb, (int)n_elec,
+                               (unsigned long long*)dens, (unsigned long long*)pair);
+        else
+            hipLaunchKernelGGL((ds::k_realspace_counts<float>), grid_dim, block, 0, st, A, (const float*)x + off, nb, (int)n_elec,
+                               (unsigned long long*)dens, (unsigned long long*)pair);
+        HIP_OK(hipGetLastError());
+    }
     return 0;
 }
 

@@ -832,6 +832,58 @@ def observable_sums(recvec, x, q_int, pol_direction):
     return out
 
 
+def realspace_counts(x, n_up, dens=None, fold_lattice=None, pair=None, latvec=None, r_max=None):
+    """Add the real-space counts of the walkers x to caller-owned int64 device buffers (`ds_realspace_counts`,
+    csrc/ds_realspace.h); needs no handle, returns nothing and copies nothing to the host.
+    x (B, 3N) float64 / float32 device tensor; electrons e < n_up are spin up.
+    dens: int64 device tensor (2, g0, g1, g2), the density counts on the grid of `fold_lattice` (3, 3; rows = lattice vectors),
+    or None.  pair: int64 device tensor (3, n_r), the up-up / up-down / down-down histogram of minimum-image distances below
+    `r_max` in the simulation cell `latvec` (3, 3), or None.  The caller guarantees r_max <= half the shortest lattice vector and
+    r_max < 1.5 x the smallest plane spacing (`estimator.RealSpaceAccumulator` checks both)."""
+    _require_gpu()
+    if not x.is_cuda:
+        raise RuntimeError('realspace_counts: walkers must live on the ROCm device (no CPU path)')
+    if x.dtype not in _DTYPES:
+        raise TypeError(f'realspace_counts: walkers must be float64 or float32, got {x.dtype}')
+    if x.dim() != 2 or x.shape[1] % 3:
+        raise ValueError(f'realspace_counts: walkers must have shape (B, 3N), got {tuple(x.shape)}')
+    if x.shape[0] < 1:
+        raise ValueError('realspace_counts: empty walker batch')
+    if dens is None and pair is None:
+        raise ValueError('realspace_counts: neither a density nor a pair buffer was given')
+    for name, buf, lead in (('dens', dens, 2), ('pair', pair, 3)):
+        if buf is None:
+            continue
+        if not (isinstance(buf, torch.Tensor) and buf.dtype == torch.int64 and buf.is_contiguous()):
+            raise TypeError(f'realspace_counts: {name} must be a contiguous int64 tensor')
+        if buf.device != x.device:
+            raise RuntimeError(f'realspace_counts: {name} lives on {buf.device}, the walkers on {x.device}')
+        if buf.dim() != (4 if lead == 2 else 2) or buf.shape[0] != lead:
+            raise ValueError(f'realspace_counts: {name} must have shape ' + ('(2, g0, g1, g2)' if lead == 2 else '(3, n_r)')
+                             + f', got {tuple(buf.shape)}')
+    lib = _lib.load()
+    x = x.contiguous()
+    f8 = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(3, 3))
+    fold_inv = grid = a = a_inv = None
+    n_r, rm = 0, 0.0
+    if dens is not None:
+        if fold_lattice is None:
+            raise ValueError('realspace_counts: the density needs fold_lattice')
+        fold_inv = np.ascontiguousarray(np.linalg.inv(f8(fold_lattice)))
+        grid = np.asarray(dens.shape[1:], dtype=np.int32)
+    if pair is not None:
+        if latvec is None or r_max is None:
+            raise ValueError('realspace_counts: the pair counts need latvec and r_max')
+        a = f8(latvec)
+        a_inv = np.ascontiguousarray(np.linalg.inv(a))
+        n_r, rm = int(pair.shape[1]), float(r_max)
+    _lib.check(lib.ds_realspace_counts(_pd(fold_inv) if fold_inv is not None else None,
+                                       grid.ctypes.data_as(C.POINTER(C.c_int32)) if grid is not None else None,
+                                       _pd(a) if a is not None else None, _pd(a_inv) if a_inv is not None else None, rm, n_r,
+                                       _DTYPES[x.dtype], _ptr(x), x.shape[0], x.shape[1] // 3, int(n_up), _ptr(dens), _ptr(pair),
+                                       _stream()), 'ds_realspace_counts')
+
+
 class HfOrbitalTables:
     """The device tables of one `hf.GaussianOrbitals` (`ds_hf_create`, csrc/ds_hf.h); needs no DeviceSystem.  The arrays are
     the fields of `ds_hf_desc` (include/deepsolid_hip.h); `mo` is the pair of (nao, n_s) complex128 coefficient matrices."""

@@ -95,3 +95,253 @@ def append_structure_factor_row(path, sk):
     sk = np.asarray(sk.detach().cpu() if isinstance(sk, torch.Tensor) else sk).reshape(-1)
     with open(path, 'a') as f:
         f.write(','.join(['0'] + [_csv_value(v) for v in sk]) + '\n')
+
+
+# ------------------------------------------------------------------ real-space observables (csrc/ds_realspace.h)
+# The reference has no real-space estimator; the conventions of this section are this project's own.
+PAIR_CHANNELS = ('up-up', 'up-down', 'down-down')
+
+
+def wigner_seitz_radius(a):
+    """Half the length of the shortest non-zero lattice vector of `a` (3, 3; rows = lattice vectors), from the vectors with
+    coefficients in -3..3."""
+    a = np.asarray(a, dtype=np.float64).reshape(3, 3)
+    n = np.stack([m.ravel() for m in np.meshgrid(*[np.arange(-3, 4)] * 3, indexing='ij')], axis=1)
+    n = n[np.any(n != 0, axis=1)]
+    return 0.5 * float(np.sqrt(((n @ a) ** 2).sum(axis=1)).min())
+
+
+def plane_spacings(a):
+    """The three distances between neighbouring lattice planes of `a`: spacing j = 1 / |column j of inv(a)|."""
+    return 1.0 / np.sqrt((np.linalg.inv(np.asarray(a, dtype=np.float64).reshape(3, 3)) ** 2).sum(axis=0))
+
+
+class _Lattices:
+    """What `RealSpaceAccumulator` reads of a simulation cell, rebuilt from a saved state."""
+
+    def __init__(self, a, nelec):
+        self.a, self.nelec = np.asarray(a, dtype=np.float64), tuple(int(n) for n in nelec)
+        self.original_cell = self
+
+
+class RealSpaceAccumulator:
+    """Spin-resolved electron density and radial pair-correlation function g(r), accumulated as integer counts on the device over
+    any number of walker batches (`update`), summed over the ranks once (`reduce`) and normalised on the host.
+
+    `density_grid`: G or (g0, g1, g2), the grid on the folding lattice `density_cell`: 'primitive'
+    (``simulation_cell.original_cell.a``), 'simulation', or a 3x3 array of any lattice whose translations are symmetries; None: no
+    density.  `pair_bins`: number of radial bins on [0, pair_rmax); None: no g(r).  `pair_rmax` None: the Wigner-Seitz radius
+    r_ws (half the shortest lattice vector of the simulation cell).  pair_rmax > r_ws, or pair_rmax >= 1.5 x the smallest plane
+    spacing (the kernel looks at the 27 nearest images only), is a ValueError."""
+
+    def __init__(self, simulation_cell, density_grid=None, density_cell='primitive', pair_bins=None, pair_rmax=None):
+        self.a = np.array(simulation_cell.a, dtype=np.float64).reshape(3, 3)
+        self.nelec = (int(simulation_cell.nelec[0]), int(simulation_cell.nelec[1]))
+        n = sum(self.nelec)
+        if not 1 <= n <= 128 or min(self.nelec) < 0:
+            raise ValueError(f'nelec = {self.nelec}: between 1 and 128 electrons are supported')
+        if density_grid is None and pair_bins is None:
+            raise ValueError('RealSpaceAccumulator: neither density_grid nor pair_bins was given')
+        self.grid = self.fold = None
+        if density_grid is not None:
+            g = np.asarray(density_grid)
+            if g.ndim > 1 or g.size not in (1, 3) or not np.all(g == np.floor(g)):
+                raise ValueError(f'density_grid must be an integer or three integers, got {density_grid!r}')
+            g = tuple(int(v) for v in (np.repeat(g.reshape(-1), 3) if g.size == 1 else g))
+            if min(g) < 1 or max(g) > 256 or g[0] * g[1] * g[2] > 1 << 22:
+                raise ValueError(f'density_grid = {g}: 1 <= g_j <= 256 and g0 g1 g2 <= 2^22 are supported')
+            self.grid = g
+            if isinstance(density_cell, str):
+                if density_cell == 'primitive':
+                    fold = simulation_cell.original_cell.a
+                elif density_cell == 'simulation':
+                    fold = simulation_cell.a
+                else:
+                    raise ValueError(f"density_cell must be 'primitive', 'simulation' or a 3x3 array, got {density_cell!r}")
+            else:
+                fold = density_cell
+            fold = np.array(fold, dtype=np.float64)
+            if fold.shape != (3, 3) or not np.all(np.isfinite(fold)) or abs(np.linalg.det(fold)) < 1e-12:
+                raise ValueError('density_cell must be a non-singular 3x3 lattice')
+            self.fold = fold
+        self.n_r = self.r_max = None
+        self.r_ws, self.spacings = wigner_seitz_radius(self.a), plane_spacings(self.a)
+        if pair_bins is not None:
+            if int(pair_bins) != pair_bins or not 1 <= int(pair_bins) <= 1024:
+                raise ValueError(f'pair_bins = {pair_bins!r}: 1 <= pair_bins <= 1024 is supported')
+            r_max = self.r_ws if pair_rmax is None else float(pair_rmax)
+            if not (r_max > 0 and np.isfinite(r_max)):
+                raise ValueError(f'pair_rmax = {pair_rmax!r} must be positive')
+            if r_max > self.r_ws:
+                raise ValueError(f'pair_rmax = {r_max} is beyond the Wigner-Seitz radius {self.r_ws} of the simulation cell: '
+                                 'more than one image of a pair could be counted')
+            if not r_max < 1.5 * self.spacings.min():
+                raise ValueError(f'pair_rmax = {r_max} is not below 1.5 x the smallest plane spacing {self.spacings.min()}: '
+                                 'the nearest image may lie outside the 27 shifts the kernel searches')
+            self.n_r, self.r_max = int(pair_bins), r_max
+        elif pair_rmax is not None:
+            raise ValueError('pair_rmax without pair_bins')
+        self.dens = self.pair = None        # int64 tensors (2, g0, g1, g2) / (3, n_r), made on the walkers' device by the first update
+        self.n_walkers = 0
+        self.reduced = False
+
+    # ---- accumulation
+    def _buffers(self, device):
+        if self.grid is not None:
+            self.dens = torch.zeros((2,) + self.grid, dtype=torch.int64, device=device) if self.dens is None \
+                else self.dens.to(device)
+        if self.n_r is not None:
+            self.pair = torch.zeros((3, self.n_r), dtype=torch.int64, device=device) if self.pair is None else self.pair.to(device)
+
+    def update(self, data):
+        """Add the walkers `data` (B, 3N) to the counts: one kernel call, no device -> host copy."""
+        from . import device
+        if self.reduced:
+            raise RuntimeError('RealSpaceAccumulator.update after reduce(): the counts are already summed over the ranks')
+        n = sum(self.nelec)
+        if data.shape[-1] != 3 * n:
+            raise ValueError(f'walkers have {data.shape[-1]} coordinates, the cell has {n} electrons')
+        x = data.reshape(-1, 3 * n)
+        if not x.is_cuda:
+            raise RuntimeError('RealSpaceAccumulator.update: walkers must live on the ROCm device (no CPU path)')
+        self._buffers(x.device)
+        device.realspace_counts(x, self.nelec[0], dens=self.dens, fold_lattice=self.fold, pair=self.pair, latvec=self.a,
+                                r_max=self.r_max)
+        self.n_walkers += int(x.shape[0])
+
+    def _same_setup(self, other):
+        same = lambda p, q: (p is None) == (q is None) and (p is None or np.array_equal(np.asarray(p), np.asarray(q)))
+        return all(same(getattr(self, k), getattr(other, k)) for k in ('a', 'nelec', 'grid', 'fold', 'n_r', 'r_max'))
+
+    def merge(self, other):
+        """Add the counts and the walker number of another accumulator of the same setup (a continued run, another seed).
+        The counts are added as they are, so both sides must be in the same state: both rank-local (before `reduce`) or both
+        summed over the ranks.  With more than one rank a mixed pair is refused, since a later `reduce` would count one side
+        once per rank.  A loaded file counts as rank-local (see `load`)."""
+        if not self._same_setup(other):
+            raise ValueError('RealSpaceAccumulator.merge: the two accumulators differ in cell, grid or bins')
+        if self.reduced != other.reduced and constants.world_size() > 1:
+            raise ValueError('RealSpaceAccumulator.merge: one side is summed over the ranks and the other is rank-local')
+        for k in ('dens', 'pair'):
+            mine, theirs = getattr(self, k), getattr(other, k)
+            if theirs is not None:
+                setattr(self, k, theirs.clone() if mine is None else mine + theirs.to(mine.device))
+        self.n_walkers += other.n_walkers
+        return self
+
+    def reduce(self):
+        """Sum the counts and the walker number over the ranks in ONE all-reduce (`constants.psum_if_pmap`; the identity at
+        world size 1).  Once per accumulator: a second call raises."""
+        if self.reduced:
+            raise RuntimeError('RealSpaceAccumulator.reduce was already called: reducing twice would count every rank again')
+        if constants.world_size() == 1:
+            self.reduced = True
+            return self
+        if (self.grid is not None and self.dens is None) or (self.n_r is not None and self.pair is None):
+            self._buffers('cuda' if torch.cuda.is_available() else 'cpu')
+        parts = [t.reshape(-1) for t in (self.dens, self.pair) if t is not None]
+        packed = torch.cat(parts + [torch.tensor([self.n_walkers], dtype=torch.int64, device=parts[0].device)])
+        packed = constants.psum_if_pmap(packed)
+        off = 0
+        for k in ('dens', 'pair'):
+            t = getattr(self, k)
+            if t is not None:
+                setattr(self, k, packed[off:off + t.numel()].reshape(t.shape).clone())
+                off += t.numel()
+        self.n_walkers = int(packed[-1])
+        self.reduced = True                 # only now: a collective that raised leaves the accumulator as it was
+        return self
+
+    # ---- normalisation (host)
+    def _counts(self, t, shape):
+        return np.zeros(shape, np.int64) if t is None else t.detach().cpu().numpy()
+
+    def density_counts(self):
+        if self.grid is None:
+            raise ValueError('this accumulator holds no density (density_grid=None)')
+        return self._counts(self.dens, (2,) + self.grid)
+
+    def pair_counts(self):
+        if self.n_r is None:
+            raise ValueError('this accumulator holds no pair counts (pair_bins=None)')
+        return self._counts(self.pair, (3, self.n_r))
+
+    def r_edges(self):
+        return np.arange(self.n_r + 1, dtype=np.float64) * (self.r_max / self.n_r)
+
+    def density(self):
+        """(2, g0, g1, g2) float64, electrons / Bohr^3: counts / (n_walkers dV V_sim / V_fold), dV = V_fold / (g0 g1 g2); each
+        spin integrates over the folding cell to the electrons of that spin per folding cell."""
+        counts = self.density_counts()
+        v_sim, v_fold = abs(np.linalg.det(self.a)), abs(np.linalg.det(self.fold))
+        dv = v_fold / float(np.prod(self.grid))
+        return counts / (self.n_walkers * dv * v_sim / v_fold) if self.n_walkers else np.full(counts.shape, np.nan)
+
+    def pair_correlation(self):
+        """-> (r_mid (n_r,), g (3, n_r)): g_c[k] = counts_c[k] V_sim / (n_walkers P_c V_shell_k) with
+        V_shell_k = 4 pi / 3 (r_{k+1}^3 - r_k^3), P_c = N_s (N_s - 1) / 2 for up-up and down-down and N_up N_down for up-down;
+        a channel without pairs is NaN.  Independent uniform walkers give g = 1 in expectation for any N."""
+        counts = self.pair_counts()
+        edges = self.r_edges()
+        shell = 4.0 * np.pi / 3.0 * (edges[1:] ** 3 - edges[:-1] ** 3)
+        nu, nd = self.nelec
+        g = np.full((3, self.n_r), np.nan)
+        for c, p in enumerate((nu * (nu - 1) // 2, nu * nd, nd * (nd - 1) // 2)):
+            if p > 0 and self.n_walkers:
+                g[c] = counts[c] * abs(np.linalg.det(self.a)) / (self.n_walkers * p * shell)
+        return 0.5 * (edges[1:] + edges[:-1]), g
+
+    # ---- persistence
+    def state_dict(self):
+        """Plain numpy arrays: the counts, the walker number and the setup they belong to ('reduced' records whether the counts
+        were summed over the ranks when they were written; loading does not restore it, see `load`)."""
+        sd = {'n_walkers': np.int64(self.n_walkers), 'simulation_lattice': self.a.copy(), 'nelec': np.asarray(self.nelec, np.int64),
+              'reduced': np.bool_(self.reduced)}
+        if self.grid is not None:
+            sd.update(density_counts=self.density_counts(), fold_lattice=self.fold.copy(), grid=np.asarray(self.grid, np.int64))
+        if self.n_r is not None:
+            sd.update(pair_counts=self.pair_counts(), r_edges=self.r_edges(), pair_rmax=np.float64(self.r_max))
+        return sd
+
+    def load_state_dict(self, sd):
+        """Replace the counts by those of `sd` (of an accumulator of the same setup); the accumulator is rank-local and open
+        for `update` afterwards, as after `load`."""
+        other = RealSpaceAccumulator.from_state_dict(sd)
+        if not self._same_setup(other):
+            raise ValueError('RealSpaceAccumulator.load_state_dict: the state belongs to another cell, grid or bins')
+        self.dens, self.pair, self.n_walkers, self.reduced = other.dens, other.pair, other.n_walkers, other.reduced
+        return self
+
+    @classmethod
+    def from_state_dict(cls, sd):
+        has_d, has_p = 'density_counts' in sd, 'pair_counts' in sd
+        acc = cls(_Lattices(sd['simulation_lattice'], sd['nelec']),
+                  density_grid=tuple(int(v) for v in sd['grid']) if has_d else None,
+                  density_cell=np.asarray(sd['fold_lattice']) if has_d else 'primitive',
+                  pair_bins=len(sd['r_edges']) - 1 if has_p else None, pair_rmax=float(sd['pair_rmax']) if has_p else None)
+        if has_d:
+            acc.dens = torch.as_tensor(np.array(sd['density_counts'], dtype=np.int64).reshape((2,) + acc.grid))
+        if has_p:
+            acc.pair = torch.as_tensor(np.array(sd['pair_counts'], dtype=np.int64).reshape(3, acc.n_r))
+        acc.n_walkers = int(sd['n_walkers'])
+        return acc                          # reduced stays False: the loaded counts are this rank's contribution from here on
+
+    def save(self, path, results=False):
+        """One .npz of `state_dict()`; `results`: also the normalised density and g(r) (what `run_inference` writes)."""
+        sd = self.state_dict()
+        if results:
+            if self.grid is not None:
+                sd['density'] = self.density()
+            if self.n_r is not None:
+                sd['r_mid'], sd['g'] = self.pair_correlation()
+        with open(path, 'wb') as f:
+            np.savez(f, **sd)
+
+    @classmethod
+    def load(cls, path):
+        """The accumulator saved at `path`, as a fresh rank-local one: `update` or `merge` go on adding to its counts and
+        `reduce` may be called once more, whether or not the file was written after a `reduce` (`run_inference` always writes
+        after one).  The loaded counts then are this rank's contribution, so in a run of several ranks load the file on ONE
+        rank only and start the others empty, or the old counts are summed once per rank."""
+        with np.load(path) as f:
+            return cls.from_state_dict({k: f[k] for k in f.files})

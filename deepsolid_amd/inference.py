@@ -92,14 +92,23 @@ def _csv_row(row, schema):
 def run_inference(slog_net, logdet_net, params, data, simulation_cell, iterations, key=0, move_width=0.02,
                   mcmc_steps=20, burn_in=100, adapt_frequency=100, stats_frequency=1, save_path=None,
                   stats_file_name='train_stats', laplacian_mode='for', partition_number=3, complex_polarization=False,
-                  structure_factor=False, structure_factor_nq=4):
+                  structure_factor=False, structure_factor_nq=4, accumulators=()):
     """Returns (data, mcmc_width, rows).  `slog_net` / `logdet_net` are the objects returned by
     ``make_solid_fermi_net(method_name='eval_slogdet' | 'eval_logdet')``; `data` is (B, 3N) on the device.
     Energies are reported per primitive cell like process.py:330-334 (divided by ``simulation_cell.scale``).
     `complex_polarization` / `structure_factor` (cfg.log switches, base_config.py:94-95): evaluate the observables of
     `deepsolid_amd.estimator` on the walkers after every step; rows carry 'complex_polarization' (also a CSV column) and
     'structure_factor' (the nq^3 values, `structure_factor_nq` = nq, one row per iteration in
-    <save_path>/structure_factor.csv)."""
+    <save_path>/structure_factor.csv).
+    `accumulators`: `estimator.RealSpaceAccumulator` objects (or anything with `update(data)`, `reduce()` and `save(path,
+    results=True)`): each takes the walkers of every iteration after its `total_energy` (one kernel call, nothing is read back),
+    is summed over the ranks once on exit and, on rank 0 with a `save_path`, written to <save_path>/realspace.npz (the i-th of
+    several to realspace_<i>.npz): counts, walker number, lattices, grid, r edges, normalised density and g(r).  A run that
+    raises inside the loop does not reduce (a collective on the way out of an exception could hang the other ranks): with a
+    `save_path` every rank writes the counts it has, unreduced, to realspace_partial_rank<r>.npz (realspace_<i>_partial_rank<r>.npz)
+    before the exception goes on; `RealSpaceAccumulator.load` + `merge` put such files together.  The return value and the CSV do
+    not change; with the default () nothing changes at all."""
+    accumulators = tuple(accumulators)
     gen = _rank_generator(key, data.device)
     batch = data.shape[0]
     mcmc_step = qmc.make_mcmc_step(slog_net.apply, batch, latvec=simulation_cell.a, steps=mcmc_steps)
@@ -115,6 +124,7 @@ def run_inference(slog_net, logdet_net, params, data, simulation_cell, iteration
     writer = Writer(stats_file_name, schema, save_path) if save_path else None
     if writer:
         writer.__enter__()
+    finished = False
     try:
         for t in range(iterations):
             data, pmove = mcmc_step(params, data, gen, width)            # process.py:320
@@ -128,6 +138,8 @@ def run_inference(slog_net, logdet_net, params, data, simulation_cell, iteration
                    'ewald': float(aux.ewald.mean()) / scale}
             if observe:                                                  # process.py:337-342
                 row.update(observe(data))
+            for acc in accumulators:
+                acc.update(data)
             if t % stats_frequency == 0:
                 rows.append(row)
                 if writer:
@@ -139,9 +151,21 @@ def run_inference(slog_net, logdet_net, params, data, simulation_cell, iteration
                     width /= 1.1
                 pmoves[:] = 0
             pmoves[t % adapt_frequency] = row['pmove']
+        finished = True
     finally:
         if writer:
             writer.__exit__(None, None, None)
+        if accumulators and save_path and not finished:
+            from . import constants
+            for i, acc in enumerate(accumulators):
+                stem = 'realspace' if i == 0 else f'realspace_{i}'
+                acc.save(os.path.join(save_path, f'{stem}_partial_rank{constants.rank()}.npz'))
+    if accumulators:
+        from . import constants
+        for i, acc in enumerate(accumulators):
+            acc.reduce()
+            if save_path and constants.rank() == 0:
+                acc.save(os.path.join(save_path, 'realspace.npz' if i == 0 else f'realspace_{i}.npz'), results=True)
     return data, width, rows
 
 

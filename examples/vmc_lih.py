@@ -7,11 +7,15 @@ the plane waves of the network's own k list first, process.py:148-177; --optimiz
 process.py:209-228, with the learning-rate schedule of base_config.py:46-51;
 --hf FILE.npz: pretrain against the Hartree-Fock orbitals dumped into FILE.npz (deepsolid_amd.hf.GaussianOrbitals, INTEGRATION.md:
 a calculation of THIS 4-electron cell) instead of plane waves, the network taking the file's k list; --pretrain-method net|hf:
-move the pretraining walkers on the network's density or on the Hartree-Fock density, process.py:148,164; hf needs --hf)"""
+move the pretraining walkers on the network's density or on the Hartree-Fock density, process.py:148,164; hf needs --hf;
+--density G: accumulate the spin-resolved electron density on a G^3 grid of the primitive cell over the evaluation;
+--pair-correlation BINS: the spin-resolved g(r) on BINS radial bins up to the Wigner-Seitz radius -- both through
+deepsolid_amd.estimator.RealSpaceAccumulator, written to realspace.npz in the working directory)"""
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
 import torch
 
 from deepsolid_amd import inference, network, systems
@@ -36,6 +40,15 @@ if '--pretrain-method' in sys.argv:
     i = sys.argv.index('--pretrain-method')
     pretrain_method = sys.argv[i + 1]
     del sys.argv[i:i + 2]
+density_grid = pair_bins = None
+if '--density' in sys.argv:
+    i = sys.argv.index('--density')
+    density_grid = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
+if '--pair-correlation' in sys.argv:
+    i = sys.argv.index('--pair-correlation')
+    pair_bins = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 batch = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
 cell, klist = systems.build('lih')
@@ -53,6 +66,22 @@ data, params, state, width, rows = inference.run_training(slogdet, logdet, param
                                                           pretrain_iterations=n_pre, optimizer=optimizer, scf_approx=scf_approx,
                                                           pretrain_method=pretrain_method)
 print('training:   E[0] = %.4f  ->  E[%d] = %.4f Ha   (pmove %.2f)' % (rows[0]['energy'], iters - 1, rows[-1]['energy'], rows[-1]['pmove']))
-data, width, rows = inference.run_inference(slogdet, logdet, params, data, cell, iterations=10, burn_in=10, move_width=width)
+accumulators = ()
+if density_grid is not None or pair_bins is not None:
+    from deepsolid_amd import estimator
+    accumulators = (estimator.RealSpaceAccumulator(cell, density_grid=density_grid, pair_bins=pair_bins),)
+data, width, rows = inference.run_inference(slogdet, logdet, params, data, cell, iterations=10, burn_in=10, move_width=width,
+                                            accumulators=accumulators)
 print('evaluation: E = %.4f +- %.4f Ha over 10 x %d walkers' % (sum(r['energy'] for r in rows) / len(rows),
                                                                 (sum(r['variance'] for r in rows) / len(rows) / (10 * batch)) ** 0.5, batch))
+for acc in accumulators:
+    acc.save('realspace.npz', results=True)
+    if density_grid is not None:
+        rho = acc.density()
+        dv = abs(float(np.linalg.det(acc.fold))) / rho[0].size
+        print('density:    %d^3 grid, %d walkers, up / down electrons per primitive cell = %.6f / %.6f, max %.4f e/Bohr^3'
+              % (density_grid, acc.n_walkers, rho[0].sum() * dv, rho[1].sum() * dv, rho.max()))
+    if pair_bins is not None:
+        r, g = acc.pair_correlation()
+        print('g(r):       %d bins to r_max = %.3f Bohr; last bin up-up %.3f, up-down %.3f, down-down %.3f'
+              % (pair_bins, acc.r_max, g[0, -1], g[1, -1], g[2, -1]))

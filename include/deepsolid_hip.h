@@ -272,6 +272,36 @@ int64_t ds_observables_workspace_bytes(int64_t B, int n_q);
 int ds_observables(const double* recvec, int dtype, const void* x, int64_t B, int64_t n_elec, const int32_t* q_int, int n_q,
                    int pol_direction, double* out_sums, void* ws, int64_t ws_bytes, void* stream);
 
+/* Real-space walker observables as integer counts (csrc/ds_realspace.h): the spin-resolved electron density on a grid of a
+ * folding lattice, and the spin-resolved radial pair histogram behind g(r).  Needs no handle and no workspace.  The reference has
+ * no such estimator: the conventions are this library's own.  One call takes the walkers x (B, 3 n_elec) (device array; dtype
+ * 0 = f64, 1 = f32 widened to f64 on load; all arithmetic is float64) and ADDS to two caller-owned int64 device buffers; it never
+ * zeroes them.  Either buffer may be NULL: that part is skipped and its arguments are not read; both NULL is an error.
+ *
+ * Density counts dens[2][g0*g1*g2]:
+ *   - Spin of electron e is 0 if e < n_up, else 1.
+ *   - The electron is folded into a folding lattice A_f (3x3, rows = lattice vectors; normally the primitive cell, or any lattice
+ *     whose translations are symmetries, for example the simulation cell itself).
+ *   - Folding rule: f = r . inv(A_f), f -= floor(f), i_j = min(int(f_j * g_j), g_j - 1).
+ *   - Flat bin index: (i0*g1 + i1)*g2 + i2.
+ *   fold_inv: HOST pointer to inv(A_f), row-major; grid: HOST pointer to (g0, g1, g2).
+ *
+ * Pair counts pair[3][n_r]:
+ *   - Channels are up-up, up-down, down-down.
+ *   - For each pair i < j, take the minimum-image distance in the simulation cell A.
+ *   - Rule: f = (r_i - r_j) . inv(A), f -= floor(f + 1/2).  Then take the shortest of |(f + s) . A| over s in {-1,0,1}^3.
+ *   - Bin index: k = int(r * n_r / r_max).  Count the pair only if r < r_max.
+ *   latvec / latvec_inv: HOST pointers to A (rows = lattice vectors) and inv(A).  The caller guarantees two conditions:
+ *   r_max <= r_ws, half the shortest non-zero lattice vector (at most one image can then lie inside r_max), and
+ *   r_max < 1.5 * the smallest plane spacing of A (the 27 shifts are then enough).
+ *
+ * Limits, refused with a ds_last_error message before any launch: 1 <= n_elec <= 128, 0 <= n_up <= n_elec, 1 <= g_j <= 256,
+ * g0*g1*g2 <= 2^22, 1 <= n_r <= 1024, r_max > 0, B >= 1.  Counts are added with integer atomics, so the buffers do not depend on
+ * the order of the additions: the same input gives bit-identical counts. */
+int ds_realspace_counts(const double* fold_inv, const int32_t* grid, const double* latvec, const double* latvec_inv, double r_max,
+                        int n_r, int dtype, const void* x, int64_t B, int64_t n_elec, int64_t n_up, int64_t* dens, int64_t* pair,
+                        void* stream);
+
 /* qmc.mh_update symmetric branch (qmc.py:190-196, 217-222) split around the network call:
  *   propose: x2 = wrap(x1 + width * normal)
  *   accept : cond = (lp2 - lp1) > log(uniform); x1,lp1 <- select; n_accept[0] += sum(cond)
