@@ -60,7 +60,37 @@ int fail(const char* fmt, ...) {
         if (e_ != hipSuccess) return fail("%s: %s", #call, hipGetErrorString(e_)); \
     } while (0)
 
-inline int rup(int x, int m) { return (x + m - 1) / m * m; }
+template <typename I> inline I rup(I x, int m) { return (x + m - 1) / m * m; }
+
+// A workspace as a stack of elements of T.  Every layout below is ONE function over an arena and serves both as the size of the
+// layout and as its pointers: with a base, take(n) hands out the next n elements (carve mode); with a null base it only counts
+// (measure mode: `used` is the extent).  An entry point checks `ok` after carving and before its first launch.
+template <typename T> struct Arena {
+    T* base = nullptr;
+    size_t cap = SIZE_MAX, used = 0;
+    bool ok = true;                                  // false once more was taken than `cap` -- here or in a part() of this arena
+    T* take(size_t n) { T* p = base ? base + used : nullptr; used += n; ok = ok && used <= cap; return p; }
+    void align(size_t k) { take((k - used % k) % k); }
+    // a buffer of n elements already handed out, carved up again (buffers that live inside an idle one); its overrun counts here
+    template <typename F> void part(T* buf, size_t n, F&& carve) { Arena a{buf, n}; carve(a); ok = ok && a.ok; }
+};
+template <typename T> Arena<T> arena_of(void* ws, int64_t ws_bytes) { return Arena<T>{(T*)ws, (size_t)std::max<int64_t>(ws_bytes, 0) / sizeof(T)}; }
+// extent, in elements, of a layout function
+template <typename F> size_t measure(F&& layout) { Arena<double> a; layout(a); return a.used; }
+
+// A pass over groups of PV walkers: elements shared by all groups and elements per group (measured from the pass's layout function)
+struct PassSize { size_t fixed, per_group; };
+// The groups per pass a *_workspace_bytes entry point provides for a batch of B walkers: all of them, at most 64, within a byte budget ...
+inline int64_t groups_per_pass(int64_t B, int64_t esz, const PassSize& z, int64_t budget) {
+    const int64_t groups = std::min<int64_t>((std::max<int64_t>(B, 1) + ds::PV - 1) / ds::PV, 64);
+    return std::max<int64_t>(1, std::min<int64_t>(groups, budget / ((int64_t)z.per_group * esz)));
+}
+// ... and its inverse: the groups a workspace of ws_bytes has room for (< 1: too small)
+inline int64_t groups_that_fit(int64_t ws_bytes, int64_t esz, const PassSize& z) {
+    return (ws_bytes / esz - (int64_t)z.fixed) / (int64_t)z.per_group;
+}
+
+inline int carve_fail(const char* what) { return fail("internal: %s: workspace carve exceeds its size", what); }
 
 void inv3(const double* a, double* o) {
     const double det = a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) +
@@ -77,7 +107,7 @@ struct WsLayout {
     size_t XL = 0;                                         // layer-0 input tiles [N][h1[0] + nch h2[0]][P] (low-rank first hidden layer)
     size_t YO = 0;                                         // (y, oL) of the layer-0 output per electron and feature [N][h1[1]][2]
     size_t mout_off[2], minv_off[2], dets_off[2], tr_off[2];
-    size_t per_walker;                                     // total elements per walker
+    size_t per_walker;                                     // measured extent of carve() / carve_value() at one walker / one group
 };
 
 }  // namespace
@@ -273,6 +303,70 @@ template <typename T> ds::SysDev<T>& dev(ds_system* s);
 template <> ds::SysDev<double>& dev<double>(ds_system* s) { return s->sd; }
 template <> ds::SysDev<float>& dev<float>(ds_system* s) { return s->sf; }
 
+// ---------------------------------------------------------------- the workspace layouts of the two chains
+// forward-Laplacian chain on Bc walkers
+template <typename T> struct Carve {
+    T *G[2], *MEAN[2], *ZB, *H2[2], *Q, *MOUT, *MINV, *DETS, *TR, *XL, *YO;
+};
+template <typename T> Carve<T> carve(const ds_system* s, Arena<T>& a, int64_t Bc) {
+    const WsLayout& w = s->ws;
+    Carve<T> c;
+    for (T*& g : c.G) g = a.take(w.G * Bc);
+    for (T*& m : c.MEAN) m = a.take(w.MEAN * Bc);
+    c.ZB = a.take(w.ZB * Bc);
+    for (T*& h : c.H2) h = a.take(w.H2 * Bc);
+    c.Q = a.take(w.Q * Bc);
+    c.MOUT = a.take(w.MOUT * Bc); c.MINV = a.take(w.MINV * Bc);
+    c.DETS = a.take(w.DETS * Bc); c.TR = a.take(w.TR * Bc);
+    c.XL = a.take(w.XL * Bc); c.YO = a.take(w.YO * Bc);
+    return c;
+}
+
+// The value chain (log psi only) on `Bc` walkers = ceil(Bc / PV) groups; see ds_value.h.
+// Buffers of one value-chain pass over ng groups.  The plain pass ping-pongs two G / H2 buffers; the
+// gradient pass keeps every layer's activations (Gl[l] = input of layer l, Gl[n_layers] = orbital-head input).
+template <typename T> struct ValBufs {
+    T* Gl[DS_MAX_LAYERS + 1];
+    T* H2l[DS_MAX_LAYERS + 1];
+    T *MEAN0, *MEANS, *ZB, *Q, *MOUT, *DETS, *PARTM;     // MEANS: spin means of a hidden layer's input (scratch of k_spin_mean)
+    T* PHI[2];              // orbital GEMM output per spin channel (the plain pass reuses ZB for both)
+    T* SORB[2];             // use_last_layer: shared term of the orbital head
+    T* MINV;                // optional inverses, laid out like MOUT (walker-interleaved)
+    T* PM[DS_MAX_LAYERS];   // fused pair stream (k_pair_stream_val): segment sums of pair layer l (PM[0] = PARTM) ...
+    bool pm_fit;            // ... which have room in the H2 buffer that path leaves idle
+    bool keep;              // gradient passes: every layer's activations and the raw orbital products PHI stay in memory
+                            // (MOUT may then be null: the orbital matrices themselves are not formed, ds_pretrain_loss_vjp)
+};
+
+template <typename T>
+ValBufs<T> carve_value(const ds_system* s, Arena<T>& a, int64_t ng) {
+    const ds::SysDev<double>& S = s->sd;      // (the dims of sd and sf are the same)
+    const WsLayout& L = s->wsv;
+    ValBufs<T> b{};
+    T* G[2]; T* MEAN[2]; T* H2[2];
+    for (T*& g : G) g = a.take(L.G * ng);
+    for (T*& m : MEAN) m = a.take(L.MEAN * ng);
+    b.ZB = a.take(L.ZB * ng);
+    for (T*& h : H2) h = a.take(L.H2 * ng);
+    b.Q = a.take(L.Q * ng); b.MOUT = a.take(L.MOUT * ng);
+    b.DETS = a.take(L.DETS * ng); b.PARTM = a.take(L.PARTM * ng);
+    b.MEAN0 = MEAN[0]; b.MEANS = MEAN[1];
+    for (int l = 0; l <= S.n_layers; ++l) { b.Gl[l] = G[l & 1]; b.H2l[l] = H2[l & 1]; }
+    for (int sp = 0; sp < 2; ++sp)            // inside ZB, once per spin: PHI first, S of the orbital head behind it
+        a.part(b.ZB, L.ZB * ng, [&](Arena<T>& z) {
+            b.PHI[sp] = z.take((size_t)(sp == 0 ? S.n_up : S.n_dn) * S.ocols[sp] * ds::PV * ng);
+            b.SORB[sp] = z.take((size_t)S.ocols[sp] * ds::PV * ng);
+        });
+    // the sums of the fused pair stream's layers 1.. go into the second H2 buffer, which that path leaves unused (a PARTM block is
+    // 3/16 of an H2 buffer); without room for them the pair layers run one by one
+    Arena<T> idle{H2[1], L.H2 * ng};
+    b.PM[0] = b.PARTM;
+    for (int l = 1; l < S.n_double && l < DS_MAX_LAYERS; ++l) b.PM[l] = idle.take(L.PARTM * ng);
+    b.pm_fit = idle.ok;
+    b.MINV = nullptr;
+    return b;
+}
+
 void build_layouts(ds_system* s) {
     const ds::SysDev<double>& S = s->sd;
     int64_t off = 0;
@@ -321,10 +415,10 @@ void build_layouts(ds_system* s) {
         de += (size_t)S.K * 4;
         tr += (size_t)S.K * 2 * S.P;
     }
-    w.MOUT = mo; w.MINV = rup((int)mi, 16); w.DETS = rup((int)de, 16); w.TR = tr;
+    w.MOUT = mo; w.MINV = rup(mi, 16); w.DETS = rup(de, 16); w.TR = tr;
     w.XL = (size_t)S.N * (S.h1[0] + S.nch * S.h2[0]) * S.P;
     w.YO = (size_t)rup(S.N * S.h1[1] * 2, 16);
-    w.per_walker = 2 * w.G + 2 * w.MEAN + w.ZB + 2 * w.H2 + w.Q + w.MOUT + w.MINV + w.DETS + w.TR + w.XL + w.YO;
+    w.per_walker = measure([&](Arena<double>& a) { carve<double>(s, a, 1); });
     // value chain: the slot axis carries PV walkers (ds_value.h)
     WsLayout& v = s->wsv;
     const size_t PV = ds::PV;
@@ -344,28 +438,7 @@ void build_layouts(ds_system* s) {
     v.MOUT = mo; v.MINV = 0; v.TR = 0;
     v.DETS = w.DETS * PV;             // DETS stays per walker
     v.PARTM = (size_t)(PV / 5) * h2max * 5 * (S.NP / 16) * ds::PM_SLOTS;
-    v.per_walker = 2 * v.G + 2 * v.MEAN + v.ZB + 2 * v.H2 + v.Q + v.MOUT + v.DETS + v.PARTM;
-}
-
-template <typename T> struct Carve {
-    T *G[2], *MEAN[2], *ZB, *H2[2], *Q, *MOUT, *MINV, *DETS, *TR, *XL, *YO;
-};
-template <typename T> Carve<T> carve(const ds_system* s, void* ws, int64_t Bc) {
-    const WsLayout& w = s->ws;
-    T* p = (T*)ws;
-    Carve<T> c;
-    c.G[0] = p; p += w.G * Bc; c.G[1] = p; p += w.G * Bc;
-    c.MEAN[0] = p; p += w.MEAN * Bc; c.MEAN[1] = p; p += w.MEAN * Bc;
-    c.ZB = p; p += w.ZB * Bc;
-    c.H2[0] = p; p += w.H2 * Bc; c.H2[1] = p; p += w.H2 * Bc;
-    c.Q = p; p += w.Q * Bc;
-    c.MOUT = p; p += w.MOUT * Bc;
-    c.MINV = p; p += w.MINV * Bc;
-    c.DETS = p; p += w.DETS * Bc;
-    c.TR = p; p += w.TR * Bc;
-    c.XL = p; p += w.XL * Bc;
-    c.YO = p; p += w.YO * Bc;
-    return c;
+    v.per_walker = measure([&](Arena<double>& a) { carve_value<double>(s, a, 1); });
 }
 
 // ---------------------------------------------------------------- launch helpers
@@ -647,11 +720,12 @@ int launch_det_trace(const ds_system* s, const ds::SysDev<T>& S, const Carve<T>&
 
 // The forward-Laplacian chain on a chunk of Bc walkers: executes plan_chain's plan.
 template <typename T>
-int run_chain(ds_system* s, const T* params, const T* x, int64_t Bc, void* ws, hipStream_t st, T* out_ke, T* out_logabs,
+int run_chain(ds_system* s, const T* params, const T* x, int64_t Bc, Arena<T> ws, hipStream_t st, T* out_ke, T* out_logabs,
               T* out_phase, DumpReq<T>* dr, T* out_grad = nullptr) {
     const ds::SysDev<T>& S = dev<T>(s);
     const WsLayout& L = s->ws;
-    Carve<T> c = carve<T>(s, ws, Bc);
+    const Carve<T> c = carve<T>(s, ws, Bc);
+    if (!ws.ok) return carve_fail("forward-Laplacian chain");
     auto blk = [&](int i) { return params + s->blocks[i].offset; };
     const int stop = dr ? dr->stop : STOP_NONE;
     ChainPlan<T> plan;
@@ -872,47 +946,6 @@ int run_chain(ds_system* s, const T* params, const T* x, int64_t Bc, void* ws, h
     return 0;
 }
 
-// The value chain (log psi only) on `Bc` walkers = ceil(Bc / PV) groups; see ds_value.h.
-// Buffers of one value-chain pass over ng groups.  The plain pass ping-pongs two G / H2 buffers; the
-// gradient pass keeps every layer's activations (Gl[l] = input of layer l, Gl[n_layers] = orbital-head input).
-template <typename T> struct ValBufs {
-    T* Gl[DS_MAX_LAYERS + 1];
-    T* H2l[DS_MAX_LAYERS + 1];
-    T *MEAN0, *MEANS, *ZB, *Q, *MOUT, *DETS, *PARTM;     // MEANS: spin means of a hidden layer's input (scratch of k_spin_mean)
-    T* PHI[2];              // orbital GEMM output per spin channel (the plain pass reuses ZB for both)
-    T* SORB[2];             // use_last_layer: shared term of the orbital head
-    T* MINV;                // optional inverses, laid out like MOUT (walker-interleaved)
-    bool keep;              // gradient passes: every layer's activations and the raw orbital products PHI stay in memory
-                            // (MOUT may then be null: the orbital matrices themselves are not formed, ds_pretrain_loss_vjp)
-};
-
-template <typename T>
-ValBufs<T> carve_value(ds_system* s, void* ws, int64_t ng) {
-    const ds::SysDev<T>& S = dev<T>(s);
-    const WsLayout& L = s->wsv;
-    ValBufs<T> b{};
-    T* p = (T*)ws;
-    T* G[2]; T* MEAN[2]; T* H2[2];
-    G[0] = p; p += L.G * ng; G[1] = p; p += L.G * ng;
-    MEAN[0] = p; p += L.MEAN * ng; MEAN[1] = p; p += L.MEAN * ng;
-    b.ZB = p; p += L.ZB * ng;
-    H2[0] = p; p += L.H2 * ng; H2[1] = p; p += L.H2 * ng;
-    b.Q = p; p += L.Q * ng;
-    b.MOUT = p; p += L.MOUT * ng;
-    b.DETS = p; p += L.DETS * ng;
-    b.PARTM = p; p += L.PARTM * ng;
-    b.MEAN0 = MEAN[0];
-    b.MEANS = MEAN[1];
-    for (int l = 0; l <= S.n_layers; ++l) { b.Gl[l] = G[l & 1]; b.H2l[l] = H2[l & 1]; }
-    for (int sp = 0; sp < 2; ++sp) {
-        const int ns = sp == 0 ? S.n_up : S.n_dn;
-        b.PHI[sp] = b.ZB;                                            // PHI first, S of the orbital head behind it
-        b.SORB[sp] = b.ZB + (size_t)ns * S.ocols[sp] * ds::PV * ng;
-    }
-    b.MINV = nullptr;
-    return b;
-}
-
 // The value chain (log psi / orbital matrices) on a chunk of Bc walkers.
 template <typename T>
 int run_value_chain(ds_system* s, const T* params, const T* x, int64_t Bc, const ValBufs<T>& vb, hipStream_t st, T* out_logabs,
@@ -935,12 +968,11 @@ int run_value_chain(ds_system* s, const T* params, const T* x, int64_t Bc, const
     const bool fuse_means = S.n_up >= 8 && (S.n_dn >= 8 || S.n_dn == 0) && !(S.n_double >= 1 && s->res2[0]);
     // log psi only: every pair layer in one launch, activations in registers (k_pair_stream_val).  Needs equal pair widths with a
     // kernel instance, no residual on the first pair layer (its input has another width anyway) and the segment sums as the only
-    // consumer of the pair stream.  The sums of layer l go to PARTM (l = 0) and into the second H2 buffer, which this path leaves
-    // unused (a PARTM block is 3/16 of an H2 buffer).
+    // consumer of the pair stream.  The sums of layer l go to vb.PM[l] (carve_value).
     bool fuse_pairs = fuse_means && !vb.keep && s->use_pair_fuse && S.n_double >= 1 && S.n_double <= ds::PS_MAX_LAYERS && !s->res2[0] &&
-                      S.h2[0] % 4 == 0 && (S.h2[1] == 16 || S.h2[1] == 32) && (size_t)(S.n_double - 1) * L.PARTM <= L.H2;
+                      S.h2[0] % 4 == 0 && (S.h2[1] == 16 || S.h2[1] == 32) && vb.pm_fit;
     for (int l = 1; l < S.n_double; ++l) fuse_pairs = fuse_pairs && S.h2[l + 1] == S.h2[1];
-    auto pm_of = [&](int l) -> T* { return (!fuse_pairs || l == 0) ? vb.PARTM : vb.H2l[1] + (size_t)(l - 1) * L.PARTM * ng; };
+    auto pm_of = [&](int l) -> T* { return fuse_pairs ? vb.PM[l] : vb.PARTM; };
     if (fuse_pairs) {
         ds::PairStreamArgs<T> pa{};
         pa.H0 = vb.H2l[0]; pa.Kin0 = S.h2[0]; pa.nl = S.n_double;
@@ -1114,12 +1146,14 @@ template <typename T>
 int logpsi_impl(ds_system* s, const void* params, const void* x, int64_t B, void* out_logabs, void* out_phase, void* ws, int64_t ws_bytes,
                 hipStream_t st) {
     const ds::SysDev<T>& S = dev<T>(s);
-    const int64_t cg = ws_bytes / (int64_t)(s->wsv.per_walker * sizeof(T));
+    const int64_t cg = groups_that_fit(ws_bytes, sizeof(T), PassSize{0, s->wsv.per_walker});
     if (cg < 1) return fail("workspace too small for the value chain: %lld bytes < %zu per group", (long long)ws_bytes, s->wsv.per_walker * sizeof(T));
     const int64_t chunk = cg * ds::PV;
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
         const int64_t Bc = std::min(chunk, B - b0);
-        const ValBufs<T> vb = carve_value<T>(s, ws, (Bc + ds::PV - 1) / ds::PV);
+        Arena<T> a = arena_of<T>(ws, ws_bytes);
+        const ValBufs<T> vb = carve_value<T>(s, a, (Bc + ds::PV - 1) / ds::PV);
+        if (!a.ok) return carve_fail("value chain");
         int rc = run_value_chain<T>(s, (const T*)params, (const T*)x + b0 * 3 * S.N, Bc, vb, st, out_logabs ? (T*)out_logabs + b0 : nullptr,
                                     out_phase ? (T*)out_phase + 2 * b0 : nullptr);
         if (rc) return rc;
@@ -1131,12 +1165,14 @@ template <typename T>
 int orbitals_impl(ds_system* s, const void* params, const void* x, int64_t B, void* out_up, void* out_dn, void* ws, int64_t ws_bytes,
                   hipStream_t st) {
     const ds::SysDev<T>& S = dev<T>(s);
-    const int64_t cg = ws_bytes / (int64_t)(s->wsv.per_walker * sizeof(T));
+    const int64_t cg = groups_that_fit(ws_bytes, sizeof(T), PassSize{0, s->wsv.per_walker});
     if (cg < 1) return fail("workspace too small for the value chain");
     const int64_t chunk = cg * ds::PV;
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
         const int64_t Bc = std::min(chunk, B - b0);
-        const ValBufs<T> vb = carve_value<T>(s, ws, (Bc + ds::PV - 1) / ds::PV);
+        Arena<T> a = arena_of<T>(ws, ws_bytes);
+        const ValBufs<T> vb = carve_value<T>(s, a, (Bc + ds::PV - 1) / ds::PV);
+        if (!a.ok) return carve_fail("value chain");
         T* mout = vb.MOUT;
         int rc = run_value_chain<T>(s, (const T*)params, (const T*)x + b0 * 3 * S.N, Bc, vb, st, nullptr, nullptr);
         if (rc) return rc;
@@ -1163,7 +1199,7 @@ int local_energy_impl(ds_system* s, const void* params, const void* x, int64_t B
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
         const int64_t Bc = std::min(chunk, B - b0);
         const T* xb = (const T*)x + b0 * 3 * S.N;
-        int rc = run_chain<T>(s, (const T*)params, xb, Bc, ws, st, out_ke ? (T*)out_ke + 2 * b0 : nullptr,
+        int rc = run_chain<T>(s, (const T*)params, xb, Bc, arena_of<T>(ws, ws_bytes), st, out_ke ? (T*)out_ke + 2 * b0 : nullptr,
                               out_logabs ? (T*)out_logabs + b0 : nullptr, out_phase ? (T*)out_phase + 2 * b0 : nullptr, nullptr);
         if (rc) return rc;
     }
@@ -1190,7 +1226,7 @@ int logpsi_grad_impl(ds_system* s, const void* params, const void* x, int64_t B,
     if (chunk < 1) return fail("workspace too small");
     for (int64_t b0 = 0; b0 < B; b0 += chunk) {
         const int64_t Bc = std::min(chunk, B - b0);
-        int rc = run_chain<T>(s, (const T*)params, (const T*)x + b0 * 3 * S.N, Bc, ws, st, nullptr, out_logabs ? (T*)out_logabs + b0 : nullptr,
+        int rc = run_chain<T>(s, (const T*)params, (const T*)x + b0 * 3 * S.N, Bc, arena_of<T>(ws, ws_bytes), st, nullptr, out_logabs ? (T*)out_logabs + b0 : nullptr,
                               out_phase ? (T*)out_phase + 2 * b0 : nullptr, nullptr, (T*)out_grad + b0 * 3 * S.N * 2);
         if (rc) return rc;
     }
@@ -1202,7 +1238,6 @@ struct GradPlan {
     size_t wt_total;                 // transposed weights, shared by all groups (elements)
     size_t wlocT[DS_MAX_LAYERS], wshT[DS_MAX_LAYERS], worbT[2];
     int kpad[DS_MAX_LAYERS];         // rows of W * ZBAR per layer (Kloc rounded up to the GEMM's 64-feature blocks)
-    size_t per_group;                // elements per group of PV walkers
     size_t phi_off[2], phi_total, gbar, hb, h2, w2s, sbar, wshorbT[2];
     int korb, korb_pad;                // rows of the orbital-head input (with use_last_layer: h | pair means) and padded
 };
@@ -1230,7 +1265,7 @@ int grad_plan(const ds_system* s, GradPlan* gp) {
         gp->wshorbT[c] = off; if (s->use_last) off += (size_t)S.ocols[c] * S.nch * Kl;
         ocmax = std::max(ocmax, S.ocols[c]);
     }
-    gp->wt_total = rup((int)off, 16);
+    gp->wt_total = rup(off, 16);
     size_t phi = 0;
     for (int c = 0; c < S.nch; ++c) { gp->phi_off[c] = phi; phi += (size_t)(c == 0 ? S.n_up : S.n_dn) * S.ocols[c] * PV; }
     gp->phi_total = phi;
@@ -1239,14 +1274,10 @@ int grad_plan(const ds_system* s, GradPlan* gp) {
     gp->h2 = (size_t)(PV / 5) * h2max * 5 * S.NP;
     gp->w2s = (size_t)(PV / 5) * h2max * h2max;
     gp->sbar = (size_t)std::max(h1max, ocmax) * PV;
-    const WsLayout& v = s->wsv;
-    gp->per_group = (size_t)(S.n_layers + 1) * v.G + (size_t)(S.n_double + 1) * gp->h2 + 3 * v.MEAN + v.ZB + 2 * v.Q + 2 * v.MOUT + v.DETS + v.PARTM +
-                    2 * phi + (size_t)S.K * 2 * PV + gp->gbar + 3 * gp->hb + gp->sbar + 3 * gp->h2 + (size_t)s->nparams +
-                    gp->w2s + (s->use_last ? v.MEAN + (size_t)S.nch * ocmax * PV : 0);
     return 0;
 }
 
-// A gradient pass has three parts, shared by its two entry points (ds_logpsi_vjp, ds_pretrain_loss_vjp):
+// A gradient pass has three parts, shared by its three entry points (ds_logpsi_vjp, ds_kfac_factors, ds_pretrain_loss_vjp):
 //   1. run_value_chain with every activation kept (buffers: carve_grad),
 //   2. a seed that fills PHIBAR / QBAR (seed_logdet: cotangent of log psi; seed_mse: residual of the orbital-matching loss),
 //   3. sweep_from_seed: PHIBAR / QBAR -> every parameter's partial sums -> grad.
@@ -1256,44 +1287,40 @@ template <typename T> struct GradBufs {
 };
 
 template <typename T>
-GradBufs<T> carve_grad(ds_system* s, const GradPlan& gp, T* p, int64_t ng) {
-    const ds::SysDev<T>& S = dev<T>(s);
+GradBufs<T> carve_grad(const ds_system* s, const GradPlan& gp, Arena<T>& a, int64_t ng) {
+    const ds::SysDev<double>& S = s->sd;      // (the dims of sd and sf are the same)
     const WsLayout& V = s->wsv;
-    const int PV = ds::PV, L = S.n_layers;
-    const size_t np = (size_t)s->nparams;
+    const size_t PV = ds::PV;
+    const int L = S.n_layers;
     GradBufs<T> b{};
     ValBufs<T>& vb = b.vb;
     vb.keep = true;
-    for (int l = 0; l <= L; ++l) { vb.Gl[l] = p; p += V.G * ng; }
-    for (int l = 0; l <= S.n_double; ++l) { vb.H2l[l] = p; p += gp.h2 * ng; }
+    for (int l = 0; l <= L; ++l) vb.Gl[l] = a.take(V.G * ng);
+    for (int l = 0; l <= S.n_double; ++l) vb.H2l[l] = a.take(gp.h2 * ng);
     for (int l = S.n_double + 1; l <= L; ++l) vb.H2l[l] = vb.H2l[S.n_double];
-    vb.MEAN0 = p; p += V.MEAN * ng;
-    b.MEANL = p; p += V.MEAN * ng;
+    vb.MEAN0 = a.take(V.MEAN * ng);
+    b.MEANL = a.take(V.MEAN * ng);
     vb.MEANS = b.MEANL;                       // forward scratch; the reverse sweep refills it layer by layer
-    b.MEANBAR = p; p += V.MEAN * ng;
-    vb.ZB = p; p += V.ZB * ng;
-    vb.Q = p; p += V.Q * ng;
-    b.QBAR = p; p += V.Q * ng;
-    vb.MOUT = p; p += V.MOUT * ng;
-    vb.MINV = p; p += V.MOUT * ng;
-    vb.DETS = p; p += V.DETS * ng;
-    vb.PARTM = p; p += V.PARTM * ng;
-    for (int c = 0; c < S.nch; ++c) { vb.PHI[c] = p + gp.phi_off[c] * ng; vb.SORB[c] = nullptr; }
-    p += gp.phi_total * ng;
-    for (int c = 0; c < S.nch; ++c) b.PB[c] = p + gp.phi_off[c] * ng;
-    p += gp.phi_total * ng;
-    b.CW = p; p += (size_t)S.K * 2 * PV * ng;
-    b.GBAR = p; p += gp.gbar * ng;
-    b.HB[0] = p; p += gp.hb * ng; b.HB[1] = p; p += gp.hb * ng;
-    b.ZBAR = p; p += gp.hb * ng;
-    b.SBAR = p; p += gp.sbar * ng;
-    b.H2BAR[0] = p; p += gp.h2 * ng; b.H2BAR[1] = p; p += gp.h2 * ng;
-    b.Z2BAR = p; p += gp.h2 * ng;
-    b.PART = p; p += np * ng;
-    b.W2S = p; p += gp.w2s * ng;       // split partials of the pair-stream weight gradients
+    b.MEANBAR = a.take(V.MEAN * ng);
+    vb.ZB = a.take(V.ZB * ng);
+    vb.Q = a.take(V.Q * ng); b.QBAR = a.take(V.Q * ng);
+    vb.MOUT = a.take(V.MOUT * ng); vb.MINV = a.take(V.MOUT * ng);
+    vb.DETS = a.take(V.DETS * ng); vb.PARTM = a.take(V.PARTM * ng);
+    T* const phi = a.take(gp.phi_total * ng);
+    T* const pb = a.take(gp.phi_total * ng);
+    for (int c = 0; c < S.nch; ++c) { vb.PHI[c] = phi + gp.phi_off[c] * ng; b.PB[c] = pb + gp.phi_off[c] * ng; }
+    b.CW = a.take((size_t)S.K * 2 * PV * ng);
+    b.GBAR = a.take(gp.gbar * ng);
+    for (T*& h : b.HB) h = a.take(gp.hb * ng);
+    b.ZBAR = a.take(gp.hb * ng);
+    b.SBAR = a.take(gp.sbar * ng);
+    for (T*& h : b.H2BAR) h = a.take(gp.h2 * ng);
+    b.Z2BAR = a.take(gp.h2 * ng);
+    b.PART = a.take((size_t)s->nparams * ng);
+    b.W2S = a.take(gp.w2s * ng);              // split partials of the pair-stream weight gradients
     if (s->use_last) {
-        b.MEANBAR2 = p; p += V.MEAN * ng;
-        for (int c = 0; c < S.nch; ++c) { vb.SORB[c] = p; p += (size_t)S.ocols[c] * PV * ng; }
+        b.MEANBAR2 = a.take(V.MEAN * ng);
+        for (int c = 0; c < S.nch; ++c) vb.SORB[c] = a.take((size_t)S.ocols[c] * PV * ng);
     }
     return b;
 }
@@ -1377,7 +1404,7 @@ struct KfacBlockPlan {
 struct KfacPlan {
     std::vector<KfacBlockPlan> blocks;
     int64_t total = 0;               // elements of `factors`
-    size_t p1 = 0, p2 = 0, p3 = 0, aux = 0, per_group = 0;   // per group of PV walkers: partials of P1 / P2 / G and the operand v
+    size_t p1 = 0, p2 = 0, p3 = 0, aux = 0;                  // per group of PV walkers: partials of P1 / P2 / G and the operand v
     int nsplit2 = ds::PV / 5;        // pair layers: waves per 32 x 32 block (one per 5-walker tile, as their weight gradient)
 };
 
@@ -1414,7 +1441,6 @@ int kfac_plan(const ds_system* s, KfacPlan* kp) {
     }
     auto r4 = [](size_t v) { return (v + 3) / 4 * 4; };       // (the operands are read as 4-element vectors)
     kp->p1 = r4(kp->p1); kp->p2 = r4(kp->p2); kp->p3 = r4(kp->p3); kp->aux = r4(kp->aux);
-    kp->per_group = kp->p1 + kp->p2 + kp->p3 + kp->aux;
     return 0;
 }
 
@@ -1650,127 +1676,159 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
     return 0;
 }
 
-// workspace of a gradient pass: [transposed weights | cg groups of GradPlan::per_group] -> groups per chunk
-template <typename T>
-int grad_chunk_groups(const GradPlan& gp, int64_t ws_bytes, int64_t* cg) {
-    *cg = (ws_bytes / (int64_t)sizeof(T) - (int64_t)gp.wt_total) / (int64_t)gp.per_group;
-    if (*cg < 1) return fail("workspace too small for the parameter gradient: %lld bytes", (long long)ws_bytes);
-    return 0;
-}
+// Workspace of a gradient pass over ng groups: [transposed weights | ng groups of carve_grad | KFAC factor pass: ng groups of
+// partials, operand and seed cotangent].  `kp`: the KFAC factor pass; `dets` false: the pretraining pass, which forms no orbital
+// matrices -- its loss partials (N per group) live in the idle MINV buffer.
+template <typename T> struct GradWs {
+    T* WT;
+    GradBufs<T> gb;
+    T *P1, *P2, *P3, *AUX, *cot;     // KFAC factor pass
+    T* LPART;                        // pretraining pass
+};
 
 template <typename T>
-int logpsi_vjp_impl(ds_system* s, const void* params_, const void* x_, int64_t B, const void* cot_, void* grad_, void* out_logabs,
-                    void* out_phase, void* ws, int64_t ws_bytes, hipStream_t st) {
+GradWs<T> carve_grad_pass(const ds_system* s, const GradPlan& gp, const KfacPlan* kp, bool dets, Arena<T>& a, int64_t ng) {
+    GradWs<T> w{};
+    w.WT = a.take(gp.wt_total);
+    w.gb = carve_grad<T>(s, gp, a, ng);
+    if (kp) {
+        a.align(4);                  // k_syrk reads its operands as 4-element vectors
+        w.P1 = a.take(kp->p1 * ng);
+        w.P2 = a.take(kp->p2 * ng);
+        w.P3 = a.take(kp->p3 * ng);
+        w.AUX = a.take(kp->aux * ng);
+        w.cot = a.take((size_t)2 * ds::PV * ng);
+    }
+    if (!dets) {
+        a.part(w.gb.vb.MINV, s->wsv.MOUT * ng, [&](Arena<T>& idle) { w.LPART = idle.take((size_t)s->sd.N * ng); });
+        w.gb.vb.MOUT = w.gb.vb.MINV = nullptr;
+    }
+    return w;
+}
+
+inline PassSize grad_pass_size(const ds_system* s, const GradPlan& gp, const KfacPlan* kp) {
+    auto extent = [&](int64_t ng) { return measure([&](Arena<double>& a) { carve_grad_pass<double>(s, gp, kp, true, a, ng); }); };
+    return PassSize{extent(0), extent(1) - extent(0)};
+}
+
+// ds_vjp_workspace_bytes / ds_kfac_workspace_bytes: the budget of a gradient pass is 32 GiB
+int64_t grad_pass_bytes(const ds_system* s, int64_t B, bool kfac) {
+    GradPlan gp;
+    KfacPlan kp;
+    if (grad_plan(s, &gp) || (kfac && kfac_plan(s, &kp))) return -1;
+    const int64_t esz = s->dtype == 0 ? 8 : 4;
+    const int64_t groups = groups_per_pass(B, esz, grad_pass_size(s, gp, kfac ? &kp : nullptr), (int64_t)32 << 30);
+    return (int64_t)measure([&](Arena<double>& a) { carve_grad_pass<double>(s, gp, kfac ? &kp : nullptr, true, a, groups); }) * esz + 256;
+}
+
+// The driver of the three passes: per chunk of groups the value chain, `seed(gp, w, b0, Bc, first)` (fills PHIBAR / QBAR of the chunk
+// that starts at walker b0), the reverse sweep.  `factors` with `kp`: the KFAC factor pass (ds_kfac_factors).
+template <typename T, typename Seed>
+int grad_pass(ds_system* s, const char* what, const T* params, const T* x_, int64_t B, T* grad, T* out_logabs, T* out_phase,
+              const KfacPlan* kp, T* factors, bool dets, void* ws, int64_t ws_bytes, hipStream_t st, Seed&& seed) {
     const ds::SysDev<T>& S = dev<T>(s);
     const int PV = ds::PV;
     GradPlan gp;
     if (int rc = grad_plan(s, &gp)) return rc;
-    int64_t cg;
-    if (int rc = grad_chunk_groups<T>(gp, ws_bytes, &cg)) return rc;
-    const T* params = (const T*)params_;
-    T* WT = (T*)ws;
-    grad_transposes<T>(s, gp, params, WT, st);
+    const int64_t cg = groups_that_fit(ws_bytes, sizeof(T), grad_pass_size(s, gp, kp));
+    if (cg < 1) return fail("workspace too small for %s: %lld bytes", what, (long long)ws_bytes);
     bool first = true;
     for (int64_t b0 = 0; b0 < B; b0 += cg * PV) {
         const int64_t Bc = std::min<int64_t>(cg * PV, B - b0);
-        const T* x = (const T*)x_ + b0 * 3 * S.N;
-        const GradBufs<T> gb = carve_grad<T>(s, gp, WT + gp.wt_total, (Bc + PV - 1) / PV);
-        if (int rc = run_value_chain<T>(s, params, x, Bc, gb.vb, st, out_logabs ? (T*)out_logabs + b0 : nullptr,
-                                        out_phase ? (T*)out_phase + 2 * b0 : nullptr)) return rc;
-        if (int rc = seed_logdet<T>(s, gp, gb, params, (const T*)cot_ + 2 * b0, Bc, st)) return rc;
-        if (int rc = sweep_from_seed<T>(s, gp, gb, params, WT, x, Bc, first, (T*)grad_, st)) return rc;
+        const T* x = x_ + b0 * 3 * S.N;
+        Arena<T> a = arena_of<T>(ws, ws_bytes);
+        const GradWs<T> w = carve_grad_pass<T>(s, gp, kp, dets, a, (Bc + PV - 1) / PV);
+        if (!a.ok) return carve_fail(what);
+        if (first) grad_transposes<T>(s, gp, params, w.WT, st);
+        if (int rc = run_value_chain<T>(s, params, x, Bc, w.gb.vb, st, out_logabs ? out_logabs + b0 : nullptr,
+                                        out_phase ? out_phase + 2 * b0 : nullptr)) return rc;
+        if (int rc = seed(gp, w, b0, Bc, first)) return rc;
+        const KfacSink<T> ks{kp, w.P1, w.P2, w.P3, w.AUX, factors, B, first};
+        if (int rc = sweep_from_seed<T>(s, gp, w.gb, params, w.WT, x, Bc, first, grad, st, kp ? &ks : nullptr)) return rc;
         first = false;
     }
     HIP_OK(hipGetLastError());
     return 0;
 }
 
-// KFAC factor pass: the value chain, the seed (sqrt2, 0) on every walker, one reverse sweep.
-// workspace: [transposed weights | cg groups of (GradPlan::per_group + KfacPlan::per_group + 2 PV seed entries)]
 template <typename T>
-int kfac_factors_impl(ds_system* s, const void* params_, const void* x_, int64_t B, void* factors_, void* grad_, void* ws, int64_t ws_bytes,
+int logpsi_vjp_impl(ds_system* s, const void* params, const void* x, int64_t B, const void* cot, void* grad, void* out_logabs,
+                    void* out_phase, void* ws, int64_t ws_bytes, hipStream_t st) {
+    return grad_pass<T>(s, "the parameter gradient", (const T*)params, (const T*)x, B, (T*)grad, (T*)out_logabs, (T*)out_phase, nullptr, nullptr,
+                        true, ws, ws_bytes, st, [&](const GradPlan& gp, const GradWs<T>& w, int64_t b0, int64_t Bc, bool) {
+                            return seed_logdet<T>(s, gp, w.gb, (const T*)params, (const T*)cot + 2 * b0, Bc, st);
+                        });
+}
+
+// KFAC factor pass: the value chain, the seed (sqrt2, 0) on every walker, one reverse sweep.
+template <typename T>
+int kfac_factors_impl(ds_system* s, const void* params, const void* x, int64_t B, void* factors, void* grad, void* ws, int64_t ws_bytes,
                       hipStream_t st) {
-    const ds::SysDev<T>& S = dev<T>(s);
-    const int PV = ds::PV;
-    GradPlan gp;
-    if (int rc = grad_plan(s, &gp)) return rc;
     KfacPlan kp;
     if (int rc = kfac_plan(s, &kp)) return rc;
-    const int64_t per_group = (int64_t)gp.per_group + (int64_t)kp.per_group + 2 * PV;
-    const int64_t cg = (ws_bytes / (int64_t)sizeof(T) - (int64_t)gp.wt_total - 4) / per_group;     // (4: alignment of the partials)
-    if (cg < 1) return fail("workspace too small for the KFAC factor pass: %lld bytes", (long long)ws_bytes);
-    const T* params = (const T*)params_;
-    T* WT = (T*)ws;
-    grad_transposes<T>(s, gp, params, WT, st);
-    bool first = true;
-    for (int64_t b0 = 0; b0 < B; b0 += cg * PV) {
-        const int64_t Bc = std::min<int64_t>(cg * PV, B - b0), ng = (Bc + PV - 1) / PV;
-        const T* x = (const T*)x_ + b0 * 3 * S.N;
-        T* base = WT + gp.wt_total;
-        const GradBufs<T> gb = carve_grad<T>(s, gp, base, ng);
-        T* p = WT + (gp.wt_total + gp.per_group * ng + 3) / 4 * 4;       // k_syrk reads its operands as 4-element vectors
-        KfacSink<T> ks{&kp, nullptr, nullptr, nullptr, nullptr, (T*)factors_, B, first};
-        ks.P1 = p; p += kp.p1 * ng;
-        ks.P2 = p; p += kp.p2 * ng;
-        ks.P3 = p; p += kp.p3 * ng;
-        ks.AUX = p; p += kp.aux * ng;
-        T* cot = p;
-        hipLaunchKernelGGL((ds::k_kfac_seed<T>), dim3((unsigned)((Bc + 255) / 256)), dim3(256), 0, st, cot, (long)Bc);
-        if (int rc = run_value_chain<T>(s, params, x, Bc, gb.vb, st, nullptr, nullptr)) return rc;
-        if (int rc = seed_logdet<T>(s, gp, gb, params, cot, Bc, st)) return rc;
-        if (int rc = sweep_from_seed<T>(s, gp, gb, params, WT, x, Bc, first, (T*)grad_, st, &ks)) return rc;
-        first = false;
-    }
-    HIP_OK(hipGetLastError());
-    return 0;
+    return grad_pass<T>(s, "the KFAC factor pass", (const T*)params, (const T*)x, B, (T*)grad, nullptr, nullptr, &kp, (T*)factors, true, ws,
+                        ws_bytes, st, [&](const GradPlan& gp, const GradWs<T>& w, int64_t, int64_t Bc, bool) {
+                            hipLaunchKernelGGL((ds::k_kfac_seed<T>), dim3((unsigned)((Bc + 255) / 256)), dim3(256), 0, st, w.cot, (long)Bc);
+                            return seed_logdet<T>(s, gp, w.gb, (const T*)params, w.cot, Bc, st);
+                        });
 }
 
 // Loss and gradient of the orbital-matching pretraining (reference pretrain.py:70-94): the forward stops behind the orbital
 // head (no orbital matrices, LU, inverses or determinant weights), the seed is the residual against the target
 template <typename T>
-int pretrain_loss_vjp_impl(ds_system* s, const void* params_, const void* x_, int64_t B, const void* target_up, const void* target_dn,
-                           void* out_loss, void* grad_, void* ws, int64_t ws_bytes, hipStream_t st) {
+int pretrain_loss_vjp_impl(ds_system* s, const void* params, const void* x, int64_t B, const void* target_up, const void* target_dn,
+                           void* out_loss, void* grad, void* ws, int64_t ws_bytes, hipStream_t st) {
     const ds::SysDev<T>& S = dev<T>(s);
-    const int PV = ds::PV;
-    GradPlan gp;
-    if (int rc = grad_plan(s, &gp)) return rc;
-    int64_t cg;
-    if (int rc = grad_chunk_groups<T>(gp, ws_bytes, &cg)) return rc;
-    if (B > 0 && (!target_up || (S.n_dn > 0 && !target_dn))) return fail("ds_pretrain_loss_vjp: a target is needed for every spin with electrons");
-    if ((size_t)S.N > s->wsv.MOUT) return fail("ds_pretrain_loss_vjp: internal: no room for the loss partials");
     if (B <= 0) {                                       // the empty batch: zero loss, zero gradient
         HIP_OK(hipMemsetAsync(out_loss, 0, sizeof(double), st));
-        HIP_OK(hipMemsetAsync(grad_, 0, (size_t)s->nparams * sizeof(T), st));
+        HIP_OK(hipMemsetAsync(grad, 0, (size_t)s->nparams * sizeof(T), st));
         return 0;
     }
-    const T* params = (const T*)params_;
-    T* WT = (T*)ws;
-    grad_transposes<T>(s, gp, params, WT, st);
-    bool first = true;
-    for (int64_t b0 = 0; b0 < B; b0 += cg * PV) {
-        const int64_t Bc = std::min<int64_t>(cg * PV, B - b0);
-        const T* x = (const T*)x_ + b0 * 3 * S.N;
-        GradBufs<T> gb = carve_grad<T>(s, gp, WT + gp.wt_total, (Bc + PV - 1) / PV);
-        T* LPART = gb.vb.MINV;                          // the determinant buffers are idle in this pass
-        gb.vb.MOUT = nullptr; gb.vb.MINV = nullptr;
-        if (int rc = run_value_chain<T>(s, params, x, Bc, gb.vb, st, nullptr, nullptr)) return rc;
-        const T* tgt[2] = {(const T*)target_up + (size_t)b0 * S.n_up * S.n_up * 2,
-                           target_dn ? (const T*)target_dn + (size_t)b0 * S.n_dn * S.n_dn * 2 : nullptr};
-        if (int rc = seed_mse<T>(s, gp, gb, params, tgt, Bc, B, LPART, first, (double*)out_loss, st)) return rc;
-        if (int rc = sweep_from_seed<T>(s, gp, gb, params, WT, x, Bc, first, (T*)grad_, st)) return rc;
-        first = false;
-    }
-    HIP_OK(hipGetLastError());
-    return 0;
+    if (!target_up || (S.n_dn > 0 && !target_dn)) return fail("ds_pretrain_loss_vjp: a target is needed for every spin with electrons");
+    return grad_pass<T>(s, "the parameter gradient", (const T*)params, (const T*)x, B, (T*)grad, nullptr, nullptr, nullptr, nullptr, false, ws,
+                        ws_bytes, st, [&](const GradPlan& gp, const GradWs<T>& w, int64_t b0, int64_t Bc, bool first) {
+                            const T* tgt[2] = {(const T*)target_up + (size_t)b0 * S.n_up * S.n_up * 2,
+                                               target_dn ? (const T*)target_dn + (size_t)b0 * S.n_dn * S.n_dn * 2 : nullptr};
+                            return seed_mse<T>(s, gp, w.gb, (const T*)params, tgt, Bc, B, w.LPART, first, (double*)out_loss, st);
+                        });
 }
 
 
 // ------------------------------------------------------------------ Metropolis loop (qmc.py:335-362), ds_mcmc.h
+// Scratch of the three move loops, in front of the chains' workspace: proposal x2 (B,3N) + log|psi(x2)| (B,); the importance-
+// sampled loop adds the complex gradient (B,3N,2), the drifts at x1 / x2, the normal deviates ((B,3N) each), the uniforms (B,) and
+// the two batch maxima
+template <typename T> struct McmcScratch {
+    T *X2, *GC, *G1, *G2, *NZ, *LA2, *UN, *SCR;
+    void* wsv; int64_t wsv_bytes;                        // what is left for the value / energy chain
+};
+template <typename T> McmcScratch<T> carve_mcmc(const ds_system* s, Arena<T>& a, int64_t B) {
+    const size_t n3 = (size_t)B * 3 * s->sd.N;
+    McmcScratch<T> m{};
+    m.X2 = a.take(n3); m.GC = a.take(2 * n3); m.G1 = a.take(n3); m.G2 = a.take(n3); m.NZ = a.take(n3);
+    m.LA2 = a.take((size_t)B); m.UN = a.take((size_t)B); m.SCR = a.take(2);
+    return m;
+}
 inline size_t mcmc_scratch_bytes(const ds_system* s, int64_t B) {
-    const size_t esz = s->dtype == 0 ? 8 : 4;
-    // proposal x2 (B,3N) + log|psi(x2)| (B,); the importance-sampled loop adds the complex gradient (B,3N,2), the drifts at
-    // x1 / x2, the normal deviates (3 x (B,3N)), the uniforms (B,) and the two batch maxima
-    return (((size_t)B * 3 * s->sd.N * 6 + (size_t)B * 2 + 2) * esz + 255) / 256 * 256;
+    return rup(measure([&](Arena<double>& a) { carve_mcmc<double>(s, a, B); }) * (s->dtype == 0 ? 8 : 4), 256);
+}
+
+// What the three loops begin with: the workspace check, the carve, and logprob = 2 f(data) (qmc.py:357) unless lp is valid
+template <typename T>
+int mcmc_begin(ds_system* s, const char* what, const void* params, const T* x, T* lp, int64_t B, int lp_valid, void* ws,
+               int64_t ws_bytes, hipStream_t st, McmcScratch<T>* m) {
+    const size_t head = mcmc_scratch_bytes(s, B);
+    if ((int64_t)head >= ws_bytes) return fail("workspace too small for %s (see ds_mcmc_workspace_bytes)", what);
+    Arena<T> a = arena_of<T>(ws, (int64_t)head);
+    *m = carve_mcmc<T>(s, a, B);
+    if (!a.ok) return carve_fail(what);
+    m->wsv = (char*)ws + head;
+    m->wsv_bytes = ws_bytes - (int64_t)head;
+    if (!lp_valid) {
+        if (int rc = logpsi_impl<T>(s, params, x, B, m->LA2, nullptr, m->wsv, m->wsv_bytes, st)) return rc;
+        hipLaunchKernelGGL((ds::k_scale2<T>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, m->LA2, (long)B, lp);
+    }
+    return 0;
 }
 
 template <typename T>
@@ -1778,28 +1836,21 @@ int mcmc_step_impl(ds_system* s, const void* params, void* x_, void* lp_, int64_
                    uint64_t offset, const void* normals_, const void* uniforms_, int lp_valid, void* n_accept, void* ws,
                    int64_t ws_bytes, hipStream_t st, int first_electron = -1) {
     const ds::SysDev<T>& S = dev<T>(s);
-    const size_t head = mcmc_scratch_bytes(s, B);
-    if ((int64_t)head >= ws_bytes) return fail("workspace too small for ds_mcmc_step (see ds_mcmc_workspace_bytes)");
     T* x = (T*)x_; T* lp = (T*)lp_;
-    T* X2 = (T*)ws; T* LA2 = X2 + (size_t)B * 3 * S.N;
-    void* wsv = (char*)ws + head;
-    const int64_t wsv_bytes = ws_bytes - (int64_t)head;
+    McmcScratch<T> m;
+    if (int rc = mcmc_begin<T>(s, "ds_mcmc_step", params, x, lp, B, lp_valid, ws, ws_bytes, st, &m)) return rc;
     const T* normals = (const T*)normals_; const T* uniforms = (const T*)uniforms_;
     const size_t ne = (size_t)B * S.N;
     const ds::PhiloxKey key{seed, offset};
-    if (!lp_valid) {                                                     // logprob = 2 f(data)   qmc.py:357
-        if (int rc = logpsi_impl<T>(s, params, x, B, LA2, nullptr, wsv, wsv_bytes, st)) return rc;
-        hipLaunchKernelGGL((ds::k_scale2<T>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, LA2, (long)B, lp);
-    }
     for (int i = 0; i < steps; ++i) {                                    // lax.fori_loop(0, nsteps, ...)   :358
         // all-electron move, or (first_electron >= 0) move i displaces electron (first_electron + i) % N only  (qmc.py:266)
         const int only = first_electron < 0 ? -1 : (int)(((int64_t)first_electron + i) % S.N);
         const size_t nstride = (size_t)B * 3 * (only < 0 ? S.N : 1);
         hipLaunchKernelGGL((ds::k_mcmc_propose<T>), dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, S.sim_a, S.sim_ainv, x,
-                           normals ? normals + (size_t)i * nstride : (const T*)nullptr, key, (unsigned long long)i, (T)width, ne, X2,
+                           normals ? normals + (size_t)i * nstride : (const T*)nullptr, key, (unsigned long long)i, (T)width, ne, m.X2,
                            S.N, only);
-        if (int rc = logpsi_impl<T>(s, params, X2, B, LA2, nullptr, wsv, wsv_bytes, st)) return rc;
-        hipLaunchKernelGGL((ds::k_mcmc_accept<T>), dim3((unsigned)((B + 63) / 64)), dim3(256), 0, st, x, lp, X2, LA2,
+        if (int rc = logpsi_impl<T>(s, params, m.X2, B, m.LA2, nullptr, m.wsv, m.wsv_bytes, st)) return rc;
+        hipLaunchKernelGGL((ds::k_mcmc_accept<T>), dim3((unsigned)((B + 63) / 64)), dim3(256), 0, st, x, lp, m.X2, m.LA2,
                            uniforms ? uniforms + (size_t)i * B : (const T*)nullptr, key, (unsigned long long)i, 3 * S.N, 0L, (long)B, (T*)n_accept);
     }
     HIP_OK(hipGetLastError());
@@ -1814,33 +1865,26 @@ int mcmc_importance_impl(ds_system* s, const void* params, void* x_, void* lp_, 
                          uint64_t offset, const void* normals_, const void* uniforms_, int lp_valid, void* n_accept, void* ws,
                          int64_t ws_bytes, hipStream_t st) {
     const ds::SysDev<T>& S = dev<T>(s);
-    const size_t head = mcmc_scratch_bytes(s, B);
-    if ((int64_t)head >= ws_bytes) return fail("workspace too small for ds_mcmc_step_importance (see ds_mcmc_workspace_bytes)");
     const size_t n3 = (size_t)B * 3 * S.N, ne = (size_t)B * S.N;
     T* x = (T*)x_; T* lp = (T*)lp_;
-    T* X2 = (T*)ws; T* GC = X2 + n3; T* G1 = GC + 2 * n3; T* G2 = G1 + n3; T* NZ = G2 + n3; T* LA2 = NZ + n3; T* UN = LA2 + B; T* SCR = UN + B;
-    void* wsv = (char*)ws + head;
-    const int64_t wsv_bytes = ws_bytes - (int64_t)head;
+    McmcScratch<T> m;
+    if (int rc = mcmc_begin<T>(s, "ds_mcmc_step_importance", params, x, lp, B, lp_valid, ws, ws_bytes, st, &m)) return rc;
     const ds::PhiloxKey key{seed, offset};
     const dim3 ge((unsigned)((n3 + 255) / 256)), gn((unsigned)((std::max<size_t>(ne, (size_t)B) + 255) / 256)), blk(256);
-    if (!lp_valid) {                                                     // logprob = 2 f(data)   qmc.py:357
-        if (int rc = logpsi_impl<T>(s, params, x, B, LA2, nullptr, wsv, wsv_bytes, st)) return rc;
-        hipLaunchKernelGGL((ds::k_scale2<T>), dim3((unsigned)((B + 255) / 256)), blk, 0, st, LA2, (long)B, lp);
-    }
     for (int i = 0; i < steps; ++i) {
-        if (int rc = logpsi_grad_impl<T>(s, params, x, B, LA2, nullptr, GC, wsv, wsv_bytes, st)) return rc;          // :111
-        hipLaunchKernelGGL((ds::k_real_part<T>), ge, blk, 0, st, GC, n3, G1);
-        const T* nz = normals_ ? (const T*)normals_ + (size_t)i * n3 : NZ;
-        const T* un = uniforms_ ? (const T*)uniforms_ + (size_t)i * B : UN;
-        if (!normals_) hipLaunchKernelGGL((ds::k_philox_noise<T>), gn, blk, 0, st, key, (unsigned long long)i, ne, (long)B, NZ, UN);
-        hipLaunchKernelGGL((ds::k_max_norm3<T>), dim3(1), dim3(1024), 0, st, G1, ne, SCR);
+        if (int rc = logpsi_grad_impl<T>(s, params, x, B, m.LA2, nullptr, m.GC, m.wsv, m.wsv_bytes, st)) return rc;          // :111
+        hipLaunchKernelGGL((ds::k_real_part<T>), ge, blk, 0, st, m.GC, n3, m.G1);
+        const T* nz = normals_ ? (const T*)normals_ + (size_t)i * n3 : m.NZ;
+        const T* un = uniforms_ ? (const T*)uniforms_ + (size_t)i * B : m.UN;
+        if (!normals_) hipLaunchKernelGGL((ds::k_philox_noise<T>), gn, blk, 0, st, key, (unsigned long long)i, ne, (long)B, m.NZ, m.UN);
+        hipLaunchKernelGGL((ds::k_max_norm3<T>), dim3(1), dim3(1024), 0, st, m.G1, ne, m.SCR);
         hipLaunchKernelGGL((ds::k_mh_propose_ex<T>), dim3((unsigned)((ne + 255) / 256)), blk, 0, st, S.sim_a, S.sim_ainv, 2, x, nz, (T)width,
-                           G1, 0, ne, X2, SCR);                                                                      // :112-115
-        if (int rc = logpsi_grad_impl<T>(s, params, X2, B, LA2, nullptr, GC, wsv, wsv_bytes, st)) return rc;         // :118
-        hipLaunchKernelGGL((ds::k_real_part<T>), ge, blk, 0, st, GC, n3, G2);
-        hipLaunchKernelGGL((ds::k_max_norm3<T>), dim3(1), dim3(1024), 0, st, G2, ne, SCR + 1);
-        hipLaunchKernelGGL((ds::k_mh_accept_ex<T>), dim3((unsigned)B), dim3(64), 0, st, 2, x, lp, X2, LA2, un, nz, (T)width, G1, G2, 0, S.N,
-                           (T*)n_accept, SCR);                                                                       // :119-137
+                           m.G1, 0, ne, m.X2, m.SCR);                                                                      // :112-115
+        if (int rc = logpsi_grad_impl<T>(s, params, m.X2, B, m.LA2, nullptr, m.GC, m.wsv, m.wsv_bytes, st)) return rc;         // :118
+        hipLaunchKernelGGL((ds::k_real_part<T>), ge, blk, 0, st, m.GC, n3, m.G2);
+        hipLaunchKernelGGL((ds::k_max_norm3<T>), dim3(1), dim3(1024), 0, st, m.G2, ne, m.SCR + 1);
+        hipLaunchKernelGGL((ds::k_mh_accept_ex<T>), dim3((unsigned)B), dim3(64), 0, st, 2, x, lp, m.X2, m.LA2, un, nz, (T)width, m.G1, m.G2, 0, S.N,
+                           (T*)n_accept, m.SCR);                                                                       // :119-137
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -1853,27 +1897,20 @@ int mcmc_asymmetric_impl(ds_system* s, const void* params, void* x_, void* lp_, 
                          int n_atoms, uint64_t seed, uint64_t offset, const void* normals_, const void* uniforms_, int lp_valid,
                          void* n_accept, void* ws, int64_t ws_bytes, hipStream_t st) {
     const ds::SysDev<T>& S = dev<T>(s);
-    const size_t head = mcmc_scratch_bytes(s, B);
-    if ((int64_t)head >= ws_bytes) return fail("workspace too small for ds_mcmc_step_asymmetric (see ds_mcmc_workspace_bytes)");
     const size_t n3 = (size_t)B * 3 * S.N, ne = (size_t)B * S.N;
     T* x = (T*)x_; T* lp = (T*)lp_;
-    T* X2 = (T*)ws; T* NZ = X2 + n3; T* LA2 = NZ + n3; T* UN = LA2 + B;
-    void* wsv = (char*)ws + head;
-    const int64_t wsv_bytes = ws_bytes - (int64_t)head;
+    McmcScratch<T> m;
+    if (int rc = mcmc_begin<T>(s, "ds_mcmc_step_asymmetric", params, x, lp, B, lp_valid, ws, ws_bytes, st, &m)) return rc;
     const ds::PhiloxKey key{seed, offset};
     const dim3 gn((unsigned)((std::max<size_t>(ne, (size_t)B) + 255) / 256)), blk(256);
-    if (!lp_valid) {
-        if (int rc = logpsi_impl<T>(s, params, x, B, LA2, nullptr, wsv, wsv_bytes, st)) return rc;
-        hipLaunchKernelGGL((ds::k_scale2<T>), dim3((unsigned)((B + 255) / 256)), blk, 0, st, LA2, (long)B, lp);
-    }
     for (int i = 0; i < steps; ++i) {
-        const T* nz = normals_ ? (const T*)normals_ + (size_t)i * n3 : NZ;
-        const T* un = uniforms_ ? (const T*)uniforms_ + (size_t)i * B : UN;
-        if (!normals_) hipLaunchKernelGGL((ds::k_philox_noise<T>), gn, blk, 0, st, key, (unsigned long long)i, ne, (long)B, NZ, UN);
+        const T* nz = normals_ ? (const T*)normals_ + (size_t)i * n3 : m.NZ;
+        const T* un = uniforms_ ? (const T*)uniforms_ + (size_t)i * B : m.UN;
+        if (!normals_) hipLaunchKernelGGL((ds::k_philox_noise<T>), gn, blk, 0, st, key, (unsigned long long)i, ne, (long)B, m.NZ, m.UN);
         hipLaunchKernelGGL((ds::k_mh_propose_ex<T>), dim3((unsigned)((ne + 255) / 256)), blk, 0, st, S.sim_a, S.sim_ainv, 1, x, nz, (T)width,
-                           (const T*)atoms, n_atoms, ne, X2, (const T*)nullptr);                                     // :200-204
-        if (int rc = logpsi_impl<T>(s, params, X2, B, LA2, nullptr, wsv, wsv_bytes, st)) return rc;                  // :205
-        hipLaunchKernelGGL((ds::k_mh_accept_ex<T>), dim3((unsigned)B), dim3(64), 0, st, 1, x, lp, X2, LA2, un, (const T*)nullptr, (T)width,
+                           (const T*)atoms, n_atoms, ne, m.X2, (const T*)nullptr);                                     // :200-204
+        if (int rc = logpsi_impl<T>(s, params, m.X2, B, m.LA2, nullptr, m.wsv, m.wsv_bytes, st)) return rc;                  // :205
+        hipLaunchKernelGGL((ds::k_mh_accept_ex<T>), dim3((unsigned)B), dim3(64), 0, st, 1, x, lp, m.X2, m.LA2, un, (const T*)nullptr, (T)width,
                            (const T*)atoms, (const T*)nullptr, n_atoms, S.N, (T*)n_accept, (const T*)nullptr);       // :208-222
     }
     HIP_OK(hipGetLastError());
@@ -1949,8 +1986,6 @@ void obs_partial(const ds::ObsArgs& A, const void* x, int64_t B, int N, int G, d
     }
 }
 }  // namespace
-
-// =============================================================================== C ABI
 
 // ------------------------------------------------------------------ KFAC step (ds_kfac.h): damped inverses, preconditioner
 namespace {
@@ -2064,6 +2099,7 @@ namespace ds {
 void set_last_error(const char* msg) { g_err = msg; }
 }  // namespace ds
 
+// =============================================================================== C ABI
 extern "C" {
 
 const char* ds_last_error(void) { return g_err.c_str(); }
@@ -2221,8 +2257,7 @@ int64_t ds_workspace_bytes(const ds_system* s, int64_t B) {
     const int64_t cap = s->chunk_cap;
     int64_t chunk = std::min<int64_t>(std::max<int64_t>(B, 1), cap);
     chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, budget / ((int64_t)s->ws.per_walker * esz)));
-    int64_t groups = std::min<int64_t>((std::max<int64_t>(B, 1) + ds::PV - 1) / ds::PV, 64);
-    groups = std::max<int64_t>(1, std::min<int64_t>(groups, budget / ((int64_t)s->wsv.per_walker * esz)));
+    const int64_t groups = groups_per_pass(B, esz, PassSize{0, s->wsv.per_walker}, budget);
     return std::max((int64_t)s->ws.per_walker * esz * chunk, (int64_t)s->wsv.per_walker * esz * groups) + 256;
 }
 
@@ -2258,13 +2293,7 @@ int ds_logpsi_grad(ds_system* s, const void* params, const void* x, int64_t B, v
 
 int64_t ds_vjp_workspace_bytes(const ds_system* s, int64_t B) {
     if (!s) return -1;
-    GradPlan gp;
-    if (grad_plan(s, &gp)) return -1;
-    const int64_t esz = s->dtype == 0 ? 8 : 4;
-    const int64_t budget = (int64_t)32 << 30;
-    int64_t groups = std::min<int64_t>((std::max<int64_t>(B, 1) + ds::PV - 1) / ds::PV, 64);
-    groups = std::max<int64_t>(1, std::min<int64_t>(groups, budget / ((int64_t)gp.per_group * esz)));
-    return ((int64_t)gp.wt_total + (int64_t)gp.per_group * groups) * esz + 256;
+    return grad_pass_bytes(s, B, false);
 }
 
 int ds_logpsi_vjp(ds_system* s, const void* params, const void* x, int64_t B, const void* cot, void* grad, void* out_logabs,
@@ -2297,14 +2326,7 @@ int ds_kfac_layout(const ds_system* s, ds_kfac_block* blocks, int max_blocks) {
 
 int64_t ds_kfac_workspace_bytes(const ds_system* s, int64_t B) {
     if (!s) return -1;
-    GradPlan gp;
-    KfacPlan kp;
-    if (grad_plan(s, &gp) || kfac_plan(s, &kp)) return -1;
-    const int64_t esz = s->dtype == 0 ? 8 : 4;
-    const int64_t budget = (int64_t)32 << 30, per_group = (int64_t)gp.per_group + (int64_t)kp.per_group + 2 * ds::PV;
-    int64_t groups = std::min<int64_t>((std::max<int64_t>(B, 1) + ds::PV - 1) / ds::PV, 64);
-    groups = std::max<int64_t>(1, std::min<int64_t>(groups, budget / (per_group * esz)));
-    return ((int64_t)gp.wt_total + per_group * groups) * esz + 256;
+    return grad_pass_bytes(s, B, true);
 }
 
 int ds_kfac_factors(ds_system* s, const void* params, const void* x, int64_t B, void* factors, void* grad_seed, void* ws, int64_t ws_bytes,
@@ -2714,11 +2736,11 @@ int64_t ds_debug_stage(ds_system* s, const void* params, const void* x, int64_t 
     int64_t written;
     if (s->dtype == 0) {
         DumpReq<double> dr{stop, (double*)out, out_elems, 0};
-        rc = run_chain<double>(s, (const double*)params, (const double*)x, B, ws, st, nullptr, nullptr, nullptr, &dr);
+        rc = run_chain<double>(s, (const double*)params, (const double*)x, B, arena_of<double>(ws, ws_bytes), st, nullptr, nullptr, nullptr, &dr);
         written = dr.written;
     } else {
         DumpReq<float> dr{stop, (float*)out, out_elems, 0};
-        rc = run_chain<float>(s, (const float*)params, (const float*)x, B, ws, st, nullptr, nullptr, nullptr, &dr);
+        rc = run_chain<float>(s, (const float*)params, (const float*)x, B, arena_of<float>(ws, ws_bytes), st, nullptr, nullptr, nullptr, &dr);
         written = dr.written;
     }
     return rc ? -1 : written;

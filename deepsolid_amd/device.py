@@ -198,15 +198,22 @@ class DeviceSystem:
             raise ValueError(f'walkers must be (B, {3 * self.n}), got {tuple(x.shape)}')
         return x.contiguous()
 
-    def workspace(self, B, max_bytes=None):
-        need = int(self.lib.ds_workspace_bytes(self.handle, int(B)))
+    def _workspace(self, size_fn, *args, max_bytes=None, whole=False):
+        """The cached device workspace, grown to what `size_fn(handle, *args)` reports or to the cap `max_bytes` (the library then
+        walks the batch in more passes) -> its first `need` bytes, or with `whole` all of it.  A cap holds even when an earlier,
+        larger call left a bigger buffer behind: the library sizes its passes by what it is given."""
+        need = int(getattr(self.lib, size_fn)(self.handle, *args))
+        if need < 0:
+            _lib.check(1, size_fn)
         if max_bytes is not None:
             need = min(need, int(max_bytes))
         if self._ws is None or self._ws.numel() < need:
             self._ws = None
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        # a cap holds even when an earlier, larger call left a bigger buffer behind: the library sizes its chunks by what it is given
-        return self._ws if max_bytes is None else self._ws[:need]
+        return self._ws if whole else self._ws[:need]
+
+    def workspace(self, B, max_bytes=None):
+        return self._workspace('ds_workspace_bytes', int(B), max_bytes=max_bytes, whole=max_bytes is None)
 
     def pack_params(self, params):
         """Reference parameter tree (network.py:135-186) -> the flat device buffer of
@@ -394,15 +401,7 @@ class DeviceSystem:
             return (torch.zeros(self.param_count, dtype=self.dtype, device=self.device),
                     torch.empty(0, dtype=self.dtype, device=self.device),
                     torch.empty(0, dtype=torch.complex128 if self.dtype == torch.float64 else torch.complex64, device=self.device))
-        need = int(self.lib.ds_vjp_workspace_bytes(self.handle, int(B)))
-        if need < 0:
-            _lib.check(1, 'ds_vjp_workspace_bytes')
-        if max_bytes is not None:
-            need = min(need, int(max_bytes))      # fewer walker groups per pass (the library chunks the batch)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ws = self._ws[:need]
+        ws = self._workspace('ds_vjp_workspace_bytes', int(B), max_bytes=max_bytes)
         grad = torch.empty(self.param_count, dtype=self.dtype, device=self.device)
         la = torch.empty(B, dtype=self.dtype, device=self.device)
         ph = torch.empty(B, 2, dtype=self.dtype, device=self.device)
@@ -435,15 +434,7 @@ class DeviceSystem:
         if B == 0:
             return (torch.zeros((), dtype=torch.float64, device=self.device),
                     torch.zeros(self.param_count, dtype=self.dtype, device=self.device))
-        need = int(self.lib.ds_pretrain_workspace_bytes(self.handle, int(B)))
-        if need < 0:
-            _lib.check(1, 'ds_pretrain_workspace_bytes')
-        if max_bytes is not None:
-            need = min(need, int(max_bytes))      # fewer walker groups per pass (the library chunks the batch)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ws = self._ws[:need]
+        ws = self._workspace('ds_pretrain_workspace_bytes', int(B), max_bytes=max_bytes)
         loss = torch.empty(1, dtype=torch.float64, device=self.device)
         grad = torch.empty(self.param_count, dtype=self.dtype, device=self.device)
         _lib.check(self.lib.ds_pretrain_loss_vjp(self.handle, _ptr(p), _ptr(x), B, _ptr(tg[0]), _ptr(tg[1] if len(tg) > 1 else None),
@@ -480,15 +471,7 @@ class DeviceSystem:
         p = self.pack_params(params)
         layout = self.kfac_layout()
         total = layout[-1]['g_offset'] + layout[-1]['d_out'] ** 2
-        need = int(self.lib.ds_kfac_workspace_bytes(self.handle, int(B)))
-        if need < 0:
-            _lib.check(1, 'ds_kfac_workspace_bytes')
-        if max_bytes is not None:
-            need = min(need, int(max_bytes))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ws = self._ws[:need]
+        ws = self._workspace('ds_kfac_workspace_bytes', int(B), max_bytes=max_bytes)
         flat = torch.empty(total, dtype=self.dtype, device=self.device)
         grad = torch.empty(self.param_count, dtype=self.dtype, device=self.device) if want_grad else None
         _lib.check(self.lib.ds_kfac_factors(self.handle, _ptr(p), _ptr(x), B, _ptr(flat), _ptr(grad), _ptr(ws), ws.numel(),
@@ -503,15 +486,6 @@ class DeviceSystem:
         return [(flat[b['a_offset']:b['a_offset'] + b['d_in'] ** 2].view(b['d_in'], b['d_in']),
                  flat[b['g_offset']:b['g_offset'] + b['d_out'] ** 2].view(b['d_out'], b['d_out'])) for b in layout]
 
-    def _kfac_step_ws(self):
-        need = int(self.lib.ds_kfac_step_workspace_bytes(self.handle))
-        if need < 0:
-            _lib.check(1, 'ds_kfac_step_workspace_bytes')
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws[:need]
-
     def kfac_inverses(self, factors_flat, ema_weight, damping):
         """Damped inverses of every block's factors (`ds_kfac_inverses`, reference utils.py:155-218): `factors_flat` holds the raw
         moving-average arrays in the flat layout of `kfac_factors(flat=True)`, their value is array / `ema_weight`; `damping` is
@@ -521,7 +495,7 @@ class DeviceSystem:
         f = factors_flat.to(device=self.device, dtype=self.dtype).contiguous()
         if f.numel() != total:
             raise ValueError(f'factors must hold {total} elements, got {f.numel()}')
-        ws = self._kfac_step_ws()
+        ws = self._workspace('ds_kfac_step_workspace_bytes')
         out = torch.empty(total, dtype=self.dtype, device=self.device)
         _lib.check(self.lib.ds_kfac_inverses(self.handle, _ptr(f), float(ema_weight), float(damping), _ptr(out), _ptr(ws), ws.numel(),
                                              _stream()), 'ds_kfac_inverses')
@@ -537,7 +511,7 @@ class DeviceSystem:
         v = v_flat.to(device=self.device, dtype=self.dtype).contiguous()
         if inv.numel() != total or v.numel() != nv:
             raise ValueError(f'inverses / v must hold {total} / {nv} elements, got {inv.numel()} / {v.numel()}')
-        ws = self._kfac_step_ws()
+        ws = self._workspace('ds_kfac_step_workspace_bytes')
         out = torch.empty(nv, dtype=self.dtype, device=self.device)
         sq = torch.empty(len(layout), dtype=torch.float64, device=self.device)
         _lib.check(self.lib.ds_kfac_precondition(self.handle, _ptr(inv), _ptr(v), _ptr(out), _ptr(sq), _ptr(ws), ws.numel(), _stream()),
@@ -731,32 +705,29 @@ class DeviceSystem:
             if tuple(normals.shape) != (steps, B, width3) or tuple(uniforms.shape) != (steps, B):
                 raise ValueError('explicit noise must be normals (steps, B, 3N) -- (steps, B, 3) for one-electron moves -- '
                                  'and uniforms (steps, B)')
-        need = int(self.lib.ds_mcmc_workspace_bytes(self.handle, int(B)))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = self._workspace('ds_mcmc_workspace_bytes', int(B), whole=True)
         if atoms is not None:
             atoms = torch.as_tensor(atoms, dtype=self.dtype, device=self.device).reshape(-1, 3).contiguous()
             _lib.check(self.lib.ds_mcmc_step_asymmetric(
                 self.handle, _ptr(p), _ptr(x), _ptr(lp), B, int(steps), float(width), _ptr(atoms), int(atoms.shape[0]),
                 int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), _ptr(normals), _ptr(uniforms), int(bool(lp_valid)),
-                _ptr(n_accept), _ptr(self._ws), self._ws.numel(), _stream()), 'ds_mcmc_step_asymmetric')
+                _ptr(n_accept), _ptr(ws), ws.numel(), _stream()), 'ds_mcmc_step_asymmetric')
             return n_accept
         if importance:
             _lib.check(self.lib.ds_mcmc_step_importance(
                 self.handle, _ptr(p), _ptr(x), _ptr(lp), B, int(steps), float(width), int(seed) & (2 ** 64 - 1),
-                int(offset) & (2 ** 64 - 1), _ptr(normals), _ptr(uniforms), int(bool(lp_valid)), _ptr(n_accept), _ptr(self._ws),
-                self._ws.numel(), _stream()), 'ds_mcmc_step_importance')
+                int(offset) & (2 ** 64 - 1), _ptr(normals), _ptr(uniforms), int(bool(lp_valid)), _ptr(n_accept), _ptr(ws),
+                ws.numel(), _stream()), 'ds_mcmc_step_importance')
             return n_accept
         if first_electron is not None:
             _lib.check(self.lib.ds_mcmc_step_one_electron(
                 self.handle, _ptr(p), _ptr(x), _ptr(lp), B, int(steps), int(first_electron), float(width), int(seed) & (2 ** 64 - 1),
-                int(offset) & (2 ** 64 - 1), _ptr(normals), _ptr(uniforms), int(bool(lp_valid)), _ptr(n_accept), _ptr(self._ws),
-                self._ws.numel(), _stream()), 'ds_mcmc_step_one_electron')
+                int(offset) & (2 ** 64 - 1), _ptr(normals), _ptr(uniforms), int(bool(lp_valid)), _ptr(n_accept), _ptr(ws),
+                ws.numel(), _stream()), 'ds_mcmc_step_one_electron')
             return n_accept
         _lib.check(self.lib.ds_mcmc_step(self.handle, _ptr(p), _ptr(x), _ptr(lp), B, int(steps), float(width),
                                          int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), _ptr(normals), _ptr(uniforms),
-                                         int(bool(lp_valid)), _ptr(n_accept), _ptr(self._ws), self._ws.numel(), _stream()),
+                                         int(bool(lp_valid)), _ptr(n_accept), _ptr(ws), ws.numel(), _stream()),
                    'ds_mcmc_step')
         return n_accept
 
