@@ -19,6 +19,7 @@
 #include "ds_mcmc.h"
 #include "ds_obs.h"
 #include "ds_realspace.h"
+#include "ds_onebody.h"
 #include "ds_i8.h"
 
 // the per-slot-tile-count kernel instances live in ds_tiles_inst.hip (five slot-tile ranges x two element types)
@@ -1857,6 +1858,74 @@ int mcmc_step_impl(ds_system* s, const void* params, void* x_, void* lp_, int64_
     return 0;
 }
 
+// ------------------------------------------------------------------ one-body ratios and n(k), ds_onebody.h
+// Workspace of ds_one_body_ratios for B walkers and chunks of ng groups of PV displaced configurations.  Shared by all chunks:
+// log|psi(R)| (B,), phase(R) (B,2) and the call's running sums (one row of float64, taken as 2 elements per double: room in
+// either element size).  Per chunk: one row of float64 partials per group, the displaced rows, their log|psi| / phase, and the value chain's buffers for ng groups (on a 64-element
+// border), which also serve the forward of the undisplaced walkers.
+template <typename T> struct OneBodyWs {
+    T *LA0, *PH0, *XD, *LA, *PH;
+    double *ACC, *PART;
+    void* wsv; int64_t wsv_bytes;
+};
+template <typename T> OneBodyWs<T> carve_onebody(const ds_system* s, Arena<T>& a, int64_t B, int64_t ng) {
+    const size_t nc = (size_t)ng * ds::PV;
+    OneBodyWs<T> w{};
+    w.LA0 = a.take((size_t)B); w.PH0 = a.take(2 * (size_t)B);
+    a.align(2);
+    w.ACC = (double*)a.take(2 * (size_t)ds::OB_ROW);
+    w.PART = (double*)a.take(2 * (size_t)ng * ds::OB_ROW);
+    w.XD = a.take(nc * 3 * s->sd.N); w.LA = a.take(nc); w.PH = a.take(2 * nc);
+    a.align(64);
+    w.wsv = a.take(s->wsv.per_walker * (size_t)ng);
+    w.wsv_bytes = (int64_t)(s->wsv.per_walker * (size_t)ng * sizeof(T));
+    return w;
+}
+inline int64_t onebody_bytes(const ds_system* s, int64_t B, int64_t ng) {
+    return (int64_t)measure([&](Arena<double>& a) { carve_onebody<double>(s, a, B, ng); }) * (s->dtype == 0 ? 8 : 4);
+}
+// groups per chunk: at most 65535 configurations (the grid limit of the chains)
+constexpr int64_t OB_MAX_GROUPS = 65535 / ds::PV;
+
+template <typename T>
+int one_body_impl(ds_system* s, const void* params, const void* x_, int64_t B, int M, int first, uint64_t seed, uint64_t offset,
+                  const void* shifts_, const double* kvec, int n_k, double* nk_sums, void* out_ratio, void* out_shift,
+                  int64_t* n_bad, void* ws, int64_t ws_bytes, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const T* x = (const T*)x_; const T* shifts = (const T*)shifts_;
+    const int64_t total = B * (int64_t)M;
+    // the chunk length follows from the workspace: the largest number of groups whose layout fits (the layout is linear in ng up
+    // to its two alignment pads, so the estimate is at most a few groups high)
+    const int64_t fixed = onebody_bytes(s, B, 0), per = onebody_bytes(s, B, 1) - fixed;
+    int64_t ng = std::min<int64_t>({(ws_bytes - fixed) / per + 1, OB_MAX_GROUPS, (total + ds::PV - 1) / ds::PV});
+    while (ng >= 1 && onebody_bytes(s, B, ng) > ws_bytes) --ng;
+    if (ng < 1) return fail("workspace too small for ds_one_body_ratios: %lld bytes < %lld for one group of %d configurations",
+                            (long long)ws_bytes, (long long)onebody_bytes(s, B, 1), ds::PV);
+    Arena<T> a = arena_of<T>(ws, ws_bytes);
+    const OneBodyWs<T> w = carve_onebody<T>(s, a, B, ng);
+    if (!a.ok) return carve_fail("one-body ratios");
+    if (int rc = logpsi_impl<T>(s, params, x, B, w.LA0, w.PH0, w.wsv, w.wsv_bytes, st)) return rc;
+    ds::OneBodyArgs A;
+    for (int i = 0; i < 9; ++i) A.a[i] = s->d.sim_a[i];
+    A.key = ds::PhiloxKey{seed, offset};
+    A.M = M; A.N = S.N; A.n_up = S.n_up; A.first = first;
+    const int64_t chunk = ng * ds::PV;
+    for (int64_t g0 = 0; g0 < total; g0 += chunk) {
+        A.g0 = g0; A.n = std::min(chunk, total - g0);
+        const int64_t groups = (A.n + ds::OB_GROUP - 1) / ds::OB_GROUP;
+        hipLaunchKernelGGL((ds::k_onebody_propose<T>), dim3((unsigned)((A.n * S.N + 255) / 256)), dim3(256), 0, st, A, x, shifts, w.XD,
+                           (T*)out_shift);
+        if (int rc = logpsi_impl<T>(s, params, w.XD, A.n, w.LA, w.PH, w.wsv, w.wsv_bytes, st)) return rc;
+        hipLaunchKernelGGL((ds::k_onebody_accumulate<T>), dim3((unsigned)groups), dim3(64 * ds::OB_WAVES), 0, st, A, shifts, (const T*)w.LA0,
+                           (const T*)w.PH0, (const T*)w.LA, (const T*)w.PH, kvec, n_k, (T*)out_ratio, w.PART);
+        if (n_k > 0 || n_bad)
+            hipLaunchKernelGGL(ds::k_onebody_final, dim3((unsigned)((4 * n_k + 2 + 255) / 256)), dim3(256), 0, st, (const double*)w.PART,
+                               (long long)groups, n_k, g0 == 0 ? 1 : 0, g0 + chunk >= total ? 1 : 0, w.ACC, nk_sums, (long long*)n_bad);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 // Drift-biased importance sampling (qmc.importance_update, qmc.py:83-150, as make_mcmc_step drives it): per move the drift
 // grad log|psi| at x1, the proposal x2 = wrap(x1 + w N + w^2 limdrift(g1)), (log|psi|, drift) at x2, and the selection with
 // the forward / reverse proposal densities -- the kernels of ds_mh_propose_ex / ds_mh_accept_ex (mode 2), enqueued back to back.
@@ -2685,6 +2754,38 @@ int ds_mcmc_step_importance(ds_system* s, const void* params, void* x, void* lp,
                                                         lp_valid, n_accept, ws, ws_bytes, st)
                          : mcmc_importance_impl<float>(s, params, x, lp, B, steps, width, philox_seed, philox_offset, normals, uniforms,
                                                        lp_valid, n_accept, ws, ws_bytes, st);
+}
+
+int64_t ds_one_body_workspace_bytes(const ds_system* s, int64_t B, int n_samples) {
+    if (!s || B < 1 || n_samples < 1) return -1;
+    // as many groups per chunk as ds_workspace_bytes gives the value chain of B * n_samples walkers
+    const int64_t esz = s->dtype == 0 ? 8 : 4, total = B * (int64_t)n_samples;
+    int64_t budget = (int64_t)80 << 30;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0)
+        budget = std::min<int64_t>(budget, std::max<int64_t>((int64_t)(free_b / 10 * 4), (int64_t)1 << 30));
+    const int64_t fixed = onebody_bytes(s, B, 0), per = onebody_bytes(s, B, 1) - fixed;
+    const int64_t ng = std::min(groups_per_pass(total, esz, PassSize{0, (size_t)(per / esz)}, budget), OB_MAX_GROUPS);
+    return onebody_bytes(s, B, ng);
+}
+
+int ds_one_body_ratios(ds_system* s, const void* params, const void* x, int64_t B, int n_samples, int first_electron,
+                       uint64_t philox_seed, uint64_t philox_offset, const void* shifts, const double* kvec, int n_k, double* nk_sums,
+                       void* out_ratio, void* out_shift, int64_t* n_bad, void* ws, int64_t ws_bytes, void* stream) {
+    if (s) ++s->call_seq;
+    if (!s || !params || !x || !ws) return fail("null argument");
+    if (B < 1) return fail("ds_one_body_ratios: B must be >= 1 (got %lld)", (long long)B);
+    if (n_samples < 1) return fail("ds_one_body_ratios: n_samples must be >= 1 (got %d)", n_samples);
+    if (first_electron < 0 || first_electron >= s->sd.N)
+        return fail("ds_one_body_ratios: first_electron must be in 0..%d (got %d)", s->sd.N - 1, first_electron);
+    if (n_k < 0 || n_k > ds::OB_MAX_K) return fail("ds_one_body_ratios: n_k must be in 0..%d (got %d)", ds::OB_MAX_K, n_k);
+    if (n_k > 0 && (!kvec || !nk_sums)) return fail("ds_one_body_ratios: n_k = %d needs kvec and nk_sums", n_k);
+    if (n_k == 0 && !out_ratio) return fail("ds_one_body_ratios: n_k is 0 and out_ratio is null, nothing to write");
+    hipStream_t st = (hipStream_t)stream;
+    return s->dtype == 0 ? one_body_impl<double>(s, params, x, B, n_samples, first_electron, philox_seed, philox_offset, shifts, kvec,
+                                                 n_k, nk_sums, out_ratio, out_shift, n_bad, ws, ws_bytes, st)
+                         : one_body_impl<float>(s, params, x, B, n_samples, first_electron, philox_seed, philox_offset, shifts, kvec,
+                                                n_k, nk_sums, out_ratio, out_shift, n_bad, ws, ws_bytes, st);
 }
 
 int ds_energy_stats(ds_system* s, const void* ke, const void* ewald, int64_t B, double* out_stats, void* stream) {

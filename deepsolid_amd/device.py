@@ -731,6 +731,45 @@ class DeviceSystem:
                    'ds_mcmc_step')
         return n_accept
 
+    def one_body_ratios(self, params, x, n_samples, kvec=None, first_electron=0, seed=0, offset=0, shifts=None, nk_sums=None,
+                        want_ratios=False, want_shifts=False, max_bytes=None):
+        """`ds_one_body_ratios`: per walker `n_samples` ratios q = psi(R') / psi(R) with electron (first_electron + m) % N moved by a
+        shift uniform in the simulation cell (in-kernel Philox stream (seed, offset); `shifts` (B, M, 3) replays given ones), folded
+        into the momentum sums nk_sums[spin][k] += q exp(-i k.s) for the Cartesian points `kvec` (n_k, 3), n_k <= 512.
+        `nk_sums`: float64 device tensor (2, n_k, 2) that is ADDED to (None: a fresh zero one).  `max_bytes` caps the workspace:
+        the library then walks the samples in more chunks, with bit-identical results.
+        -> dict(nk_sums (2, n_k, 2) or None without kvec, n_bad (2,) int64 device tensor: samples left out because q was not
+        finite, ratios (B, M) complex with `want_ratios`, shifts (B, M, 3) with `want_shifts`).  No host synchronisation."""
+        x = self._check_x(x)
+        B, M = x.shape[0], int(n_samples)
+        p = self.pack_params(params)
+        kv = None
+        n_k = 0
+        if kvec is not None:
+            kv = kvec if isinstance(kvec, torch.Tensor) else torch.as_tensor(np.asarray(kvec, dtype=np.float64))
+            kv = kv.to(device=self.device, dtype=torch.float64).reshape(-1, 3).contiguous()
+            n_k = int(kv.shape[0])
+        if n_k:
+            if nk_sums is None:
+                nk_sums = torch.zeros(2, n_k, 2, dtype=torch.float64, device=self.device)
+            elif not (nk_sums.is_cuda and nk_sums.dtype == torch.float64 and nk_sums.is_contiguous() and tuple(nk_sums.shape) == (2, n_k, 2)):
+                raise ValueError(f'nk_sums must be a contiguous float64 device tensor of shape (2, {n_k}, 2)')
+        else:
+            kv = nk_sums = None
+        if shifts is not None:
+            shifts = shifts.to(device=self.device, dtype=self.dtype).contiguous()
+            if tuple(shifts.shape) != (B, M, 3):
+                raise ValueError(f'shifts must be ({B}, {M}, 3), got {tuple(shifts.shape)}')
+        ratios = torch.empty(B, M, 2, dtype=self.dtype, device=self.device) if want_ratios else None
+        out_s = torch.empty(B, M, 3, dtype=self.dtype, device=self.device) if want_shifts else None
+        n_bad = torch.zeros(2, dtype=torch.int64, device=self.device)
+        ws = self._workspace('ds_one_body_workspace_bytes', int(B), M, max_bytes=max_bytes) if B >= 1 and M >= 1 else \
+            self.workspace(max(B, 1))                  # (the library refuses B < 1 / n_samples < 1 itself)
+        _lib.check(self.lib.ds_one_body_ratios(self.handle, _ptr(p), _ptr(x), B, M, int(first_electron), int(seed) & (2 ** 64 - 1),
+                                               int(offset) & (2 ** 64 - 1), _ptr(shifts), _ptr(kv), n_k, _ptr(nk_sums), _ptr(ratios),
+                                               _ptr(out_s), _ptr(n_bad), _ptr(ws), ws.numel(), _stream()), 'ds_one_body_ratios')
+        return dict(nk_sums=nk_sums, n_bad=n_bad, ratios=torch.view_as_complex(ratios) if want_ratios else None, shifts=out_s)
+
     def energy_stats(self, ke, ew):
         """`ds_energy_stats`: (8,) float64 = [sum Re E_L, sum Im E_L, sum |E_L|^2, n, n_nonfinite, sum Re ke, sum Im ke, sum ew]."""
         out = torch.empty(8, dtype=torch.float64, device=self.device)

@@ -345,3 +345,176 @@ class RealSpaceAccumulator:
         rank only and start the others empty, or the old counts are summed once per rank."""
         with np.load(path) as f:
             return cls.from_state_dict({k: f[k] for k in f.files})
+
+
+# ------------------------------------------------------------------ momentum distribution (csrc/ds_onebody.h)
+# The reference has no off-diagonal estimator; the conventions of this section are this project's own (DESIGN.md section 16).
+def momentum_kpoints(simulation_cell, klist, shells=1):
+    """The Bloch-allowed wave vectors k = k_t + n . G_S of a network with the k list `klist` in the simulation cell, for
+    |n_j| <= shells: k_t is the first entry of `klist` (all entries differ by supercell reciprocal vectors, so any entry spans
+    the same set), G_S are the rows of 2 pi inv(a)^T.  -> (k (n_k, 3) float64, n (n_k, 3) int64), n = 0 first, the others in
+    lexicographic order.  At most 512 points (shells <= 3): the limit of one `ds_one_body_ratios` call."""
+    shells = int(shells)
+    if not 0 <= shells <= 3:
+        raise ValueError(f'shells = {shells}: 0 <= shells <= 3 is supported ((2 shells + 1)^3 <= 512 points per call)')
+    kl = [np.asarray(k, dtype=np.float64).reshape(-1, 3) for k in klist]
+    kt = np.concatenate(kl, axis=0)[0]
+    g = 2.0 * np.pi * np.linalg.inv(np.asarray(simulation_cell.a, dtype=np.float64).reshape(3, 3)).T
+    r = np.arange(-shells, shells + 1)
+    n = np.stack([m.ravel() for m in np.meshgrid(r, r, r, indexing='ij')], axis=1).astype(np.int64)
+    zero = np.all(n == 0, axis=1)
+    n = np.concatenate([n[zero], n[~zero]], axis=0)
+    return kt[None, :] + n @ g, n
+
+
+class MomentumDistribution:
+    """Spin-resolved momentum distribution n_s(k) of a network's wavefunction, accumulated on the device over any number of walker
+    batches: an accumulator for `run_inference(accumulators=...)`.  Every `update` is ONE `ds_one_body_ratios` call that moves,
+    per walker, `samples_per_walker` electrons in turn (default N: one shift per electron) by shifts uniform in the simulation
+    cell and adds q exp(-i k.s) to float64 sums; nothing is read back.  `net`: the object `make_solid_fermi_net` returns (or its
+    `.apply`); `kpoints`: (k (n_k, 3), n (n_k, 3)) as `momentum_kpoints` returns them, None: that function with `shells`.
+    The in-kernel noise is the Philox stream (seed, offset): the offset advances by 1 per update, the seed is decorrelated over
+    the ranks the way `inference._rank_generator` does it."""
+
+    def __init__(self, net, params, kpoints=None, shells=1, samples_per_walker=None, seed=0):
+        self.apply = getattr(net, 'apply', net)
+        self.params = params
+        cell = self.apply.simulation_cell
+        self.nelec = (int(cell.nelec[0]), int(cell.nelec[1]))
+        k, n = momentum_kpoints(cell, self.apply.klist, shells) if kpoints is None else kpoints
+        self._setup(k, n, samples_per_walker)
+        self.seed = (int(seed) * max(1, constants.world_size()) + constants.rank()) % (1 << 63)
+
+    def _setup(self, k, n, samples_per_walker):
+        self.kpoints = np.ascontiguousarray(np.asarray(k, dtype=np.float64).reshape(-1, 3))
+        self.k_int = np.ascontiguousarray(np.asarray(n, dtype=np.int64).reshape(-1, 3))
+        if not 1 <= len(self.kpoints) <= 512 or len(self.k_int) != len(self.kpoints):
+            raise ValueError(f'MomentumDistribution: between 1 and 512 k points (with one integer triple each) are supported, '
+                             f'got {len(self.kpoints)} / {len(self.k_int)}')
+        n_el = sum(self.nelec)
+        self.samples_per_walker = n_el if samples_per_walker is None else int(samples_per_walker)
+        if self.samples_per_walker < 1:
+            raise ValueError(f'samples_per_walker = {samples_per_walker} must be >= 1')
+        self.sums = torch.zeros(2, len(self.kpoints), 2, dtype=torch.float64)      # moved to the walkers' device by the first update
+        self.n_bad = torch.zeros(2, dtype=torch.int64)
+        self.samples = np.zeros(2, dtype=np.int64)
+        self.offset = 0
+        self.first_electron = 0
+        self.seed = 0
+        self.reduced = False
+        self._kdev = None
+
+    # ---- accumulation
+    def update(self, data):
+        """Add `samples_per_walker` ratios of every walker of `data` (B, 3N) to the sums: one library call, no device -> host
+        copy.  The samples per spin are counted on the host: they follow from first_electron alone."""
+        if self.apply is None:
+            raise RuntimeError('MomentumDistribution.update: a loaded accumulator has no network; merge it into one that has')
+        if self.reduced:
+            raise RuntimeError('MomentumDistribution.update after reduce(): the sums are already summed over the ranks')
+        n_el, m = sum(self.nelec), self.samples_per_walker
+        if data.shape[-1] != 3 * n_el:
+            raise ValueError(f'walkers have {data.shape[-1]} coordinates, the cell has {n_el} electrons')
+        x = data.reshape(-1, 3 * n_el)
+        sysd = self.apply.system
+        if self.sums.device != x.device:
+            self.sums, self.n_bad = self.sums.to(x.device), self.n_bad.to(x.device)
+        if self._kdev is None or self._kdev.device != x.device:
+            self._kdev = torch.as_tensor(self.kpoints).to(x.device)
+        out = sysd.one_body_ratios(self.params, x, m, kvec=self._kdev, first_electron=self.first_electron, seed=self.seed,
+                                   offset=self.offset, nk_sums=self.sums)
+        self.n_bad += out['n_bad']
+        up = int(np.count_nonzero((self.first_electron + np.arange(m)) % n_el < self.nelec[0]))
+        self.samples += np.asarray([up, m - up], dtype=np.int64) * int(x.shape[0])
+        self.offset += 1
+        self.first_electron = (self.first_electron + m) % n_el
+
+    def _same_setup(self, other):
+        return self.nelec == other.nelec and np.array_equal(self.kpoints, other.kpoints) and np.array_equal(self.k_int, other.k_int)
+
+    def merge(self, other):
+        """Add the sums, sample counts and bad counts of another accumulator with the same electrons and k list.  Both sides must
+        be in the same state (rank-local or summed over the ranks), as for `RealSpaceAccumulator.merge`."""
+        if not self._same_setup(other):
+            raise ValueError('MomentumDistribution.merge: the two accumulators differ in electron numbers or k points')
+        if self.reduced != other.reduced and constants.world_size() > 1:
+            raise ValueError('MomentumDistribution.merge: one side is summed over the ranks and the other is rank-local')
+        self.sums = self.sums + other.sums.to(self.sums.device)
+        self.n_bad = self.n_bad + other.n_bad.to(self.n_bad.device)
+        self.samples = self.samples + other.samples
+        return self
+
+    def reduce(self):
+        """Sum the sums, the bad counts and the sample counts over the ranks in ONE packed float64 all-reduce (counts below 2^53
+        are exact; the identity at world size 1).  Once per accumulator: a second call raises."""
+        if self.reduced:
+            raise RuntimeError('MomentumDistribution.reduce was already called: reducing twice would count every rank again')
+        if constants.world_size() > 1:
+            dev = self.sums.device if self.sums.is_cuda else torch.device('cuda' if torch.cuda.is_available() else 'cpu')
+            n = self.sums.numel()
+            packed = torch.cat([self.sums.reshape(-1).to(dev), self.n_bad.to(dev, torch.float64),
+                                torch.as_tensor(self.samples, dtype=torch.float64, device=dev)])
+            packed = constants.psum_if_pmap(packed)
+            self.sums = packed[:n].reshape(self.sums.shape).clone()
+            self.n_bad = packed[n:n + 2].round().to(torch.int64)
+            self.samples = packed[n + 2:n + 4].round().cpu().numpy().astype(np.int64)
+        self.reduced = True
+        return self
+
+    # ---- normalisation (host)
+    def momentum_distribution(self):
+        """(2, n_k) complex128: n_s(k) = N_s sums_s(k) / (samples on spin s - bad samples on spin s); the real part is the
+        estimate, the imaginary part vanishes in expectation.  A spin without electrons is 0, one without good samples NaN."""
+        s = self.sums.detach().cpu().numpy()
+        good = self.samples - self.n_bad.detach().cpu().numpy()
+        out = np.zeros((2, len(self.kpoints)), dtype=np.complex128)
+        for sp in range(2):
+            if self.nelec[sp] > 0:
+                out[sp] = self.nelec[sp] * (s[sp, :, 0] + 1j * s[sp, :, 1]) / good[sp] if good[sp] > 0 else np.nan
+        return out
+
+    # ---- persistence
+    def state_dict(self):
+        """Plain numpy arrays: the sums and counts, the k list they belong to and where the noise stream stands."""
+        return {'sums': self.sums.detach().cpu().numpy().copy(), 'samples': self.samples.copy(),
+                'n_bad': self.n_bad.detach().cpu().numpy().copy(), 'kpoints': self.kpoints.copy(), 'k_int': self.k_int.copy(),
+                'nelec': np.asarray(self.nelec, np.int64), 'samples_per_walker': np.int64(self.samples_per_walker),
+                'offset': np.int64(self.offset), 'first_electron': np.int64(self.first_electron), 'reduced': np.bool_(self.reduced)}
+
+    def load_state_dict(self, sd):
+        """Replace the sums, counts and stream position by those of `sd` (same electrons and k list); the accumulator is
+        rank-local and open for `update` afterwards."""
+        other = MomentumDistribution.from_state_dict(sd)
+        if not self._same_setup(other):
+            raise ValueError('MomentumDistribution.load_state_dict: the state belongs to other electron numbers or k points')
+        self.sums, self.n_bad, self.samples = other.sums.to(self.sums.device), other.n_bad.to(self.n_bad.device), other.samples
+        self.offset, self.first_electron, self.reduced = other.offset, other.first_electron, False
+        return self
+
+    @classmethod
+    def from_state_dict(cls, sd):
+        """An accumulator without a network: it can be merged, normalised and saved, not updated."""
+        acc = cls.__new__(cls)
+        acc.apply = acc.params = None
+        acc.nelec = tuple(int(v) for v in sd['nelec'])
+        acc._setup(sd['kpoints'], sd['k_int'], int(sd['samples_per_walker']) if 'samples_per_walker' in sd else None)
+        acc.sums = torch.as_tensor(np.array(sd['sums'], dtype=np.float64).reshape(2, -1, 2))
+        acc.n_bad = torch.as_tensor(np.array(sd['n_bad'], dtype=np.int64).reshape(2))
+        acc.samples = np.array(sd['samples'], dtype=np.int64).reshape(2)
+        acc.offset = int(sd['offset']) if 'offset' in sd else 0
+        acc.first_electron = int(sd['first_electron']) if 'first_electron' in sd else 0
+        return acc                          # reduced stays False: the loaded sums are this rank's contribution from here on
+
+    def save(self, path, results=True):
+        """One .npz of `state_dict()`; `results`: also `n_k`, the normalised complex (2, n_k) distribution."""
+        sd = self.state_dict()
+        if results:
+            sd['n_k'] = self.momentum_distribution()
+        with open(path, 'wb') as f:
+            np.savez(f, **sd)
+
+    @classmethod
+    def load(cls, path):
+        """The accumulator saved at `path` as a fresh rank-local one without a network (see `from_state_dict`)."""
+        with np.load(path) as f:
+            return cls.from_state_dict({k: f[k] for k in f.files})

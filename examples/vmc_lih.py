@@ -10,7 +10,9 @@ a calculation of THIS 4-electron cell) instead of plane waves, the network takin
 move the pretraining walkers on the network's density or on the Hartree-Fock density, process.py:148,164; hf needs --hf;
 --density G: accumulate the spin-resolved electron density on a G^3 grid of the primitive cell over the evaluation;
 --pair-correlation BINS: the spin-resolved g(r) on BINS radial bins up to the Wigner-Seitz radius -- both through
-deepsolid_amd.estimator.RealSpaceAccumulator, written to realspace.npz in the working directory)"""
+deepsolid_amd.estimator.RealSpaceAccumulator, written to realspace.npz in the working directory;
+--momentum SHELLS: the spin-resolved momentum distribution n(k) on the (2 SHELLS + 1)^3 Bloch-allowed k points around the twist,
+through deepsolid_amd.estimator.MomentumDistribution, written to momentum.npz)"""
 import os
 import sys
 
@@ -49,6 +51,11 @@ if '--pair-correlation' in sys.argv:
     i = sys.argv.index('--pair-correlation')
     pair_bins = int(sys.argv[i + 1])
     del sys.argv[i:i + 2]
+momentum_shells = None
+if '--momentum' in sys.argv:
+    i = sys.argv.index('--momentum')
+    momentum_shells = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 batch = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
 cell, klist = systems.build('lih')
@@ -70,11 +77,21 @@ accumulators = ()
 if density_grid is not None or pair_bins is not None:
     from deepsolid_amd import estimator
     accumulators = (estimator.RealSpaceAccumulator(cell, density_grid=density_grid, pair_bins=pair_bins),)
+if momentum_shells is not None:
+    from deepsolid_amd import estimator
+    accumulators += (estimator.MomentumDistribution(logdet, params, shells=momentum_shells),)
 data, width, rows = inference.run_inference(slogdet, logdet, params, data, cell, iterations=10, burn_in=10, move_width=width,
                                             accumulators=accumulators)
 print('evaluation: E = %.4f +- %.4f Ha over 10 x %d walkers' % (sum(r['energy'] for r in rows) / len(rows),
                                                                 (sum(r['variance'] for r in rows) / len(rows) / (10 * batch)) ** 0.5, batch))
 for acc in accumulators:
+    if momentum_shells is not None and acc is accumulators[-1]:
+        acc.save('momentum.npz', results=True)
+        nk = acc.momentum_distribution().real
+        print('n(k):       %d k points, %d / %d samples (%d / %d left out); n_up(k_t) = %.4f, n_down(k_t) = %.4f, sums over k = %.4f / %.4f'
+              % (nk.shape[1], acc.samples[0], acc.samples[1], int(acc.n_bad[0]), int(acc.n_bad[1]), nk[0, 0], nk[1, 0],
+                 nk[0].sum(), nk[1].sum()))
+        continue
     acc.save('realspace.npz', results=True)
     if density_grid is not None:
         rho = acc.density()

@@ -367,8 +367,43 @@ int ds_mcmc_step_asymmetric(ds_system* sys, const void* params, void* x, void* l
                             const void* atoms, int n_atoms, uint64_t philox_seed, uint64_t philox_offset, const void* normals,
                             const void* uniforms, int lp_valid, void* n_accept, void* ws, int64_t ws_bytes, void* stream);
 /* the raw Philox block ds_mcmc_step uses for (seed, offset + step, index, stream_id): host evaluation for tests
- * (stream_id 0 / 1: normal deviates of electron `index`, 2: the uniform deviate of walker `index`). */
+ * (stream_id 0 / 1: normal deviates of electron `index`, 2: the uniform deviate of walker `index`, 3: the shifts of
+ * ds_one_body_ratios). */
 void ds_philox_host(uint64_t seed, uint64_t offset, uint64_t step, uint64_t index, int stream_id, uint32_t out[4]);
+
+/* One-body ratios q = psi(R') / psi(R), with R' = R except for ONE displaced electron, and the momentum distribution n(k) folded
+ * from them (csrc/ds_onebody.h).  The reference has no such estimator: the conventions are this library's own.
+ *   n_s(k) = < sum_{i in spin s} (1 / V) int_V ds  psi(.., r_i + s, ..) / psi(R)  exp(-i k.s) >_{|psi|^2},  V = the simulation cell,
+ * for the Bloch-allowed k = k_t + n . G_S (k_t any entry of the network's klist, G_S the rows of 2 pi inv(a)^T); sum_k n_s(k) = N_s.
+ *
+ * One call draws M = n_samples shifts per walker:
+ *   - Sample (w, m) moves electron e = (first_electron + m) % N of walker w by s; every other coordinate is copied.  R' is NOT
+ *     wrapped: the Bloch phase of the network reads the unwrapped coordinates.
+ *   - Philox mode (shifts == NULL): stream 3 of the generator of ds_mcmc_step.  Block A = (philox_seed, philox_offset, step 0,
+ *     index 2 (w M + m)), block B = the same at index 2 (w M + m) + 1 (both are ds_philox_host(.., stream_id 3));
+ *     f = (u53_co(A0, A1), u53_co(A2, A3), u53_co(B0, B1)) in [0, 1)^3 and s = f . a (rows of a = lattice vectors) in float64,
+ *     products and sums rounded one by one.  A caller advances philox_offset by 1 per call.
+ *   - Test mode: shifts (B, M, 3), a device array of the system's dtype, replaces the draw.
+ *   - q = exp(log|psi(R')| - log|psi(R)|) phase(R') conj(phase(R)), formed in float64 from the outputs of the value chain
+ *     (that of ds_logpsi: batches large enough for the int8 value layers use them here too).
+ *   - nk_sums[s(e)][k] += q exp(-i k.s), s(e) = 0 if e < n_up else 1.  kvec: DEVICE array (n_k, 3) float64, Cartesian, n_k in
+ *     0..512.  nk_sums: device (2, n_k, 2) float64 for either dtype, ADDED to and never zeroed; NULL iff n_k == 0.
+ *   - A sample whose q is not finite (this covers a walker whose own log psi is not finite) is left out of the sums and counted
+ *     per spin in n_bad (device (2,) int64, ADDED to; optional).
+ *   - Normalisation is the caller's: n_s(k) = N_s sums_s(k) / (samples taken on spin s - n_bad_s).
+ *   - out_ratio (B, M, 2) = (Re q, Im q) and out_shift (B, M, 3) = s: device arrays of the system's dtype, optional.
+ * The call runs one forward of the B walkers, then per chunk of displaced rows: propose, value chain, accumulate, and a second
+ * stage that adds the per-workgroup partials in a fixed order.  No floating-point atomics, no host synchronisation, no
+ * allocation: the same input gives bit-identical sums, for ANY workspace size -- the chunk length follows from ws_bytes (at most
+ * 65535 configurations; a smaller workspace means more chunks; below one group of 80 configurations it is an error), and the
+ * partials are formed over fixed groups of 80 consecutive samples whatever the chunks are.
+ * Refused with a ds_last_error message before any launch: B < 1, n_samples < 1, first_electron outside 0..N-1, n_k outside
+ * 0..512, n_k > 0 with a NULL kvec or nk_sums, and nothing to write at all (n_k == 0 and out_ratio == NULL).
+ * A cell with spin-down electrons only runs as its mirror image: its electrons count as spin 0. */
+int64_t ds_one_body_workspace_bytes(const ds_system* sys, int64_t B, int n_samples);
+int ds_one_body_ratios(ds_system* sys, const void* params, const void* x, int64_t B, int n_samples, int first_electron,
+                       uint64_t philox_seed, uint64_t philox_offset, const void* shifts, const double* kvec, int n_k,
+                       double* nk_sums, void* out_ratio, void* out_shift, int64_t* n_bad, void* ws, int64_t ws_bytes, void* stream);
 
 /* Packed batch statistics of train.make_loss.total_energy (train.py:74-82) in one deterministic reduction:
  * out_stats (8,) float64 on the device =
