@@ -1,0 +1,45 @@
+// ds_base.h -- the part of the host code that needs no kernel header: the error slot of ds_last_error, HIP_OK, the dtype dispatch
+// and the 3 x 3 inverse.  ds_host.h builds on it; ds_hf.hip needs nothing more.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/deepsolid_hip.h"
+
+namespace ds {
+
+// the message slot of ds_last_error (one per thread, ds_api.hip)
+void set_last_error(const char* msg);
+
+namespace host {
+
+// formats the message into that slot; returns 1
+int fail(const char* fmt, ...);
+
+#define HIP_OK(call)                                                              \
+    do {                                                                          \
+        hipError_t e_ = (call);                                                   \
+        if (e_ != hipSuccess) return fail("%s: %s", #call, hipGetErrorString(e_)); \
+    } while (0)
+
+// f<double>(args) or f<float>(args) by the element type code of the C ABI (0: float64, else float32)
+#define DS_BY_DTYPE(dtype, f, ...) ((dtype) == 0 ? f<double>(__VA_ARGS__) : f<float>(__VA_ARGS__))
+
+inline void inv3(const double* a, double* o) {
+    const double det = a[0] * (a[4] * a[8] - a[5] * a[7]) - a[1] * (a[3] * a[8] - a[5] * a[6]) +
+                       a[2] * (a[3] * a[7] - a[4] * a[6]);
+    o[0] = (a[4] * a[8] - a[5] * a[7]) / det; o[1] = (a[2] * a[7] - a[1] * a[8]) / det; o[2] = (a[1] * a[5] - a[2] * a[4]) / det;
+    o[3] = (a[5] * a[6] - a[3] * a[8]) / det; o[4] = (a[0] * a[8] - a[2] * a[6]) / det; o[5] = (a[2] * a[3] - a[0] * a[5]) / det;
+    o[6] = (a[3] * a[7] - a[4] * a[6]) / det; o[7] = (a[1] * a[6] - a[0] * a[7]) / det; o[8] = (a[0] * a[4] - a[1] * a[3]) / det;
+}
+
+}  // namespace host
+}  // namespace ds

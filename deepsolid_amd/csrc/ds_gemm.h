@@ -83,7 +83,7 @@ template <typename T, int NB, int ST> inline size_t gemm_stash_bytes(unsigned th
 }
 
 // Residual-layer instances (k_jet_gemm<T, NB, ST, 2>) that skip the structurally zero slot tiles of the pair-mean rows: float64 up to
-// 20 slot tiles (beyond, the masked rounds spill -- cells that run the chunked kernels of ds_wide.h anyway).  ds_api.hip asks the same
+// 20 slot tiles (beyond, the masked rounds spill -- cells that run the chunked kernels of ds_wide.h anyway).  ds_chain.hip asks the same
 // question before it lets k_m2_expand leave those tiles unwritten.
 // float64 only: a float32 MFMA lasts 32 cycles, a mask branch then guards too little work (diamond f32, 19 tiles: hidden layers
 // 45.2 -> 48.1 ms WITH the masks); a float64 branch guards 128-256 cycles of products.

@@ -1,0 +1,134 @@
+// ds_observe.hip -- observables of a batch of walkers that need no wave function (ds_obs.h, ds_realspace.h): structure factor and
+// polarization sums, electron density and pair-correlation counts.
+#include "ds_host.h"
+#include "ds_obs.h"
+#include "ds_realspace.h"
+
+namespace ds {
+namespace host {
+
+// observables (ds_obs.h): one kernel instance per number of q points per lane
+template <typename T, int QJ>
+void launch_obs_partial(const ds::ObsArgs& A, const void* x, int64_t B, int N, int G, double* part, hipStream_t st) {
+    hipLaunchKernelGGL((ds::k_obs_partial<T, QJ>), dim3(G), dim3(64), 0, st, A, (const T*)x, (long long)B, N, part);
+}
+
+template <typename T>
+void obs_partial(const ds::ObsArgs& A, const void* x, int64_t B, int N, int G, double* part, hipStream_t st) {
+    switch ((A.n_q + 63) / 64) {    // points per lane
+        case 0: case 1: launch_obs_partial<T, 1>(A, x, B, N, G, part, st); break;
+        case 2: launch_obs_partial<T, 2>(A, x, B, N, G, part, st); break;
+        case 3: case 4: launch_obs_partial<T, 4>(A, x, B, N, G, part, st); break;
+        default: launch_obs_partial<T, 8>(A, x, B, N, G, part, st); break;
+    }
+}
+
+
+template <typename T>
+void realspace_counts(const ds::RealSpaceArgs& A, const void* x, size_t off, long long nb, int N, int64_t* dens, int64_t* pair, hipStream_t st) {
+    hipLaunchKernelGGL((ds::k_realspace_counts<T>), dim3((unsigned)ds::rs_groups(nb)), dim3(ds::RS_THREADS), 0, st, A, (const T*)x + off, nb, N,
+                       (unsigned long long*)dens, (unsigned long long*)pair);
+}
+
+}  // namespace host
+}  // namespace ds
+
+using namespace ds::host;
+
+extern "C" {
+
+int64_t ds_observables_workspace_bytes(int64_t B, int n_q) {
+    if (B < 1 || n_q < 0 || n_q > ds::OBS_MAX_Q) return -1;
+    return (int64_t)ds::obs_groups(B) * (2 + 3 * n_q) * (int64_t)sizeof(double);
+}
+
+int ds_observables(const double* recvec, int dtype, const void* x, int64_t B, int64_t n_elec, const int32_t* q_int, int n_q,
+                   int pol_direction, double* out_sums, void* ws, int64_t ws_bytes, void* stream) {
+    if (!recvec || !x || !out_sums || !ws) return fail("null argument");
+    if (dtype != 0 && dtype != 1) return fail("dtype must be 0 or 1");
+    if (B < 1) return fail("B must be >= 1 (got %lld)", (long long)B);
+    if (n_elec < 1 || n_elec > ds::OBS_MAX_N) return fail("n_elec must be in 1..%d (got %lld)", ds::OBS_MAX_N, (long long)n_elec);
+    if (n_q < 0 || n_q > ds::OBS_MAX_Q) return fail("n_q must be in 0..%d (got %d)", ds::OBS_MAX_Q, n_q);
+    if (n_q > 0 && !q_int) return fail("null q_int with n_q = %d", n_q);
+    if (pol_direction < -1 || pol_direction > 2) return fail("pol_direction must be -1, 0, 1 or 2 (got %d)", pol_direction);
+    const int64_t need = ds_observables_workspace_bytes(B, n_q);
+    if (ws_bytes < need) return fail("workspace too small for ds_observables: %lld bytes < %lld", (long long)ws_bytes, (long long)need);
+    ds::ObsArgs A;
+    for (int i = 0; i < 9; ++i) {
+        if (!std::isfinite(recvec[i])) return fail("recvec[%d] is not finite", i);
+        A.g[i] = recvec[i];
+    }
+    A.n_q = n_q;
+    A.pol = pol_direction;
+    int pmax = 0;
+    for (int k = 0; k < 3 * n_q; ++k) {
+        const int32_t n = q_int[k];
+        if (n < 0 || n >= ds::OBS_MAX_POW)
+            return fail("q point %d: lattice coordinate %d is outside 0..%d", k / 3, (int)n, ds::OBS_MAX_POW - 1);
+        A.qn[k] = (signed char)n;
+        pmax = std::max(pmax, (int)n);
+    }
+    for (int k = 3 * n_q; k < 3 * ds::OBS_MAX_Q; ++k) A.qn[k] = 0;
+    A.n_pow = pmax + 1;
+    hipStream_t st = (hipStream_t)stream;
+    const int G = ds::obs_groups(B), K = 2 + 3 * n_q;
+    double* part = (double*)ws;
+    DS_BY_DTYPE(dtype, obs_partial, A, x, B, (int)n_elec, G, part, st);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(ds::k_obs_final, dim3((K + 255) / 256), dim3(256), 0, st, (const double*)part, G, K, out_sums);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int ds_realspace_counts(const double* fold_inv, const int32_t* grid, const double* latvec, const double* latvec_inv, double r_max,
+                        int n_r, int dtype, const void* x, int64_t B, int64_t n_elec, int64_t n_up, int64_t* dens, int64_t* pair,
+                        void* stream) {
+    if (!x) return fail("null argument");
+    if (!dens && !pair) return fail("ds_realspace_counts: dens and pair are both null, nothing to count");
+    if (dtype != 0 && dtype != 1) return fail("dtype must be 0 or 1");
+    if (B < 1) return fail("B must be >= 1 (got %lld)", (long long)B);
+    if (n_elec < 1 || n_elec > ds::RS_MAX_N) return fail("n_elec must be in 1..%d (got %lld)", ds::RS_MAX_N, (long long)n_elec);
+    if (n_up < 0 || n_up > n_elec) return fail("n_up must be in 0..n_elec = %lld (got %lld)", (long long)n_elec, (long long)n_up);
+    ds::RealSpaceArgs A;
+    std::memset(&A, 0, sizeof(A));
+    A.n_up = (int)n_up;
+    A.do_dens = dens != nullptr;
+    A.do_pair = pair != nullptr;
+    if (dens) {
+        if (!fold_inv || !grid) return fail("ds_realspace_counts: the density needs fold_inv and grid");
+        long long cells = 1;
+        for (int j = 0; j < 3; ++j) {
+            if (grid[j] < 1 || grid[j] > ds::RS_MAX_G) return fail("grid[%d] must be in 1..%d (got %d)", j, ds::RS_MAX_G, (int)grid[j]);
+            A.g[j] = grid[j];
+            cells *= grid[j];
+        }
+        if (cells > ds::RS_MAX_BINS) return fail("grid has %lld points, at most %lld are supported", cells, ds::RS_MAX_BINS);
+        for (int i = 0; i < 9; ++i) {
+            if (!std::isfinite(fold_inv[i])) return fail("fold_inv[%d] is not finite", i);
+            A.fold_inv[i] = fold_inv[i];
+        }
+    }
+    if (pair) {
+        if (!latvec || !latvec_inv) return fail("ds_realspace_counts: the pair counts need latvec and latvec_inv");
+        if (n_r < 1 || n_r > ds::RS_MAX_NR) return fail("n_r must be in 1..%d (got %d)", ds::RS_MAX_NR, n_r);
+        if (!(r_max > 0.0) || !std::isfinite(r_max)) return fail("r_max must be positive and finite (got %g)", r_max);
+        for (int i = 0; i < 9; ++i) {
+            if (!std::isfinite(latvec[i]) || !std::isfinite(latvec_inv[i])) return fail("latvec / latvec_inv [%d] is not finite", i);
+            A.a[i] = latvec[i];
+            A.a_inv[i] = latvec_inv[i];
+        }
+        A.n_r = n_r;
+        A.r_max = r_max;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    // pieces of at most RS_MAX_LAUNCH_WALKERS walkers: the bound behind the uint32 LDS bins (ds_realspace.h)
+    for (int64_t b0 = 0; b0 < B; b0 += ds::RS_MAX_LAUNCH_WALKERS) {
+        const long long nb = (long long)std::min<int64_t>(B - b0, ds::RS_MAX_LAUNCH_WALKERS);
+        const size_t off = (size_t)b0 * 3 * (size_t)n_elec;
+        DS_BY_DTYPE(dtype, realspace_counts, A, x, off, nb, (int)n_elec, dens, pair, st);
+        HIP_OK(hipGetLastError());
+    }
+    return 0;
+}
+
+}  // extern "C"

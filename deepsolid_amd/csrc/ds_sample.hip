@@ -1,0 +1,392 @@
+// ds_sample.hip -- the samplers and what shares their kernels (ds_mcmc.h, ds_onebody.h): the three fused Metropolis loops, the
+// one-body ratios and n(k), the single proposal / selection steps (ds_mh_*), the batch statistics and the host side of Philox.
+#include "ds_host.h"
+#include "ds_mcmc.h"
+#include "ds_onebody.h"
+
+namespace ds {
+namespace host {
+
+// ------------------------------------------------------------------ Metropolis loop (qmc.py:335-362), ds_mcmc.h
+// Scratch of the three move loops, in front of the chains' workspace: proposal x2 (B,3N) + log|psi(x2)| (B,); the importance-
+// sampled loop adds the complex gradient (B,3N,2), the drifts at x1 / x2, the normal deviates ((B,3N) each), the uniforms (B,) and
+// the two batch maxima
+template <typename T> struct McmcScratch {
+    T *X2, *GC, *G1, *G2, *NZ, *LA2, *UN, *SCR;
+    void* wsv; int64_t wsv_bytes;                        // what is left for the value / energy chain
+};
+template <typename T> McmcScratch<T> carve_mcmc(const ds_system* s, Arena<T>& a, int64_t B) {
+    const size_t n3 = (size_t)B * 3 * s->sd.N;
+    McmcScratch<T> m{};
+    m.X2 = a.take(n3); m.GC = a.take(2 * n3); m.G1 = a.take(n3); m.G2 = a.take(n3); m.NZ = a.take(n3);
+    m.LA2 = a.take((size_t)B); m.UN = a.take((size_t)B); m.SCR = a.take(2);
+    return m;
+}
+inline size_t mcmc_scratch_bytes(const ds_system* s, int64_t B) {
+    return rup(measure([&](Arena<double>& a) { carve_mcmc<double>(s, a, B); }) * (s->dtype == 0 ? 8 : 4), 256);
+}
+
+// What the three loops begin with: the workspace check, the carve, and logprob = 2 f(data) (qmc.py:357) unless lp is valid
+template <typename T>
+int mcmc_begin(ds_system* s, const char* what, const void* params, const T* x, T* lp, int64_t B, int lp_valid, void* ws,
+               int64_t ws_bytes, hipStream_t st, McmcScratch<T>* m) {
+    const size_t head = mcmc_scratch_bytes(s, B);
+    if ((int64_t)head >= ws_bytes) return fail("workspace too small for %s (see ds_mcmc_workspace_bytes)", what);
+    Arena<T> a = arena_of<T>(ws, (int64_t)head);
+    *m = carve_mcmc<T>(s, a, B);
+    if (!a.ok) return carve_fail(what);
+    m->wsv = (char*)ws + head;
+    m->wsv_bytes = ws_bytes - (int64_t)head;
+    if (!lp_valid) {
+        if (int rc = logpsi_forward(s, params, x, B, m->LA2, nullptr, m->wsv, m->wsv_bytes, st)) return rc;
+        hipLaunchKernelGGL((ds::k_scale2<T>), dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, m->LA2, (long)B, lp);
+    }
+    return 0;
+}
+
+template <typename T>
+int mcmc_step_impl(ds_system* s, const void* params, void* x_, void* lp_, int64_t B, int steps, double width, uint64_t seed,
+                   uint64_t offset, const void* normals_, const void* uniforms_, int lp_valid, void* n_accept, void* ws,
+                   int64_t ws_bytes, hipStream_t st, int first_electron = -1) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    T* x = (T*)x_; T* lp = (T*)lp_;
+    McmcScratch<T> m;
+    if (int rc = mcmc_begin<T>(s, "ds_mcmc_step", params, x, lp, B, lp_valid, ws, ws_bytes, st, &m)) return rc;
+    const T* normals = (const T*)normals_; const T* uniforms = (const T*)uniforms_;
+    const size_t ne = (size_t)B * S.N;
+    const ds::PhiloxKey key{seed, offset};
+    for (int i = 0; i < steps; ++i) {                                    // lax.fori_loop(0, nsteps, ...)   :358
+        // all-electron move, or (first_electron >= 0) move i displaces electron (first_electron + i) % N only  (qmc.py:266)
+        const int only = first_electron < 0 ? -1 : (int)(((int64_t)first_electron + i) % S.N);
+        const size_t nstride = (size_t)B * 3 * (only < 0 ? S.N : 1);
+        hipLaunchKernelGGL((ds::k_mcmc_propose<T>), dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, S.sim_a, S.sim_ainv, x,
+                           normals ? normals + (size_t)i * nstride : (const T*)nullptr, key, (unsigned long long)i, (T)width, ne, m.X2,
+                           S.N, only);
+        if (int rc = logpsi_forward(s, params, m.X2, B, m.LA2, nullptr, m.wsv, m.wsv_bytes, st)) return rc;
+        hipLaunchKernelGGL((ds::k_mcmc_accept<T>), dim3((unsigned)((B + 63) / 64)), dim3(256), 0, st, x, lp, m.X2, m.LA2,
+                           uniforms ? uniforms + (size_t)i * B : (const T*)nullptr, key, (unsigned long long)i, 3 * S.N, 0L, (long)B, (T*)n_accept);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------ one-body ratios and n(k), ds_onebody.h
+// Workspace of ds_one_body_ratios for B walkers and chunks of ng groups of PV displaced configurations.  Shared by all chunks:
+// log|psi(R)| (B,), phase(R) (B,2) and the call's running sums (one row of float64, taken as 2 elements per double: room in
+// either element size).  Per chunk: one row of float64 partials per group, the displaced rows, their log|psi| / phase, and the value chain's buffers for ng groups (on a 64-element
+// border), which also serve the forward of the undisplaced walkers.
+template <typename T> struct OneBodyWs {
+    T *LA0, *PH0, *XD, *LA, *PH;
+    double *ACC, *PART;
+    void* wsv; int64_t wsv_bytes;
+};
+template <typename T> OneBodyWs<T> carve_onebody(const ds_system* s, Arena<T>& a, int64_t B, int64_t ng) {
+    const size_t nc = (size_t)ng * ds::PV;
+    OneBodyWs<T> w{};
+    w.LA0 = a.take((size_t)B); w.PH0 = a.take(2 * (size_t)B);
+    a.align(2);
+    w.ACC = (double*)a.take(2 * (size_t)ds::OB_ROW);
+    w.PART = (double*)a.take(2 * (size_t)ng * ds::OB_ROW);
+    w.XD = a.take(nc * 3 * s->sd.N); w.LA = a.take(nc); w.PH = a.take(2 * nc);
+    a.align(64);
+    w.wsv = a.take(s->wsv.per_walker * (size_t)ng);
+    w.wsv_bytes = (int64_t)(s->wsv.per_walker * (size_t)ng * sizeof(T));
+    return w;
+}
+inline int64_t onebody_bytes(const ds_system* s, int64_t B, int64_t ng) {
+    return (int64_t)measure([&](Arena<double>& a) { carve_onebody<double>(s, a, B, ng); }) * (s->dtype == 0 ? 8 : 4);
+}
+// groups per chunk: at most 65535 configurations (the grid limit of the chains)
+constexpr int64_t OB_MAX_GROUPS = 65535 / ds::PV;
+
+template <typename T>
+int one_body_impl(ds_system* s, const void* params, const void* x_, int64_t B, int M, int first, uint64_t seed, uint64_t offset,
+                  const void* shifts_, const double* kvec, int n_k, double* nk_sums, void* out_ratio, void* out_shift,
+                  int64_t* n_bad, void* ws, int64_t ws_bytes, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const T* x = (const T*)x_; const T* shifts = (const T*)shifts_;
+    const int64_t total = B * (int64_t)M;
+    // the chunk length follows from the workspace: the largest number of groups whose layout fits (the layout is linear in ng up
+    // to its two alignment pads, so the estimate is at most a few groups high)
+    const int64_t fixed = onebody_bytes(s, B, 0), per = onebody_bytes(s, B, 1) - fixed;
+    int64_t ng = std::min<int64_t>({(ws_bytes - fixed) / per + 1, OB_MAX_GROUPS, (total + ds::PV - 1) / ds::PV});
+    while (ng >= 1 && onebody_bytes(s, B, ng) > ws_bytes) --ng;
+    if (ng < 1) return fail("workspace too small for ds_one_body_ratios: %lld bytes < %lld for one group of %d configurations",
+                            (long long)ws_bytes, (long long)onebody_bytes(s, B, 1), ds::PV);
+    Arena<T> a = arena_of<T>(ws, ws_bytes);
+    const OneBodyWs<T> w = carve_onebody<T>(s, a, B, ng);
+    if (!a.ok) return carve_fail("one-body ratios");
+    if (int rc = logpsi_forward(s, params, x, B, w.LA0, w.PH0, w.wsv, w.wsv_bytes, st)) return rc;
+    ds::OneBodyArgs A;
+    for (int i = 0; i < 9; ++i) A.a[i] = s->d.sim_a[i];
+    A.key = ds::PhiloxKey{seed, offset};
+    A.M = M; A.N = S.N; A.n_up = S.n_up; A.first = first;
+    const int64_t chunk = ng * ds::PV;
+    for (int64_t g0 = 0; g0 < total; g0 += chunk) {
+        A.g0 = g0; A.n = std::min(chunk, total - g0);
+        const int64_t groups = (A.n + ds::OB_GROUP - 1) / ds::OB_GROUP;
+        hipLaunchKernelGGL((ds::k_onebody_propose<T>), dim3((unsigned)((A.n * S.N + 255) / 256)), dim3(256), 0, st, A, x, shifts, w.XD,
+                           (T*)out_shift);
+        if (int rc = logpsi_forward(s, params, w.XD, A.n, w.LA, w.PH, w.wsv, w.wsv_bytes, st)) return rc;
+        hipLaunchKernelGGL((ds::k_onebody_accumulate<T>), dim3((unsigned)groups), dim3(64 * ds::OB_WAVES), 0, st, A, shifts, (const T*)w.LA0,
+                           (const T*)w.PH0, (const T*)w.LA, (const T*)w.PH, kvec, n_k, (T*)out_ratio, w.PART);
+        if (n_k > 0 || n_bad)
+            hipLaunchKernelGGL(ds::k_onebody_final, dim3((unsigned)((4 * n_k + 2 + 255) / 256)), dim3(256), 0, st, (const double*)w.PART,
+                               (long long)groups, n_k, g0 == 0 ? 1 : 0, g0 + chunk >= total ? 1 : 0, w.ACC, nk_sums, (long long*)n_bad);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// Drift-biased importance sampling (qmc.importance_update, qmc.py:83-150, as make_mcmc_step drives it): per move the drift
+// grad log|psi| at x1, the proposal x2 = wrap(x1 + w N + w^2 limdrift(g1)), (log|psi|, drift) at x2, and the selection with
+// the forward / reverse proposal densities -- the kernels of ds_mh_propose_ex / ds_mh_accept_ex (mode 2), enqueued back to back.
+template <typename T>
+int mcmc_importance_impl(ds_system* s, const void* params, void* x_, void* lp_, int64_t B, int steps, double width, uint64_t seed,
+                         uint64_t offset, const void* normals_, const void* uniforms_, int lp_valid, void* n_accept, void* ws,
+                         int64_t ws_bytes, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const size_t n3 = (size_t)B * 3 * S.N, ne = (size_t)B * S.N;
+    T* x = (T*)x_; T* lp = (T*)lp_;
+    McmcScratch<T> m;
+    if (int rc = mcmc_begin<T>(s, "ds_mcmc_step_importance", params, x, lp, B, lp_valid, ws, ws_bytes, st, &m)) return rc;
+    const ds::PhiloxKey key{seed, offset};
+    const dim3 ge((unsigned)((n3 + 255) / 256)), gn((unsigned)((std::max<size_t>(ne, (size_t)B) + 255) / 256)), blk(256);
+    for (int i = 0; i < steps; ++i) {
+        if (int rc = logpsi_grad_forward(s, params, x, B, m.LA2, nullptr, m.GC, m.wsv, m.wsv_bytes, st)) return rc;          // :111
+        hipLaunchKernelGGL((ds::k_real_part<T>), ge, blk, 0, st, m.GC, n3, m.G1);
+        const T* nz = normals_ ? (const T*)normals_ + (size_t)i * n3 : m.NZ;
+        const T* un = uniforms_ ? (const T*)uniforms_ + (size_t)i * B : m.UN;
+        if (!normals_) hipLaunchKernelGGL((ds::k_philox_noise<T>), gn, blk, 0, st, key, (unsigned long long)i, ne, (long)B, m.NZ, m.UN);
+        hipLaunchKernelGGL((ds::k_max_norm3<T>), dim3(1), dim3(1024), 0, st, m.G1, ne, m.SCR);
+        hipLaunchKernelGGL((ds::k_mh_propose_ex<T>), dim3((unsigned)((ne + 255) / 256)), blk, 0, st, S.sim_a, S.sim_ainv, 2, x, nz, (T)width,
+                           m.G1, 0, ne, m.X2, m.SCR);                                                                      // :112-115
+        if (int rc = logpsi_grad_forward(s, params, m.X2, B, m.LA2, nullptr, m.GC, m.wsv, m.wsv_bytes, st)) return rc;         // :118
+        hipLaunchKernelGGL((ds::k_real_part<T>), ge, blk, 0, st, m.GC, n3, m.G2);
+        hipLaunchKernelGGL((ds::k_max_norm3<T>), dim3(1), dim3(1024), 0, st, m.G2, ne, m.SCR + 1);
+        hipLaunchKernelGGL((ds::k_mh_accept_ex<T>), dim3((unsigned)B), dim3(64), 0, st, 2, x, lp, m.X2, m.LA2, un, nz, (T)width, m.G1, m.G2, 0, S.N,
+                           (T*)n_accept, m.SCR);                                                                       // :119-137
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// Asymmetric all-electron proposal (mh_update with atoms=, qmc.py:197-215): step width per electron = width x harmonic mean of its
+// nuclear distances, forward / reverse proposal densities in the ratio -- the kernels of ds_mh_propose_ex / ds_mh_accept_ex (mode 1).
+template <typename T>
+int mcmc_asymmetric_impl(ds_system* s, const void* params, void* x_, void* lp_, int64_t B, int steps, double width, const void* atoms,
+                         int n_atoms, uint64_t seed, uint64_t offset, const void* normals_, const void* uniforms_, int lp_valid,
+                         void* n_accept, void* ws, int64_t ws_bytes, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const size_t n3 = (size_t)B * 3 * S.N, ne = (size_t)B * S.N;
+    T* x = (T*)x_; T* lp = (T*)lp_;
+    McmcScratch<T> m;
+    if (int rc = mcmc_begin<T>(s, "ds_mcmc_step_asymmetric", params, x, lp, B, lp_valid, ws, ws_bytes, st, &m)) return rc;
+    const ds::PhiloxKey key{seed, offset};
+    const dim3 gn((unsigned)((std::max<size_t>(ne, (size_t)B) + 255) / 256)), blk(256);
+    for (int i = 0; i < steps; ++i) {
+        const T* nz = normals_ ? (const T*)normals_ + (size_t)i * n3 : m.NZ;
+        const T* un = uniforms_ ? (const T*)uniforms_ + (size_t)i * B : m.UN;
+        if (!normals_) hipLaunchKernelGGL((ds::k_philox_noise<T>), gn, blk, 0, st, key, (unsigned long long)i, ne, (long)B, m.NZ, m.UN);
+        hipLaunchKernelGGL((ds::k_mh_propose_ex<T>), dim3((unsigned)((ne + 255) / 256)), blk, 0, st, S.sim_a, S.sim_ainv, 1, x, nz, (T)width,
+                           (const T*)atoms, n_atoms, ne, m.X2, (const T*)nullptr);                                     // :200-204
+        if (int rc = logpsi_forward(s, params, m.X2, B, m.LA2, nullptr, m.wsv, m.wsv_bytes, st)) return rc;                  // :205
+        hipLaunchKernelGGL((ds::k_mh_accept_ex<T>), dim3((unsigned)B), dim3(64), 0, st, 1, x, lp, m.X2, m.LA2, un, (const T*)nullptr, (T)width,
+                           (const T*)atoms, (const T*)nullptr, n_atoms, S.N, (T*)n_accept, (const T*)nullptr);       // :208-222
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------ single proposal / selection steps and the batch statistics
+template <typename T> void mh_propose(ds_system* s, const void* x1, const void* normal, double width, size_t ne, void* x2, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    hipLaunchKernelGGL((ds::k_mh_propose<T>), dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, S.sim_a, S.sim_ainv, (const T*)x1, (const T*)normal,
+                       (T)width, ne, (T*)x2);
+}
+
+template <typename T>
+void mh_accept(ds_system* s, void* x1, void* lp1, const void* x2, const void* lp2, const void* uniform, int64_t B, void* n_accept, hipStream_t st) {
+    hipLaunchKernelGGL((ds::k_mh_accept<T>), dim3((unsigned)B), dim3(64), 0, st, (T*)x1, (T*)lp1, (const T*)x2, (const T*)lp2, (const T*)uniform,
+                       3 * dev<T>(s).N, (T*)n_accept);
+}
+
+template <typename T>
+void mh_propose_ex(ds_system* s, int mode, const void* x1, const void* normal, double width, const void* aux, int n_aux, size_t ne, void* x2,
+                   void* scratch, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    if (mode == 2) hipLaunchKernelGGL((ds::k_max_norm3<T>), dim3(1), dim3(1024), 0, st, (const T*)aux, ne, (T*)scratch);
+    hipLaunchKernelGGL((ds::k_mh_propose_ex<T>), dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, S.sim_a, S.sim_ainv, mode, (const T*)x1,
+                       (const T*)normal, (T)width, (const T*)aux, n_aux, ne, (T*)x2, (const T*)scratch);
+}
+
+template <typename T>
+void mh_accept_ex(ds_system* s, int mode, void* x1, void* lp1, const void* x2, const void* logabs2, const void* uniform, const void* normal,
+                  double width, const void* aux1, const void* aux2, int n_aux, size_t ne, int64_t B, void* n_accept, void* scratch,
+                  hipStream_t st) {
+    if (mode == 2) hipLaunchKernelGGL((ds::k_max_norm3<T>), dim3(1), dim3(1024), 0, st, (const T*)aux2, ne, (T*)scratch + 1);
+    hipLaunchKernelGGL((ds::k_mh_accept_ex<T>), dim3((unsigned)B), dim3(64), 0, st, mode, (T*)x1, (T*)lp1, (const T*)x2, (const T*)logabs2,
+                       (const T*)uniform, (const T*)normal, (T)width, (const T*)aux1, (const T*)aux2, n_aux, dev<T>(s).N, (T*)n_accept,
+                       (const T*)scratch);
+}
+
+template <typename T> void energy_stats(const void* ke, const void* ewald, int64_t B, double* out_stats, hipStream_t st) {
+    hipLaunchKernelGGL((ds::k_energy_stats<T>), dim3(1), dim3(256), 0, st, (const T*)ke, (const T*)ewald, (long)B, out_stats);
+}
+
+}  // namespace host
+}  // namespace ds
+
+using namespace ds::host;
+
+extern "C" {
+
+int ds_mh_propose(ds_system* s, const void* x1, const void* normal, double width, int64_t B, void* x2, void* stream) {
+    if (!s || !x1 || !normal || !x2) return fail("null argument");
+    if (B <= 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ne = (size_t)B * s->sd.N;
+    DS_BY_DTYPE(s->dtype, mh_propose, s, x1, normal, width, ne, x2, st);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int ds_mh_accept(ds_system* s, void* x1, void* lp1, const void* x2, const void* lp2, const void* uniform, int64_t B, void* n_accept,
+                 void* stream) {
+    if (!s || !x1 || !lp1 || !x2 || !lp2 || !uniform || !n_accept) return fail("null argument");
+    if (B <= 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    DS_BY_DTYPE(s->dtype, mh_accept, s, x1, lp1, x2, lp2, uniform, B, n_accept, st);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int ds_mh_propose_ex(ds_system* s, int mode, const void* x1, const void* normal, double width, const void* aux, int n_aux, int64_t B,
+                     void* x2, void* scratch, void* stream) {
+    if (!s || !x1 || !normal || !aux || !x2) return fail("null argument");
+    if (mode == 2 && !scratch) return fail("the drift move needs a 2-element device scratch (batch maxima of the drift)");
+    if (mode != 1 && mode != 2) return fail("mode must be 1 (asymmetric) or 2 (drift)");
+    if (B <= 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ne = (size_t)B * s->sd.N;
+    DS_BY_DTYPE(s->dtype, mh_propose_ex, s, mode, x1, normal, width, aux, n_aux, ne, x2, scratch, st);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int ds_mh_accept_ex(ds_system* s, int mode, void* x1, void* lp1, const void* x2, const void* logabs2, const void* uniform,
+                    const void* normal, double width, const void* aux1, const void* aux2, int n_aux, int64_t B, void* n_accept,
+                    void* scratch, void* stream) {
+    if (!s || !x1 || !lp1 || !x2 || !logabs2 || !uniform || !aux1 || !n_accept) return fail("null argument");
+    if (mode != 1 && mode != 2) return fail("mode must be 1 (asymmetric) or 2 (drift)");
+    if (mode == 2 && (!aux2 || !normal || !scratch)) return fail("the drift move needs both gradients, the normal deviates and the scratch of ds_mh_propose_ex");
+    if (B <= 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t ne = (size_t)B * s->sd.N;
+    DS_BY_DTYPE(s->dtype, mh_accept_ex, s, mode, x1, lp1, x2, logabs2, uniform, normal, width, aux1, aux2, n_aux, ne, B, n_accept, scratch,
+                st);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int64_t ds_mcmc_workspace_bytes(const ds_system* s, int64_t B) {
+    if (!s) return -1;
+    return ds_workspace_bytes(s, B) + (int64_t)mcmc_scratch_bytes(s, std::max<int64_t>(B, 1));
+}
+
+int ds_mcmc_step(ds_system* s, const void* params, void* x, void* lp, int64_t B, int steps, double width, uint64_t philox_seed,
+                 uint64_t philox_offset, const void* normals, const void* uniforms, int lp_valid, void* n_accept, void* ws,
+                 int64_t ws_bytes, void* stream) {
+    if (s) ++s->call_seq;
+    if (!s || !params || !x || !lp || !n_accept || !ws) return fail("null argument");
+    if ((normals == nullptr) != (uniforms == nullptr)) return fail("normals and uniforms must be given together (or both NULL)");
+    if (steps < 0) return fail("steps must be >= 0");
+    if (B <= 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    return DS_BY_DTYPE(s->dtype, mcmc_step_impl, s, params, x, lp, B, steps, width, philox_seed, philox_offset, normals, uniforms, lp_valid,
+                       n_accept, ws, ws_bytes, st);
+}
+
+int ds_mcmc_step_one_electron(ds_system* s, const void* params, void* x, void* lp, int64_t B, int moves, int first_electron,
+                              double width, uint64_t philox_seed, uint64_t philox_offset, const void* normals, const void* uniforms,
+                              int lp_valid, void* n_accept, void* ws, int64_t ws_bytes, void* stream) {
+    if (s) ++s->call_seq;
+    if (!s || !params || !x || !lp || !n_accept || !ws) return fail("null argument");
+    if ((normals == nullptr) != (uniforms == nullptr)) return fail("normals and uniforms must be given together (or both NULL)");
+    if (moves < 0 || first_electron < 0) return fail("moves and first_electron must be >= 0");
+    if (B <= 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    return DS_BY_DTYPE(s->dtype, mcmc_step_impl, s, params, x, lp, B, moves, width, philox_seed, philox_offset, normals, uniforms, lp_valid,
+                       n_accept, ws, ws_bytes, st, first_electron);
+}
+
+int ds_mcmc_step_asymmetric(ds_system* s, const void* params, void* x, void* lp, int64_t B, int steps, double width, const void* atoms,
+                            int n_atoms, uint64_t philox_seed, uint64_t philox_offset, const void* normals, const void* uniforms,
+                            int lp_valid, void* n_accept, void* ws, int64_t ws_bytes, void* stream) {
+    if (s) ++s->call_seq;
+    if (!s || !params || !x || !lp || !n_accept || !ws || !atoms) return fail("null argument");
+    if ((normals == nullptr) != (uniforms == nullptr)) return fail("normals and uniforms must be given together (or both NULL)");
+    if (steps < 0 || n_atoms < 1) return fail("steps must be >= 0 and n_atoms >= 1");
+    if (B <= 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    return DS_BY_DTYPE(s->dtype, mcmc_asymmetric_impl, s, params, x, lp, B, steps, width, atoms, n_atoms, philox_seed, philox_offset,
+                       normals, uniforms, lp_valid, n_accept, ws, ws_bytes, st);
+}
+
+int ds_mcmc_step_importance(ds_system* s, const void* params, void* x, void* lp, int64_t B, int steps, double width,
+                            uint64_t philox_seed, uint64_t philox_offset, const void* normals, const void* uniforms, int lp_valid,
+                            void* n_accept, void* ws, int64_t ws_bytes, void* stream) {
+    if (s) ++s->call_seq;
+    if (!s || !params || !x || !lp || !n_accept || !ws) return fail("null argument");
+    if ((normals == nullptr) != (uniforms == nullptr)) return fail("normals and uniforms must be given together (or both NULL)");
+    if (steps < 0) return fail("steps must be >= 0");
+    if (B <= 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    return DS_BY_DTYPE(s->dtype, mcmc_importance_impl, s, params, x, lp, B, steps, width, philox_seed, philox_offset, normals, uniforms,
+                       lp_valid, n_accept, ws, ws_bytes, st);
+}
+
+int64_t ds_one_body_workspace_bytes(const ds_system* s, int64_t B, int n_samples) {
+    if (!s || B < 1 || n_samples < 1) return -1;
+    // as many groups per chunk as ds_workspace_bytes gives the value chain of B * n_samples walkers
+    const int64_t esz = s->dtype == 0 ? 8 : 4, total = B * (int64_t)n_samples;
+    const int64_t budget = workspace_budget();
+    const int64_t fixed = onebody_bytes(s, B, 0), per = onebody_bytes(s, B, 1) - fixed;
+    const int64_t ng = std::min(groups_per_pass(total, esz, PassSize{0, (size_t)(per / esz)}, budget), OB_MAX_GROUPS);
+    return onebody_bytes(s, B, ng);
+}
+
+int ds_one_body_ratios(ds_system* s, const void* params, const void* x, int64_t B, int n_samples, int first_electron,
+                       uint64_t philox_seed, uint64_t philox_offset, const void* shifts, const double* kvec, int n_k, double* nk_sums,
+                       void* out_ratio, void* out_shift, int64_t* n_bad, void* ws, int64_t ws_bytes, void* stream) {
+    if (s) ++s->call_seq;
+    if (!s || !params || !x || !ws) return fail("null argument");
+    if (B < 1) return fail("ds_one_body_ratios: B must be >= 1 (got %lld)", (long long)B);
+    if (n_samples < 1) return fail("ds_one_body_ratios: n_samples must be >= 1 (got %d)", n_samples);
+    if (first_electron < 0 || first_electron >= s->sd.N)
+        return fail("ds_one_body_ratios: first_electron must be in 0..%d (got %d)", s->sd.N - 1, first_electron);
+    if (n_k < 0 || n_k > ds::OB_MAX_K) return fail("ds_one_body_ratios: n_k must be in 0..%d (got %d)", ds::OB_MAX_K, n_k);
+    if (n_k > 0 && (!kvec || !nk_sums)) return fail("ds_one_body_ratios: n_k = %d needs kvec and nk_sums", n_k);
+    if (n_k == 0 && !out_ratio) return fail("ds_one_body_ratios: n_k is 0 and out_ratio is null, nothing to write");
+    hipStream_t st = (hipStream_t)stream;
+    return DS_BY_DTYPE(s->dtype, one_body_impl, s, params, x, B, n_samples, first_electron, philox_seed, philox_offset, shifts, kvec, n_k,
+                       nk_sums, out_ratio, out_shift, n_bad, ws, ws_bytes, st);
+}
+
+int ds_energy_stats(ds_system* s, const void* ke, const void* ewald, int64_t B, double* out_stats, void* stream) {
+    if (!s || !ke || !ewald || !out_stats) return fail("null argument");
+    hipStream_t st = (hipStream_t)stream;
+    DS_BY_DTYPE(s->dtype, energy_stats, ke, ewald, B, out_stats, st);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+void ds_philox_host(uint64_t seed, uint64_t offset, uint64_t step, uint64_t index, int stream_id, uint32_t out[4]) {
+    const uint64_t off = offset + step;
+    const ds::Philox4 r = ds::philox4x32_10((unsigned)index, (unsigned)(index >> 32), (unsigned)off,
+                                            ((unsigned)(off >> 32) & 0x3fffffffu) | ((unsigned)stream_id << 30), (unsigned)seed,
+                                            (unsigned)(seed >> 32));
+    for (int i = 0; i < 4; ++i) out[i] = r.v[i];
+}
+
+}  // extern "C"

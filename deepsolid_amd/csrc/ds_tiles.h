@@ -42,7 +42,7 @@ template <typename T> struct TileOps {
 constexpr int DS_MAX_TILES = 25;
 constexpr int tile_nb(int st, int elem_bytes) { return st <= 5 ? 4 : (st <= 10 ? 2 : (elem_bytes == 4 ? 2 : 1)); }
 
-// Which instance the host code launches (ds_api.hip: plan_chain) -- the launchers above do not decide.
+// Which instance the host code launches (ds_chain.hip: plan_chain) -- the launchers above do not decide.
 // k_layer0_stats: a wave holds all slot tiles of 16 features (ST <= 5), nks = K0 / 4 k-steps unrolled
 constexpr bool layer0_stats_instance(int st, int nks) { return st <= 5 && nks >= 2 && nks <= 4; }
 // The chunked form of a layer / orbital GEMM (epi = 1, 2, 5, 9) and of the low-rank layer 1 is the faster one -- measured: float64 all

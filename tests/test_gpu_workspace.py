@@ -1,4 +1,4 @@
-"""Canary tests of the workspace layouts of csrc/ds_api.hip: every entry point that carves a caller-supplied workspace is run in
+"""Canary tests of the workspace layouts of the host code (csrc/ds_host.h and the units over it): every entry point that carves a caller-supplied workspace is run in
 a buffer of exactly the size the library reports, followed by 1 MiB of 0xA5 inside the same torch allocation.  A carve that hands
 out more than the size function counted overwrites the canary and shows as a failed assertion (not as a memory fault); the
 result must equal the same call in the cached, uncapped workspace:
