@@ -105,6 +105,8 @@ SIGNATURES = {
     'ds_one_body_workspace_bytes': (C.c_int64, [_VP, C.c_int64, C.c_int]),
     'ds_one_body_ratios': (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _VP, _VP, C.c_int, _VP, _VP, _VP,
                                      _VP, _VP, C.c_int64, _VP]),
+    'ds_spin_exchange_workspace_bytes': (C.c_int64, [_VP, C.c_int64, C.c_int]),
+    'ds_spin_exchange_ratios': (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     'ds_philox_host': (None,[C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_uint32)]),
     'ds_energy_stats': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP]),
     'ds_debug_stage': (C.c_int64, [_VP, _VP, _VP, C.c_int64, C.c_char_p, _VP, C.c_int64, _VP, C.c_int64, _VP]),

@@ -1,8 +1,10 @@
-// ds_sample.hip -- the samplers and what shares their kernels (ds_mcmc.h, ds_onebody.h): the three fused Metropolis loops, the
-// one-body ratios and n(k), the single proposal / selection steps (ds_mh_*), the batch statistics and the host side of Philox.
+// ds_sample.hip -- the samplers and what shares their kernels (ds_mcmc.h, ds_onebody.h, ds_spin.h): the three fused Metropolis loops,
+// the one-body ratios and n(k), the spin-exchange ratios and the sums of <S^2>, the single proposal / selection steps (ds_mh_*), the
+// batch statistics and the host side of Philox.
 #include "ds_host.h"
 #include "ds_mcmc.h"
 #include "ds_onebody.h"
+#include "ds_spin.h"
 
 namespace ds {
 namespace host {
@@ -133,6 +135,69 @@ int one_body_impl(ds_system* s, const void* params, const void* x_, int64_t B, i
         if (n_k > 0 || n_bad)
             hipLaunchKernelGGL(ds::k_onebody_final, dim3((unsigned)((4 * n_k + 2 + 255) / 256)), dim3(256), 0, st, (const double*)w.PART,
                                (long long)groups, n_k, g0 == 0 ? 1 : 0, g0 + chunk >= total ? 1 : 0, w.ACC, nk_sums, (long long*)n_bad);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------ spin-exchange ratios and the sums of <S^2>, ds_spin.h
+// Workspace of ds_spin_exchange_ratios for B walkers, M samples per walker and chunks of ng groups of PV exchanged configurations.
+// Shared by all chunks: log|psi(R)| (B,), phase(R) (B,2), and in float64 (2 elements per double: room in either element size) every
+// ratio of the call (B,M,2) and the walker sums (B,2).  Per chunk: the exchanged rows, their log|psi| / phase, and the value chain's
+// buffers for ng groups (on a 64-element border), which also serve the forward of the walkers themselves.
+template <typename T> struct SpinWs {
+    T *LA0, *PH0, *XD, *LA, *PH;
+    double *Q, *TW;
+    void* wsv; int64_t wsv_bytes;
+};
+template <typename T> SpinWs<T> carve_spin(const ds_system* s, Arena<T>& a, int64_t B, int64_t M, int64_t ng) {
+    const size_t nc = (size_t)ng * ds::PV;
+    SpinWs<T> w{};
+    w.LA0 = a.take((size_t)B); w.PH0 = a.take(2 * (size_t)B);
+    a.align(2);
+    w.Q = (double*)a.take(4 * (size_t)B * (size_t)M);
+    w.TW = (double*)a.take(4 * (size_t)B);
+    w.XD = a.take(nc * 3 * s->sd.N); w.LA = a.take(nc); w.PH = a.take(2 * nc);
+    a.align(64);
+    w.wsv = a.take(s->wsv.per_walker * (size_t)ng);
+    w.wsv_bytes = (int64_t)(s->wsv.per_walker * (size_t)ng * sizeof(T));
+    return w;
+}
+inline int64_t spin_bytes(const ds_system* s, int64_t B, int64_t M, int64_t ng) {
+    return (int64_t)measure([&](Arena<double>& a) { carve_spin<double>(s, a, B, M, ng); }) * (s->dtype == 0 ? 8 : 4);
+}
+
+template <typename T>
+int spin_exchange_impl(ds_system* s, const void* params, const void* x_, int64_t B, int M, int first, double* sums, void* out_ratio,
+                       double* out_walker, int64_t* n_bad, void* ws, int64_t ws_bytes, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const T* x = (const T*)x_;
+    const int64_t total = B * (int64_t)M;
+    // the chunk length follows from the workspace, as in one_body_impl
+    const int64_t fixed = spin_bytes(s, B, M, 0), per = spin_bytes(s, B, M, 1) - fixed;
+    int64_t ng = std::min<int64_t>({(ws_bytes - fixed) / per + 1, OB_MAX_GROUPS, (total + ds::PV - 1) / ds::PV});
+    while (ng >= 1 && spin_bytes(s, B, M, ng) > ws_bytes) --ng;
+    if (ng < 1) return fail("workspace too small for ds_spin_exchange_ratios: %lld bytes < %lld for one group of %d configurations",
+                            (long long)ws_bytes, (long long)spin_bytes(s, B, M, 1), ds::PV);
+    Arena<T> a = arena_of<T>(ws, ws_bytes);
+    const SpinWs<T> w = carve_spin<T>(s, a, B, M, ng);
+    if (!a.ok) return carve_fail("spin-exchange ratios");
+    if (int rc = logpsi_forward(s, params, x, B, w.LA0, w.PH0, w.wsv, w.wsv_bytes, st)) return rc;
+    ds::SpinArgs A;
+    A.M = M; A.N = S.N; A.n_up = S.n_up; A.n_dn = S.n_dn; A.first = first;
+    const int64_t chunk = ng * ds::PV;
+    for (int64_t g0 = 0; g0 < total; g0 += chunk) {
+        A.g0 = g0; A.n = std::min(chunk, total - g0);
+        hipLaunchKernelGGL((ds::k_spin_propose<T>), dim3((unsigned)((A.n * S.N + 255) / 256)), dim3(256), 0, st, A, x, w.XD);
+        if (int rc = logpsi_forward(s, params, w.XD, A.n, w.LA, w.PH, w.wsv, w.wsv_bytes, st)) return rc;
+        hipLaunchKernelGGL((ds::k_spin_ratio<T>), dim3((unsigned)((A.n + 255) / 256)), dim3(256), 0, st, A, (const T*)w.LA0, (const T*)w.PH0,
+                           (const T*)w.LA, (const T*)w.PH, w.Q, (T*)out_ratio);
+    }
+    if (sums || out_walker || n_bad) {
+        hipLaunchKernelGGL(ds::k_spin_walker, dim3((unsigned)((B + ds::SPIN_WAVES - 1) / ds::SPIN_WAVES)), dim3(64 * ds::SPIN_WAVES), 0, st,
+                           (const double*)w.Q, (long long)B, M, w.TW, out_walker);
+        if (sums || n_bad)
+            hipLaunchKernelGGL(ds::k_spin_final, dim3(1), dim3(256), 0, st, (const double*)w.TW, (long long)B, sums, (long long*)n_bad);
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -371,6 +436,35 @@ int ds_one_body_ratios(ds_system* s, const void* params, const void* x, int64_t 
     hipStream_t st = (hipStream_t)stream;
     return DS_BY_DTYPE(s->dtype, one_body_impl, s, params, x, B, n_samples, first_electron, philox_seed, philox_offset, shifts, kvec, n_k,
                        nk_sums, out_ratio, out_shift, n_bad, ws, ws_bytes, st);
+}
+
+int64_t ds_spin_exchange_workspace_bytes(const ds_system* s, int64_t B, int n_pairs) {
+    if (!s || B < 1 || n_pairs < 1) return -1;
+    // as many groups per chunk as ds_workspace_bytes gives the value chain of B * n_pairs walkers
+    const int64_t esz = s->dtype == 0 ? 8 : 4, total = B * (int64_t)n_pairs;
+    const int64_t budget = workspace_budget();
+    const int64_t fixed = spin_bytes(s, B, n_pairs, 0), per = spin_bytes(s, B, n_pairs, 1) - fixed;
+    const int64_t ng = std::min(groups_per_pass(total, esz, PassSize{0, (size_t)(per / esz)}, budget), OB_MAX_GROUPS);
+    return spin_bytes(s, B, n_pairs, ng);
+}
+
+int ds_spin_exchange_ratios(ds_system* s, const void* params, const void* x, int64_t B, int n_pairs, int first_pair, double* sums,
+                            void* out_ratio, double* out_walker, int64_t* n_bad, void* ws, int64_t ws_bytes, void* stream) {
+    if (s) ++s->call_seq;
+    if (!s || !params || !x || !ws) return fail("null argument");
+    if (B < 1) return fail("ds_spin_exchange_ratios: B must be >= 1 (got %lld)", (long long)B);
+    const int64_t P = (int64_t)s->sd.n_up * s->sd.n_dn;
+    if (P == 0)
+        return fail("ds_spin_exchange_ratios: the cell has no pair of opposite spins (n_up = %d, n_dn = %d): S^2 = S_z (S_z + 1) exactly",
+                    s->sd.n_up, s->sd.n_dn);
+    if (n_pairs < 1) return fail("ds_spin_exchange_ratios: n_pairs must be >= 1 (got %d)", n_pairs);
+    if (first_pair < 0 || first_pair >= P)
+        return fail("ds_spin_exchange_ratios: first_pair must be in 0..%lld (got %d)", (long long)P - 1, first_pair);
+    if (!sums && !out_ratio && !out_walker)
+        return fail("ds_spin_exchange_ratios: sums, out_ratio and out_walker are all null, nothing to write");
+    hipStream_t st = (hipStream_t)stream;
+    return DS_BY_DTYPE(s->dtype, spin_exchange_impl, s, params, x, B, n_pairs, first_pair, sums, out_ratio, out_walker, n_bad, ws, ws_bytes,
+                       st);
 }
 
 int ds_energy_stats(ds_system* s, const void* ke, const void* ewald, int64_t B, double* out_stats, void* stream) {

@@ -770,6 +770,35 @@ class DeviceSystem:
                                                _ptr(out_s), _ptr(n_bad), _ptr(ws), ws.numel(), _stream()), 'ds_one_body_ratios')
         return dict(nk_sums=nk_sums, n_bad=n_bad, ratios=torch.view_as_complex(ratios) if want_ratios else None, shifts=out_s)
 
+    def spin_exchange_ratios(self, params, x, n_pairs=None, first_pair=0, sums=None, want_ratios=False, want_walker=False,
+                             max_bytes=None):
+        """`ds_spin_exchange_ratios`: per walker `n_pairs` ratios q = psi(P_p R) / psi(R), P_p exchanging the positions of the up
+        electron i and the down electron j of pair p = i n_dn + (j - n_up); sample m takes pair (first_pair + m) % P, P = n_up n_dn
+        (default n_pairs: P, every pair once).  No random numbers.  `sums`: float64 device tensor (4,) that is ADDED to (None: a
+        fresh zero one) = [sum_w Re t_w, sum_w Im t_w, sum_w (Re t_w)^2, good walkers] with t_w = sum_m q_{w,m}; a walker with a
+        non-finite q is left out and counted.  `max_bytes` caps the workspace: more chunks, bit-identical results.
+        -> dict(sums (4,), n_bad (1,) int64 device tensor, ratios (B, M) complex with `want_ratios`, walker (B,) complex128 with
+        `want_walker`: NaN for a bad walker).  <S^2> = S_z (S_z + 1) + n_dn - (P / M) sums[0] / sums[3] (`estimator.SpinSquared`).
+        No host synchronisation."""
+        x = self._check_x(x)
+        B = x.shape[0]
+        M = self.nelec[0] * self.nelec[1] if n_pairs is None else int(n_pairs)
+        p = self.pack_params(params)
+        if sums is None:
+            sums = torch.zeros(4, dtype=torch.float64, device=self.device)
+        elif not (sums.is_cuda and sums.dtype == torch.float64 and sums.is_contiguous() and tuple(sums.shape) == (4,)):
+            raise ValueError('sums must be a contiguous float64 device tensor of shape (4,)')
+        ratios = torch.empty(B, M, 2, dtype=self.dtype, device=self.device) if want_ratios and M >= 1 else None
+        walker = torch.empty(B, 2, dtype=torch.float64, device=self.device) if want_walker else None
+        n_bad = torch.zeros(1, dtype=torch.int64, device=self.device)
+        ws = self._workspace('ds_spin_exchange_workspace_bytes', int(B), M, max_bytes=max_bytes) if B >= 1 and M >= 1 else \
+            self.workspace(max(B, 1))                  # (the library refuses B < 1 / n_pairs < 1 itself)
+        _lib.check(self.lib.ds_spin_exchange_ratios(self.handle, _ptr(p), _ptr(x), B, M, int(first_pair), _ptr(sums), _ptr(ratios),
+                                                    _ptr(walker), _ptr(n_bad), _ptr(ws), ws.numel(), _stream()),
+                   'ds_spin_exchange_ratios')
+        return dict(sums=sums, n_bad=n_bad, ratios=torch.view_as_complex(ratios) if ratios is not None else None,
+                    walker=torch.view_as_complex(walker) if want_walker else None)
+
     def energy_stats(self, ke, ew):
         """`ds_energy_stats`: (8,) float64 = [sum Re E_L, sum Im E_L, sum |E_L|^2, n, n_nonfinite, sum Re ke, sum Im ke, sum ew]."""
         out = torch.empty(8, dtype=torch.float64, device=self.device)

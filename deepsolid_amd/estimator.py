@@ -518,3 +518,160 @@ class MomentumDistribution:
         """The accumulator saved at `path` as a fresh rank-local one without a network (see `from_state_dict`)."""
         with np.load(path) as f:
             return cls.from_state_dict({k: f[k] for k in f.files})
+
+
+# ------------------------------------------------------------------ total spin <S^2> (csrc/ds_spin.h)
+# The reference has no such estimator; the conventions of this section are this project's own (DESIGN.md section 17).
+class SpinSquared:
+    """Total spin <S^2> of a network's wavefunction from spin-exchange ratios, accumulated on the device over any number of walker
+    batches: an accumulator for `run_inference(accumulators=...)`.  With P = n_up n_dn pairs (i, j) of an up and a down electron and
+    q_p(R) = psi(P_p R) / psi(R), P_p exchanging the two positions,
+
+        <S^2> = S_z (S_z + 1) + n_dn - < sum_p q_p(R) >_{|psi|^2},   S_z = (n_up - n_dn) / 2.
+
+    Every `update` is ONE `ds_spin_exchange_ratios` call that takes, per walker, `pairs_per_walker` = M pairs in turn (default P:
+    every pair) and adds the walker sums t_w = sum_m q_{w,m} to four float64 numbers; nothing is read back.  psi is antisymmetric
+    within a spin channel, so every pair has the same expectation and M pairs scaled by P / M are unbiased; `first_pair` advances by
+    M mod P per update, so that all pairs are visited in turn.  No random numbers are drawn.  `net`: the object
+    `make_solid_fermi_net` returns (or its `.apply`).  A cell without a pair of opposite spins (P = 0) makes no library call."""
+
+    def __init__(self, net, params, pairs_per_walker=None):
+        self.apply = getattr(net, 'apply', net)
+        self.params = params
+        cell = self.apply.simulation_cell
+        self._setup((int(cell.nelec[0]), int(cell.nelec[1])), pairs_per_walker)
+
+    def _setup(self, nelec, pairs_per_walker):
+        self.nelec = (int(nelec[0]), int(nelec[1]))
+        self.n_pairs_total = self.nelec[0] * self.nelec[1]
+        self.pairs_per_walker = self.n_pairs_total if pairs_per_walker is None else int(pairs_per_walker)
+        if self.pairs_per_walker < 1 and self.n_pairs_total > 0:
+            raise ValueError(f'pairs_per_walker = {pairs_per_walker} must be >= 1')
+        self.sums = torch.zeros(4, dtype=torch.float64)          # moved to the walkers' device by the first update
+        self.n_bad = torch.zeros(1, dtype=torch.int64)
+        self.n_walkers = 0
+        self.first_pair = 0
+        self.reduced = False
+
+    # ---- accumulation
+    def update(self, data):
+        """Add `pairs_per_walker` exchange ratios of every walker of `data` (B, 3N) to the sums: one library call, no device -> host
+        copy.  With P = 0 the walkers are only counted."""
+        if self.apply is None:
+            raise RuntimeError('SpinSquared.update: a loaded accumulator has no network; merge it into one that has')
+        if self.reduced:
+            raise RuntimeError('SpinSquared.update after reduce(): the sums are already summed over the ranks')
+        n_el = sum(self.nelec)
+        if data.shape[-1] != 3 * n_el:
+            raise ValueError(f'walkers have {data.shape[-1]} coordinates, the cell has {n_el} electrons')
+        x = data.reshape(-1, 3 * n_el)
+        self.n_walkers += int(x.shape[0])
+        if self.n_pairs_total == 0:
+            return
+        if self.sums.device != x.device:
+            self.sums, self.n_bad = self.sums.to(x.device), self.n_bad.to(x.device)
+        out = self.apply.system.spin_exchange_ratios(self.params, x, self.pairs_per_walker, first_pair=self.first_pair, sums=self.sums)
+        self.n_bad += out['n_bad']
+        self.first_pair = (self.first_pair + self.pairs_per_walker) % self.n_pairs_total
+
+    def _same_setup(self, other):
+        return self.nelec == other.nelec and self.pairs_per_walker == other.pairs_per_walker
+
+    def merge(self, other):
+        """Add the sums, the bad count and the walker number of another accumulator with the same electrons and pairs per walker.
+        Both sides must be in the same state (rank-local or summed over the ranks), as for `RealSpaceAccumulator.merge`."""
+        if not self._same_setup(other):
+            raise ValueError('SpinSquared.merge: the two accumulators differ in electron numbers or pairs per walker')
+        if self.reduced != other.reduced and constants.world_size() > 1:
+            raise ValueError('SpinSquared.merge: one side is summed over the ranks and the other is rank-local')
+        self.sums = self.sums + other.sums.to(self.sums.device)
+        self.n_bad = self.n_bad + other.n_bad.to(self.n_bad.device)
+        self.n_walkers += other.n_walkers
+        return self
+
+    def reduce(self):
+        """Sum the four sums, the bad count and the walker number over the ranks in ONE packed float64 all-reduce (counts below
+        2^53 are exact; the identity at world size 1).  Once per accumulator: a second call raises."""
+        if self.reduced:
+            raise RuntimeError('SpinSquared.reduce was already called: reducing twice would count every rank again')
+        if constants.world_size() > 1:
+            dev = self.sums.device if self.sums.is_cuda else torch.device('cuda' if torch.cuda.is_available() else 'cpu')
+            packed = torch.cat([self.sums.to(dev), self.n_bad.to(dev, torch.float64),
+                                torch.tensor([self.n_walkers], dtype=torch.float64, device=dev)])
+            packed = constants.psum_if_pmap(packed)
+            self.sums = packed[:4].clone()
+            self.n_bad = packed[4:5].round().to(torch.int64)
+            self.n_walkers = int(packed[5].round())
+        self.reduced = True                 # only now: a collective that raised leaves the accumulator as it was
+        return self
+
+    # ---- normalisation (host)
+    def spin_squared(self):
+        """-> dict(value, error, imag, n_walkers, n_bad, sz):
+        value = S_z (S_z + 1) + n_dn - (P / M) sum_w Re t_w / n_good over the n_good walkers whose ratios were all finite;
+        error = (P / M) sqrt((sum_w (Re t_w)^2 / n_good - mean^2) / (n_good - 1)): a NAIVE standard error over walkers -- it takes
+        them as independent and ignores the autocorrelation of the Markov chain, so it is a lower bound on a real run (NaN below
+        two good walkers); imag = -(P / M) sum_w Im t_w / n_good (vanishes in expectation); n_walkers: all walkers seen; n_bad:
+        those left out.  With P = 0 there is nothing to sample: value = S_z (S_z + 1) + n_dn = s (s + 1), s = |S_z|, exactly
+        (which is S_z (S_z + 1) for the cell without down electrons), error = 0."""
+        nu, nd = self.nelec
+        sz = 0.5 * (nu - nd)
+        base = sz * (sz + 1.0) + nd
+        n_bad = int(self.n_bad.sum())
+        if self.n_pairs_total == 0:
+            return dict(value=base, error=0.0, imag=0.0, n_walkers=self.n_walkers, n_bad=n_bad, sz=sz)
+        s = self.sums.detach().cpu().numpy()
+        scale = self.n_pairs_total / self.pairs_per_walker
+        n = float(s[3])
+        if n < 1:
+            return dict(value=float('nan'), error=float('nan'), imag=float('nan'), n_walkers=self.n_walkers, n_bad=n_bad, sz=sz)
+        mean = s[0] / n
+        var = max(s[2] / n - mean * mean, 0.0)
+        error = scale * float(np.sqrt(var / (n - 1))) if n > 1 else float('nan')
+        return dict(value=float(base - scale * mean), error=error, imag=float(-scale * s[1] / n), n_walkers=self.n_walkers,
+                    n_bad=n_bad, sz=sz)
+
+    # ---- persistence
+    def state_dict(self):
+        """Plain numpy arrays: the sums and counts, the setup they belong to and the pair the next update starts from."""
+        return {'sums': self.sums.detach().cpu().numpy().copy(), 'n_bad': self.n_bad.detach().cpu().numpy().copy(),
+                'n_walkers': np.int64(self.n_walkers), 'nelec': np.asarray(self.nelec, np.int64),
+                'pairs_per_walker': np.int64(self.pairs_per_walker), 'first_pair': np.int64(self.first_pair),
+                'reduced': np.bool_(self.reduced)}
+
+    def load_state_dict(self, sd):
+        """Replace the sums, counts and the next pair by those of `sd` (same electrons and pairs per walker); the accumulator is
+        rank-local and open for `update` afterwards."""
+        other = SpinSquared.from_state_dict(sd)
+        if not self._same_setup(other):
+            raise ValueError('SpinSquared.load_state_dict: the state belongs to other electron numbers or pairs per walker')
+        self.sums, self.n_bad = other.sums.to(self.sums.device), other.n_bad.to(self.n_bad.device)
+        self.n_walkers, self.first_pair, self.reduced = other.n_walkers, other.first_pair, False
+        return self
+
+    @classmethod
+    def from_state_dict(cls, sd):
+        """An accumulator without a network: it can be merged, normalised and saved, not updated."""
+        acc = cls.__new__(cls)
+        acc.apply = acc.params = None
+        acc._setup(tuple(int(v) for v in sd['nelec']), int(sd['pairs_per_walker']))
+        acc.sums = torch.as_tensor(np.array(sd['sums'], dtype=np.float64).reshape(4))
+        acc.n_bad = torch.as_tensor(np.array(sd['n_bad'], dtype=np.int64).reshape(1))
+        acc.n_walkers = int(sd['n_walkers'])
+        acc.first_pair = int(sd['first_pair']) if 'first_pair' in sd else 0
+        return acc                          # reduced stays False: the loaded sums are this rank's contribution from here on
+
+    def save(self, path, results=True):
+        """One .npz of `state_dict()`; `results`: also `value`, `error` and `imag` of `spin_squared()`."""
+        sd = self.state_dict()
+        if results:
+            r = self.spin_squared()
+            sd.update(value=np.float64(r['value']), error=np.float64(r['error']), imag=np.float64(r['imag']))
+        with open(path, 'wb') as f:
+            np.savez(f, **sd)
+
+    @classmethod
+    def load(cls, path):
+        """The accumulator saved at `path` as a fresh rank-local one without a network (see `from_state_dict`)."""
+        with np.load(path) as f:
+            return cls.from_state_dict({k: f[k] for k in f.files})

@@ -12,7 +12,9 @@ move the pretraining walkers on the network's density or on the Hartree-Fock den
 --pair-correlation BINS: the spin-resolved g(r) on BINS radial bins up to the Wigner-Seitz radius -- both through
 deepsolid_amd.estimator.RealSpaceAccumulator, written to realspace.npz in the working directory;
 --momentum SHELLS: the spin-resolved momentum distribution n(k) on the (2 SHELLS + 1)^3 Bloch-allowed k points around the twist,
-through deepsolid_amd.estimator.MomentumDistribution, written to momentum.npz)"""
+through deepsolid_amd.estimator.MomentumDistribution, written to momentum.npz;
+--spin-squared [PAIRS]: the total spin <S^2> from PAIRS spin-exchange ratios per walker and evaluation step (default: all
+n_up n_dn pairs), through deepsolid_amd.estimator.SpinSquared, written to spin_squared.npz)"""
 import os
 import sys
 
@@ -56,6 +58,14 @@ if '--momentum' in sys.argv:
     i = sys.argv.index('--momentum')
     momentum_shells = int(sys.argv[i + 1])
     del sys.argv[i:i + 2]
+spin_squared, spin_pairs = False, None
+if '--spin-squared' in sys.argv:
+    i = sys.argv.index('--spin-squared')
+    spin_squared = True
+    if i + 1 < len(sys.argv) and sys.argv[i + 1].isdigit():      # (the option takes a number that follows it: give iterations / batch first)
+        spin_pairs = int(sys.argv[i + 1])
+        del sys.argv[i + 1]
+    del sys.argv[i]
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 batch = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
 cell, klist = systems.build('lih')
@@ -80,12 +90,24 @@ if density_grid is not None or pair_bins is not None:
 if momentum_shells is not None:
     from deepsolid_amd import estimator
     accumulators += (estimator.MomentumDistribution(logdet, params, shells=momentum_shells),)
+momentum_acc = accumulators[-1] if momentum_shells is not None else None
+spin_acc = None
+if spin_squared:
+    from deepsolid_amd import estimator
+    spin_acc = estimator.SpinSquared(logdet, params, pairs_per_walker=spin_pairs)
+    accumulators += (spin_acc,)
 data, width, rows = inference.run_inference(slogdet, logdet, params, data, cell, iterations=10, burn_in=10, move_width=width,
                                             accumulators=accumulators)
 print('evaluation: E = %.4f +- %.4f Ha over 10 x %d walkers' % (sum(r['energy'] for r in rows) / len(rows),
                                                                 (sum(r['variance'] for r in rows) / len(rows) / (10 * batch)) ** 0.5, batch))
 for acc in accumulators:
-    if momentum_shells is not None and acc is accumulators[-1]:
+    if acc is spin_acc:
+        acc.save('spin_squared.npz', results=True)
+        s2 = acc.spin_squared()
+        print('<S^2>:      %.4f +- %.4f (naive error over %d walkers, %d left out; %d of %d pairs per walker; S_z (S_z + 1) = %.2f)'
+              % (s2['value'], s2['error'], s2['n_walkers'], s2['n_bad'], acc.pairs_per_walker, acc.n_pairs_total, s2['sz'] * (s2['sz'] + 1)))
+        continue
+    if acc is momentum_acc:
         acc.save('momentum.npz', results=True)
         nk = acc.momentum_distribution().real
         print('n(k):       %d k points, %d / %d samples (%d / %d left out); n_up(k_t) = %.4f, n_down(k_t) = %.4f, sums over k = %.4f / %.4f'

@@ -405,6 +405,46 @@ int ds_one_body_ratios(ds_system* sys, const void* params, const void* x, int64_
                        uint64_t philox_seed, uint64_t philox_offset, const void* shifts, const double* kvec, int n_k,
                        double* nk_sums, void* out_ratio, void* out_shift, int64_t* n_bad, void* ws, int64_t ws_bytes, void* stream);
 
+/* Spin-exchange ratios and the per-walker sums of the total-spin estimator <S^2> (csrc/ds_spin.h).  The
+ * reference has no such estimator: the conventions are this library's own.
+ *   Electrons 0 .. n_up-1 are spin up, the rest spin down.  P = n_up n_dn pairs.  Pair p = i n_dn + (j - n_up), with i < n_up <= j.
+ *   P_p R is R with the positions of electrons i and j exchanged.  Nothing is wrapped or shifted: both positions already belong to R.
+ *       q_p(R) = psi(P_p R) / psi(R)
+ *       <S^2>  = S_z (S_z + 1) + n_dn - < sum_p q_p(R) >_{|psi|^2},   S_z = (n_up - n_dn) / 2
+ *   The real part is the estimate.  The imaginary part vanishes in expectation.
+ *   Two checks of the sign and the n_dn term: one up and one down electron in the same orbital give 0; in orthogonal orbitals
+ *   they give 1.
+ *   psi is antisymmetric within each spin channel, so every pair has the same expectation.  Any subset of M pairs scaled by P / M
+ *   is therefore unbiased.
+ *
+ * One call takes M = n_pairs pairs per walker:
+ *   - Sample (w, m), m < M, takes pair (first_pair + m) % P of walker w.  M may exceed P: the index wraps, as first_electron does in
+ *     ds_one_body_ratios.  There is no random number in this call.
+ *   - q = exp(log|psi(P R)| - log|psi(R)|) phase(P R) conj(phase(R)), formed in float64 from the outputs of the value chain (that of
+ *     ds_logpsi: batches large enough for the int8 value layers use them here too).
+ *   - t_w = sum_m q_{w,m}, added in an order that is a function of M alone: lane l of one wave adds m = l, l + 64, ... in order, then
+ *     the 64 lane results are added in lane order.
+ *   - A walker with any non-finite q among its M samples is bad: it is left out of the sums, its out_walker entry is NaN, and it is
+ *     counted in n_bad (device (1,) int64, ADDED to; optional).
+ *   - sums: device (4,) float64 for either dtype, ADDED to and never zeroed, optional:
+ *       [ sum_w Re t_w, sum_w Im t_w, sum_w (Re t_w)^2, number of good walkers ]   over the good walkers of the call.
+ *     Normalisation is the caller's: <S^2> = S_z (S_z + 1) + n_dn - (P / M) sums[0] / sums[3].
+ *   - out_ratio (B, M, 2) = (Re q, Im q): device array of the system's dtype, optional.  out_walker (B, 2) = t_w: device float64,
+ *     optional.
+ * The call runs one forward of the B walkers, then per chunk of exchanged rows: propose, value chain, ratio; after the last chunk
+ * one kernel forms the walker sums and one reduces them over the walkers in a fixed order, making ONE addition per call and entry
+ * to sums.  No floating-point atomics, no host synchronisation, no allocation: the same input gives bit-identical results, a
+ * second call doubles sums exactly, and ANY workspace size gives the same bits under the condition of ds_one_body_ratios (the
+ * chunk length follows from ws_bytes, at most 65535 configurations; below one group of 80 configurations it is an error; the
+ * value chain must pick the same kernels for the chunk lengths involved, which holds whenever no int8 value layer is in play).
+ * Refused with a ds_last_error message before any launch: B < 1, n_pairs < 1, P == 0 (a fully polarised cell, the mirrored
+ * (0, n) cell among them: there S^2 = S_z (S_z + 1) exactly), first_pair outside 0..P-1, and nothing to write at all (sums, out_ratio
+ * and out_walker all NULL). */
+int64_t ds_spin_exchange_workspace_bytes(const ds_system* sys, int64_t B, int n_pairs);
+int ds_spin_exchange_ratios(ds_system* sys, const void* params, const void* x, int64_t B, int n_pairs, int first_pair,
+                            double* sums, void* out_ratio, double* out_walker, int64_t* n_bad, void* ws, int64_t ws_bytes,
+                            void* stream);
+
 /* Packed batch statistics of train.make_loss.total_energy (train.py:74-82) in one deterministic reduction:
  * out_stats (8,) float64 on the device =
  *   [ sum Re E_L, sum Im E_L, sum |E_L|^2, n, n_nonfinite, sum Re E_kin, sum Im E_kin, sum E_ewald ],  E_L = ke + ewald.
