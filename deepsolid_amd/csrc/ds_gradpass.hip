@@ -668,11 +668,11 @@ int kfac_precondition_run(const KfacStepPlan& sp, const void* inverses, const vo
                           hipStream_t st) {
     if (ws_bytes < sp.doubles * 8) return fail("ds_kfac_precondition: workspace too small (ds_kfac_step_workspace_bytes)");
     double* base = (double*)ws;
-    T* Tm = (T*)(base + sp.o_t);
+    double* Tm = base + sp.o_t;                    // A^- V, float64 for either element type (o_t holds vtotal doubles)
     double* part = base + sp.o_part;
     const dim3 grid((unsigned)((sp.tiles_max + 3) / 4), (unsigned)sp.M.nb);
     hipLaunchKernelGGL((ds::k_kprec_gemm<T, 1>), grid, dim3(256), 0, st, sp.M, (const T*)inverses, (const T*)v, Tm, (const T*)v, part);
-    hipLaunchKernelGGL((ds::k_kprec_gemm<T, 2>), grid, dim3(256), 0, st, sp.M, (const T*)inverses, (const T*)Tm, (T*)out, (const T*)v, part);
+    hipLaunchKernelGGL((ds::k_kprec_gemm<T, 2>), grid, dim3(256), 0, st, sp.M, (const T*)inverses, (const double*)Tm, (T*)out, (const T*)v, part);
     hipLaunchKernelGGL(ds::k_kprec_final, dim3((unsigned)sp.M.nb), dim3(64), 0, st, sp.M, (const double*)part, sq);
     HIP_OK(hipGetLastError());
     return 0;

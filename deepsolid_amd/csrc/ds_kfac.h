@@ -417,48 +417,74 @@ __global__ void __launch_bounds__(256) k_kinv_finish(KfacMats M, const double* _
 //   STAGE 1: Y_b = A^-_b X_b  (the symmetric A^- is read transposed: sixteen lanes read sixteen consecutive elements)
 //   STAGE 2: Y_b = X_b G^-_b / R_b, and part[toff[b] + tile] = sum over the tile of Y o V in float64 (fixed order: registers,
 //            then a butterfly over the lanes)
+// Both products accumulate in float64 on v_mfma_f64_16x16x4_f64 for either element type, and the intermediate A^- V is kept in
+// float64 (XT / YT below): a float32 system loses only the final rounding of `out`, and <out, V> is summed from the unrounded
+// entries.  In float32 accumulators that scalar -- the q of the norm constraint -- moved by one to two decades with the order of
+// summation (EXPERIMENTS.md, "KFAC on large cells").  For T = double nothing differs from a plain float64 product.
 // grid (ceil(max tiles / 4), nb), block 256
 template <typename T, int STAGE>
-__global__ void __launch_bounds__(256) k_kprec_gemm(KfacMats M, const T* __restrict__ inv, const T* __restrict__ X, T* __restrict__ Y,
-                                                    const T* __restrict__ V, double* __restrict__ part) {
-    typedef typename Acc4<T>::type acc_t;
+struct KprecTypes {
+    typedef T XT;           // STAGE 1 reads V
+    typedef double YT;      // and writes A^- V in float64
+};
+template <typename T>
+struct KprecTypes<T, 2> {
+    typedef double XT;      // STAGE 2 reads A^- V
+    typedef T YT;           // and writes out
+};
+
+template <typename T, int STAGE>
+__global__ void __launch_bounds__(256) k_kprec_gemm(KfacMats M, const T* __restrict__ inv,
+                                                    const typename KprecTypes<T, STAGE>::XT* __restrict__ X,
+                                                    typename KprecTypes<T, STAGE>::YT* __restrict__ Y, const T* __restrict__ V,
+                                                    double* __restrict__ part) {
+    typedef Acc4<double>::type acc_t;
+    typedef typename KprecTypes<T, STAGE>::XT XT;
+    typedef typename KprecTypes<T, STAGE>::YT YT;
     const int b = blockIdx.y, rows = M.n[2 * b], cols = M.n[2 * b + 1], tn = (cols + 31) / 32, tm = (rows + 31) / 32;
     const int wt = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, lr = lane & 15, lq = lane >> 4;
     if (wt >= tm * tn) return;
     const int i0 = 32 * (wt / tn), j0 = 32 * (wt % tn);
     const int K = STAGE == 1 ? rows : cols;
-    const T* Ap = STAGE == 1 ? inv + M.off[2 * b] : X + M.voff[b];
-    const T* Bp = STAGE == 1 ? X + M.voff[b] : inv + M.off[2 * b + 1];
+    const T* Ainv = inv + M.off[2 * b + (STAGE == 1 ? 0 : 1)];
+    const XT* Xb = X + M.voff[b];
     const size_t sar = STAGE == 1 ? 1 : (size_t)cols, sak = STAGE == 1 ? (size_t)rows : 1;
     acc_t acc[2][2];
     for (int a = 0; a < 2; ++a)
         for (int c = 0; c < 2; ++c) acc[a][c] = acc_t{0, 0, 0, 0};
     for (int k0 = 0; k0 < K; k0 += 4) {
         const int kk = k0 + lq;
-        T av[2], bv[2];
+        double av[2], bv[2];
         for (int a = 0; a < 2; ++a) {
             const int row = i0 + 16 * a + lr, col = j0 + 16 * a + lr;
-            av[a] = (row < rows && kk < K) ? Ap[(size_t)row * sar + (size_t)kk * sak] : T(0);
-            bv[a] = (col < cols && kk < K) ? Bp[(size_t)kk * cols + col] : T(0);
+            const bool aok = row < rows && kk < K, bok = col < cols && kk < K;
+            const size_t ai = (size_t)row * sar + (size_t)kk * sak, bi = (size_t)kk * cols + col;
+            if (STAGE == 1) {
+                av[a] = aok ? (double)Ainv[ai] : 0.0;
+                bv[a] = bok ? (double)Xb[bi] : 0.0;
+            } else {
+                av[a] = aok ? (double)Xb[ai] : 0.0;
+                bv[a] = bok ? (double)Ainv[bi] : 0.0;
+            }
         }
         for (int a = 0; a < 2; ++a)
             for (int c = 0; c < 2; ++c) acc[a][c] = mfma16(av[a], bv[c], acc[a][c]);
     }
-    T* Yb = Y + M.voff[b];
+    YT* Yb = Y + M.voff[b];
     const T* Vb = V + M.voff[b];
-    const T rep = (T)M.rep[b];
+    const double rep = (double)M.rep[b];
     double dot = 0;
     for (int a = 0; a < 2; ++a)
         for (int r = 0; r < 4; ++r) {
-            const int row = i0 + 16 * a + acc_row<T>(lane, r);
+            const int row = i0 + 16 * a + acc_row<double>(lane, r);
             if (row >= rows) continue;
             for (int c = 0; c < 2; ++c) {
                 const int col = j0 + 16 * c + lr;
                 if (col >= cols) continue;
                 const size_t o = (size_t)row * cols + col;
-                const T y = STAGE == 1 ? acc[a][c][r] : acc[a][c][r] / rep;
-                Yb[o] = y;
-                if (STAGE == 2) dot += (double)y * (double)Vb[o];
+                const double y = STAGE == 1 ? acc[a][c][r] : acc[a][c][r] / rep;
+                Yb[o] = (YT)y;
+                if (STAGE == 2) dot += y * (double)Vb[o];
             }
         }
     if (STAGE == 2) {

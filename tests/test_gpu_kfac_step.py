@@ -5,9 +5,17 @@ restatement of tests/kfac_step_helpers.py (itself held to reference-executed inv
 Bounds (float64): every inverse within 1e-9 of its largest entry -- the bound tests/test_gpu_kfac.py holds the factors to -- after
 asserting on the CPU that two independent float64 inversions of the same damped matrix (torch.linalg.inv and Cholesky) agree to
 1e-10, so the bound does not hide conditioning; symmetry exact.  Preconditioner: 1e-9 of each block's largest entry and 1e-9
-relative on each <P, V> (plain float64 products of at most 833 terms).  The deviations measured are recorded as test properties.
-Measured on an MI355X: unmeasured.  The elimination without its Newton step missed the 1e-9 bound on `lih_mixed` at damping 1e-3
-there (EXPERIMENTS.md, last section); the module has not run on one since the step was added."""
+relative on each <P, V> (plain float64 products of at most 864 terms).  The deviations measured are recorded as test properties.
+Measured on an MI355X, worst of a matrix's largest entry (the elimination WITHOUT its Newton step had missed 1e-9 on `lih_mixed` at
+damping 1e-3, EXPERIMENTS.md "KFAC step"; with the one step):
+  inverses at damping 1e-3: 1.3e-12 over the five earlier cases; bcc_li_333 8.8e-13, diamond 3.5e-12, graphene_331 4.6e-12 (orders up to
+  865, condition up to 5.2e5: one Newton step is enough, as a numpy emulation of the block steps predicts: 4.9e-12);
+  inverses at damping 1e-1: 2.8e-13 over the earlier cases; 9.1e-14, 4.3e-13, 9.5e-13 on the three large cells;
+  synthetic SPD sizes 1 ... 97: 3.5e-15 (float64), 4.6e-8 (float32); float32 system on lih: 5.4e-8;
+  preconditioner, float64 (lih, bcc_li, lih_mixed, bcc_li_333, graphene_331): out 3.6e-16, <P, V> 7.8e-16;
+  preconditioner, float32 (lih, diamond; the products accumulate in float64): out 5.0e-8 and 5.2e-8, <P, V> 7.4e-16 and 8.4e-16;
+  with float32 accumulators <P, V> had missed its budget on diamond (see test_precondition_vs_restatement);
+  whole step on lih: 4.9e-11 of a leaf's largest entry."""
 import ctypes as C
 import math
 import types
@@ -25,7 +33,10 @@ from test_gpu_grad import dev_params, fresh_system, system_for
 pytestmark = pytest.mark.gpu
 
 DAMPINGS = [1e-3, 1e-1]
-INVERSE_CASES = [('lih', 5), ('lih_narrow', 3), ('lih_mixed', 3), ('bcc_li', 3), ('bcc_li_fulldet', 3)]
+# the last three: orbital-head G of order 656 / 640 (20 block steps and an edge block of 16), 768 and 864 (27 block steps); their
+# worst damped matrix at damping 1e-3 has condition 9.7e4, 3.6e5 and 5.2e5, where `assert_well_conditioned` still passes
+INVERSE_CASES = [('lih', 5), ('lih_narrow', 3), ('lih_mixed', 3), ('bcc_li', 3), ('bcc_li_fulldet', 3),
+                 ('bcc_li_333', 3), ('diamond', 3), ('graphene_331', 3)]
 
 
 def rel(got, ref):
@@ -149,11 +160,24 @@ def test_inverses_float32_system(record_property):
 
 
 @pytest.mark.parametrize('name,dtype', [('lih', torch.float64), ('bcc_li', torch.float64), ('lih_mixed', torch.float64),
-                                        ('lih', torch.float32)])
+                                        ('lih', torch.float32),
+                                        # 21 to 27 column tiles of 32, and the ragged 16-column tile of 656
+                                        ('bcc_li_333', torch.float64), ('graphene_331', torch.float64), ('diamond', torch.float32)])
 def test_precondition_vs_restatement(name, dtype, record_property):
     """out_b = A^- v G^- / R and <out_b, v> with random v and the DEVICE's own inverses as input (inverse error does not compound).
     float32: the bound is what the restatement's own float32 run of the two products loses against its float64 run, times 4
-    (the summation order differs), measured per block and recorded."""
+    (the summation order differs), measured per block and recorded.
+    bcc_li_333, graphene_331 and diamond bring 21 to 27 column tiles and the ragged 16-column tile of 656.
+    Measured on an MI355X.  float64: out at most 3.6e-16, <P, V> at most 7.8e-16.  float32 (the kernel accumulates both products
+    in float64 and sums <P, V> from the unrounded entries): out 5.0e-8 (lih) and 5.2e-8 (diamond) of budgets from 4.0e-7 up,
+    <P, V> 7.4e-16 and 8.4e-16 of budgets from 1.8e-10 up.
+    The (`diamond`, float32) case is why: with float32 accumulators `out` was inside its budget (1.9e-6 at worst) but <P, V> missed
+    it on three of seven blocks --
+        kernel  5.4e-9, 2.3e-10, 3.2e-9, 2.4e-8, 2.7e-8, 8.3e-10, 3.3e-9
+        budget  1.4e-9, 1.9e-9,  1.7e-9, 3.8e-8, 1.1e-7, 9.9e-9,  1.8e-10      (4 x the restatement's float32 loss)
+    -- because the float32 loss of that one number per block is the sum of the rounding errors, of either sign, of up to 213 000
+    entries and moves by one to two decades with the summation order (tools/kfac_sq_spread.py: 4.1e-11 ... 3.3e-9 on one block
+    over 12 orders on the CPU), so no float32 accumulation meets 4 x one draw reliably."""
     fx, cell, klist, net_kw, params = load_case(name)
     sysd = system_for(cell, klist, net_kw) if dtype == torch.float64 else fresh_system(cell, klist, net_kw, dtype)
     x = torch.as_tensor(systems.synthetic_walkers(cell, 3, seed=91).astype(np.float64 if dtype == torch.float64 else np.float32),

@@ -52,7 +52,10 @@ def test_kfac_block_struct_matches_header():
     assert C.sizeof(_lib.KfacBlock) == 56           # ten int32 fields, two int64 offsets, no padding
 
 
-@pytest.mark.parametrize('name', ['lih', 'lih_lastlayer', 'li_polarized', 'lih_bias'])
+@pytest.mark.parametrize('name', ['lih', 'lih_lastlayer', 'li_polarized', 'lih_bias',
+                                  'lih_twist',          # complex k-points
+                                  'bcc_li_fulldet',     # one determinant over both spin channels
+                                  'bcc_li_333'])        # unequal non-empty spin channels (41, 40)
 def test_restatement_is_the_oracle_forward(name):
     """kfac_helpers.forward_captured against oracle.network: log|psi| to round-off, the gradient of sum_b sqrt2 log|psi_b| against
     autograd over the oracle's own eval_func; the factors are symmetric, positive semi-definite on the diagonal and carry the
