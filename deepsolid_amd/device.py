@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .params import ParamMap
 
 _DTYPES = {torch.float64: 0, torch.float32: 1}
 
@@ -143,10 +144,11 @@ class DeviceSystem:
         self.lib.ds_param_layout(handle, blocks, nb)
         self.blocks = [(int(b.offset), int(b.rows), int(b.cols)) for b in blocks]
         self.param_count = int(self.lib.ds_param_count(handle))
+        # the tree <-> buffer index map, the packed-buffer cache and the KFAC index live there
+        self.param_map = ParamMap(self.nelec, self.n_det, self.hidden_dims, self.device_dims, atoms.shape[0],
+                                  net_kw.get('distance_type', 'nu'), net_kw.get('envelope_type'), d.full_det, d.use_last_layer,
+                                  d.bias_orbitals, dtype, self.blocks, self.param_count)
         self._ws = None
-        self._packed = None
-        self._packed_key = None
-        self._packed_leaves = []
 
     # ------------------------------------------------------------------ construction helpers
     @classmethod
@@ -218,121 +220,7 @@ class DeviceSystem:
     def pack_params(self, params):
         """Reference parameter tree (network.py:135-186) -> the flat device buffer of
         include/deepsolid_hip.h (`ds_param_layout`).  Cached on the leaves' versions."""
-        leaves = []
-
-        def walk(o):
-            if isinstance(o, dict):
-                for k in sorted(o):
-                    walk(o[k])
-            elif isinstance(o, (list, tuple)):
-                for v in o:
-                    walk(v)
-            else:
-                leaves.append(o)
-        walk(params)
-        # cache only trees of tensors: the key holds the leaves themselves (so ids cannot be recycled), their
-        # storage address and version counter; numpy leaves have no version counter and are packed every call
-        cacheable = all(isinstance(t, torch.Tensor) for t in leaves)
-        key = tuple((t.data_ptr(), t._version) for t in leaves) if cacheable else None
-        if cacheable and self._packed is not None and key == self._packed_key and \
-                len(leaves) == len(self._packed_leaves) and all(a is b for a, b in zip(leaves, self._packed_leaves)):
-            return self._packed
-
-        def dev(a):
-            if not isinstance(a, torch.Tensor):
-                a = torch.as_tensor(np.asarray(a))
-            return a.to(device=self.device, dtype=pdt)
-        pdt = getattr(self, '_pack_dtype', None) or self.dtype     # _grad_index packs entry numbers in float64
-        flat = torch.zeros(self.param_count, dtype=pdt, device=self.device)
-        nch = 2 if self.nelec[1] > 0 else 1
-        bi = iter(self.blocks)
-
-        def put(mat):
-            off, rows, cols = next(bi)
-            mat = mat.reshape(rows, cols) if mat.numel() == rows * cols else mat
-            if tuple(mat.shape) != (rows, cols):
-                raise ValueError(f'parameter block shape {tuple(mat.shape)} != expected {(rows, cols)}')
-            flat[off:off + rows * cols] = mat.reshape(-1)
-        natom = np.asarray(self.cell.original_cell.atom_coords()).reshape(-1, 3).shape[0]
-        nf = 4 if self.net_kw.get('distance_type', 'nu') == 'nu' else 7
-        r4 = lambda v: (v + 3) // 4 * 4
-        # reference widths (network.py:111-132) and the device widths (layer-0 rows padded to the MFMA k-step, hidden widths
-        # to what the kernels run: device_widths)
-        h1_ref = [nf * natom] + [h[0] for h in self.hidden_dims]
-        h2_ref = [nf] + [h[1] for h in self.hidden_dims]
-        h1 = [r4(nf * natom)] + [h[0] for h in self.device_dims]
-        h2 = [r4(nf)] + [h[1] for h in self.device_dims]
-
-        def pad_rows(m, rows):
-            if m.shape[0] == rows:
-                return m
-            return torch.cat([m, torch.zeros(rows - m.shape[0], m.shape[1], dtype=m.dtype, device=m.device)], dim=0)
-
-        def pad_cols(m, cols):
-            if m.shape[-1] == cols:
-                return m
-            return torch.cat([m, torch.zeros(*m.shape[:-1], cols - m.shape[-1], dtype=m.dtype, device=m.device)], dim=-1)
-        for l in range(len(self.hidden_dims)):
-            w = dev(params['single'][l]['w'])
-            kh, k2, khp, k2p = h1_ref[l], h2_ref[l], h1[l], h2[l]
-            if w.shape[0] != (nch + 1) * kh + nch * k2 or w.shape[1] != h1_ref[l + 1]:
-                raise ValueError(f"single[{l}]['w'] has shape {tuple(w.shape)}, expected {((nch + 1) * kh + nch * k2, h1_ref[l + 1])}")
-            w = pad_cols(w, h1[l + 1])
-            m2 = [pad_rows(w[(nch + 1) * kh + c * k2:(nch + 1) * kh + (c + 1) * k2], k2p) for c in range(nch)]
-            put(torch.cat([pad_rows(w[:kh], khp)] + m2, dim=0))                       # per-electron rows [h | m2_up | m2_dn]
-            put(torch.cat([pad_rows(w[(1 + c) * kh:(2 + c) * kh], khp) for c in range(nch)], dim=0))   # spin-mean rows
-            put(pad_cols(dev(params['single'][l]['b']).reshape(1, -1), h1[l + 1]))
-        use_last = bool(self.net_kw.get('use_last_layer', False))
-        for l in range(len(self.hidden_dims) - (0 if use_last else 1)):
-            put(pad_cols(pad_rows(dev(params['double'][l]['w']), h2[l]), h2[l + 1]))
-            put(pad_cols(dev(params['double'][l]['b']).reshape(1, -1), h2[l + 1]))
-        full_det = bool(self.net_kw.get('full_det', False))
-        for c in range(nch):
-            norb = self.n if full_det else self.nelec[c]
-            nparam = norb * self.n_det
-            w = dev(params['orbital'][c]['w'])
-            if w.shape[1] != 2 * nparam:
-                raise ValueError(f"orbital[{c}]['w'] has {w.shape[1]} columns, expected {2 * nparam}")
-            def put_packed(mat):
-                off, rows, cols = next(bi)
-                src = self._orbital_column_map(nparam, cols)
-                if mat.shape[0] != rows:
-                    raise ValueError(f"orbital[{c}]['w'] block has {mat.shape[0]} rows, expected {rows}")
-                packed = torch.zeros(rows, cols, dtype=pdt, device=self.device)
-                valid = src >= 0
-                packed[:, torch.as_tensor(np.nonzero(valid)[0], device=self.device)] = \
-                    mat[:, torch.as_tensor(src[valid], device=self.device)]
-                flat[off:off + rows * cols] = packed.reshape(-1)
-            kh, k2, khp, k2p = h1_ref[-1], h2_ref[-1], h1[-1], h2[-1]
-            if use_last:      # rows [h | mean_up | mean_dn | m2_up | m2_dn] (network.py:126-128) -> per-electron / shared
-                m2 = [pad_rows(w[(nch + 1) * kh + cc * k2:(nch + 1) * kh + (cc + 1) * k2], k2p) for cc in range(nch)]
-                put_packed(torch.cat([pad_rows(w[:kh], khp)] + m2, dim=0))
-                put_packed(torch.cat([pad_rows(w[(1 + cc) * kh:(2 + cc) * kh], khp) for cc in range(nch)], dim=0))
-            else:
-                put_packed(pad_rows(w, khp))
-            if self.net_kw.get('bias_orbitals', False):
-                put(dev(params['orbital'][c]['b']))
-            put(dev(params['envelope'][c]['pi']))
-            # sigma: (A, P) isotropic | (A, 3, P) diagonal -> rows a*3+c | (3, 3, A, P) full -> rows (k*3+m)*A+a
-            put(dev(params['envelope'][c]['sigma']).reshape(-1, nparam))
-        self._packed, self._packed_key, self._packed_leaves = (flat, key, leaves) if cacheable else (None, None, [])
-        return flat
-
-    def _orbital_column_map(self, nparam, cols):
-        """Packed column c -> reference column of orbital[s]['w'] (or -1 for zero padding).
-        Within every 16-column tile t the MFMA accumulator gives lane group q = lane >> 4 the rows
-        {q, q+4, q+8, q+12} (f64) or {4q .. 4q+3} (f32) in registers r = 0..3; they are assigned
-        (Re p, Im p, Re p+4, Im p+4) with p = 8t + q, so the complex product with the envelope/phase jet
-        is lane-local in the fused orbital epilogue (csrc/ds_gemm.h: orb_col)."""
-        src = -np.ones(cols, dtype=np.int64)
-        for t in range(cols // 16):
-            for q in range(4):
-                for r in range(4):
-                    row = q + 4 * r if self.dtype == torch.float64 else 4 * q + r
-                    p = 8 * t + q + 4 * (r // 2)
-                    if p < nparam:
-                        src[16 * t + row] = p + (r % 2) * nparam
-        return src
+        return self.param_map.pack(params, self.device, self.dtype)
 
     # ------------------------------------------------------------------ calls
     def ewald(self, x):
@@ -519,120 +407,12 @@ class DeviceSystem:
         return out, sq
 
     def kfac_index(self, params):
-        """Index maps of the KFAC step for a parameter tree of this shape, built once (the leaf numbering of `_grad_index`):
-        -> dict(v_src, diag_src: positions in the PACKED buffer of every entry of v (all blocks' d_in x d_out matrices in layout
-        order, rows in the reference's order w.reshape(-1, d_out) then b) and of the untagged leaves (envelope pi, sigma);
-        v_tree, diag_tree: the same entries as positions in the tree-flat vector (leaves in sorted-key order, row-major);
-        leaf_sizes: entries per leaf of that vector).  Packing is `packed.index_select(0, v_src)`, unpacking one `index_copy_`."""
-        pos = self._grad_index(params)
-        if getattr(self, '_kidx_key', None) == self._gidx_key:
-            return self._kidx
-        if bool((pos < 0).any()):
-            raise RuntimeError('parameter entries without a place in the packed buffer')
-        starts, sizes, off = {}, [], [0]
-
-        def walk(o, path):
-            if isinstance(o, dict):
-                for k in sorted(o):
-                    walk(o[k], path + (k,))
-            elif isinstance(o, (list, tuple)):
-                for i, v in enumerate(o):
-                    walk(v, path + (i,))
-            else:
-                t = torch.as_tensor(np.asarray(o)) if not isinstance(o, torch.Tensor) else o
-                starts[path] = (off[0], tuple(t.shape))
-                sizes.append(t.numel())
-                off[0] += t.numel()
-        walk(params, ())
-        tagged, v_tree = set(), []
-        for b in self.kfac_layout():
-            w0, wshape = starts[(b['kind'], b['index'], 'w')]
-            d_out = wshape[-1]
-            nw = int(np.prod(wshape))
-            rows = nw // d_out + (1 if b['has_bias'] else 0)
-            if d_out != b['d_out'] or rows != b['d_in']:
-                raise ValueError(f"{b['kind']}[{b['index']}]: the tree holds a {rows} x {d_out} block, the layout {b['d_in']} x {b['d_out']}")
-            v_tree.append(torch.arange(w0, w0 + nw))
-            tagged.add((b['kind'], b['index'], 'w'))
-            if b['has_bias']:
-                b0, bshape = starts[(b['kind'], b['index'], 'b')]
-                if int(np.prod(bshape)) != d_out:
-                    raise ValueError(f"{b['kind']}[{b['index']}]['b'] does not have {d_out} entries")
-                v_tree.append(torch.arange(b0, b0 + d_out))
-                tagged.add((b['kind'], b['index'], 'b'))
-        diag_tree = [torch.arange(s, s + int(np.prod(shp))) for path, (s, shp) in starts.items() if path not in tagged]
-        v_tree = torch.cat(v_tree).to(self.device)
-        diag_tree = (torch.cat(diag_tree) if diag_tree else torch.zeros(0, dtype=torch.int64)).to(self.device)
-        self._kidx = dict(v_src=pos[v_tree], diag_src=pos[diag_tree], v_tree=v_tree, diag_tree=diag_tree, leaf_sizes=sizes,
-                          diag_paths=[p for p in starts if p not in tagged])
-        self._kidx_key = self._gidx_key
-        return self._kidx
-
-    def _grad_index(self, params):
-        """For every leaf of the parameter tree: positions of its entries in the packed buffer (the packing
-        is a gather with zero padding, so its transpose is one index_select per leaf).  Found by packing a
-        tree whose leaves hold their own running entry number."""
-        shapes = []
-
-        def walk(o):
-            if isinstance(o, dict):
-                return {k: walk(o[k]) for k in sorted(o)}
-            if isinstance(o, (list, tuple)):
-                return [walk(v) for v in o]
-            t = torch.as_tensor(np.asarray(o)) if not isinstance(o, torch.Tensor) else o
-            shapes.append(tuple(t.shape))
-            return None
-        walk(params)
-        key = tuple(shapes)
-        if getattr(self, '_gidx_key', None) == key:
-            return self._gidx
-        counter = [1]
-
-        def number(o):
-            if isinstance(o, dict):
-                return {k: number(o[k]) for k in sorted(o)}
-            if isinstance(o, (list, tuple)):
-                return [number(v) for v in o]
-            t = torch.as_tensor(np.asarray(o)) if not isinstance(o, torch.Tensor) else o
-            n = t.numel()
-            out = torch.arange(counter[0], counter[0] + n, dtype=torch.float64).reshape(t.shape)
-            counter[0] += n
-            return out
-        numbered = number(params)
-        saved = (self._packed, self._packed_key, self._packed_leaves)
-        try:
-            self._pack_dtype = torch.float64    # entry numbers must survive the packing exactly
-            self._packed = None
-            flat = self.pack_params(numbered).round().to(torch.int64)
-        finally:
-            self._pack_dtype = None
-            self._packed, self._packed_key, self._packed_leaves = saved
-        total = counter[0] - 1
-        pos = torch.full((total + 1,), -1, dtype=torch.int64, device=self.device)
-        nz = torch.nonzero(flat > 0).reshape(-1)
-        pos[flat[nz]] = nz
-        self._gidx, self._gidx_key = pos[1:], key
-        return self._gidx
+        """Index maps of the KFAC step for a parameter tree of this shape, built once (`ParamMap.kfac_index`)."""
+        return self.param_map.kfac_index(self.kfac_layout(), params, self.device)
 
     def unpack_grad(self, flat, params):
         """Packed gradient -> a tree shaped like `params` (reference layout, network.py:135-186)."""
-        pos = self._grad_index(params)
-        if bool((pos < 0).any()):
-            raise RuntimeError('parameter entries without a place in the packed buffer')
-        vals = flat[pos]
-        off = [0]
-
-        def build(o):
-            if isinstance(o, dict):
-                return {k: build(o[k]) for k in sorted(o)}
-            if isinstance(o, (list, tuple)):
-                return [build(v) for v in o]
-            t = torch.as_tensor(np.asarray(o)) if not isinstance(o, torch.Tensor) else o
-            n = t.numel()
-            out = vals[off[0]:off[0] + n].reshape(t.shape)
-            off[0] += n
-            return out
-        return build(params)
+        return self.param_map.unpack(flat, params)
 
     def orbitals(self, params, x):
         x = self._check_x(x)

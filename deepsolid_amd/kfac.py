@@ -16,18 +16,7 @@ import numpy as np
 import torch
 
 from . import constants
-
-
-def _leaves(o, out):
-    if isinstance(o, dict):
-        for k in sorted(o):
-            _leaves(o[k], out)
-    elif isinstance(o, (list, tuple)):
-        for v in o:
-            _leaves(v, out)
-    else:
-        out.append(o)
-    return out
+from .params import tree_leaves
 
 
 def kfac(learning_rate_schedule, damping=1e-3, l2_reg=0.0, norm_constraint=1e-3, cov_ema_decay=0.95, invert_every=1, momentum=0.0,
@@ -109,7 +98,7 @@ def kfac(learning_rate_schedule, damping=1e-3, l2_reg=0.0, norm_constraint=1e-3,
         delta.index_copy_(0, index['v_tree'], p_v * scale)
         delta.index_copy_(0, index['diag_tree'], p_d * scale)
         off = 0
-        for leaf, n in zip(_leaves(params, []), index['leaf_sizes']):
+        for leaf, n in zip(tree_leaves(params), index['leaf_sizes']):
             leaf.add_(delta[off:off + n].view(leaf.shape))        # in place: bumps the tensor version, the packed cache refreshes
             off += n
         state['velocities'] = delta

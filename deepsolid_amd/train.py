@@ -16,6 +16,7 @@ from collections import namedtuple
 import torch
 
 from . import constants, hamiltonian
+from .params import tree_leaves
 
 # the reference's five fields (train.py:28-34) + the non-finite count behind its check_nan step rejection (process.py:303-318)
 AuxiliaryLossData = namedtuple('AuxiliaryLossData', ['variance', 'local_energy', 'imaginary', 'kinetic', 'ewald', 'n_nonfinite'],
@@ -91,24 +92,13 @@ def make_loss(network, batch_network, simulation_cell, clip_local_energy=5.0, cl
 def adam(learning_rate=1e-3, b1=0.9, b2=0.999, eps=1e-8):
     """Plain Adam on parameter trees (the role optax.adam plays at process.py:209-219).
     -> (init(params) -> state, update(t, grads, params, state) -> (state, params))."""
-    def leaves(o, out):
-        if isinstance(o, dict):
-            for k in sorted(o):
-                leaves(o[k], out)
-        elif isinstance(o, (list, tuple)):
-            for v in o:
-                leaves(v, out)
-        else:
-            out.append(o)
-        return out
-
     def init(params):
-        ps = leaves(params, [])
+        ps = tree_leaves(params)
         return {'count': 0, 'm': [torch.zeros_like(p) for p in ps], 'v': [torch.zeros_like(p) for p in ps]}
 
     def update(t, grads, params, state):
         lr = learning_rate(t) if callable(learning_rate) else learning_rate
-        ps, gs = leaves(params, []), leaves(grads, [])
+        ps, gs = tree_leaves(params), tree_leaves(grads)
         # the bias correction follows the optimiser's own step count (optax keeps `count` in its state), not the
         # driver's iteration index: a restored state continues where it stopped
         state['count'] = step = int(state.get('count', int(t))) + 1

@@ -96,7 +96,7 @@ typedef struct ds_system_desc {
  *   for l in double layers: W2_l [h2_in, h2_out], b2_l [1, h2_out]        (n_layers-1 of them, n_layers with use_last_layer)
  *   for s in active spins:  W_orb_s [h1_last (+ nch*h2_last with use_last_layer), cols]  cols = 2*norb*n_det rounded up to 64,
  *                             norb = n_s (N with full_det); Re/Im columns interleaved per 16-column tile, see
- *                             deepsolid_amd/device.py::_orbital_column_map and csrc/ds_gemm.h::orb_col
+ *                             deepsolid_amd/params.py::orbital_column_map and csrc/ds_gemm.h::orb_col
  *                           [W_sh_orb_s [nch*h1_last, cols]   only with use_last_layer]
  *                           [b_orb_s [1, 2*norb*n_det]        only with bias_orbitals]
  *                           pi_s [A, norb*n_det], sigma_s [A | 3A | 9A, norb*n_det] (isotropic | diagonal | full)

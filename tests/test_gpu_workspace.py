@@ -192,3 +192,19 @@ def test_samplers_stay_inside_the_reported_workspace(name, dtype, kind):
         n = sampler_call(sysd, kind, p, x, lp, 2, width, 5, atoms, can.buf, need)
         can.check()
         assert_same_bits([x, lp, n], [xr, lpr, nr])
+
+
+@pytest.mark.parametrize('name', ['lih_plain', 'lih_last_bias', 'li_polarized'])
+def test_header_block_rule_is_the_library_layout(name):
+    """The blocks tests/test_params_cpu.py lays out by the rule of include/deepsolid_hip.h are `ds_param_layout` of a real handle,
+    element count included; the buffer packed on the device is the one the CPU map packs."""
+    import param_map_helpers as pmh
+    cell, klist, net_kw = pmh.case_net(name)
+    for dtype in (F64, F32):
+        sysd = DeviceSystem.for_network(cell, klist, net_kw, dtype)
+        pm, _, _ = pmh.param_map(name, dtype)
+        assert sysd.blocks == pm.blocks and sysd.param_count == pm.param_count
+        tree = pmh.make_tree(cell, net_kw, dtype=dtype)
+        assert np.array_equal(sysd.param_map.layout(tree).gather, pm.layout(tree).gather)
+        dp = {k: [{kk: vv.cuda() for kk, vv in d.items()} for d in v] for k, v in tree.items()}
+        assert torch.equal(sysd.pack_params(dp).cpu(), pm.pack(tree, 'cpu', dtype))
