@@ -52,6 +52,15 @@ class HfDesc(C.Structure):
     ]
 
 
+class EcpDesc(C.Structure):
+    _PI = C.POINTER(C.c_int32)
+    _fields_ = [
+        ('a', C.c_double * 9), ('n_atoms', C.c_int32), ('atoms', _PD), ('atom_species', _PI), ('n_species', C.c_int32),
+        ('n_l', _PI), ('r_cut_loc', _PD), ('r_cut_nl', _PD), ('term_offset', _PI), ('term_n', _PI), ('term_zeta', _PD),
+        ('term_c', _PD), ('n_quad', C.c_int32),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/deepsolid_hip.h
 _VP = C.c_void_p
 SIGNATURES = {
@@ -107,6 +116,11 @@ SIGNATURES = {
                                      _VP, _VP, C.c_int64, _VP]),
     'ds_spin_exchange_workspace_bytes': (C.c_int64, [_VP, C.c_int64, C.c_int]),
     'ds_spin_exchange_ratios': (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    'ds_ecp_create': (C.c_int, [C.POINTER(EcpDesc), C.POINTER(_VP)]),
+    'ds_ecp_destroy': (None, [_VP]),
+    'ds_ecp_workspace_bytes': (C.c_int64, [_VP, _VP, C.c_int64, C.c_int64]),
+    'ds_ecp_energy': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_uint64, C.c_uint64, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP,
+                               C.c_int64, _VP]),
     'ds_philox_host': (None,[C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_uint32)]),
     'ds_energy_stats': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP]),
     'ds_debug_stage': (C.c_int64, [_VP, _VP, _VP, C.c_int64, C.c_char_p, _VP, C.c_int64, _VP, C.c_int64, _VP]),

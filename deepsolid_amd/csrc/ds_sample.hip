@@ -1,10 +1,16 @@
-// ds_sample.hip -- the samplers and what shares their kernels (ds_mcmc.h, ds_onebody.h, ds_spin.h): the three fused Metropolis loops,
-// the one-body ratios and n(k), the spin-exchange ratios and the sums of <S^2>, the single proposal / selection steps (ds_mh_*), the
-// batch statistics and the host side of Philox.
+// ds_sample.hip -- the samplers and what shares their kernels (ds_mcmc.h, ds_onebody.h, ds_spin.h, ds_ecp.h): the three fused Metropolis
+// loops, the one-body ratios and n(k), the spin-exchange ratios and the sums of <S^2>, the pseudopotential energy and its handle, the
+// single proposal / selection steps (ds_mh_*), the batch statistics and the host side of Philox.
 #include "ds_host.h"
 #include "ds_mcmc.h"
 #include "ds_onebody.h"
 #include "ds_spin.h"
+#include "ds_ecp.h"
+
+struct ds_ecp {
+    ds::EcpDev D;
+    std::vector<void*> dev;                 // every device allocation, freed by ds_ecp_destroy
+};
 
 namespace ds {
 namespace host {
@@ -200,6 +206,151 @@ int spin_exchange_impl(ds_system* s, const void* params, const void* x_, int64_t
             hipLaunchKernelGGL(ds::k_spin_final, dim3(1), dim3(256), 0, st, (const double*)w.TW, (long long)B, sums, (long long*)n_bad);
     }
     HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------ pseudopotential energy, ds_ecp.h
+// Workspace of ds_ecp_energy for B walkers, at most `cap` pairs, nq points per pair and chunks of ng groups of PV configurations.
+// Shared by all chunks: log|psi(R)| (B,), phase(R) (B,2), and in 8-byte elements (2 elements each: room in either element size) per
+// walker the rotation, E_loc, the pair count, the offsets (B + 1) and the flag, per pair its record (walker; electron and atom; r
+// and dhat; v_l(r)) and its nq terms.  Per chunk: the displaced rows, their log|psi| / phase, and the value chain's buffers for ng
+// groups (on a 64-element border), which also serve the forward of the walkers themselves.
+template <typename T> struct EcpWs {
+    T *LA0, *PH0, *XD, *LA, *PH;
+    double *ROT, *ELOC, *PR, *PVL, *TERM;
+    long long *CNT, *OFF, *PW;
+    int *BAD, *PI;
+    void* wsv; int64_t wsv_bytes;
+};
+template <typename T> EcpWs<T> carve_ecp(const ds_system* s, Arena<T>& a, int64_t B, int64_t cap, int nq, int64_t ng) {
+    const size_t nc = (size_t)ng * ds::PV, b = (size_t)B, p = (size_t)cap;
+    EcpWs<T> w{};
+    w.LA0 = a.take(b); w.PH0 = a.take(2 * b);
+    a.align(2);
+    w.ROT = (double*)a.take(2 * 9 * b); w.ELOC = (double*)a.take(2 * b);
+    w.CNT = (long long*)a.take(2 * b); w.OFF = (long long*)a.take(2 * (b + 1)); w.BAD = (int*)a.take(2 * ((b + 1) / 2));
+    w.PW = (long long*)a.take(2 * p); w.PI = (int*)a.take(2 * p);
+    w.PR = (double*)a.take(2 * 4 * p); w.PVL = (double*)a.take(2 * 3 * p); w.TERM = (double*)a.take(2 * 2 * p * (size_t)nq);
+    w.XD = a.take(nc * 3 * s->sd.N); w.LA = a.take(nc); w.PH = a.take(2 * nc);
+    a.align(64);
+    w.wsv = a.take(s->wsv.per_walker * (size_t)ng);
+    w.wsv_bytes = (int64_t)(s->wsv.per_walker * (size_t)ng * sizeof(T));
+    return w;
+}
+inline int64_t ecp_bytes(const ds_system* s, int64_t B, int64_t cap, int nq, int64_t ng) {
+    return (int64_t)measure([&](Arena<double>& a) { carve_ecp<double>(s, a, B, cap, nq, ng); }) * (s->dtype == 0 ? 8 : 4);
+}
+
+template <typename T>
+int ecp_energy_impl(ds_system* s, const ds_ecp* e, const void* params, const void* x_, int64_t B, uint64_t seed, uint64_t offset,
+                    const double* rotations, int64_t cap, double* out_energy, int64_t* out_pairs, void* out_ratio, double* out_rotation,
+                    void* ws, int64_t ws_bytes, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const ds::EcpDev& E = e->D;
+    const T* x = (const T*)x_;
+    const int nq = E.n_quad;
+    // the chunk length follows from the workspace, as in one_body_impl; the pair total is not known yet, the capacity bounds it
+    const int64_t fixed = ecp_bytes(s, B, cap, nq, 0), per = ecp_bytes(s, B, cap, nq, 1) - fixed;
+    int64_t ng = std::min<int64_t>({(ws_bytes - fixed) / per + 1, OB_MAX_GROUPS, (cap * nq + ds::PV - 1) / ds::PV});
+    while (ng >= 1 && ecp_bytes(s, B, cap, nq, ng) > ws_bytes) --ng;
+    if (ng < 1) return fail("workspace too small for ds_ecp_energy: %lld bytes < %lld for one group of %d configurations",
+                            (long long)ws_bytes, (long long)ecp_bytes(s, B, cap, nq, 1), ds::PV);
+    Arena<T> a = arena_of<T>(ws, ws_bytes);
+    const EcpWs<T> w = carve_ecp<T>(s, a, B, cap, nq, ng);
+    if (!a.ok) return carve_fail("pseudopotential energy");
+    const dim3 gw((unsigned)((B + 63) / 64)), bw(64);
+    hipLaunchKernelGGL((ds::k_ecp_scan<T>), gw, bw, 0, st, E, x, (long long)B, S.N, ds::PhiloxKey{seed, offset}, rotations, w.ROT, w.ELOC,
+                       w.CNT, w.BAD, out_rotation);
+    hipLaunchKernelGGL(ds::k_ecp_offsets, dim3(1), dim3(1024), 0, st, (const long long*)w.CNT, (long long)B, w.OFF, (long long*)out_pairs);
+    hipLaunchKernelGGL((ds::k_ecp_fill<T>), gw, bw, 0, st, E, x, (long long)B, S.N, (const int*)w.BAD, (const long long*)w.OFF,
+                       (long long)cap, w.PW, w.PI, w.PR, w.PVL);
+    // the one synchronisation of the call: the host needs the pair total to size the chunks
+    long long pairs = 0;
+    HIP_OK(hipMemcpyAsync(&pairs, w.OFF + B, sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (pairs > cap)
+        return fail("ds_ecp_energy: pair capacity exceeded: the walkers have %lld pairs inside the non-local cutoffs, pair_capacity is %lld",
+                    pairs, (long long)cap);
+    const int64_t total = pairs * nq;
+    if (total > 0)
+        if (int rc = logpsi_forward(s, params, x, B, w.LA0, w.PH0, w.wsv, w.wsv_bytes, st)) return rc;
+    ds::EcpChunk A;
+    A.N = S.N; A.n_quad = nq;
+    const int64_t chunk = ng * ds::PV;
+    for (int64_t c0 = 0; c0 < total; c0 += chunk) {
+        A.c0 = c0; A.n = std::min(chunk, total - c0);
+        hipLaunchKernelGGL((ds::k_ecp_propose<T>), dim3((unsigned)((A.n * S.N + 255) / 256)), dim3(256), 0, st, E, A, x, (const double*)w.ROT,
+                           (const long long*)w.PW, (const int*)w.PI, (const double*)w.PR, w.XD);
+        if (int rc = logpsi_forward(s, params, w.XD, A.n, w.LA, w.PH, w.wsv, w.wsv_bytes, st)) return rc;
+        hipLaunchKernelGGL((ds::k_ecp_term<T>), dim3((unsigned)((A.n + 255) / 256)), dim3(256), 0, st, E, A, (const double*)w.ROT,
+                           (const long long*)w.PW, (const double*)w.PR, (const double*)w.PVL, (const T*)w.LA0, (const T*)w.PH0,
+                           (const T*)w.LA, (const T*)w.PH, w.TERM, (T*)out_ratio);
+    }
+    hipLaunchKernelGGL(ds::k_ecp_walker, dim3((unsigned)((B + ds::ECP_WAVES - 1) / ds::ECP_WAVES)), dim3(64 * ds::ECP_WAVES), 0, st,
+                       (const double*)w.TERM, (const long long*)w.OFF, (const double*)w.ELOC, (const int*)w.BAD, (long long)B, nq, out_energy);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+template <typename V> int ecp_upload(ds_ecp* h, const std::vector<V>& host, const V** out) {
+    void* d = nullptr;
+    HIP_OK(hipMalloc(&d, (host.empty() ? 1 : host.size()) * sizeof(V)));
+    h->dev.push_back(d);
+    if (!host.empty()) HIP_OK(hipMemcpy(d, host.data(), host.size() * sizeof(V), hipMemcpyHostToDevice));
+    *out = (const V*)d;
+    return 0;
+}
+
+// The descriptor's checks, which need no device: the first violated one as a ds_last_error message
+int ecp_validate(const ds_ecp_desc* d) {
+    if (!d->atoms || !d->atom_species || !d->n_l || !d->r_cut_loc || !d->r_cut_nl || !d->term_offset)
+        return fail("ds_ecp_create: null array in the descriptor");
+    if (d->n_atoms < 1 || d->n_species < 1) return fail("ds_ecp_create: no atoms or no species");
+    if (d->n_quad != 6 && d->n_quad != 12) return fail("ds_ecp_create: n_quad must be 6 or 12 (got %d)", d->n_quad);
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(d->a[i])) return fail("ds_ecp_create: lattice entry %d is not finite", i);
+    double ainv[9], hmin = 1e300;
+    inv3(d->a, ainv);
+    for (int c = 0; c < 3; ++c) {
+        const double n = std::sqrt(ainv[c] * ainv[c] + ainv[3 + c] * ainv[3 + c] + ainv[6 + c] * ainv[6 + c]);
+        if (!(n > 0.0) || !std::isfinite(n)) return fail("ds_ecp_create: the simulation cell is singular");
+        hmin = std::min(hmin, 1.0 / n);
+    }
+    const int degree = d->n_quad == 6 ? 3 : 5;
+    if (d->term_offset[0] != 0) return fail("ds_ecp_create: term_offset must begin at 0");
+    for (int sp = 0; sp < d->n_species; ++sp) {
+        const int nl = d->n_l[sp];
+        if (nl < 0 || nl > 4) return fail("ds_ecp_create: species %d has n_l = %d; n_l must be in 0..4", sp, nl);
+        if (nl == 4) return fail("ds_ecp_create: species %d has n_l = 4: an l = 3 channel needs a quadrature rule of degree >= 6, which is not provided", sp);
+        if (2 * (nl - 1) > degree)
+            return fail("ds_ecp_create: species %d has n_l = %d: channels up to l = %d need a rule of degree %d, n_quad = %d is exact to degree %d",
+                        sp, nl, nl - 1, 2 * (nl - 1), d->n_quad, degree);
+        if (!std::isfinite(d->r_cut_loc[sp]) || !std::isfinite(d->r_cut_nl[sp]) || d->r_cut_loc[sp] < 0.0 || d->r_cut_nl[sp] < 0.0)
+            return fail("ds_ecp_create: species %d has a cutoff that is negative or not finite", sp);
+        for (int j = 0; j < ds::ECP_SLOTS; ++j) {
+            const int slot = sp * ds::ECP_SLOTS + j, k0 = d->term_offset[slot], k1 = d->term_offset[slot + 1];
+            if (k1 < k0) return fail("ds_ecp_create: term_offset decreases at slot %d", slot);
+            if (k1 - k0 > ds::ECP_MAX_TERMS)
+                return fail("ds_ecp_create: species %d, function %d has %d terms; at most %d terms are provided", sp, j, k1 - k0, ds::ECP_MAX_TERMS);
+            if (k1 > k0 && (!d->term_n || !d->term_zeta || !d->term_c)) return fail("ds_ecp_create: null term table");
+            for (int k = k0; k < k1; ++k) {
+                if (d->term_n[k] < 0 || d->term_n[k] > 4)
+                    return fail("ds_ecp_create: species %d, function %d, term %d has n_k = %d; n_k must be in 0..4", sp, j, k - k0, d->term_n[k]);
+                if (!std::isfinite(d->term_zeta[k]) || !std::isfinite(d->term_c[k]))
+                    return fail("ds_ecp_create: species %d, function %d, term %d is not finite", sp, j, k - k0);
+            }
+        }
+    }
+    for (int I = 0; I < d->n_atoms; ++I) {
+        const int sp = d->atom_species[I];
+        if (sp < 0 || sp >= d->n_species) return fail("ds_ecp_create: atom %d names species %d of %d", I, sp, d->n_species);
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(d->atoms[3 * I + c])) return fail("ds_ecp_create: atoms[%d][%d] is not finite", I, c);
+        const double rc = std::max(d->r_cut_loc[sp], d->n_l[sp] > 0 ? d->r_cut_nl[sp] : 0.0);
+        if (rc > 0.5 * hmin)
+            return fail("ds_ecp_create: atom %d (species %d) has the cutoff %.6f Bohr; the limit is %.6f Bohr, half the smallest height of the simulation cell",
+                        I, sp, rc, 0.5 * hmin);
+    }
     return 0;
 }
 
@@ -465,6 +616,88 @@ int ds_spin_exchange_ratios(ds_system* s, const void* params, const void* x, int
     hipStream_t st = (hipStream_t)stream;
     return DS_BY_DTYPE(s->dtype, spin_exchange_impl, s, params, x, B, n_pairs, first_pair, sums, out_ratio, out_walker, n_bad, ws, ws_bytes,
                        st);
+}
+
+void ds_ecp_destroy(ds_ecp* e) {
+    if (!e) return;
+    for (void* d : e->dev) (void)hipFree(d);
+    delete e;
+}
+
+int ds_ecp_create(const ds_ecp_desc* d, ds_ecp** out) {
+    if (!d || !out) return fail("null argument");
+    *out = nullptr;
+    if (int rc = ecp_validate(d)) return rc;
+    ds_ecp* h = new ds_ecp();
+    ds::EcpDev& E = h->D;
+    for (int i = 0; i < 9; ++i) E.a[i] = d->a[i];
+    inv3(d->a, E.ainv);
+    E.n_atoms = d->n_atoms; E.n_species = d->n_species; E.n_quad = d->n_quad;
+    for (double& v : E.quad) v = 0.0;
+    if (d->n_quad == 6) {
+        for (int q = 0; q < 6; ++q) E.quad[3 * q + q / 2] = q % 2 ? -1.0 : 1.0;              // +x, -x, +y, -y, +z, -z
+    } else {
+        const double phi = (1.0 + std::sqrt(5.0)) / 2.0, n = std::sqrt(1.0 + phi * phi);
+        const double sg[4][2] = {{1, 1}, {1, -1}, {-1, 1}, {-1, -1}};
+        for (int j = 0; j < 4; ++j) {
+            const double s1 = sg[j][0], s2 = sg[j][1];
+            const double pts[3][3] = {{0.0, s1, s2 * phi}, {s1, s2 * phi, 0.0}, {s2 * phi, 0.0, s1}};
+            for (int f = 0; f < 3; ++f)
+                for (int c = 0; c < 3; ++c) E.quad[3 * (4 * f + j) + c] = pts[f][c] / n;
+        }
+    }
+    const int n_slots = d->n_species * ds::ECP_SLOTS, n_terms = d->term_offset[n_slots];
+    std::vector<double> atoms(d->atoms, d->atoms + 3 * d->n_atoms), rcl(d->r_cut_loc, d->r_cut_loc + d->n_species),
+        rcn(d->r_cut_nl, d->r_cut_nl + d->n_species), tz, tc;
+    std::vector<int> asp(d->atom_species, d->atom_species + d->n_atoms), nl(d->n_l, d->n_l + d->n_species),
+        toff(d->term_offset, d->term_offset + n_slots + 1), tn;
+    if (n_terms > 0) {
+        tn.assign(d->term_n, d->term_n + n_terms); tz.assign(d->term_zeta, d->term_zeta + n_terms); tc.assign(d->term_c, d->term_c + n_terms);
+    }
+    const int rc = ecp_upload(h, atoms, &E.atoms) || ecp_upload(h, asp, &E.atom_species) || ecp_upload(h, nl, &E.n_l) ||
+                   ecp_upload(h, rcl, &E.rc_loc) || ecp_upload(h, rcn, &E.rc_nl) || ecp_upload(h, toff, &E.term_off) ||
+                   ecp_upload(h, tn, &E.term_n) || ecp_upload(h, tz, &E.term_z) || ecp_upload(h, tc, &E.term_c);
+    if (rc) { ds_ecp_destroy(h); return 1; }
+    *out = h;
+    return 0;
+}
+
+// what ds_ecp_workspace_bytes and ds_ecp_energy refuse alike
+static int ecp_check(const ds_system* s, const ds_ecp* e, int64_t B, int64_t pair_capacity) {
+    if (B < 1) return fail("ds_ecp_energy: B must be >= 1 (got %lld)", (long long)B);
+    if (pair_capacity < 1) return fail("ds_ecp_energy: pair_capacity must be >= 1 (got %lld)", (long long)pair_capacity);
+    if (e->D.n_atoms != s->d.n_atoms_sim)
+        return fail("ds_ecp_energy: the descriptor has %d atoms, the system's simulation cell %d", e->D.n_atoms, s->d.n_atoms_sim);
+    double scale = 0.0;
+    for (int i = 0; i < 9; ++i) scale = std::max(scale, std::fabs(s->d.sim_a[i]));
+    for (int i = 0; i < 9; ++i)
+        if (!(std::fabs(e->D.a[i] - s->d.sim_a[i]) <= 1e-12 * scale))
+            return fail("ds_ecp_energy: the descriptor's cell differs from the system's simulation cell (entry %d: %.17g against %.17g)", i,
+                        e->D.a[i], s->d.sim_a[i]);
+    return 0;
+}
+
+int64_t ds_ecp_workspace_bytes(const ds_system* s, const ds_ecp* e, int64_t B, int64_t pair_capacity) {
+    if (!s || !e) { fail("null argument"); return -1; }
+    if (ecp_check(s, e, B, pair_capacity)) return -1;
+    // as many groups per chunk as ds_workspace_bytes gives the value chain of pair_capacity * n_quad walkers
+    const int nq = e->D.n_quad;
+    const int64_t esz = s->dtype == 0 ? 8 : 4, total = pair_capacity * nq;
+    const int64_t fixed = ecp_bytes(s, B, pair_capacity, nq, 0), per = ecp_bytes(s, B, pair_capacity, nq, 1) - fixed;
+    const int64_t ng = std::min(groups_per_pass(total, esz, PassSize{0, (size_t)(per / esz)}, workspace_budget()), OB_MAX_GROUPS);
+    return ecp_bytes(s, B, pair_capacity, nq, ng);
+}
+
+int ds_ecp_energy(ds_system* s, const ds_ecp* e, const void* params, const void* x, int64_t B, uint64_t philox_seed, uint64_t philox_offset,
+                  const double* rotations, int64_t pair_capacity, double* out_energy, int64_t* out_pairs, void* out_ratio,
+                  double* out_rotation, void* ws, int64_t ws_bytes, void* stream) {
+    if (s) ++s->call_seq;
+    if (!s || !e || !params || !x || !ws) return fail("null argument");
+    if (!out_energy) return fail("ds_ecp_energy: out_energy is null, nothing to write");
+    if (int rc = ecp_check(s, e, B, pair_capacity)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    return DS_BY_DTYPE(s->dtype, ecp_energy_impl, s, e, params, x, B, philox_seed, philox_offset, rotations, pair_capacity, out_energy,
+                       out_pairs, out_ratio, out_rotation, ws, ws_bytes, st);
 }
 
 int ds_energy_stats(ds_system* s, const void* ke, const void* ewald, int64_t B, double* out_stats, void* stream) {

@@ -579,6 +579,54 @@ class DeviceSystem:
         return dict(sums=sums, n_bad=n_bad, ratios=torch.view_as_complex(ratios) if ratios is not None else None,
                     walker=torch.view_as_complex(walker) if want_walker else None)
 
+    def ecp_energy(self, params, x, ecp, seed=0, offset=0, rotations=None, pair_capacity=None, want_pairs=False, want_ratios=False,
+                   want_rotations=False, max_bytes=None):
+        """`ds_ecp_energy`: the semi-local pseudopotential energy of every walker.  `ecp`: an `EcpTables` (or a
+        `pseudopotential.SemiLocalECP`, whose device tables are then built once and kept on it).  One rotation of the quadrature
+        points per walker and call from the in-kernel Philox stream (seed, offset) -- the caller advances `offset` by 1 per call --
+        or `rotations` (B, 3, 3) float64 replays given ones.  `pair_capacity`: room for the (electron, ion) pairs inside the non-local
+        cutoffs (default B * N, which always suffices when every atom's cutoff sphere holds each electron at most once); when the
+        walkers have more the call is repeated once with the number the library reports.  `max_bytes` caps the workspace: more
+        chunks, bit-identical results.
+        -> dict(e_loc (B,) float64, e_nl (B,) complex128, pairs (B,) int64 with `want_pairs`, ratios (n_pairs * N_q,) complex with
+        `want_ratios` (configuration pair * N_q + q, pairs ordered by (w, i, I)), rotations (B, 3, 3) with `want_rotations`,
+        pair_capacity: the capacity the call ran with).
+        The call synchronises the stream once (the pair total) and cannot be captured into a graph."""
+        import re
+        x = self._check_x(x)
+        B = x.shape[0]
+        if not isinstance(ecp, EcpTables):
+            tables = ecp.__dict__.get('_ds_tables')
+            if tables is None or tables.device != self.device:
+                tables = ecp.__dict__['_ds_tables'] = EcpTables(ecp, device=self.device)
+            ecp = tables
+        p = self.pack_params(params)
+        if rotations is not None:
+            rotations = rotations.to(device=self.device, dtype=torch.float64).contiguous()
+            if tuple(rotations.shape) != (B, 3, 3):
+                raise ValueError(f'rotations must be ({B}, 3, 3), got {tuple(rotations.shape)}')
+        cap = B * self.n if pair_capacity is None else int(pair_capacity)
+        energy = torch.empty(B, 3, dtype=torch.float64, device=self.device)
+        pairs = torch.empty(B, dtype=torch.int64, device=self.device) if want_pairs or want_ratios else None
+        rot = torch.empty(B, 3, 3, dtype=torch.float64, device=self.device) if want_rotations else None
+        for attempt in range(2):
+            ratios = torch.empty(max(cap, 1) * ecp.n_quad, 2, dtype=self.dtype, device=self.device) if want_ratios else None
+            # (the library refuses B < 1 / pair_capacity < 1 / another cell itself, here already)
+            ws = self._workspace('ds_ecp_workspace_bytes', ecp.handle, B, cap, max_bytes=max_bytes)
+            rc = self.lib.ds_ecp_energy(self.handle, ecp.handle, _ptr(p), _ptr(x), B, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
+                                        _ptr(rotations), cap, _ptr(energy), _ptr(pairs), _ptr(ratios), _ptr(rot), _ptr(ws), ws.numel(),
+                                        _stream())
+            if rc != 0 and attempt == 0:
+                m = re.search(r'pair capacity exceeded: the walkers have (\d+) pairs', self.lib.ds_last_error().decode())
+                if m:
+                    cap = int(m.group(1))
+                    continue
+            _lib.check(rc, 'ds_ecp_energy')
+            break
+        return dict(e_loc=energy[:, 0], e_nl=torch.complex(energy[:, 1], energy[:, 2]), pairs=pairs if want_pairs else None,
+                    rotations=rot, pair_capacity=cap,
+                    ratios=torch.view_as_complex(ratios)[:int(pairs.sum()) * ecp.n_quad] if want_ratios else None)
+
     def energy_stats(self, ke, ew):
         """`ds_energy_stats`: (8,) float64 = [sum Re E_L, sum Im E_L, sum |E_L|^2, n, n_nonfinite, sum Re ke, sum Im ke, sum ew]."""
         out = torch.empty(8, dtype=torch.float64, device=self.device)
@@ -759,3 +807,50 @@ class HfOrbitalTables:
                 _lib.check(self.lib.ds_hf_orbitals(self.handle, _DTYPES[x.dtype], _ptr(x), B, _ptr(outs[0] if self.nelec[0] else None),
                                                    _ptr(outs[1] if self.nelec[1] else None), _stream()), 'ds_hf_orbitals')
         return [torch.view_as_complex(o) for o in outs]
+
+
+class EcpTables:
+    """The device tables of one `pseudopotential.SemiLocalECP` (`ds_ecp_create`, csrc/ds_ecp.h): the fields of `ds_ecp_desc`
+    (include/deepsolid_hip.h).  The library repeats the checks of `SemiLocalECP` (cutoffs, n_quad, n_l, term tables)."""
+
+    def __init__(self, ecp, device=None):
+        _require_gpu()
+        self.lib = _lib.load()
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.ecp = ecp
+        self.n_quad = int(ecp.n_quad)
+        d, self._keep = ecp_desc(ecp)
+        self.handle = C.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.ds_ecp_create(C.byref(d), C.byref(self.handle)), 'ds_ecp_create')
+
+    def __del__(self):
+        h, self.handle = getattr(self, 'handle', None), None
+        if h:
+            try:
+                self.lib.ds_ecp_destroy(h)
+            except Exception:
+                pass
+
+
+def ecp_desc(ecp, **override):
+    """-> (`_lib.EcpDesc` of a `pseudopotential.SemiLocalECP`, the host arrays it points to: keep them alive as long as the
+    descriptor).  `override` replaces fields (arrays or scalars) by name: the refusal tests of the C ABI."""
+    f8 = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
+    i4 = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.int32).reshape(-1))
+    t = ecp.tables()
+    arrays = dict(atoms=f8(ecp.atoms), atom_species=i4(ecp.atom_species), n_l=i4(ecp.n_l), r_cut_loc=f8(ecp.r_cut_loc),
+                  r_cut_nl=f8(ecp.r_cut_nl), term_offset=i4(t['term_offset']), term_n=i4(t['term_n']), term_zeta=f8(t['term_zeta']),
+                  term_c=f8(t['term_c']))
+    scalars = dict(a=f8(ecp.a), n_atoms=len(ecp.atoms), n_species=ecp.n_species, n_quad=ecp.n_quad)
+    for k, v in override.items():
+        if k in arrays:
+            arrays[k] = (f8 if arrays[k].dtype == np.float64 else i4)(v)
+        else:
+            scalars[k] = f8(v) if k == 'a' else int(v)
+    d = _lib.EcpDesc()
+    d.a[:] = scalars['a'].tolist()
+    d.n_atoms, d.n_species, d.n_quad = scalars['n_atoms'], scalars['n_species'], scalars['n_quad']
+    for k, v in arrays.items():
+        setattr(d, k, v.ctypes.data_as(C.POINTER(C.c_double if v.dtype == np.float64 else C.c_int32)))
+    return d, arrays

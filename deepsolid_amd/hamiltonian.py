@@ -58,6 +58,27 @@ def local_energy_seperate(f, simulation_cell, mode='for', partition_number=3):
     return _local_energy
 
 
+def local_pseudopotential_energy(f, simulation_cell, ecp, key=0):
+    """-> (params, x) -> (E_loc: real, E_nl: complex) of the semi-local pseudopotential `ecp` (`pseudopotential.SemiLocalECP` or
+    `device.EcpTables`; `ds_ecp_energy`); x is (3N,) or (B, 3N).  No counterpart in the reference.  The
+    returned function owns the Philox offset of the quadrature rotations and advances it by 1 per call (`.offset`); the seed is
+    `key` folded with the rank as `inference._rank_generator` folds it.  The total to add to kinetic + ewald is E_loc + E_nl."""
+    from . import constants
+    system = _system_of(f)
+    if simulation_cell is not system.cell:
+        raise ValueError('simulation_cell differs from the one the network was built for')
+    seed = (int(key) * max(1, constants.world_size()) + constants.rank()) % (1 << 63)
+
+    def _pseudopotential_energy(params, x):
+        single = x.dim() == 1
+        out = system.ecp_energy(params, x.reshape(1, -1) if single else x, ecp, seed=seed, offset=_pseudopotential_energy.offset)
+        _pseudopotential_energy.offset += 1
+        return (out['e_loc'][0], out['e_nl'][0]) if single else (out['e_loc'], out['e_nl'])
+    _pseudopotential_energy.offset = 0
+    _pseudopotential_energy.seed = seed
+    return _pseudopotential_energy
+
+
 def local_energy(f, simulation_cell):
     """kinetic + ewald as one complex number (hamiltonian.py:182-191)."""
     sep = local_energy_seperate(f, simulation_cell)

@@ -84,6 +84,14 @@ def _observables(simulation_cell, complex_polarization, structure_factor, struct
     return schema, evaluate
 
 
+def _pseudopotential_kw(pseudopotential, key):
+    """Keywords of `train.make_loss` for a run with a pseudopotential (none without: the call is then the one it always was).  A
+    generator as `key` has no integer to fold: the rotations are then seeded with 0."""
+    if pseudopotential is None:
+        return {}
+    return dict(pseudopotential=pseudopotential, key=0 if isinstance(key, torch.Generator) else int(key))
+
+
 def _csv_row(row, schema):
     """The keys of a returned row that are CSV columns (S(k) has a file of its own)."""
     return {k: v for k, v in row.items() if k in schema}
@@ -92,7 +100,7 @@ def _csv_row(row, schema):
 def run_inference(slog_net, logdet_net, params, data, simulation_cell, iterations, key=0, move_width=0.02,
                   mcmc_steps=20, burn_in=100, adapt_frequency=100, stats_frequency=1, save_path=None,
                   stats_file_name='train_stats', laplacian_mode='for', partition_number=3, complex_polarization=False,
-                  structure_factor=False, structure_factor_nq=4, accumulators=()):
+                  structure_factor=False, structure_factor_nq=4, accumulators=(), pseudopotential=None):
     """Returns (data, mcmc_width, rows).  `slog_net` / `logdet_net` are the objects returned by
     ``make_solid_fermi_net(method_name='eval_slogdet' | 'eval_logdet')``; `data` is (B, 3N) on the device.
     Energies are reported per primitive cell like process.py:330-334 (divided by ``simulation_cell.scale``).
@@ -107,13 +115,15 @@ def run_inference(slog_net, logdet_net, params, data, simulation_cell, iteration
     raises inside the loop does not reduce (a collective on the way out of an exception could hang the other ranks): with a
     `save_path` every rank writes the counts it has, unreduced, to realspace_partial_rank<r>.npz (realspace_<i>_partial_rank<r>.npz)
     before the exception goes on; `RealSpaceAccumulator.load` + `merge` put such files together.  The return value and the CSV do
-    not change; with the default () nothing changes at all."""
+    not change; with the default () nothing changes at all.
+    `pseudopotential` (`pseudopotential.SemiLocalECP`): passed on to `train.make_loss` with `key`; rows and the CSV then carry a
+    'pseudopotential' column (the batch mean of E_loc + E_nl, complex, per primitive cell)."""
     accumulators = tuple(accumulators)
     gen = _rank_generator(key, data.device)
     batch = data.shape[0]
     mcmc_step = qmc.make_mcmc_step(slog_net.apply, batch, latvec=simulation_cell.a, steps=mcmc_steps)
     total_energy = train.make_loss(logdet_net.apply, None, simulation_cell, mode=laplacian_mode,
-                                   partition_number=partition_number)
+                                   partition_number=partition_number, **_pseudopotential_kw(pseudopotential, key))
     width = float(move_width)
     for _ in range(burn_in):                                             # process.py:256-261
         data, _ = mcmc_step(params, data, gen, width)
@@ -121,6 +131,8 @@ def run_inference(slog_net, logdet_net, params, data, simulation_cell, iteration
     pmoves = np.zeros(adapt_frequency)
     rows = []
     schema, observe = _observables(simulation_cell, complex_polarization, structure_factor, structure_factor_nq, save_path)
+    if pseudopotential is not None:
+        schema.append('pseudopotential')
     writer = Writer(stats_file_name, schema, save_path) if save_path else None
     if writer:
         writer.__enter__()
@@ -136,6 +148,8 @@ def run_inference(slog_net, logdet_net, params, data, simulation_cell, iteration
                    'imaginary': float(aux.imaginary) / scale,
                    'kinetic': complex(aux.kinetic.mean().item()) / scale,
                    'ewald': float(aux.ewald.mean()) / scale}
+            if aux.pseudopotential is not None:
+                row['pseudopotential'] = complex(aux.pseudopotential.mean().item()) / scale
             if observe:                                                  # process.py:337-342
                 row.update(observe(data))
             for acc in accumulators:
@@ -179,7 +193,7 @@ def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations
                  save_path=None, save_every=None, stats_file_name='train_stats', laplacian_mode='for',
                  partition_number=3, t_init=0, opt_state=None, check_nan=True, max_rejected=20, complex_polarization=False,
                  structure_factor=False, structure_factor_nq=4, pretrain_iterations=0, pretrain_lr=5e-3, scf_approx=None,
-                 optimizer='adam', kfac=None, pretrain_method='net', pretrain_steps=1):
+                 optimizer='adam', kfac=None, pretrain_method='net', pretrain_steps=1, pseudopotential=None):
     """The `optimizer='adam'` branch of the reference driver (process.py:204-219, 256-383): burn-in, then per iteration
     ``mcmc_step -> value_and_grad(total_energy) -> gradient pmean -> Adam -> CSV row -> width adaptation``, with
     checkpoints in the reference's layout (`deepsolid_amd.checkpoint.save`) every `save_every` iterations.
@@ -207,7 +221,9 @@ def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations
     damped inverses and the preconditioner run on the GPU every iteration.  `kfac`: dict of the keys of base_config.py:62-75
     (invert_every, damping, cov_ema_decay, norm_constraint, l2_reg; momentum must be 0, register_only_generic False); `learning_rate`
     is then the schedule of the optimizer's own step count.  `opt_state` of a resumed run is the dict `checkpoint.restore` returns
-    (through `checkpoint.opt_state_to_single_device`)."""
+    (through `checkpoint.opt_state_to_single_device`).
+    `pseudopotential`: as in `run_inference`; both optimizers take their energies from `aux.local_energy` of the same
+    `total_energy`, so the gradient follows without another change."""
     from . import checkpoint
     if optimizer not in ('adam', 'kfac'):
         raise ValueError(f"optimizer must be 'adam' or 'kfac', got {optimizer!r}")
@@ -236,7 +252,8 @@ def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations
     batch = data.shape[0]
     mcmc_step = qmc.make_mcmc_step(slog_net.apply, batch, latvec=simulation_cell.a, steps=mcmc_steps)
     total_energy = train.make_loss(logdet_net.apply, None, simulation_cell, clip_local_energy=clip_local_energy,
-                                   clip_type=clip_type, mode=laplacian_mode, partition_number=partition_number)
+                                   clip_type=clip_type, mode=laplacian_mode, partition_number=partition_number,
+                                   **_pseudopotential_kw(pseudopotential, key))
     schedule = learning_rate if learning_rate is not None else learning_rate_schedule()
     if optimizer == 'kfac':
         from . import kfac as kfac_mod
@@ -269,6 +286,8 @@ def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations
     pmoves = np.zeros(adapt_frequency)
     rows = []
     schema, observe = _observables(simulation_cell, complex_polarization, structure_factor, structure_factor_nq, save_path)
+    if pseudopotential is not None:
+        schema.append('pseudopotential')
     writer = Writer(stats_file_name, schema, save_path) if save_path else None
     if writer:
         writer.__enter__()
@@ -293,6 +312,8 @@ def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations
                 row = {'step': t, 'energy': float(loss) / scale, 'variance': float(aux.variance) / scale ** 2,
                        'pmove': float(pmove), 'imaginary': float(aux.imaginary) / scale,
                        'kinetic': complex(aux.kinetic.mean().item()) / scale, 'ewald': float(aux.ewald.mean()) / scale}
+                if aux.pseudopotential is not None:
+                    row['pseudopotential'] = complex(aux.pseudopotential.mean().item()) / scale
                 row.update(observed)
                 n_rejected = 0
                 rows.append(row)

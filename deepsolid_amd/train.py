@@ -19,8 +19,18 @@ from . import constants, hamiltonian
 from .params import tree_leaves
 
 # the reference's five fields (train.py:28-34) + the non-finite count behind its check_nan step rejection (process.py:303-318)
-AuxiliaryLossData = namedtuple('AuxiliaryLossData', ['variance', 'local_energy', 'imaginary', 'kinetic', 'ewald', 'n_nonfinite'],
-                               defaults=[None])
+# + the pseudopotential energy E_loc + E_nl per walker when make_loss was given one
+class AuxiliaryLossData(namedtuple('AuxiliaryLossData', ['variance', 'local_energy', 'imaginary', 'kinetic', 'ewald', 'n_nonfinite',
+                                                         'pseudopotential'], defaults=[None, None])):
+    __slots__ = ()
+
+    def _asdict(self):
+        """The fields by name; without a pseudopotential its (empty) field is left out, so that whoever walks the mapping -- the
+        benchmark dumps every entry as an array -- sees the fields it always saw."""
+        d = super()._asdict()
+        if d['pseudopotential'] is None:
+            del d['pseudopotential']
+        return d
 
 
 def clip_difference(diff, clip_local_energy, clip_type):
@@ -48,27 +58,38 @@ def clip_difference(diff, clip_local_energy, clip_type):
 
 
 def make_loss(network, batch_network, simulation_cell, clip_local_energy=5.0, clip_type='real', mode='for',
-              partition_number=3):
+              partition_number=3, pseudopotential=None, key=0):
     """Same signature as train.py:37-43; ``batch_network`` is accepted and unused (the
-    HIP network is batched natively)."""
+    HIP network is batched natively).  `pseudopotential` (beyond the reference; `pseudopotential.SemiLocalECP`): the local energy
+    becomes kinetic + ewald + E_loc + E_nl (`hamiltonian.local_pseudopotential_energy`, quadrature rotations seeded by `key`);
+    the gradient needs no other change, its cotangent is built from `aux.local_energy`."""
     del batch_network
     if clip_type not in ('real', 'complex'):
         raise ValueError('Unrecognized clip type.')
     el_fun = hamiltonian.local_energy_seperate(network, simulation_cell, mode=mode,
                                                partition_number=partition_number)
     system = hamiltonian._system_of(network)
+    pp_fun = None if pseudopotential is None else hamiltonian.local_pseudopotential_energy(network, simulation_cell, pseudopotential,
+                                                                                           key=key)
 
     def total_energy(params, data):
         ke, ew = el_fun(params, data)                                  # train.py:74
         e_l = ke + ew                                                  # :75
-        # one deterministic device reduction (ds_energy_stats) -> [sum Re, sum Im, sum |E|^2, n, n_nonfinite, ...]
-        st = system.energy_stats(torch.view_as_real(ke), ew)
+        pp = None
+        if pp_fun is not None:
+            e_loc, e_nl = pp_fun(params, data)
+            pp = (e_loc + e_nl).to(ke.dtype)
+            e_l = e_l + pp
+        # one deterministic device reduction (ds_energy_stats) -> [sum Re, sum Im, sum |E|^2, n, n_nonfinite, ...]; with a
+        # pseudopotential it rides in the kinetic slot: only entries 0..4 are read here, and they are those of E_L
+        st = system.energy_stats(torch.view_as_real(ke if pp is None else ke + pp).contiguous(), ew)
         n = st[3].clamp(min=1.0)
         mean_re, mean_im = st[0] / n, st[1] / n                        # :76
         var_local = st[2] / n - mean_re.abs() ** 2                     # :79 (per-device variance, then pmean)
         # :78-80 (+ the non-finite count, summed not averaged) in ONE all-reduce of a packed vector
         re, im, var, bad = constants.pmean_packed(mean_re, mean_im, var_local, st[4] * constants.world_size())
-        return re, AuxiliaryLossData(variance=var, local_energy=e_l, imaginary=im, kinetic=ke, ewald=ew, n_nonfinite=bad)
+        return re, AuxiliaryLossData(variance=var, local_energy=e_l, imaginary=im, kinetic=ke, ewald=ew, n_nonfinite=bad,
+                                     pseudopotential=pp)
 
     def value_and_grad_packed(params, data):
         """-> ((loss, aux), packed gradient of this rank's walkers)."""
@@ -86,6 +107,7 @@ def make_loss(network, batch_network, simulation_cell, clip_local_energy=5.0, cl
     total_energy.value_and_grad = value_and_grad
     total_energy.value_and_grad_packed = value_and_grad_packed
     total_energy.system = system
+    total_energy.pseudopotential_energy = pp_fun
     return total_energy
 
 

@@ -14,7 +14,10 @@ deepsolid_amd.estimator.RealSpaceAccumulator, written to realspace.npz in the wo
 --momentum SHELLS: the spin-resolved momentum distribution n(k) on the (2 SHELLS + 1)^3 Bloch-allowed k points around the twist,
 through deepsolid_amd.estimator.MomentumDistribution, written to momentum.npz;
 --spin-squared [PAIRS]: the total spin <S^2> from PAIRS spin-exchange ratios per walker and evaluation step (default: all
-n_up n_dn pairs), through deepsolid_amd.estimator.SpinSquared, written to spin_squared.npz)"""
+n_up n_dn pairs), through deepsolid_amd.estimator.SpinSquared, written to spin_squared.npz;
+--ecp FILE.npz: add the semi-local pseudopotential saved in FILE.npz (deepsolid_amd.pseudopotential.SemiLocalECP.save, built for
+THIS cell) to the local energy of training and evaluation: the rows then carry its batch mean E_loc + E_nl.  The
+cell of this example is all-electron, so with a real potential the numbers mean nothing: the point is the call sequence)"""
 import os
 import sys
 
@@ -66,6 +69,11 @@ if '--spin-squared' in sys.argv:
         spin_pairs = int(sys.argv[i + 1])
         del sys.argv[i + 1]
     del sys.argv[i]
+ecp_file = None
+if '--ecp' in sys.argv:
+    i = sys.argv.index('--ecp')
+    ecp_file = sys.argv[i + 1]
+    del sys.argv[i:i + 2]
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 batch = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
 cell, klist = systems.build('lih')
@@ -73,6 +81,10 @@ if scf_approx is not None:
     if scf_approx.nelec != tuple(cell.nelec):
         sys.exit(f'--hf: the file holds nelec = {scf_approx.nelec}, this cell has {tuple(cell.nelec)}')
     klist = scf_approx.klist
+ecp = None
+if ecp_file is not None:
+    from deepsolid_amd.pseudopotential import SemiLocalECP
+    ecp = SemiLocalECP.load(ecp_file, cell)
 kw = dict(systems.DETNET_DEFAULTS)
 logdet = network.make_solid_fermi_net(klist=klist, simulation_cell=cell, method_name='eval_logdet', **kw)
 slogdet = network.make_solid_fermi_net(klist=klist, simulation_cell=cell, method_name='eval_slogdet', **kw)
@@ -81,7 +93,7 @@ data = torch.as_tensor(systems.synthetic_walkers(cell, batch), device='cuda')
 data, params, state, width, rows = inference.run_training(slogdet, logdet, params, data, cell, iterations=iters, burn_in=20,
                                                           learning_rate=2e-3 if optimizer == 'adam' else None, move_width=0.1,
                                                           pretrain_iterations=n_pre, optimizer=optimizer, scf_approx=scf_approx,
-                                                          pretrain_method=pretrain_method)
+                                                          pretrain_method=pretrain_method, pseudopotential=ecp)
 print('training:   E[0] = %.4f  ->  E[%d] = %.4f Ha   (pmove %.2f)' % (rows[0]['energy'], iters - 1, rows[-1]['energy'], rows[-1]['pmove']))
 accumulators = ()
 if density_grid is not None or pair_bins is not None:
@@ -97,7 +109,9 @@ if spin_squared:
     spin_acc = estimator.SpinSquared(logdet, params, pairs_per_walker=spin_pairs)
     accumulators += (spin_acc,)
 data, width, rows = inference.run_inference(slogdet, logdet, params, data, cell, iterations=10, burn_in=10, move_width=width,
-                                            accumulators=accumulators)
+                                            accumulators=accumulators, pseudopotential=ecp)
+if ecp is not None:
+    print('pseudopotential: <E_loc + E_nl> = %.4f Ha (N_q = %d)' % (sum(r['pseudopotential'].real for r in rows) / len(rows), ecp.n_quad))
 print('evaluation: E = %.4f +- %.4f Ha over 10 x %d walkers' % (sum(r['energy'] for r in rows) / len(rows),
                                                                 (sum(r['variance'] for r in rows) / len(rows) / (10 * batch)) ** 0.5, batch))
 for acc in accumulators:

@@ -368,7 +368,7 @@ int ds_mcmc_step_asymmetric(ds_system* sys, const void* params, void* x, void* l
                             const void* uniforms, int lp_valid, void* n_accept, void* ws, int64_t ws_bytes, void* stream);
 /* the raw Philox block ds_mcmc_step uses for (seed, offset + step, index, stream_id): host evaluation for tests
  * (stream_id 0 / 1: normal deviates of electron `index`, 2: the uniform deviate of walker `index`, 3: the shifts of
- * ds_one_body_ratios). */
+ * ds_one_body_ratios; the rotations of ds_ecp_energy, its stream 4, are stream_id 0 at offset + 2^61). */
 void ds_philox_host(uint64_t seed, uint64_t offset, uint64_t step, uint64_t index, int stream_id, uint32_t out[4]);
 
 /* One-body ratios q = psi(R') / psi(R), with R' = R except for ONE displaced electron, and the momentum distribution n(k) folded
@@ -444,6 +444,117 @@ int64_t ds_spin_exchange_workspace_bytes(const ds_system* sys, int64_t B, int n_
 int ds_spin_exchange_ratios(ds_system* sys, const void* params, const void* x, int64_t B, int n_pairs, int first_pair,
                             double* sums, void* out_ratio, double* out_walker, int64_t* n_bad, void* ws, int64_t ws_bytes,
                             void* stream);
+
+/* Semi-local pseudopotential (ECP) energy of a batch of walkers (csrc/ds_ecp.h).  The reference has no
+ * pseudopotentials: the conventions are this library's own.
+ *
+ * Potential.  Each atom I of the simulation cell has a species.  A species has a local radial function v_loc and n_l in 0..4
+ * non-local channels v_l, l = 0 .. n_l-1.  Every radial function has the form
+ *       v(r) = sum_k c_k r^(n_k - 2) exp(-zeta_k r^2),   n_k in {0, 1, 2, 3, 4},   at most 16 terms
+ *   - This is the Gaussian expansion in which ccECP, BFD and Stuttgart potentials are published.
+ *   - v_loc is the local part WITHOUT the -Z_eff / r tail.  Ewald carries that tail.
+ *   - The caller's cell already has the valence electron count in nelec and Z_eff in atom_charges().
+ *
+ * Cutoffs.  Each species has two cutoffs: r_cut_loc and r_cut_nl, the latter one value for all of its channels.
+ *   - Inside the cutoff the function is used as it is.  Outside it is exactly 0.  Nothing is smoothed.
+ *   - Every cutoff must be <= half the smallest height of the simulation cell, where height c = 1 / ||column c of inv(a)||.
+ *     Creation refuses a larger cutoff with a message that names the atom, the cutoff and the limit.
+ *   Under the height condition exactly one periodic image of an ion can lie inside the cutoff.  It is the one with all fractional
+ *   components in [-1/2, 1/2):
+ *       f = (r_i - R_I) . inv(a);   f <- f - floor(f + 1/2);   d = f . a;   r = |d|;   dhat = d / r   (dhat = z if r = 0)
+ *   (r >= |f_c| height_c for each c, so r below half the smallest height forces every |f_c| < 1/2: csrc/ds_ecp.h has the proof.)
+ *
+ * Energy of walker w.
+ *       E_loc(w) = sum_i sum_I [r_iI < r_cut_loc,I] v_loc,I(r_iI)
+ *       E_nl(w)  = sum_{(i,I): r_iI < r_cut_nl,I}  sum_{q < N_q} (1 / N_q) W_iIq psi(R'_iIq) / psi(R)
+ *       W_iIq    = sum_l (2l + 1) v_I,l(r_iI) P_l(U_q . dhat_iI)
+ *       R'_iIq   = R with r_i replaced by r_i - d_iI + r_iI U_q
+ *   - R' is not wrapped, as in ds_one_body_ratios.
+ *   - E_loc is real and E_nl is complex.
+ *   - The total to add to E_L is E_loc + E_nl.
+ *
+ * Quadrature.  N_q in {6, 12}, with equal weights.  U_q = Rot_w u_q.
+ *   - Octahedron, exact to degree 3: +x, -x, +y, -y, +z, -z.
+ *   - Icosahedron, exact to degree 5.  Let phi = (1 + sqrt 5) / 2 and n = sqrt(1 + phi^2).  For (s1, s2) in the order
+ *     (+,+), (+,-), (-,+), (-,-), take all four of (0, s1, s2 phi) / n, then all four of (s1, s2 phi, 0) / n, then all four of
+ *     (s2 phi, 0, s1) / n.
+ *   - Creation refuses n_l such that 2 (n_l - 1) exceeds the degree of the rule.  That is l <= 1 with 6 points and l <= 2 with 12.
+ *     It refuses l = 3 altogether with these two rules.  n_l up to 3 is therefore what runs, and the n_l <= 4 of the table format
+ *     is reserved.
+ *
+ * Rotation.  There is one rotation per walker and call.  It is a pure function of (seed, offset, w).
+ *   - It uses Philox stream 4.  Streams 0-3 are taken.  The stream number of ds_philox_host fills the two top bits of the fourth
+ *     counter word, which hold 0..3; stream 4 is stream number 0 with bit 29 of that word set, i.e. the block
+ *     ds_philox_host(seed, offset + 2^61, step, index, 0).  philox_offset must stay below 2^61.
+ *   - Block A is at index 2w and block B at index 2w + 1, with counter philox_offset and step 0.
+ *   - u1 = u53_co(A0, A1), u2 = u53_co(A2, A3), u3 = u53_co(B0, B1).
+ *   - The quaternion follows Shoemake: (x, y, z, w) = (sqrt(1 - u1) sin 2 pi u2, sqrt(1 - u1) cos 2 pi u2, sqrt(u1) sin 2 pi u3,
+ *     sqrt(u1) cos 2 pi u3).  The matrix is the standard one of a unit quaternion, in float64 (its factor 2 is taken as
+ *     2 / |quaternion|^2, so that the rounding of the norm does not enter the orthogonality).
+ *   - Test mode takes caller-supplied rotations (B, 3, 3) in float64 [device, row-major].
+ *   - The caller advances the offset by 1 per call.
+ *
+ * Arithmetic.
+ *   - Distances, radial functions, Legendre polynomials and weights are float64 for either dtype, computed from the walker
+ *     coordinates as stored.  A float32 system reads float32 positions and widens them.
+ *   - q = exp(log|psi(R')| - log|psi(R)|) phase(R') conj(phase(R)) in float64 from the value chain's outputs, as in
+ *     ds_one_body_ratios.
+ *
+ * Pair order.  Pairs are ordered by (w, i, I) and configurations by (pair, q).  That order fixes every sum.
+ *
+ * Non-finite input.
+ *   - A walker with a non-finite coordinate gets NaN in all three of its outputs and contributes no pair.
+ *   - A non-finite ratio makes that walker's E_nl non-finite and nothing else.  It shows up in n_nonfinite of ds_energy_stats as
+ *     any non-finite E_L does.
+ *   - There is no n_bad.
+ *
+ * The descriptor holds HOST arrays that ds_ecp_create copies: the cell a (rows = lattice vectors, Bohr); atoms (n_atoms, 3) of the
+ * SIMULATION cell and atom_species (n_atoms,); per species n_l, r_cut_loc, r_cut_nl (n_species,); the term tables term_n / term_zeta
+ * / term_c of all radial functions back to back, with term_offset (5 n_species + 1,): slot 5 s is v_loc of species s, slot 5 s + 1
+ * + l its v_l, and the terms of slot j are term_offset[j] .. term_offset[j + 1] - 1; n_quad.
+ * ds_ecp_create refuses, before it touches the device: n_quad other than 6 or 12, n_l outside 0..4 or beyond the rule (above), more
+ * than 16 terms in a function, n_k outside 0..4, non-finite entries, an atom_species outside the species, and a cutoff beyond half
+ * the smallest height.
+ *
+ * ds_ecp_energy, one call:
+ *   1. per walker: the rotation, the minimum image of every (i, I), E_loc added in (i, I) order, the pairs inside r_cut_nl counted;
+ *   2. an exclusive scan of the counts over the walkers, and the pair records (w, i, I, r, dhat, v_l(r)) at their offsets;
+ *   3. the pair total is read back: ONE 8-byte copy and ONE stream synchronisation, the only synchronisation of the call.  The
+ *      call therefore CANNOT be captured into a graph.  A total above pair_capacity fails the call before any forward; the message
+ *      carries the number needed ("... the walkers have <n> pairs ...");
+ *   4. one forward of the B walkers (none when there is no pair), then per chunk of a whole number of 80-configuration groups --
+ *      the chunk length follows from ws_bytes as in ds_one_body_ratios, at most 65535 configurations -- propose, value chain (that
+ *      of ds_logpsi), and the term (W / N_q) q of every configuration in float64 into the workspace (q into out_ratio on request);
+ *   5. per walker, one wave: lane l adds the walker's terms l, l + 64, ... in order, then lane 0 adds the 64 results in lane order.
+ * out_energy (B, 3) float64 = (E_loc, Re E_nl, Im E_nl), written by step 5 only; out_pairs (B,) int64: pairs per walker;
+ * out_ratio (pair_capacity N_q, 2) of the system's dtype: q of configuration pair * N_q + q; out_rotation (B, 3, 3) float64: all
+ * device arrays, the last three optional.  No floating-point atomics, no allocation, 64-bit indices; results are bit-identical
+ * from run to run and for ANY workspace size under the condition of ds_spin_exchange_ratios (the value chain must pick the same
+ * kernels for the chunk lengths involved).
+ * Refused with a ds_last_error message before any launch: B < 1, out_energy NULL, pair_capacity < 1, a workspace below one group
+ * ("workspace too small"), and a descriptor whose cell or atom count differs from the system's. */
+typedef struct ds_ecp ds_ecp;
+typedef struct ds_ecp_desc {
+    double a[9];
+    int32_t n_atoms;
+    const double* atoms;
+    const int32_t* atom_species;
+    int32_t n_species;
+    const int32_t* n_l;
+    const double* r_cut_loc;
+    const double* r_cut_nl;
+    const int32_t* term_offset;
+    const int32_t* term_n;
+    const double* term_zeta;
+    const double* term_c;
+    int32_t n_quad;
+} ds_ecp_desc;
+int ds_ecp_create(const ds_ecp_desc* desc, ds_ecp** out);
+void ds_ecp_destroy(ds_ecp* ecp);
+int64_t ds_ecp_workspace_bytes(const ds_system* sys, const ds_ecp* ecp, int64_t B, int64_t pair_capacity);
+int ds_ecp_energy(ds_system* sys, const ds_ecp* ecp, const void* params, const void* x, int64_t B, uint64_t philox_seed,
+                  uint64_t philox_offset, const double* rotations, int64_t pair_capacity, double* out_energy, int64_t* out_pairs,
+                  void* out_ratio, double* out_rotation, void* ws, int64_t ws_bytes, void* stream);
 
 /* Packed batch statistics of train.make_loss.total_energy (train.py:74-82) in one deterministic reduction:
  * out_stats (8,) float64 on the device =
