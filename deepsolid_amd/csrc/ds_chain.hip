@@ -424,6 +424,32 @@ int logpsi_grad_impl(ds_system* s, const void* params, const void* x, int64_t B,
     }
     return 0;
 }
+// One pass with BOTH outputs of k_combine, plus the Ewald triple (the DMC step, ds_dmc.hip): ke (B,2), grad (B,3N,2), log|psi|,
+// phase and ew3 (B,3), chunked by ws_bytes as the two functions above chunk it.
+template <typename T>
+int energy_grad_impl(ds_system* s, const void* params, const void* x, int64_t B, void* out_ke, void* out_ew3, void* out_logabs,
+                     void* out_phase, void* out_grad, void* ws, int64_t ws_bytes, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const int64_t chunk = std::min<int64_t>(ws_bytes / (int64_t)(s->ws.per_walker * sizeof(T)), 65535);
+    if (chunk < 1) return fail("workspace too small: %lld bytes < %zu per walker", (long long)ws_bytes, s->ws.per_walker * sizeof(T));
+    for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+        const int64_t Bc = std::min(chunk, B - b0);
+        int rc = run_chain<T>(s, (const T*)params, (const T*)x + b0 * 3 * S.N, Bc, arena_of<T>(ws, ws_bytes), st, (T*)out_ke + 2 * b0,
+                              (T*)out_logabs + b0, (T*)out_phase + 2 * b0, nullptr, (T*)out_grad + b0 * 3 * S.N * 2);
+        if (rc) return rc;
+    }
+    {
+        ProfScope ps(s, DS_PROF_EWALD, st);
+        hipLaunchKernelGGL((ds::k_ewald<T>), dim3((unsigned)B), dim3(256), ds::ewald_lds_bytes(S), st, S, (const T*)x, (T*)out_ew3);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+int energy_grad_forward(ds_system* s, const void* params, const void* x, int64_t B, void* out_ke, void* out_ew3, void* out_logabs,
+                        void* out_phase, void* out_grad, void* ws, int64_t ws_bytes, hipStream_t st) {
+    return DS_BY_DTYPE(s->dtype, energy_grad_impl, s, params, x, B, out_ke, out_ew3, out_logabs, out_phase, out_grad, ws, ws_bytes, st);
+}
+
 // the Ewald triple (ee, ei, ii) per walker: out (B, 3)
 template <typename T> void ewald_triple(ds_system* s, const void* x, int64_t B, void* out, hipStream_t st) {
     const ds::SysDev<T>& S = dev<T>(s);

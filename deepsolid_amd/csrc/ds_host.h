@@ -1,5 +1,5 @@
 // ds_host.h -- what the host units of libdeepsolid_hip.so share (ds_api.hip, ds_chain.hip, ds_det.hip, ds_value.hip,
-// ds_gradpass.hip, ds_sample.hip, ds_observe.hip) on top of ds_base.h: the workspace arena, the handle, the workspace layouts of the
+// ds_gradpass.hip, ds_sample.hip, ds_dmc.hip, ds_observe.hip) on top of ds_base.h: the workspace arena, the handle, the workspace layouts of the
 // two chains and the few functions that one unit calls in another.  Internal to the library.
 #pragma once
 #include "ds_base.h"
@@ -243,6 +243,9 @@ template <typename T> void launch_spin_mean(dim3 grid, hipStream_t st, const ds:
 // ds_chain.hip: the walker gradient of log psi (the importance sampler)
 int logpsi_grad_forward(ds_system* s, const void* params, const void* x, int64_t B, void* out_logabs, void* out_phase, void* out_grad,
                         void* ws, int64_t ws_bytes, hipStream_t st);
+// ... the same chain with the kinetic energy as well, and the Ewald triple (B,3) behind it (the DMC step)
+int energy_grad_forward(ds_system* s, const void* params, const void* x, int64_t B, void* out_ke, void* out_ew3, void* out_logabs,
+                        void* out_phase, void* out_grad, void* ws, int64_t ws_bytes, hipStream_t st);
 // ... the number of its layers that run as an int8 split (dump: in a stage dump, which has no low-rank layer 1)
 int int8_energy_layers(const ds_system* s, bool dump);
 // ... and the two residual kernels that both chains launch (block 256, arguments as the kernels')

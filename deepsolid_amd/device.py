@@ -579,6 +579,83 @@ class DeviceSystem:
         return dict(sums=sums, n_bad=n_bad, ratios=torch.view_as_complex(ratios) if ratios is not None else None,
                     walker=torch.view_as_complex(walker) if want_walker else None)
 
+    def dmc_state(self, x, weight=None):
+        """Fresh DMC walker state for `dmc_step(..., state_valid=False)`: dict of the six caller-owned device buffers (x is copied;
+        logabs, phase, drift and eloc are filled by the first call; weights are 1 or `weight`)."""
+        x = self._check_x(x).clone()
+        B = x.shape[0]
+        f64 = dict(dtype=torch.float64, device=self.device)
+        w = torch.ones(B, **f64) if weight is None else torch.as_tensor(weight).to(**f64).reshape(B).clone()
+        return dict(x=x, logabs=torch.zeros(B, dtype=self.dtype, device=self.device),
+                    phase=torch.zeros(B, 2, dtype=self.dtype, device=self.device), drift=torch.zeros_like(x),
+                    eloc=torch.zeros(B, **f64), weight=w)
+
+    def _check_dmc_state(self, state):
+        B = state['x'].shape[0]
+        shapes = dict(x=((B, 3 * self.n), self.dtype), logabs=((B,), self.dtype), phase=((B, 2), self.dtype),
+                      drift=((B, 3 * self.n), self.dtype), eloc=((B,), torch.float64), weight=((B,), torch.float64))
+        for k, (shape, dt) in shapes.items():
+            t = state[k]
+            if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
+                raise ValueError(f'DMC state entry {k!r} must be a contiguous {dt} device tensor of shape {shape}')
+        return B
+
+    def dmc_step(self, params, state, steps, tau, tau_eff=None, e_trial=0.0, e_ref=0.0, e_cut=0.0, node_mode=0, branch_every=1,
+                 seed=0, offset=0, normals=None, uniforms=None, comb_uniforms=None, state_valid=True, want_parents=False,
+                 max_bytes=None):
+        """`ds_dmc_step`: `steps` fixed-phase DMC steps on the walker state IN PLACE (dict of x, logabs, phase, drift, eloc, weight:
+        `dmc_state`), enqueued without a host synchronisation; the algorithm is stated in include/deepsolid_hip.h.  Noise from
+        the in-kernel Philox stream (seed, offset) or replayed from `normals` (steps,B,3N), `uniforms` (steps,B) and
+        `comb_uniforms` (steps,) float64 -- all three or none.  `max_bytes` caps the workspace: more chain chunks.
+        -> dict(stats (steps, 9) float64 device tensor, parents (steps, B) int32 with `want_parents`)."""
+        B = self._check_dmc_state(state)
+        steps = int(steps)
+        p = self.pack_params(params)
+        given = [t is not None for t in (normals, uniforms, comb_uniforms)]
+        if all(given):
+            normals = normals.to(device=self.device, dtype=self.dtype).contiguous()
+            uniforms = uniforms.to(device=self.device, dtype=self.dtype).contiguous()
+            comb_uniforms = comb_uniforms.to(device=self.device, dtype=torch.float64).contiguous()
+            if tuple(normals.shape) != (steps, B, 3 * self.n) or tuple(uniforms.shape) != (steps, B) or tuple(comb_uniforms.shape) != (steps,):
+                raise ValueError('explicit noise must be normals (steps, B, 3N), uniforms (steps, B) and comb_uniforms (steps,)')
+        stats = torch.zeros(max(steps, 1), 9, dtype=torch.float64, device=self.device)
+        parents = torch.empty(max(steps, 1), B, dtype=torch.int32, device=self.device) if want_parents else None
+        ws = self._workspace('ds_dmc_workspace_bytes', int(B), max_bytes=max_bytes) if 1 <= B <= 2 ** 20 else self.workspace(1)
+        _lib.check(self.lib.ds_dmc_step(
+            self.handle, _ptr(p), _ptr(state['x']), _ptr(state['logabs']), _ptr(state['phase']), _ptr(state['drift']),
+            _ptr(state['eloc']), _ptr(state['weight']), B, steps, float(tau), float(tau if tau_eff is None else tau_eff),
+            float(e_trial), float(e_ref), float(e_cut), int(node_mode), int(branch_every), int(seed) & (2 ** 64 - 1),
+            int(offset) & (2 ** 64 - 1), _ptr(normals), _ptr(uniforms), _ptr(comb_uniforms), int(bool(state_valid)), _ptr(stats),
+            _ptr(parents), _ptr(ws), ws.numel(), _stream()), 'ds_dmc_step')
+        return dict(stats=stats, parents=parents)
+
+    def dmc_noise(self, B, steps, seed=0, offset=0):
+        """`ds_dmc_noise`: what `dmc_step` draws in Philox mode for (seed, offset), as the arrays its explicit mode takes
+        -> (normals (steps, B, 3N), uniforms (steps, B), comb_uniforms (steps,) float64)."""
+        nz = torch.empty(steps, B, 3 * self.n, dtype=self.dtype, device=self.device)
+        un = torch.empty(steps, B, dtype=self.dtype, device=self.device)
+        xi = torch.empty(steps, dtype=torch.float64, device=self.device)
+        _lib.check(self.lib.ds_dmc_noise(0 if self.dtype == torch.float64 else 1, self.n, int(B), int(steps), int(seed) & (2 ** 64 - 1),
+                                         int(offset) & (2 ** 64 - 1), _ptr(nz), _ptr(un), _ptr(xi), _stream()), 'ds_dmc_noise')
+        return nz, un, xi
+
+    def dmc_branch(self, state, xi, want_parents=True):
+        """`ds_dmc_branch`: the fixed-population comb alone on a walker state, IN PLACE, with the given xi in [0, 1).
+        -> parents (B,) int32 device tensor (None without `want_parents`)."""
+        B = self._check_dmc_state(state)
+        need = int(self.lib.ds_dmc_branch_workspace_bytes(0 if self.dtype == torch.float64 else 1, self.n, B))
+        if need < 0:
+            need = 256                                     # (the library refuses such a B itself)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        parents = torch.empty(B, dtype=torch.int32, device=self.device) if want_parents else None
+        _lib.check(self.lib.ds_dmc_branch(0 if self.dtype == torch.float64 else 1, self.n, B, float(xi), _ptr(state['x']),
+                                          _ptr(state['logabs']), _ptr(state['phase']), _ptr(state['drift']), _ptr(state['eloc']),
+                                          _ptr(state['weight']), _ptr(parents), _ptr(self._ws), self._ws.numel(), _stream()),
+                   'ds_dmc_branch')
+        return parents
+
     def ecp_energy(self, params, x, ecp, seed=0, offset=0, rotations=None, pair_capacity=None, want_pairs=False, want_ratios=False,
                    want_rotations=False, max_bytes=None):
         """`ds_ecp_energy`: the semi-local pseudopotential energy of every walker.  `ecp`: an `EcpTables` (or a

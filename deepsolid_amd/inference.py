@@ -183,6 +183,92 @@ def run_inference(slog_net, logdet_net, params, data, simulation_cell, iteration
     return data, width, rows
 
 
+DMC_SCHEMA = ['block', 'energy', 'variance', 'acceptance', 'tau_eff', 'e_trial', 'weight', 'killed']
+
+
+def run_dmc(slog_net, logdet_net, params, data, simulation_cell, blocks, steps_per_block, tau, key=0, move_width=0.02, mcmc_steps=20,
+            burn_in=100, vmc_iterations=20, branch_every=1, e_cut=None, node_mode=0, feedback=10.0, save_path=None,
+            stats_file_name='dmc_stats', accumulators=(), pseudopotential=None, state=None):
+    """Fixed-phase diffusion Monte Carlo of a fixed wavefunction (`deepsolid_amd.dmc`).
+    Returns (state, rows, info).  Equilibrate `data` (B, 3N) with the existing `qmc.make_mcmc_step` (`burn_in` iterations), take
+    the VMC energy over `vmc_iterations` more (info['vmc_energy'], info['vmc_error']: reblocked batch means, per primitive cell;
+    info['vmc_series']), initialise the DMC state with e_ref = e_trial = that energy, then run `blocks` blocks of
+    `steps_per_block` steps, each ONE `ds_dmc_step` call.  Between blocks, on the host, after one packed all-reduce of the stats
+    rows: tau_eff = tau * sum p / (B * steps) of the block; e_ref = the running mixed estimate; e_trial = e_ref -
+    log(W_global / W_target) / (feedback * tau * steps), W_target = the number of walkers of all ranks.  Ranks comb their own
+    populations.  `e_cut` defaults to 0.2 sqrt(N / tau).  One CSV row per block through `Writer`: block, mixed energy per primitive
+    cell, variance, acceptance, tau_eff, e_trial, total weight, walkers killed.  `accumulators` are fed the walkers on blocks that
+    end on a comb (all weights are then equal, so the unweighted accumulators give mixed estimates); they are refused when
+    steps_per_block % branch_every != 0.  `state` (a `dmc.DmcState`, e.g. `DmcState.load`) resumes a run: no equilibration, and the
+    same bits as the run that was not interrupted; with a `save_path` the state is written to <save_path>/dmc_state.npz on exit.
+    `pseudopotential` is refused (out of scope: see `dmc.make_dmc_step`)."""
+    from . import constants, dmc
+    accumulators = tuple(accumulators)
+    if pseudopotential is not None:
+        dmc.make_dmc_step(logdet_net, simulation_cell, tau, steps_per_block, pseudopotential=pseudopotential)
+    if accumulators and (branch_every <= 0 or steps_per_block % branch_every != 0):
+        raise ValueError('accumulators need blocks that end on a comb: steps_per_block must be a multiple of branch_every')
+    system = logdet_net.apply.system
+    scale = float(getattr(simulation_cell, 'scale', 1))
+    batch = data.shape[0]
+    seed = (int(key) if not isinstance(key, torch.Generator) else 0) * max(1, constants.world_size()) + constants.rank()
+    info = {}
+    if state is None:
+        gen = _rank_generator(key, data.device)
+        mcmc_step = qmc.make_mcmc_step(slog_net.apply, batch, latvec=simulation_cell.a, steps=mcmc_steps)
+        for _ in range(burn_in):
+            data, _ = mcmc_step(params, data, gen, float(move_width))
+        series = []
+        for _ in range(max(int(vmc_iterations), 1)):
+            data, _ = mcmc_step(params, data, gen, float(move_width))
+            ke, ew, _, _ = system.local_energy(params, data)
+            mean = constants.pmean_if_pmap((ke[:, 0].double() + ew.double()).mean())
+            series.append(float(mean))
+        e_vmc, err_vmc, _ = dmc.reblock(series)
+        info.update(vmc_energy=e_vmc / scale, vmc_error=err_vmc / scale, vmc_series=np.asarray(series) / scale)
+        state = dmc.DmcState.fresh(system, data, tau, e_vmc)
+    block_fn = dmc.make_dmc_step(logdet_net, simulation_cell, tau, steps_per_block, e_cut=e_cut, node_mode=node_mode,
+                                 branch_every=branch_every, seed=seed)
+    w_target = float(batch * max(1, constants.world_size()))
+    rows = []
+    writer = Writer(stats_file_name, DMC_SCHEMA, save_path) if save_path else None
+    if writer:
+        writer.__enter__()
+    try:
+        for b in range(blocks):
+            tau_eff, e_trial = state.tau_eff, state.e_trial
+            st = constants.psum_if_pmap(block_fn(params, state)).cpu().numpy()          # ONE packed all-reduce per block
+            w, we, we2 = st[:, 0].sum(), st[:, 1].sum(), st[:, 2].sum()
+            energy = we / w
+            state.sum_w, state.sum_we = state.sum_w + float(w), state.sum_we + float(we)
+            combed = st[:, 8] > 0
+            row = {'block': b, 'energy': energy / scale, 'variance': (we2 / w - energy ** 2) / scale ** 2,
+                   'acceptance': st[:, 3].sum() / (w_target * steps_per_block), 'tau_eff': tau_eff, 'e_trial': e_trial / scale,
+                   'weight': float(st[-1, 0]), 'killed': int((w_target - st[combed, 8]).sum()) if branch_every > 0 else 0}
+            rows.append(row)
+            if writer:
+                writer.write(b, **row)
+            state.tau_eff = float(tau) * float(st[:, 4].sum()) / (w_target * steps_per_block)
+            state.e_ref = state.sum_we / state.sum_w
+            state.e_trial = state.e_ref - float(np.log(st[-1, 0] / w_target)) / (float(feedback) * float(tau) * steps_per_block)
+            for acc in accumulators:
+                acc.update(state.arrays['x'])
+    finally:
+        if writer:
+            writer.__exit__(None, None, None)
+    for i, acc in enumerate(accumulators):
+        acc.reduce()
+        if save_path and constants.rank() == 0:
+            acc.save(os.path.join(save_path, 'realspace.npz' if i == 0 else f'realspace_{i}.npz'), results=True)
+    if save_path:
+        state.save(os.path.join(save_path, f'dmc_state_rank{constants.rank()}.npz' if constants.world_size() > 1 else 'dmc_state.npz'))
+    series = np.asarray([r['energy'] for r in rows])
+    if len(series):
+        e, err, _ = dmc.reblock(series)
+        info.update(energy=e, error=err)
+    return state, rows, info
+
+
 def learning_rate_schedule(rate=5e-2, decay=1.0, delay=10000.0):
     """process.py:200-202 with the defaults of base_config.py:46-51."""
     return lambda t: rate * (1.0 / (1.0 + t / delay)) ** decay

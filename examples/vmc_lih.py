@@ -17,7 +17,9 @@ through deepsolid_amd.estimator.MomentumDistribution, written to momentum.npz;
 n_up n_dn pairs), through deepsolid_amd.estimator.SpinSquared, written to spin_squared.npz;
 --ecp FILE.npz: add the semi-local pseudopotential saved in FILE.npz (deepsolid_amd.pseudopotential.SemiLocalECP.save, built for
 THIS cell) to the local energy of training and evaluation: the rows then carry its batch mean E_loc + E_nl.  The
-cell of this example is all-electron, so with a real potential the numbers mean nothing: the point is the call sequence)"""
+cell of this example is all-electron, so with a real potential the numbers mean nothing: the point is the call sequence);
+--dmc BLOCKS [--dmc-tau TAU]: after the evaluation, BLOCKS blocks of 20 steps of fixed-phase diffusion Monte Carlo at time step TAU
+(default 0.01) from the evaluation's walkers, through deepsolid_amd.inference.run_dmc; not with --ecp)"""
 import os
 import sys
 
@@ -69,6 +71,15 @@ if '--spin-squared' in sys.argv:
         spin_pairs = int(sys.argv[i + 1])
         del sys.argv[i + 1]
     del sys.argv[i]
+dmc_blocks, dmc_tau = 0, 0.01
+if '--dmc-tau' in sys.argv:
+    i = sys.argv.index('--dmc-tau')
+    dmc_tau = float(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
+if '--dmc' in sys.argv:
+    i = sys.argv.index('--dmc')
+    dmc_blocks = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
 ecp_file = None
 if '--ecp' in sys.argv:
     i = sys.argv.index('--ecp')
@@ -138,3 +149,12 @@ for acc in accumulators:
         r, g = acc.pair_correlation()
         print('g(r):       %d bins to r_max = %.3f Bohr; last bin up-up %.3f, up-down %.3f, down-down %.3f'
               % (pair_bins, acc.r_max, g[0, -1], g[1, -1], g[2, -1]))
+if dmc_blocks > 0:
+    from deepsolid_amd import dmc
+    state, dmc_rows, info = inference.run_dmc(slogdet, logdet, params, data, cell, blocks=dmc_blocks, steps_per_block=20, tau=dmc_tau,
+                                              move_width=width, burn_in=10, pseudopotential=ecp)
+    e, err, length = dmc.reblock([r['energy'] for r in dmc_rows[len(dmc_rows) // 4:]])
+    print('VMC:        E = %.4f +- %.4f Ha' % (info['vmc_energy'], info['vmc_error']))
+    print('DMC:        E = %.4f +- %.4f Ha (tau = %g, %d blocks of 20 steps, the first quarter left out; acceptance %.4f, '
+          'tau_eff %.5f, %d walkers killed)' % (e, err, dmc_tau, dmc_blocks, sum(r['acceptance'] for r in dmc_rows) / len(dmc_rows),
+                                                dmc_rows[-1]['tau_eff'], sum(r['killed'] for r in dmc_rows)))

@@ -556,6 +556,91 @@ int ds_ecp_energy(ds_system* sys, const ds_ecp* ecp, const void* params, const v
                   uint64_t philox_offset, const double* rotations, int64_t pair_capacity, double* out_energy, int64_t* out_pairs,
                   void* out_ratio, double* out_rotation, void* ws, int64_t ws_bytes, void* stream);
 
+/* Fixed-phase diffusion Monte Carlo (csrc/ds_dmc.h): all-electron drift-diffusion move, Metropolis
+ * acceptance, symmetric branching weights, energy cut-off, fixed-population comb.  The reference has no DMC: the conventions are
+ * this library's own.  One call runs a block of `steps` steps with no host synchronisation and no allocation.
+ *
+ * Walker state.  Caller-owned device buffers, T = the system's dtype:
+ *       x (B, 3N) T        walker coordinates
+ *       logabs (B,) T      log|psi|
+ *       phase (B, 2) T     (Re, Im) of the unit phase
+ *       drift (B, 3N) T    Re grad log psi
+ *       eloc (B,) float64  Re E_kin + E_ewald
+ *       weight (B,) float64  branching weight, >= 0
+ *   With state_valid = 0 the call first fills logabs, phase, drift and eloc from x by one chain pass plus Ewald.  Weights are not
+ *   touched, except that a walker whose log|psi| or E_L is not finite gets weight 0.
+ *
+ * Step i of a call, with tau, tau_eff, e_trial, e_ref, e_cut, node_mode:
+ *   1. Limited drift per electron: vbar_e = v_e * 2 / (1 + sqrt(1 + 2 |v_e|^2 tau)).  This is the Umrigar-Nightingale-Runge limiter
+ *      with a = 1, written in the form that has no cancellation.  It is NOT qmc.limdrift (the clip by the batch maximum that
+ *      ds_mcmc_step_importance uses): it needs nothing from the other walkers.
+ *   2. Proposal: x' = wrap(x + tau vbar + sqrt(tau) chi).  chi is the samplers' normals: streams 0 and 1, index w N + e, counter
+ *      philox_offset + i, rounded to T.  Wrap as ds_mh_propose_ex does.
+ *   3. One chain pass at x' with both outputs (kinetic energy and walker gradient), plus the Ewald kernel: log|psi'|, phase',
+ *      grad', ke'.  E' = Re ke' + ewald' in float64 (the Ewald triple summed in T as ds_local_energy sums it).
+ *   4. Log ratio: A = 2 (log|psi'| - log|psi|) + 1/2 (|chi|^2 - |chi + sqrt(tau) (vbar + vbar')|^2), float64.  It is built from chi
+ *      and the drifts, never from wrapped position differences, as mode 2 of ds_mh_accept_ex does.  Accept iff all of: A and E'
+ *      are finite; A > log u, u = stream 2 at index w; node_mode == 0 or Re(phase' conj(phase)) > 0.  node_mode = 1 is fixed-node
+ *      for real wavefunctions: a sign change is a node crossing.  p = min(1, e^A), and p = 0 for a move refused as non-finite or
+ *      node-crossing.
+ *   5. Weight update, all float64: E_new = E' if accepted else E;
+ *        weight <- weight * exp(-tau_eff (1/2 (clip(E_new) + clip(E)) - e_trial)),  clip(e) = e_ref + clamp(e - e_ref, +-e_cut);
+ *      e_cut <= 0 switches the clip off.  A weight that comes out not finite (the walker's energy is not finite) becomes 0.
+ *   6. x, logabs, phase, drift and eloc are selected in place.
+ *   7. One row of out_stats (steps, 9) float64, taken after the weight update and before branching:
+ *        [0] sum w   [1] sum w E (unclipped)   [2] sum w E^2   [3] number accepted   [4] sum p   [5] number of walkers whose E_new
+ *        was clipped   [6] number of non-finite proposals   [7] sum w^2   [8] distinct parents of this step's comb (B if the step
+ *        has none, 0 if its comb was skipped).
+ *      A walker of weight 0 adds nothing to [1] and [2] (its energy may be NaN).  Fixed order, no floating-point atomics: one row of
+ *      partials per 256 consecutive walkers (thread t holds walker t; a tree adds t and t + s for s = 128, 64, .., 1), then the
+ *      rows are added in order.
+ *   8. If branch_every > 0 and (i + 1) % branch_every == 0, the comb:
+ *        xi = the stream-2 uniform at index B (one past the walkers), counter philox_offset + i.
+ *        C = inclusive prefix sums of the weights in this order: chunk c holds walkers 256 c .. 256 c + 255; inside a chunk
+ *          r_0 = w_first, r_i = r_{i-1} + w_i; chunk offsets O_0 = 0, O_c = O_{c-1} + r_last(c-1); C_j = O_c + r_i.  Every sum is
+ *          one rounded float64 addition.  W = C_{B-1}.
+ *        Tooth k = (k + xi) (W/B), taken as its two products k (W/B) and xi (W/B), each rounded on its own:
+ *          parent of k = number of j with (C_j - k (W/B)) <= xi (W/B), the difference rounded too, clamped to the last walker of
+ *          positive weight (= the number of j with C_j < W; B - 1 unless the batch ends in dead walkers, which a tooth that
+ *          rounding puts on the last edge must not revive).
+ *          (A single rounded (k + xi) (W/B) would round xi = 1 - 2^-53 up to the next edge; in this form equal weights give the
+ *          identity for every xi in [0, 1).)
+ *        All state arrays are gathered from the parents and every weight becomes W/B.  A total W that is not finite or not
+ *        positive skips the comb: the state stays, the parents are the identity and entry [8] of the row is 0.
+ *      The comb keeps sum w, so the library has no trial-energy feedback of its own: e_trial only keeps W in range and the host
+ *      moves it between calls.  Ranks comb their own populations.
+ * Noise.  Philox as above, or explicit: normals (steps, B, 3N) and uniforms (steps, B) of dtype T and comb_uniforms (steps,)
+ * float64, all three or none.  A caller advances philox_offset by `steps` between calls; `steps` steps in one call and `steps`
+ * calls of one step with the offset advanced and state_valid = 1 give the same bits when branch_every is 0 or 1.
+ * out_parents (steps, B) int32, optional: the parents of every step (the identity for a step without a comb).
+ * The chain is chunked by ws_bytes as ds_logpsi_grad chunks it; results are bit-identical from run to run and for any workspace
+ * size under the condition of ds_spin_exchange_ratios (the chain picks the same kernels for the chunk lengths involved).
+ * Refused with a ds_last_error message before any launch: null state pointers or out_stats; B < 1 or B > 2^20 (the chunk offsets
+ * of the scan are kept in one workgroup's LDS); steps < 1; tau <= 0, tau_eff < 0 or a non-finite scalar; node_mode outside
+ * {0, 1}; branch_every < 0; noise arrays given in part; a workspace below one chain chunk ("workspace too small").
+ * Out of scope: pseudopotentials (ds_ecp_energy synchronises once per call and draws a rotation; locality approximation against
+ * T-moves is a design of its own -- this call takes no ds_ecp and adds no ECP term), electron-by-electron moves, forward
+ * walking and pure estimators, weighted accumulators, cross-rank walker exchange (ranks keep fixed populations with their own
+ * total weights, which is unbiased).
+ *
+ * ds_dmc_branch is the comb of step 8 alone with a given xi in [0, 1); it needs no handle (dtype: 0 float64, else float32) and is
+ * the code ds_dmc_step runs.  Workspace: ds_dmc_branch_workspace_bytes.  The caller's buffers may alias nothing else. */
+int64_t ds_dmc_workspace_bytes(const ds_system* sys, int64_t B);
+int ds_dmc_step(ds_system* sys, const void* params, void* x, void* logabs, void* phase, void* drift, double* eloc, double* weight,
+                int64_t B, int steps, double tau, double tau_eff, double e_trial, double e_ref, double e_cut, int node_mode,
+                int branch_every, uint64_t philox_seed, uint64_t philox_offset, const void* normals, const void* uniforms,
+                const double* comb_uniforms, int state_valid, double* out_stats, int32_t* out_parents, void* ws, int64_t ws_bytes,
+                void* stream);
+/* What a Philox-mode ds_dmc_step call of `steps` steps draws, written out in the layout of its explicit mode: normals
+ * (steps, B, 3N) and uniforms (steps, B) of dtype T, comb_uniforms (steps,) float64 [device].  The normals are the device's own
+ * Box-Muller values (a host model agrees with them to a few ulp, not to the bit), so a float64 call that replays these arrays
+ * gives the bits of the Philox-mode call.  (In float32 the explicit uniforms are rounded to T; the Philox mode compares in float64.) */
+int ds_dmc_noise(int dtype, int n_elec, int64_t B, int steps, uint64_t philox_seed, uint64_t philox_offset, void* normals,
+                 void* uniforms, double* comb_uniforms, void* stream);
+int64_t ds_dmc_branch_workspace_bytes(int dtype, int n_elec, int64_t B);
+int ds_dmc_branch(int dtype, int n_elec, int64_t B, double xi, void* x, void* logabs, void* phase, void* drift, double* eloc,
+                  double* weight, int32_t* out_parents, void* ws, int64_t ws_bytes, void* stream);
+
 /* Packed batch statistics of train.make_loss.total_energy (train.py:74-82) in one deterministic reduction:
  * out_stats (8,) float64 on the device =
  *   [ sum Re E_L, sum Im E_L, sum |E_L|^2, n, n_nonfinite, sum Re E_kin, sum Im E_kin, sum E_ewald ],  E_L = ke + ewald.
