@@ -7,6 +7,9 @@
 //   k_dmc_accept       one wave per walker: the two squared norms, the decision, the weight, the selected rows, (p, flags)
 //   k_dmc_stats        one workgroup per DMC_GROUP consecutive walkers: one row of float64 partials
 //   k_dmc_stats_final  adds the rows in workgroup order: one row of out_stats
+// With a pseudopotential (ds_dmc_step_ecp, locality approximation) ds_ecp_energy's launches follow the chain pass at x', the ECP
+// instances of k_dmc_init / k_dmc_accept take its float64 triple, k_dmc_ecp_stats / k_dmc_ecp_stats_final form the row of
+// out_ecp_stats, and k_dmc_gather_epp follows the comb.
 // and on a branching step the comb (k_dmc_scan_chunks, k_dmc_scan_offsets, k_dmc_select, k_dmc_gather, k_dmc_copy_back).
 //
 // Prefix sums of the weights, the order the numpy model reproduces bit for bit (DMC_CHUNK = 256):
@@ -76,17 +79,30 @@ __global__ void __launch_bounds__(256) k_dmc_propose(const T* __restrict__ a, co
     for (int c = 0; c < 3; ++c) x2[3 * e + c] = o[c];
 }
 
-// state_valid = 0: drift = Re grad, eloc = Re ke + ewald; a walker whose log|psi| or E_L is not finite gets weight 0
-template <typename T>
+// E = ((Re ke + ewald) + E_loc) + Re E_nl with the pseudopotential triple (E_loc, Re E_nl, Im E_nl) of ds_ecp_energy: float64, one
+// rounded addition each, in this order (the locality approximation: ds_dmc_step_ecp)
+__device__ __forceinline__ double dmc_energy_ecp(double e, const double* __restrict__ epp, long long w) {
+#pragma clang fp contract(off)
+    return (e + epp[3 * w]) + epp[3 * w + 1];
+}
+
+// state_valid = 0: drift = Re grad, eloc = Re ke + ewald; a walker whose log|psi| or E_L is not finite gets weight 0.  ECP: the
+// triple epp2 enters E_L and becomes the walker's epp
+template <typename T, bool ECP = false>
 __global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_init(long long B, int n3, const T* __restrict__ gc, const T* __restrict__ ke,
                                                              const T* __restrict__ ew3, const T* __restrict__ logabs,
-                                                             T* __restrict__ drift, double* __restrict__ eloc, double* __restrict__ weight) {
+                                                             T* __restrict__ drift, double* __restrict__ eloc, double* __restrict__ weight,
+                                                             const double* __restrict__ epp2 = nullptr, double* __restrict__ epp = nullptr) {
     const long long w = (long long)blockIdx.x * DMC_WAVES + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (w >= B) return;
     for (int c = lane; c < n3; c += 64) drift[(size_t)w * n3 + c] = gc[2 * ((size_t)w * n3 + c)];
     if (lane == 0) {
-        const double e = dmc_energy(ke, ew3, w);
+        double e = dmc_energy(ke, ew3, w);
+        if constexpr (ECP) {
+            e = dmc_energy_ecp(e, epp2, w);
+            for (int c = 0; c < 3; ++c) epp[3 * w + c] = epp2[3 * w + c];
+        }
         eloc[w] = e;
         if (!isfinite(e) || !isfinite((double)logabs[w])) weight[w] = 0.0;
     }
@@ -94,7 +110,9 @@ __global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_init(long long B, int n3
 
 // One wave per walker.  Lanes stride the electrons for |chi|^2 and |chi + sqrt(tau) (vbar + vbar')|^2 (float64 sums; the butterfly
 // adds them in a fixed order), every lane then holds the same decision, lane 0 updates the scalars, the wave copies the rows.
-template <typename T>
+// ECP: the triple epp2 at x' enters E' and is selected into epp with the other rows; epp2 then holds the walker's selected triple
+// too (the source of the comb's gather, k_dmc_gather_epp).
+template <typename T, bool ECP = false>
 __global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_accept(DmcArgs A, T* __restrict__ x, T* __restrict__ logabs, T* __restrict__ phase,
                                                                T* __restrict__ drift, double* __restrict__ eloc,
                                                                double* __restrict__ weight, const T* __restrict__ x2,
@@ -102,7 +120,8 @@ __global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_accept(DmcArgs A, T* __r
                                                                const T* __restrict__ gc2, const T* __restrict__ ke2,
                                                                const T* __restrict__ ew2, const T* __restrict__ chi,
                                                                const T* __restrict__ uniform, PhiloxKey key, unsigned long long step,
-                                                               double* __restrict__ pacc, int* __restrict__ flags) {
+                                                               double* __restrict__ pacc, int* __restrict__ flags,
+                                                               double* __restrict__ epp2 = nullptr, double* __restrict__ epp = nullptr) {
     const long long w = (long long)blockIdx.x * DMC_WAVES + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (w >= A.B) return;
@@ -122,7 +141,9 @@ __global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_accept(DmcArgs A, T* __r
     s1 = wave_sum(s1); s2 = wave_sum(s2);
     const double la_new = (double)la2[w], la_old = (double)logabs[w];
     const double a_log = 2.0 * (la_new - la_old) + 0.5 * (s1 - s2);
-    const double e_prop = dmc_energy(ke2, ew2, w), e_old = eloc[w];
+    double e_prop = dmc_energy(ke2, ew2, w);
+    if constexpr (ECP) e_prop = dmc_energy_ecp(e_prop, epp2, w);
+    const double e_old = eloc[w];
     const double u = uniform ? (double)uniform[w] : philox_uniform(key, step, (unsigned long long)w);
     const bool finite = isfinite(a_log) && isfinite(e_prop);
     const double overlap = (double)ph2[2 * w] * (double)phase[2 * w] + (double)ph2[2 * w + 1] * (double)phase[2 * w + 1];
@@ -150,7 +171,54 @@ __global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_accept(DmcArgs A, T* __r
         if (acc) { logabs[w] = la2[w]; phase[2 * w] = ph2[2 * w]; phase[2 * w + 1] = ph2[2 * w + 1]; eloc[w] = e_prop; }
         pacc[w] = (finite && node_ok) ? (a_log < 0.0 ? exp(a_log) : 1.0) : 0.0;
         flags[w] = fl;
+        if constexpr (ECP) {
+            for (int c = 0; c < 3; ++c) {
+                if (acc) epp[3 * w + c] = epp2[3 * w + c];
+                else epp2[3 * w + c] = epp[3 * w + c];
+            }
+        }
     }
+}
+
+// ds_dmc_step_ecp: one row of partials per DMC_GROUP walkers, [sum w E_loc, sum w Re E_nl, sum w Im E_nl] over the walkers of
+// non-zero weight, in the order of k_dmc_stats (thread t takes walker g0 + t; the tree adds t and t + s) ...
+__global__ void __launch_bounds__(DMC_GROUP) k_dmc_ecp_stats(long long B, const double* __restrict__ weight, const double* __restrict__ epp,
+                                                             double* __restrict__ part) {
+    __shared__ double sh[3][DMC_GROUP];
+    const long long w = (long long)blockIdx.x * DMC_GROUP + threadIdx.x;
+    double v[3] = {0, 0, 0};
+    if (w < B) {
+        const double wt = weight[w];
+        if (wt != 0.0)
+            for (int j = 0; j < 3; ++j) v[j] = wt * epp[3 * w + j];
+    }
+    for (int j = 0; j < 3; ++j) sh[j][threadIdx.x] = v[j];
+    __syncthreads();
+    for (int s = DMC_GROUP / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+            for (int j = 0; j < 3; ++j) sh[j][threadIdx.x] += sh[j][threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x < 3) part[(long long)blockIdx.x * 3 + threadIdx.x] = sh[threadIdx.x][0];
+}
+
+// ... and the rows added in workgroup order: one row of out_ecp_stats
+__global__ void __launch_bounds__(64) k_dmc_ecp_stats_final(const double* __restrict__ part, long long n_groups, double* __restrict__ out) {
+    const int j = threadIdx.x;
+    if (j >= 3) return;
+    double s = 0.0;
+    for (long long g = 0; g < n_groups; ++g) s += part[g * 3 + j];
+    out[j] = s;
+}
+
+// after the comb: epp of walker k = the triple of its parent.  Reads the comb's parents and its run flag (tot[2]); the source is
+// epp2, which k_dmc_accept left equal to epp, so no walker reads a row that another one writes.  A skipped comb changes nothing.
+__global__ void __launch_bounds__(256) k_dmc_gather_epp(long long B, const double* __restrict__ tot, const int* __restrict__ parent,
+                                                        const double* __restrict__ epp2, double* __restrict__ epp) {
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= B || tot[2] == 0.0) return;
+    const long long p = parent[k];
+    for (int c = 0; c < 3; ++c) epp[3 * k + c] = epp2[3 * p + c];
 }
 
 // One row of partials per DMC_GROUP walkers: [sum w, sum w E, sum w E^2, accepted, sum p, clipped, non-finite, sum w^2]; a walker of

@@ -200,6 +200,42 @@ ValBufs<T> carve_value(const ds_system* s, Arena<T>& a, int64_t ng) {
     return b;
 }
 
+// ---------------------------------------------------------------- the workspace of the pseudopotential energy (ds_sample.hip, ds_dmc.hip)
+// groups of PV configurations per chunk of the passes that walk configurations: a chunk has at most 65535 of them
+constexpr int64_t OB_MAX_GROUPS = 65535 / ds::PV;
+// groups per chunk that a *_workspace_bytes entry point provides at most (groups_per_pass): what ds_dmc_step_ecp keeps room for
+constexpr int64_t ECP_RESERVE = 64;
+// Workspace of ds_ecp_energy for B walkers, at most `cap` pairs, nq points per pair and chunks of ng groups of PV configurations.
+// Shared by all chunks: log|psi(R)| (B,), phase(R) (B,2), and in 8-byte elements (2 elements each: room in either element size) per
+// walker the rotation, E_loc, the pair count, the offsets (B + 1) and the flag, per pair its record (walker; electron and atom; r
+// and dhat; v_l(r)) and its nq terms.  Per chunk: the displaced rows, their log|psi| / phase, and the value chain's buffers for ng
+// groups (on a 64-element border), which also serve the forward of the walkers themselves.
+template <typename T> struct EcpWs {
+    T *LA0, *PH0, *XD, *LA, *PH;
+    double *ROT, *ELOC, *PR, *PVL, *TERM;
+    long long *CNT, *OFF, *PW;
+    int *BAD, *PI;
+    void* wsv; int64_t wsv_bytes;
+};
+template <typename T> EcpWs<T> carve_ecp(const ds_system* s, Arena<T>& a, int64_t B, int64_t cap, int nq, int64_t ng) {
+    const size_t nc = (size_t)ng * ds::PV, b = (size_t)B, p = (size_t)cap;
+    EcpWs<T> w{};
+    w.LA0 = a.take(b); w.PH0 = a.take(2 * b);
+    a.align(2);
+    w.ROT = (double*)a.take(2 * 9 * b); w.ELOC = (double*)a.take(2 * b);
+    w.CNT = (long long*)a.take(2 * b); w.OFF = (long long*)a.take(2 * (b + 1)); w.BAD = (int*)a.take(2 * ((b + 1) / 2));
+    w.PW = (long long*)a.take(2 * p); w.PI = (int*)a.take(2 * p);
+    w.PR = (double*)a.take(2 * 4 * p); w.PVL = (double*)a.take(2 * 3 * p); w.TERM = (double*)a.take(2 * 2 * p * (size_t)nq);
+    w.XD = a.take(nc * 3 * s->sd.N); w.LA = a.take(nc); w.PH = a.take(2 * nc);
+    a.align(64);
+    w.wsv = a.take(s->wsv.per_walker * (size_t)ng);
+    w.wsv_bytes = (int64_t)(s->wsv.per_walker * (size_t)ng * sizeof(T));
+    return w;
+}
+inline int64_t ecp_bytes(const ds_system* s, int64_t B, int64_t cap, int nq, int64_t ng) {
+    return (int64_t)measure([&](Arena<double>& a) { carve_ecp<double>(s, a, B, cap, nq, ng); }) * (s->dtype == 0 ? 8 : 4);
+}
+
 // ---------------------------------------------------------------- launch geometry that the chains and the reverse sweep share
 // workgroup size and grid.z of k_jet_gemm<NB>: at most 1024/NB threads (= its launch bound) per workgroup
 inline void gemm_geom(int Nout, int NB, dim3* block, unsigned* gz, int ST = 0) {
@@ -253,6 +289,18 @@ template <typename T> void launch_pair_res_add(dim3 grid, hipStream_t st, const 
 template <typename T>
 void launch_layer_res_add(dim3 grid, hipStream_t st, const T* Xin, size_t x_ws, size_t x_ts, T* Gout, size_t g_ws, size_t g_ts, int n_res,
                           int Nout, int P);
+
+// ds_sample.hip: the pseudopotential energy (ds_ecp.h) on a workspace of its own layout (carve_ecp): the body of ds_ecp_energy, which
+// the DMC step runs on a sub-range of its workspace.  Arguments as ds_ecp_energy's; *pairs_total (host, optional) receives the pair
+// total that the call reads back -- also when it fails because the total exceeds `cap` -- and pairs_total_dev (device, optional) a
+// copy of it.  ecp_check: what ds_ecp_workspace_bytes and ds_ecp_energy refuse alike (also a null descriptor); ecp_n_quad: N_q;
+// ecp_default_groups: the groups per chunk that ds_ecp_workspace_bytes provides
+int ecp_energy_forward(ds_system* s, const ds_ecp* e, const void* params, const void* x, int64_t B, uint64_t seed, uint64_t offset,
+                       const double* rotations, int64_t cap, double* out_energy, int64_t* out_pairs, void* out_ratio, double* out_rotation,
+                       void* ws, int64_t ws_bytes, hipStream_t st, int64_t* pairs_total, int64_t* pairs_total_dev);
+int ecp_check(const ds_system* s, const ds_ecp* e, int64_t B, int64_t pair_capacity);
+int ecp_n_quad(const ds_ecp* e);
+int64_t ecp_default_groups(const ds_system* s, int64_t B, int64_t pair_capacity, int nq);
 
 // ds_det.hip: the determinant stage of both chains.  Energy chain: inverse + determinant of channel ch, then tr(Y_d), sum Y_d Y_d^T;
 // value chain: log det of every channel (and the inverses when vb.MINV is set)

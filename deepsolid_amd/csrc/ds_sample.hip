@@ -104,8 +104,6 @@ template <typename T> OneBodyWs<T> carve_onebody(const ds_system* s, Arena<T>& a
 inline int64_t onebody_bytes(const ds_system* s, int64_t B, int64_t ng) {
     return (int64_t)measure([&](Arena<double>& a) { carve_onebody<double>(s, a, B, ng); }) * (s->dtype == 0 ? 8 : 4);
 }
-// groups per chunk: at most 65535 configurations (the grid limit of the chains)
-constexpr int64_t OB_MAX_GROUPS = 65535 / ds::PV;
 
 template <typename T>
 int one_body_impl(ds_system* s, const void* params, const void* x_, int64_t B, int M, int first, uint64_t seed, uint64_t offset,
@@ -210,41 +208,10 @@ int spin_exchange_impl(ds_system* s, const void* params, const void* x_, int64_t
 }
 
 // ------------------------------------------------------------------ pseudopotential energy, ds_ecp.h
-// Workspace of ds_ecp_energy for B walkers, at most `cap` pairs, nq points per pair and chunks of ng groups of PV configurations.
-// Shared by all chunks: log|psi(R)| (B,), phase(R) (B,2), and in 8-byte elements (2 elements each: room in either element size) per
-// walker the rotation, E_loc, the pair count, the offsets (B + 1) and the flag, per pair its record (walker; electron and atom; r
-// and dhat; v_l(r)) and its nq terms.  Per chunk: the displaced rows, their log|psi| / phase, and the value chain's buffers for ng
-// groups (on a 64-element border), which also serve the forward of the walkers themselves.
-template <typename T> struct EcpWs {
-    T *LA0, *PH0, *XD, *LA, *PH;
-    double *ROT, *ELOC, *PR, *PVL, *TERM;
-    long long *CNT, *OFF, *PW;
-    int *BAD, *PI;
-    void* wsv; int64_t wsv_bytes;
-};
-template <typename T> EcpWs<T> carve_ecp(const ds_system* s, Arena<T>& a, int64_t B, int64_t cap, int nq, int64_t ng) {
-    const size_t nc = (size_t)ng * ds::PV, b = (size_t)B, p = (size_t)cap;
-    EcpWs<T> w{};
-    w.LA0 = a.take(b); w.PH0 = a.take(2 * b);
-    a.align(2);
-    w.ROT = (double*)a.take(2 * 9 * b); w.ELOC = (double*)a.take(2 * b);
-    w.CNT = (long long*)a.take(2 * b); w.OFF = (long long*)a.take(2 * (b + 1)); w.BAD = (int*)a.take(2 * ((b + 1) / 2));
-    w.PW = (long long*)a.take(2 * p); w.PI = (int*)a.take(2 * p);
-    w.PR = (double*)a.take(2 * 4 * p); w.PVL = (double*)a.take(2 * 3 * p); w.TERM = (double*)a.take(2 * 2 * p * (size_t)nq);
-    w.XD = a.take(nc * 3 * s->sd.N); w.LA = a.take(nc); w.PH = a.take(2 * nc);
-    a.align(64);
-    w.wsv = a.take(s->wsv.per_walker * (size_t)ng);
-    w.wsv_bytes = (int64_t)(s->wsv.per_walker * (size_t)ng * sizeof(T));
-    return w;
-}
-inline int64_t ecp_bytes(const ds_system* s, int64_t B, int64_t cap, int nq, int64_t ng) {
-    return (int64_t)measure([&](Arena<double>& a) { carve_ecp<double>(s, a, B, cap, nq, ng); }) * (s->dtype == 0 ? 8 : 4);
-}
-
 template <typename T>
 int ecp_energy_impl(ds_system* s, const ds_ecp* e, const void* params, const void* x_, int64_t B, uint64_t seed, uint64_t offset,
                     const double* rotations, int64_t cap, double* out_energy, int64_t* out_pairs, void* out_ratio, double* out_rotation,
-                    void* ws, int64_t ws_bytes, hipStream_t st) {
+                    void* ws, int64_t ws_bytes, hipStream_t st, int64_t* pairs_total, int64_t* pairs_total_dev) {
     const ds::SysDev<T>& S = dev<T>(s);
     const ds::EcpDev& E = e->D;
     const T* x = (const T*)x_;
@@ -267,7 +234,9 @@ int ecp_energy_impl(ds_system* s, const ds_ecp* e, const void* params, const voi
     // the one synchronisation of the call: the host needs the pair total to size the chunks
     long long pairs = 0;
     HIP_OK(hipMemcpyAsync(&pairs, w.OFF + B, sizeof(long long), hipMemcpyDeviceToHost, st));
+    if (pairs_total_dev) HIP_OK(hipMemcpyAsync(pairs_total_dev, w.OFF + B, sizeof(long long), hipMemcpyDeviceToDevice, st));
     HIP_OK(hipStreamSynchronize(st));
+    if (pairs_total) *pairs_total = pairs;
     if (pairs > cap)
         return fail("ds_ecp_energy: pair capacity exceeded: the walkers have %lld pairs inside the non-local cutoffs, pair_capacity is %lld",
                     pairs, (long long)cap);
@@ -289,6 +258,38 @@ int ecp_energy_impl(ds_system* s, const ds_ecp* e, const void* params, const voi
     hipLaunchKernelGGL(ds::k_ecp_walker, dim3((unsigned)((B + ds::ECP_WAVES - 1) / ds::ECP_WAVES)), dim3(64 * ds::ECP_WAVES), 0, st,
                        (const double*)w.TERM, (const long long*)w.OFF, (const double*)w.ELOC, (const int*)w.BAD, (long long)B, nq, out_energy);
     HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int ecp_energy_forward(ds_system* s, const ds_ecp* e, const void* params, const void* x, int64_t B, uint64_t seed, uint64_t offset,
+                       const double* rotations, int64_t cap, double* out_energy, int64_t* out_pairs, void* out_ratio, double* out_rotation,
+                       void* ws, int64_t ws_bytes, hipStream_t st, int64_t* pairs_total, int64_t* pairs_total_dev) {
+    return DS_BY_DTYPE(s->dtype, ecp_energy_impl, s, e, params, x, B, seed, offset, rotations, cap, out_energy, out_pairs, out_ratio,
+                       out_rotation, ws, ws_bytes, st, pairs_total, pairs_total_dev);
+}
+
+int ecp_n_quad(const ds_ecp* e) { return e->D.n_quad; }
+
+int64_t ecp_default_groups(const ds_system* s, int64_t B, int64_t pair_capacity, int nq) {
+    // as many groups per chunk as ds_workspace_bytes gives the value chain of pair_capacity * n_quad walkers
+    const int64_t esz = s->dtype == 0 ? 8 : 4, total = pair_capacity * nq;
+    const int64_t fixed = ecp_bytes(s, B, pair_capacity, nq, 0), per = ecp_bytes(s, B, pair_capacity, nq, 1) - fixed;
+    return std::min(groups_per_pass(total, esz, PassSize{0, (size_t)(per / esz)}, workspace_budget()), OB_MAX_GROUPS);
+}
+
+// what ds_ecp_workspace_bytes and ds_ecp_energy refuse alike
+int ecp_check(const ds_system* s, const ds_ecp* e, int64_t B, int64_t pair_capacity) {
+    if (!s || !e) return fail("ds_ecp_energy: null system or pseudopotential descriptor");
+    if (B < 1) return fail("ds_ecp_energy: B must be >= 1 (got %lld)", (long long)B);
+    if (pair_capacity < 1) return fail("ds_ecp_energy: pair_capacity must be >= 1 (got %lld)", (long long)pair_capacity);
+    if (e->D.n_atoms != s->d.n_atoms_sim)
+        return fail("ds_ecp_energy: the descriptor has %d atoms, the system's simulation cell %d", e->D.n_atoms, s->d.n_atoms_sim);
+    double scale = 0.0;
+    for (int i = 0; i < 9; ++i) scale = std::max(scale, std::fabs(s->d.sim_a[i]));
+    for (int i = 0; i < 9; ++i)
+        if (!(std::fabs(e->D.a[i] - s->d.sim_a[i]) <= 1e-12 * scale))
+            return fail("ds_ecp_energy: the descriptor's cell differs from the system's simulation cell (entry %d: %.17g against %.17g)", i,
+                        e->D.a[i], s->d.sim_a[i]);
     return 0;
 }
 
@@ -662,30 +663,11 @@ int ds_ecp_create(const ds_ecp_desc* d, ds_ecp** out) {
     return 0;
 }
 
-// what ds_ecp_workspace_bytes and ds_ecp_energy refuse alike
-static int ecp_check(const ds_system* s, const ds_ecp* e, int64_t B, int64_t pair_capacity) {
-    if (B < 1) return fail("ds_ecp_energy: B must be >= 1 (got %lld)", (long long)B);
-    if (pair_capacity < 1) return fail("ds_ecp_energy: pair_capacity must be >= 1 (got %lld)", (long long)pair_capacity);
-    if (e->D.n_atoms != s->d.n_atoms_sim)
-        return fail("ds_ecp_energy: the descriptor has %d atoms, the system's simulation cell %d", e->D.n_atoms, s->d.n_atoms_sim);
-    double scale = 0.0;
-    for (int i = 0; i < 9; ++i) scale = std::max(scale, std::fabs(s->d.sim_a[i]));
-    for (int i = 0; i < 9; ++i)
-        if (!(std::fabs(e->D.a[i] - s->d.sim_a[i]) <= 1e-12 * scale))
-            return fail("ds_ecp_energy: the descriptor's cell differs from the system's simulation cell (entry %d: %.17g against %.17g)", i,
-                        e->D.a[i], s->d.sim_a[i]);
-    return 0;
-}
-
 int64_t ds_ecp_workspace_bytes(const ds_system* s, const ds_ecp* e, int64_t B, int64_t pair_capacity) {
     if (!s || !e) { fail("null argument"); return -1; }
     if (ecp_check(s, e, B, pair_capacity)) return -1;
-    // as many groups per chunk as ds_workspace_bytes gives the value chain of pair_capacity * n_quad walkers
     const int nq = e->D.n_quad;
-    const int64_t esz = s->dtype == 0 ? 8 : 4, total = pair_capacity * nq;
-    const int64_t fixed = ecp_bytes(s, B, pair_capacity, nq, 0), per = ecp_bytes(s, B, pair_capacity, nq, 1) - fixed;
-    const int64_t ng = std::min(groups_per_pass(total, esz, PassSize{0, (size_t)(per / esz)}, workspace_budget()), OB_MAX_GROUPS);
-    return ecp_bytes(s, B, pair_capacity, nq, ng);
+    return ecp_bytes(s, B, pair_capacity, nq, ecp_default_groups(s, B, pair_capacity, nq));
 }
 
 int ds_ecp_energy(ds_system* s, const ds_ecp* e, const void* params, const void* x, int64_t B, uint64_t philox_seed, uint64_t philox_offset,
@@ -696,8 +678,8 @@ int ds_ecp_energy(ds_system* s, const ds_ecp* e, const void* params, const void*
     if (!out_energy) return fail("ds_ecp_energy: out_energy is null, nothing to write");
     if (int rc = ecp_check(s, e, B, pair_capacity)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    return DS_BY_DTYPE(s->dtype, ecp_energy_impl, s, e, params, x, B, philox_seed, philox_offset, rotations, pair_capacity, out_energy,
-                       out_pairs, out_ratio, out_rotation, ws, ws_bytes, st);
+    return ecp_energy_forward(s, e, params, x, B, philox_seed, philox_offset, rotations, pair_capacity, out_energy, out_pairs, out_ratio,
+                              out_rotation, ws, ws_bytes, st, nullptr, nullptr);
 }
 
 int ds_energy_stats(ds_system* s, const void* ke, const void* ewald, int64_t B, double* out_stats, void* stream) {

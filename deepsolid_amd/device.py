@@ -579,21 +579,30 @@ class DeviceSystem:
         return dict(sums=sums, n_bad=n_bad, ratios=torch.view_as_complex(ratios) if ratios is not None else None,
                     walker=torch.view_as_complex(walker) if want_walker else None)
 
-    def dmc_state(self, x, weight=None):
+    def dmc_state(self, x, weight=None, ecp=False):
         """Fresh DMC walker state for `dmc_step(..., state_valid=False)`: dict of the six caller-owned device buffers (x is copied;
-        logabs, phase, drift and eloc are filled by the first call; weights are 1 or `weight`)."""
+        logabs, phase, drift and eloc are filled by the first call; weights are 1 or `weight`).  `ecp=True` adds the seventh, 'epp'
+        (B, 3) float64 = (E_loc, Re E_nl, Im E_nl), which `dmc_step(..., ecp=...)` needs; the six others remain a valid state of the
+        plain call."""
         x = self._check_x(x).clone()
         B = x.shape[0]
         f64 = dict(dtype=torch.float64, device=self.device)
         w = torch.ones(B, **f64) if weight is None else torch.as_tensor(weight).to(**f64).reshape(B).clone()
-        return dict(x=x, logabs=torch.zeros(B, dtype=self.dtype, device=self.device),
-                    phase=torch.zeros(B, 2, dtype=self.dtype, device=self.device), drift=torch.zeros_like(x),
-                    eloc=torch.zeros(B, **f64), weight=w)
+        state = dict(x=x, logabs=torch.zeros(B, dtype=self.dtype, device=self.device),
+                     phase=torch.zeros(B, 2, dtype=self.dtype, device=self.device), drift=torch.zeros_like(x),
+                     eloc=torch.zeros(B, **f64), weight=w)
+        if ecp:
+            state['epp'] = torch.zeros(B, 3, **f64)
+        return state
 
-    def _check_dmc_state(self, state):
+    def _check_dmc_state(self, state, ecp=False):
         B = state['x'].shape[0]
         shapes = dict(x=((B, 3 * self.n), self.dtype), logabs=((B,), self.dtype), phase=((B, 2), self.dtype),
                       drift=((B, 3 * self.n), self.dtype), eloc=((B,), torch.float64), weight=((B,), torch.float64))
+        if ecp or 'epp' in state:
+            if 'epp' not in state:
+                raise ValueError("DMC with a pseudopotential needs the state entry 'epp' (dmc_state(..., ecp=True))")
+            shapes['epp'] = ((B, 3), torch.float64)
         for k, (shape, dt) in shapes.items():
             t = state[k]
             if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape):
@@ -602,12 +611,27 @@ class DeviceSystem:
 
     def dmc_step(self, params, state, steps, tau, tau_eff=None, e_trial=0.0, e_ref=0.0, e_cut=0.0, node_mode=0, branch_every=1,
                  seed=0, offset=0, normals=None, uniforms=None, comb_uniforms=None, state_valid=True, want_parents=False,
-                 max_bytes=None):
+                 max_bytes=None, ecp=None, pair_capacity=None, rotations=None, want_pairs=False):
         """`ds_dmc_step`: `steps` fixed-phase DMC steps on the walker state IN PLACE (dict of x, logabs, phase, drift, eloc, weight:
         `dmc_state`), enqueued without a host synchronisation; the algorithm is stated in include/deepsolid_hip.h.  Noise from
         the in-kernel Philox stream (seed, offset) or replayed from `normals` (steps,B,3N), `uniforms` (steps,B) and
         `comb_uniforms` (steps,) float64 -- all three or none.  `max_bytes` caps the workspace: more chain chunks.
-        -> dict(stats (steps, 9) float64 device tensor, parents (steps, B) int32 with `want_parents`)."""
+        -> dict(stats (steps, 9) float64 device tensor, parents (steps, B) int32 with `want_parents`).
+
+        `ecp` (an `EcpTables` or a `pseudopotential.SemiLocalECP`, as in `ecp_energy`): `ds_dmc_step_ecp`, the locality
+        approximation; the state then has the seventh array 'epp'.  That call SYNCHRONISES the stream once per step, and once more
+        for an initialisation (the pair total of every pseudopotential evaluation).  `rotations` (steps + 1, B, 3, 3) float64
+        goes with the explicit noise: all four or none.  `pair_capacity` defaults to the hard bound B * N * (atoms whose species
+        has a non-local channel), which cannot overflow; where the pair records of that bound exceed `ECP_PAIR_BUDGET` bytes the
+        default is B * N, and on overflow the call is repeated once with the number the library reports, continuing from the
+        steps that were completed.  The dict gains ecp_stats (steps, 3) float64 = per step sum w E_loc, sum w Re E_nl, sum w Im E_nl,
+        pairs (steps + 1,) int64 with `want_pairs` (entry 0: the initialisation), and pair_capacity."""
+        if ecp is not None:
+            return self._dmc_step_ecp(params, state, int(steps), tau, tau_eff, e_trial, e_ref, e_cut, node_mode, branch_every, seed,
+                                      offset, normals, uniforms, comb_uniforms, state_valid, want_parents, max_bytes, ecp,
+                                      pair_capacity, rotations, want_pairs)
+        if rotations is not None or pair_capacity is not None or want_pairs:
+            raise ValueError('rotations, pair_capacity and want_pairs go with a pseudopotential (ecp=...)')
         B = self._check_dmc_state(state)
         steps = int(steps)
         p = self.pack_params(params)
@@ -629,6 +653,71 @@ class DeviceSystem:
             _ptr(parents), _ptr(ws), ws.numel(), _stream()), 'ds_dmc_step')
         return dict(stats=stats, parents=parents)
 
+    ECP_PAIR_BUDGET = 1 << 30              # bytes of pair records up to which dmc_step's default capacity is the hard bound
+
+    def _ecp_tables(self, ecp):
+        if not isinstance(ecp, EcpTables):
+            tables = ecp.__dict__.get('_ds_tables')
+            if tables is None or tables.device != self.device:
+                tables = ecp.__dict__['_ds_tables'] = EcpTables(ecp, device=self.device)
+            ecp = tables
+        return ecp
+
+    def _dmc_step_ecp(self, params, state, steps, tau, tau_eff, e_trial, e_ref, e_cut, node_mode, branch_every, seed, offset, normals,
+                      uniforms, comb_uniforms, state_valid, want_parents, max_bytes, ecp, pair_capacity, rotations, want_pairs):
+        import re
+        B = self._check_dmc_state(state, ecp=True)
+        ecp = self._ecp_tables(ecp)
+        p = self.pack_params(params)
+        given = [t is not None for t in (normals, uniforms, comb_uniforms, rotations)]
+        if all(given):
+            normals = normals.to(device=self.device, dtype=self.dtype).contiguous()
+            uniforms = uniforms.to(device=self.device, dtype=self.dtype).contiguous()
+            comb_uniforms = comb_uniforms.to(device=self.device, dtype=torch.float64).contiguous()
+            rotations = rotations.to(device=self.device, dtype=torch.float64).contiguous()
+            if tuple(normals.shape) != (steps, B, 3 * self.n) or tuple(uniforms.shape) != (steps, B) or \
+                    tuple(comb_uniforms.shape) != (steps,) or tuple(rotations.shape) != (steps + 1, B, 3, 3):
+                raise ValueError('explicit noise must be normals (steps, B, 3N), uniforms (steps, B), comb_uniforms (steps,) and '
+                                 'rotations (steps + 1, B, 3, 3)')
+        if pair_capacity is None:
+            src = ecp.ecp
+            n_nl = int(np.count_nonzero(np.asarray(src.n_l)[np.asarray(src.atom_species)] > 0))
+            cap = B * self.n * max(n_nl, 1)
+            if cap * (72 + 16 * ecp.n_quad) > self.ECP_PAIR_BUDGET:
+                cap = B * self.n
+        else:
+            cap = int(pair_capacity)
+        stats = torch.zeros(max(steps, 1), 9, dtype=torch.float64, device=self.device)
+        ecp_stats = torch.zeros(max(steps, 1), 3, dtype=torch.float64, device=self.device)
+        parents = torch.empty(max(steps, 1), B, dtype=torch.int32, device=self.device) if want_parents else None
+        pairs = torch.zeros(max(steps, 1) + 1, dtype=torch.int64, device=self.device) if want_pairs else None
+        done, valid = 0, bool(state_valid)
+        for attempt in range(2):
+            k, left = done, steps - done
+            ws = self._workspace('ds_dmc_ecp_workspace_bytes', ecp.handle, int(B), cap, max_bytes=max_bytes) \
+                if 1 <= B <= 2 ** 20 and cap >= 1 else self.workspace(1)         # (the library refuses such a B or capacity itself)
+            n_done = C.c_int(0)
+            rc = self.lib.ds_dmc_step_ecp(
+                self.handle, ecp.handle, _ptr(p), _ptr(state['x']), _ptr(state['logabs']), _ptr(state['phase']), _ptr(state['drift']),
+                _ptr(state['eloc']), _ptr(state['weight']), _ptr(state['epp']), B, left, float(tau),
+                float(tau if tau_eff is None else tau_eff), float(e_trial), float(e_ref), float(e_cut), int(node_mode), int(branch_every),
+                int(seed) & (2 ** 64 - 1), (int(offset) + k) & (2 ** 64 - 1), _ptr(normals[k:] if all(given) else normals),
+                _ptr(uniforms[k:] if all(given) else uniforms), _ptr(comb_uniforms[k:] if all(given) else comb_uniforms),
+                _ptr(rotations[k:] if all(given) else rotations), cap, int(valid), _ptr(stats[k:]), _ptr(ecp_stats[k:]),
+                _ptr(parents[k:] if parents is not None else None), _ptr(pairs[k:] if pairs is not None else None), C.byref(n_done),
+                _ptr(ws), ws.numel(), _stream())
+            if rc != 0 and attempt == 0 and pair_capacity is None:
+                m = re.search(r'pair capacity exceeded: the walkers have (\d+) pairs', self.lib.ds_last_error().decode())
+                # (the comb's schedule counts the steps of a call: a continuation keeps it only from a multiple of branch_every)
+                if m and (branch_every <= 1 or n_done.value % int(branch_every) == 0):
+                    cap = int(m.group(1))
+                    done += n_done.value
+                    valid = valid or done > 0
+                    continue
+            _lib.check(rc, 'ds_dmc_step_ecp')
+            break
+        return dict(stats=stats, parents=parents, ecp_stats=ecp_stats, pairs=pairs, pair_capacity=cap)
+
     def dmc_noise(self, B, steps, seed=0, offset=0):
         """`ds_dmc_noise`: what `dmc_step` draws in Philox mode for (seed, offset), as the arrays its explicit mode takes
         -> (normals (steps, B, 3N), uniforms (steps, B), comb_uniforms (steps,) float64)."""
@@ -640,9 +729,11 @@ class DeviceSystem:
         return nz, un, xi
 
     def dmc_branch(self, state, xi, want_parents=True):
-        """`ds_dmc_branch`: the fixed-population comb alone on a walker state, IN PLACE, with the given xi in [0, 1).
+        """`ds_dmc_branch`: the fixed-population comb alone on a walker state, IN PLACE, with the given xi in [0, 1).  A state with
+        the seventh array 'epp' has it gathered from the same parents.
         -> parents (B,) int32 device tensor (None without `want_parents`)."""
         B = self._check_dmc_state(state)
+        want_parents, asked = want_parents or 'epp' in state, want_parents
         need = int(self.lib.ds_dmc_branch_workspace_bytes(0 if self.dtype == torch.float64 else 1, self.n, B))
         if need < 0:
             need = 256                                     # (the library refuses such a B itself)
@@ -654,7 +745,9 @@ class DeviceSystem:
                                           _ptr(state['logabs']), _ptr(state['phase']), _ptr(state['drift']), _ptr(state['eloc']),
                                           _ptr(state['weight']), _ptr(parents), _ptr(self._ws), self._ws.numel(), _stream()),
                    'ds_dmc_branch')
-        return parents
+        if 'epp' in state:
+            state['epp'].copy_(state['epp'][parents.long()])        # (a skipped comb returns the identity)
+        return parents if asked else None
 
     def ecp_energy(self, params, x, ecp, seed=0, offset=0, rotations=None, pair_capacity=None, want_pairs=False, want_ratios=False,
                    want_rotations=False, max_bytes=None):
@@ -672,11 +765,7 @@ class DeviceSystem:
         import re
         x = self._check_x(x)
         B = x.shape[0]
-        if not isinstance(ecp, EcpTables):
-            tables = ecp.__dict__.get('_ds_tables')
-            if tables is None or tables.device != self.device:
-                tables = ecp.__dict__['_ds_tables'] = EcpTables(ecp, device=self.device)
-            ecp = tables
+        ecp = self._ecp_tables(ecp)
         p = self.pack_params(params)
         if rotations is not None:
             rotations = rotations.to(device=self.device, dtype=torch.float64).contiguous()

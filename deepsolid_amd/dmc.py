@@ -1,8 +1,10 @@
 """Fixed-phase diffusion Monte Carlo on the device: host bookkeeping around `ds_dmc_step` (csrc/ds_dmc.h; the algorithm is stated
 in include/deepsolid_hip.h and DESIGN.md section 19).  The reference has no DMC; the conventions are this project's own.
 
-`make_dmc_step` returns the block function (one C-ABI call per block of steps, no host synchronisation inside), `DmcState` holds
-the six walker arrays with the scalars a run carries between blocks (`save` / `load`: one .npz of numbers; a resumed run continues
+`make_dmc_step` returns the block function (one C-ABI call per block of steps; no host synchronisation inside WITHOUT a
+pseudopotential -- with one, `ds_dmc_step_ecp` synchronises the stream once per step and once more for the initialisation, to
+read the pair total of every pseudopotential evaluation), `DmcState` holds
+the six walker arrays (seven with a pseudopotential: 'epp') with the scalars a run carries between blocks (`save` / `load`: one .npz of numbers; a resumed run continues
 bit-identically), `reblock` is the blocking error bar of a correlated series.  The driver loop is `inference.run_dmc`.
 """
 import numpy as np
@@ -17,8 +19,8 @@ def default_e_cut(n_elec, tau):
 
 
 class DmcState:
-    """Walker state of a DMC run: `arrays` = dict of x, logabs, phase, drift, eloc, weight (device tensors, updated in place by
-    every block) and the scalars e_trial, e_ref, tau_eff, offset (the Philox offset of the next step), valid (False until the
+    """Walker state of a DMC run: `arrays` = dict of x, logabs, phase, drift, eloc, weight -- and epp (B, 3) float64 = (E_loc,
+    Re E_nl, Im E_nl) in a run with a pseudopotential -- (device tensors, updated in place by every block) and the scalars e_trial, e_ref, tau_eff, offset (the Philox offset of the next step), valid (False until the
     first block has filled logabs .. eloc from x)."""
 
     def __init__(self, arrays, e_trial=0.0, e_ref=0.0, tau_eff=0.0, offset=0, valid=False, sum_w=0.0, sum_we=0.0):
@@ -27,11 +29,11 @@ class DmcState:
         self.sum_w, self.sum_we = float(sum_w), float(sum_we)        # the running mixed estimate e_ref = sum_we / sum_w
 
     @classmethod
-    def fresh(cls, system, x, tau, e_trial, e_ref=None, weight=None):
-        return cls(system.dmc_state(x, weight), e_trial, e_trial if e_ref is None else e_ref, tau, 0, False)
+    def fresh(cls, system, x, tau, e_trial, e_ref=None, weight=None, ecp=False):
+        return cls(system.dmc_state(x, weight, ecp=True) if ecp else system.dmc_state(x, weight), e_trial, e_trial if e_ref is None else e_ref, tau, 0, False)
 
     def save(self, path):
-        """One .npz of numbers: the six arrays, e_trial, e_ref (with the two sums behind it), tau_eff and the Philox offset."""
+        """One .npz of numbers: the six arrays (and epp when the state has it), e_trial, e_ref (with the two sums behind it), tau_eff and the Philox offset."""
         np.savez(path, **{k: v.cpu().numpy() for k, v in self.arrays.items()}, e_trial=np.float64(self.e_trial),
                  e_ref=np.float64(self.e_ref), tau_eff=np.float64(self.tau_eff), offset=np.uint64(self.offset),
                  valid=np.int64(self.valid), sum_w=np.float64(self.sum_w), sum_we=np.float64(self.sum_we))
@@ -39,7 +41,8 @@ class DmcState:
     @classmethod
     def load(cls, path, device='cuda'):
         with np.load(path) as f:
-            arrays = {k: torch.as_tensor(f[k], device=device).contiguous() for k in ('x', 'logabs', 'phase', 'drift', 'eloc', 'weight')}
+            names = ('x', 'logabs', 'phase', 'drift', 'eloc', 'weight') + (('epp',) if 'epp' in f.files else ())
+            arrays = {k: torch.as_tensor(f[k], device=device).contiguous() for k in names}
             return cls(arrays, float(f['e_trial']), float(f['e_ref']), float(f['tau_eff']), int(f['offset']), bool(int(f['valid'])),
                        float(f['sum_w']), float(f['sum_we']))
 
@@ -47,11 +50,15 @@ class DmcState:
 def make_dmc_step(logdet_net, simulation_cell, tau, steps, e_cut=None, node_mode=0, branch_every=1, seed=0, pseudopotential=None):
     """-> block(params, state) -> stats (steps, 9) float64 device tensor: `steps` DMC steps on `state` (a `DmcState`) in place as ONE
     `ds_dmc_step` call, with the state's e_trial, e_ref and tau_eff; the state's Philox offset advances by `steps`.  `e_cut`
-    defaults to `default_e_cut`; 0 switches the clip off.  `seed`: the Philox seed (fold the rank into it)."""
-    if pseudopotential is not None:
-        raise NotImplementedError('DMC with a pseudopotential is not provided: ds_ecp_energy synchronises once per call and draws a '
-                                  'random quadrature rotation, and the choice between the locality approximation and T-moves is '
-                                  'a design of its own (DESIGN.md section 19)')
+    defaults to `default_e_cut`; 0 switches the clip off.  `seed`: the Philox seed (fold the rank into it).
+    `pseudopotential` (a `pseudopotential.SemiLocalECP`): the locality approximation, ONE `ds_dmc_step_ecp` call per block, which
+    synchronises the stream once per step (and once for the initialisation); the state needs 'epp' (`DmcState.fresh(...,
+    ecp=True)`), and the block's `ecp_stats` (steps, 3) = per step sum w E_loc, sum w Re E_nl, sum w Im E_nl stay on
+    `block.ecp_stats`.  Any other form of potential is refused."""
+    from .pseudopotential import SemiLocalECP
+    if pseudopotential is not None and not isinstance(pseudopotential, SemiLocalECP):
+        raise NotImplementedError('DMC with this form of pseudopotential is not provided: only a pseudopotential.SemiLocalECP in the '
+                                  'locality approximation is (no T-moves: DESIGN.md section 19)')
     system = logdet_net.apply.system
     tau = float(tau)
     e_cut = default_e_cut(system.n, tau) if e_cut is None else float(e_cut)
@@ -60,10 +67,12 @@ def make_dmc_step(logdet_net, simulation_cell, tau, steps, e_cut=None, node_mode
     def block(params, state):
         out = system.dmc_step(params, state.arrays, steps, tau, tau_eff=state.tau_eff, e_trial=state.e_trial, e_ref=state.e_ref,
                               e_cut=e_cut, node_mode=node_mode, branch_every=branch_every, seed=seed, offset=state.offset,
-                              state_valid=state.valid)
+                              state_valid=state.valid, **({} if pseudopotential is None else {'ecp': pseudopotential}))
         state.valid = True
         state.offset += steps
+        block.ecp_stats = out.get('ecp_stats')
         return out['stats']
+    block.ecp_stats = None
     block.system, block.e_cut, block.steps, block.branch_every = system, e_cut, int(steps), int(branch_every)
     return block
 

@@ -201,11 +201,16 @@ def run_dmc(slog_net, logdet_net, params, data, simulation_cell, blocks, steps_p
     end on a comb (all weights are then equal, so the unweighted accumulators give mixed estimates); they are refused when
     steps_per_block % branch_every != 0.  `state` (a `dmc.DmcState`, e.g. `DmcState.load`) resumes a run: no equilibration, and the
     same bits as the run that was not interrupted; with a `save_path` the state is written to <save_path>/dmc_state.npz on exit.
-    `pseudopotential` is refused (out of scope: see `dmc.make_dmc_step`)."""
+    `pseudopotential` (`pseudopotential.SemiLocalECP`): the locality approximation (`dmc.make_dmc_step`; each block then
+    synchronises once per step).  The VMC energy that seeds e_ref goes through `train.make_loss(..., pseudopotential=...)`;
+    rows and the CSV carry a 'pseudopotential' column: the mixed estimate sum w (E_loc + E_nl) / sum w of the block, complex, per
+    primitive cell, from the block's ecp_stats, which cross the ranks in the same packed all-reduce as the stats rows.  Any
+    other form of potential is refused (`dmc.make_dmc_step`)."""
     from . import constants, dmc
     accumulators = tuple(accumulators)
-    if pseudopotential is not None:
-        dmc.make_dmc_step(logdet_net, simulation_cell, tau, steps_per_block, pseudopotential=pseudopotential)
+    from .pseudopotential import SemiLocalECP
+    if pseudopotential is not None and not isinstance(pseudopotential, SemiLocalECP):
+        dmc.make_dmc_step(logdet_net, simulation_cell, tau, steps_per_block, pseudopotential=pseudopotential)      # (refuses it)
     if accumulators and (branch_every <= 0 or steps_per_block % branch_every != 0):
         raise ValueError('accumulators need blocks that end on a comb: steps_per_block must be a multiple of branch_every')
     system = logdet_net.apply.system
@@ -216,28 +221,37 @@ def run_dmc(slog_net, logdet_net, params, data, simulation_cell, blocks, steps_p
     if state is None:
         gen = _rank_generator(key, data.device)
         mcmc_step = qmc.make_mcmc_step(slog_net.apply, batch, latvec=simulation_cell.a, steps=mcmc_steps)
+        total_energy = None if pseudopotential is None else train.make_loss(logdet_net.apply, None, simulation_cell,
+                                                                            **_pseudopotential_kw(pseudopotential, key))
         for _ in range(burn_in):
             data, _ = mcmc_step(params, data, gen, float(move_width))
         series = []
         for _ in range(max(int(vmc_iterations), 1)):
             data, _ = mcmc_step(params, data, gen, float(move_width))
+            if total_energy is not None:
+                series.append(float(total_energy(params, data)[0]))        # (the loss is the mean over all ranks already)
+                continue
             ke, ew, _, _ = system.local_energy(params, data)
             mean = constants.pmean_if_pmap((ke[:, 0].double() + ew.double()).mean())
             series.append(float(mean))
         e_vmc, err_vmc, _ = dmc.reblock(series)
         info.update(vmc_energy=e_vmc / scale, vmc_error=err_vmc / scale, vmc_series=np.asarray(series) / scale)
-        state = dmc.DmcState.fresh(system, data, tau, e_vmc)
+        state = dmc.DmcState.fresh(system, data, tau, e_vmc, ecp=pseudopotential is not None)
     block_fn = dmc.make_dmc_step(logdet_net, simulation_cell, tau, steps_per_block, e_cut=e_cut, node_mode=node_mode,
-                                 branch_every=branch_every, seed=seed)
+                                 branch_every=branch_every, seed=seed, pseudopotential=pseudopotential)
     w_target = float(batch * max(1, constants.world_size()))
     rows = []
-    writer = Writer(stats_file_name, DMC_SCHEMA, save_path) if save_path else None
+    schema = DMC_SCHEMA + (['pseudopotential'] if pseudopotential is not None else [])
+    writer = Writer(stats_file_name, schema, save_path) if save_path else None
     if writer:
         writer.__enter__()
     try:
         for b in range(blocks):
             tau_eff, e_trial = state.tau_eff, state.e_trial
-            st = constants.psum_if_pmap(block_fn(params, state)).cpu().numpy()          # ONE packed all-reduce per block
+            st = block_fn(params, state)
+            if pseudopotential is not None:                # (the three ecp_stats columns ride behind the nine of the stats rows)
+                st = torch.cat([st, block_fn.ecp_stats], dim=1)
+            st = constants.psum_if_pmap(st).cpu().numpy()                               # ONE packed all-reduce per block
             w, we, we2 = st[:, 0].sum(), st[:, 1].sum(), st[:, 2].sum()
             energy = we / w
             state.sum_w, state.sum_we = state.sum_w + float(w), state.sum_we + float(we)
@@ -245,6 +259,8 @@ def run_dmc(slog_net, logdet_net, params, data, simulation_cell, blocks, steps_p
             row = {'block': b, 'energy': energy / scale, 'variance': (we2 / w - energy ** 2) / scale ** 2,
                    'acceptance': st[:, 3].sum() / (w_target * steps_per_block), 'tau_eff': tau_eff, 'e_trial': e_trial / scale,
                    'weight': float(st[-1, 0]), 'killed': int((w_target - st[combed, 8]).sum()) if branch_every > 0 else 0}
+            if pseudopotential is not None:
+                row['pseudopotential'] = complex(st[:, 9].sum() + st[:, 10].sum(), st[:, 11].sum()) / w / scale
             rows.append(row)
             if writer:
                 writer.write(b, **row)

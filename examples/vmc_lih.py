@@ -19,7 +19,8 @@ n_up n_dn pairs), through deepsolid_amd.estimator.SpinSquared, written to spin_s
 THIS cell) to the local energy of training and evaluation: the rows then carry its batch mean E_loc + E_nl.  The
 cell of this example is all-electron, so with a real potential the numbers mean nothing: the point is the call sequence);
 --dmc BLOCKS [--dmc-tau TAU]: after the evaluation, BLOCKS blocks of 20 steps of fixed-phase diffusion Monte Carlo at time step TAU
-(default 0.01) from the evaluation's walkers, through deepsolid_amd.inference.run_dmc; not with --ecp)"""
+(default 0.01) from the evaluation's walkers, through deepsolid_amd.inference.run_dmc; with --ecp in the locality
+approximation, the rows then carrying the mixed estimate of E_loc + E_nl)"""
 import os
 import sys
 
@@ -158,3 +159,6 @@ if dmc_blocks > 0:
     print('DMC:        E = %.4f +- %.4f Ha (tau = %g, %d blocks of 20 steps, the first quarter left out; acceptance %.4f, '
           'tau_eff %.5f, %d walkers killed)' % (e, err, dmc_tau, dmc_blocks, sum(r['acceptance'] for r in dmc_rows) / len(dmc_rows),
                                                 dmc_rows[-1]['tau_eff'], sum(r['killed'] for r in dmc_rows)))
+    if ecp is not None:
+        print('            locality approximation: mixed <E_loc + E_nl> = %.4f Ha'
+              % (sum(r['pseudopotential'].real for r in dmc_rows) / len(dmc_rows)))

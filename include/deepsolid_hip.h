@@ -618,10 +618,9 @@ int ds_ecp_energy(ds_system* sys, const ds_ecp* ecp, const void* params, const v
  * Refused with a ds_last_error message before any launch: null state pointers or out_stats; B < 1 or B > 2^20 (the chunk offsets
  * of the scan are kept in one workgroup's LDS); steps < 1; tau <= 0, tau_eff < 0 or a non-finite scalar; node_mode outside
  * {0, 1}; branch_every < 0; noise arrays given in part; a workspace below one chain chunk ("workspace too small").
- * Out of scope: pseudopotentials (ds_ecp_energy synchronises once per call and draws a rotation; locality approximation against
- * T-moves is a design of its own -- this call takes no ds_ecp and adds no ECP term), electron-by-electron moves, forward
- * walking and pure estimators, weighted accumulators, cross-rank walker exchange (ranks keep fixed populations with their own
- * total weights, which is unbiased).
+ * Out of scope: T-moves (ds_dmc_step_ecp below is the locality approximation; ds_dmc_step itself takes no ds_ecp and adds no ECP
+ * term), electron-by-electron moves, forward walking and pure estimators, weighted accumulators, cross-rank walker exchange
+ * (ranks keep fixed populations with their own total weights, which is unbiased).
  *
  * ds_dmc_branch is the comb of step 8 alone with a given xi in [0, 1); it needs no handle (dtype: 0 float64, else float32) and is
  * the code ds_dmc_step runs.  Workspace: ds_dmc_branch_workspace_bytes.  The caller's buffers may alias nothing else. */
@@ -631,6 +630,59 @@ int ds_dmc_step(ds_system* sys, const void* params, void* x, void* logabs, void*
                 int branch_every, uint64_t philox_seed, uint64_t philox_offset, const void* normals, const void* uniforms,
                 const double* comb_uniforms, int state_valid, double* out_stats, int32_t* out_parents, void* ws, int64_t ws_bytes,
                 void* stream);
+/* DMC with a semi-local pseudopotential in the LOCALITY APPROXIMATION: the branching energy is
+ *   E = ((Re E_kin + E_ewald) + E_loc) + Re E_nl,
+ * with E_loc and E_nl projected on the trial function exactly as ds_ecp_energy defines them.  No T-moves.
+ * ds_dmc_step_ecp takes every argument of ds_dmc_step, plus:
+ *   ecp             the descriptor's handle (ds_ecp_create)
+ *   pair_capacity   as in ds_ecp_energy, for ONE evaluation (all B walkers at one position each)
+ *   rotations       NULL, or (steps + 1, B, 3, 3) float64 [device]: slot 0 is for the initialisation (ignored when state_valid = 1),
+ *                   slot i + 1 for step i
+ *   epp             caller-owned state, (B, 3) float64 = (E_loc, Re E_nl, Im E_nl) at the walker's current position: the SEVENTH
+ *                   state array
+ *   out_ecp_stats   NULL, or (steps, 3) float64 [device]: per step sum w E_loc, sum w Re E_nl, sum w Im E_nl over the walkers of
+ *                   non-zero weight, taken at the same point as the out_stats row (after the weight update, before the comb) and in
+ *                   the same fixed order: partials per 256 consecutive walkers, then one pass in row order.  No floating-point atomics
+ *   out_pairs       NULL, or (steps + 1,) int64 [device]: the pair total of the initialisation (entry 0, untouched when
+ *                   state_valid = 1) and of every step's evaluation (entry i + 1)
+ *   steps_done      host pointer, may be NULL: receives the number of completed steps
+ * The algorithm is that of ds_dmc_step word for word, with three changes.
+ *   Initialisation (state_valid = 0).  The pseudopotential is evaluated at x exactly as ds_ecp_energy(x, philox_seed,
+ *     philox_offset) evaluates it.  eloc = ((what ds_dmc_step's initialisation computes) + E_loc) + Re E_nl, each addition rounded
+ *     in float64, in that order; epp is the triple.  A walker whose total is not finite gets weight 0.
+ *   Step i.  After the chain pass at x' the pseudopotential is evaluated at x' exactly as ds_ecp_energy(x', philox_seed,
+ *     philox_offset + 1 + i) evaluates it, and E' = ((Re ke' + ewald') + E_loc') + Re E_nl' in float64.  Everything downstream
+ *     (the finiteness test of step 4, the clip, the symmetric weight, the stats row, the comb) sees only E' and eloc.  A
+ *     non-finite ratio makes E' non-finite: the move is refused as non-finite and counted in column [6].  epp is selected with
+ *     the other rows on acceptance.
+ *   Comb.  epp is gathered from the same parents by one small kernel after the comb's own; a skipped comb leaves it untouched.
+ * The pseudopotential term never passes through the system's element type: the float64 triple goes to the acceptance kernel as it is.
+ * Rotations: Philox stream 4 of ds_ecp_energy with the counter philox_offset for the initialisation and philox_offset + 1 + i for
+ * step i (the move's noise is on streams 0-2).  With these counters `steps` steps in one call equal `steps` calls of one step
+ * with the offset advanced.  The explicit inputs (normals, uniforms, comb_uniforms, rotations) come all together or not at all.
+ * SYNCHRONISATION.  Every pseudopotential evaluation keeps ds_ecp_energy's one 8-byte read-back of the pair total: a call
+ * synchronises the stream `steps` times, plus once for an initialisation, and CANNOT be captured into a graph.
+ * Capacity.  The pair total of step i is checked before that step's acceptance kernel.  A total above pair_capacity fails the call
+ * with ds_ecp_energy's message, which carries the number needed; *steps_done is then the number of completed steps, the state
+ * is exactly that after those steps, and the out_stats rows of the completed steps are valid.  An overflow at the initialisation
+ * leaves all seven arrays untouched.
+ * Workspace: ds_dmc_ecp_workspace_bytes = the layout of ds_dmc_step followed by that of ds_ecp_energy for (B, pair_capacity).  A
+ * smaller one is split so: beside ONE chain walker the pseudopotential keeps room for up to 64 groups of 80 configurations (what
+ * ds_ecp_workspace_bytes provides at most); the chain's chunk then takes what fits; the groups follow from what is left, as
+ * ds_ecp_energy derives them.  Results are bit-identical for any split under the condition of ds_dmc_step and
+ * ds_ecp_energy.  The in-step evaluation is bit-identical to a ds_ecp_energy call on the same array with the same counter.
+ * Refused with a ds_last_error message before any launch: everything ds_dmc_step refuses; everything ds_ecp_energy refuses of a
+ * descriptor (NULL, atom count or cell differing from the system's) and pair_capacity < 1; epp NULL; philox_offset + steps >= 2^61;
+ * explicit inputs given in part; a workspace below one chain walker plus one 80-configuration group ("workspace too small").
+ * ds_dmc_step, ds_dmc_branch, ds_dmc_noise and ds_ecp_energy are unchanged.  ds_dmc_branch knows no epp: a caller gathers it from
+ * the parents that call returns. */
+int64_t ds_dmc_ecp_workspace_bytes(const ds_system* sys, const ds_ecp* ecp, int64_t B, int64_t pair_capacity);
+int ds_dmc_step_ecp(ds_system* sys, const ds_ecp* ecp, const void* params, void* x, void* logabs, void* phase, void* drift,
+                    double* eloc, double* weight, double* epp, int64_t B, int steps, double tau, double tau_eff, double e_trial,
+                    double e_ref, double e_cut, int node_mode, int branch_every, uint64_t philox_seed, uint64_t philox_offset,
+                    const void* normals, const void* uniforms, const double* comb_uniforms, const double* rotations,
+                    int64_t pair_capacity, int state_valid, double* out_stats, double* out_ecp_stats, int32_t* out_parents,
+                    int64_t* out_pairs, int* steps_done, void* ws, int64_t ws_bytes, void* stream);
 /* What a Philox-mode ds_dmc_step call of `steps` steps draws, written out in the layout of its explicit mode: normals
  * (steps, B, 3N) and uniforms (steps, B) of dtype T, comb_uniforms (steps,) float64 [device].  The normals are the device's own
  * Box-Muller values (a host model agrees with them to a few ulp, not to the bit), so a float64 call that replays these arrays

@@ -5,14 +5,18 @@
 Prints one JSON line: ms per DMC step with the comb on every step and without any, ms per `ds_local_energy`, ms per importance
 move, the ratio step / local_energy, `outside_chain` = 1 - local_energy / step (the share of a step that the chain pass does not
 account for: the kernels of ds_dmc.h, the gradient half of k_combine, launch gaps) and ms of the comb alone (`ds_dmc_branch`).
-usage: python tools/dmc_bench.py [--reps R] [--steps S] [--batch B] [--once]
-`--once`: one call and no timing -- the run to put under a kernel trace for the share of the k_dmc_* kernels."""
+usage: python tools/dmc_bench.py [--reps R] [--steps S] [--batch B] [--once] [--ecp [FILE.npz]] [--r-cut-nl R]
+`--once`: one call and no timing -- the run to put under a kernel trace for the share of the k_dmc_* kernels.
+`--ecp`: the cost of the locality approximation instead, one JSON line: (a) ms per `ds_dmc_step` step, (b) ms per stand-alone
+`ds_ecp_energy` call on the same walkers, (c) ms per `ds_dmc_step_ecp` step, and (c) / ((a) + (b)); all with the comb on every
+step.  The potential is the one saved in FILE.npz (`SemiLocalECP.save`, built for the bcc-Li cell) or, without a file, the
+synthetic species of tools/ecp_bench.py on all 8 atoms with the non-local cutoff `--r-cut-nl` (default 2.747 Bohr), N_q = 12."""
 import argparse
 import json
 import os
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path[:0] = [os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__))]
 import torch
 
 from deepsolid_amd import network, systems
@@ -30,6 +34,48 @@ def timed(fn, reps):
     return t0.elapsed_time(t1) / reps
 
 
+def bench_ecp(args, cell, sysd, params, x):
+    from deepsolid_amd.device import EcpTables
+    from deepsolid_amd.pseudopotential import SemiLocalECP
+    from ecp_bench import SPECIES
+    B, S = args.batch, args.steps
+    if args.ecp:
+        pot = SemiLocalECP.load(args.ecp, cell)
+    else:
+        pot = SemiLocalECP(cell, [dict(SPECIES, r_cut_loc=0.8 * args.r_cut_nl, r_cut_nl=args.r_cut_nl)], [0] * 8, n_quad=12)
+    ecp = EcpTables(pot)
+    plain, state = sysd.dmc_state(x), sysd.dmc_state(x, ecp=True)
+    sysd.dmc_step(params, plain, 1, args.tau, branch_every=0, state_valid=False)
+    first = sysd.dmc_step(params, state, 1, args.tau, branch_every=0, state_valid=False, ecp=ecp, want_pairs=True)
+    cap = first['pair_capacity']
+    e0 = float(state['eloc'][torch.isfinite(state['eloc'])].mean())
+    kw = dict(e_trial=e0, e_ref=e0, e_cut=0.2 * (sysd.n / args.tau) ** 0.5, branch_every=1)
+    offset = [10]
+
+    def step_ecp():
+        offset[0] += S
+        return sysd.dmc_step(params, state, S, args.tau, ecp=ecp, pair_capacity=cap, offset=offset[0], **kw)
+
+    def ecp_alone():
+        offset[0] += 1
+        return sysd.ecp_energy(params, x, ecp, offset=offset[0], pair_capacity=cap)
+    if args.once:                                      # (the run to put under a kernel trace: one call of each kind)
+        sysd.dmc_step(params, plain, S, args.tau, **kw)
+        ecp_alone()
+        step_ecp()
+        torch.cuda.synchronize()
+        return
+    ms_a = timed(lambda: sysd.dmc_step(params, plain, S, args.tau, **kw), args.reps) / S
+    ms_b = timed(ecp_alone, args.reps)
+    ms_c = timed(step_ecp, args.reps) / S
+    pairs = first['pairs'].cpu().numpy()
+    print(json.dumps({'case': 'bcc_li', 'electrons': sysd.n, 'B': B, 'steps_per_call': S, 'tau': args.tau, 'n_quad': pot.n_quad,
+                      'r_cut_nl': pot.r_cut_nl.tolist(), 'pair_capacity': cap, 'pairs_per_walker': float(pairs[0]) / B,
+                      'workspace_bytes': int(sysd.lib.ds_dmc_ecp_workspace_bytes(sysd.handle, ecp.handle, B, cap)),
+                      'dmc_step_ms': round(ms_a, 3), 'ecp_energy_ms': round(ms_b, 3), 'dmc_step_ecp_ms': round(ms_c, 3),
+                      'ratio_c_over_a_plus_b': round(ms_c / (ms_a + ms_b), 4), 'total_weight': float(state['weight'].sum())}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=3)
@@ -37,6 +83,8 @@ def main():
     ap.add_argument('--batch', type=int, default=4096)
     ap.add_argument('--tau', type=float, default=0.01)
     ap.add_argument('--once', action='store_true')
+    ap.add_argument('--ecp', nargs='?', const='', default=None)
+    ap.add_argument('--r-cut-nl', type=float, default=2.747)
     args = ap.parse_args()
     cell, klist = systems.build('bcc_li')
     net = network.make_solid_fermi_net(klist=klist, simulation_cell=cell, method_name='eval_logdet', **systems.DETNET_DEFAULTS)
@@ -44,6 +92,8 @@ def main():
     sysd = net.apply.system
     B, S = args.batch, args.steps
     x = torch.as_tensor(systems.synthetic_walkers(cell, B, seed=1234), device='cuda')
+    if args.ecp is not None:
+        return bench_ecp(args, cell, sysd, params, x)
     state = sysd.dmc_state(x)
     sysd.dmc_step(params, state, 1, args.tau, branch_every=0, state_valid=False)          # initialise once
     e0 = float(state['eloc'][torch.isfinite(state['eloc'])].mean())
