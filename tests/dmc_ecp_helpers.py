@@ -10,19 +10,19 @@ import dmc_helpers as dh
 import ecp_helpers as eh
 import sampler_helpers as sh
 
-NAME = 'lih'                       # the case of every test here: 4 electrons, 3-5 pairs per fixture walker at r_cut 2.18
-R_CUT = eh.CASES[NAME][0]
+NAME = 'lih'                       # the default case: 4 electrons, 3-5 pairs per fixture walker at r_cut 2.18
+R_CUT = eh.CASES[NAME][0]          # (every case's non-local cutoff is ecp_helpers.CASES[name][0])
 KEYS7 = ('x', 'logabs', 'phase', 'drift', 'eloc', 'weight', 'epp')
 
 
-def cell():
-    return sh.case(NAME)[1]
+def cell(name=NAME):
+    return sh.case(name)[1]
 
 
 @functools.lru_cache(maxsize=None)
-def potential(n_quad=12):
-    """The synthetic potential of ecp_helpers on the lih cell."""
-    return eh.make_ecp(cell(), R_CUT, n_quad)
+def potential(name=NAME, n_quad=12):
+    """The synthetic potential of ecp_helpers on the cell of case `name`, with that case's cutoff."""
+    return eh.make_ecp(cell(name), eh.CASES[name][0], n_quad)
 
 
 @functools.lru_cache(maxsize=None)
@@ -44,7 +44,7 @@ class DmcEcpOracle(dh.DmcOracle):
 
     def __init__(self, name, ecp, seed):
         super().__init__(name)
-        self.ecp, self.seed = ecp, seed
+        self.ecp, self.seed, self.r_cut = ecp, seed, eh.CASES[name][0]
         self._ecp_cache = {}
 
     def evaluate(self, x, counter=None):
@@ -70,7 +70,7 @@ class DmcEcpOracle(dh.DmcOracle):
         e_nl, scale = eh.energy(q, Wn, pl, B, nq)
         e_loc, mag, cnt = eh.local_energy(ecp, xs)
         r = eh.min_image(xs, ecp.atoms, ecp.a)[0][ok]
-        cut = min(float(np.abs(r - rc).min()) for rc in (R_CUT, eh.LOCAL_FRACTION * R_CUT)) if ok.any() else np.inf
+        cut = min(float(np.abs(r - rc).min()) for rc in (self.r_cut, eh.LOCAL_FRACTION * self.r_cut)) if ok.any() else np.inf
         bad = ~ok
         e_loc[bad], e_nl[bad] = np.nan, np.nan
         with np.errstate(invalid='ignore'):
@@ -164,35 +164,44 @@ def dh_eloc_tolerance(ke, aux):
         return (1e-8 * np.maximum(1.0, np.abs(ke)) + 1e-9) + tol_q() * aux['e_nl_scale'] + aux['e_loc_bound']
 
 
-# name -> (B, tau, steps, seed): the replay of the GPU suite.  The seed is from tools/find_dmc_ecp_seeds.py (oracle only).
-REPLAY = (12, 0.1, 2, 1)
+# case -> (B, tau, steps, seed): the replays of the GPU suite.  The seeds are from tools/find_dmc_ecp_seeds.py (oracle only); the
+# comments are what they gave.  lih is a real wavefunction (Im E_nl = 0 to rounding); the two others have a complex one.
+REPLAYS = {
+    'lih': (12, 0.1, 2, 1),
+    # 21 accepted, 3 rejected, 2 duplicated, min |A - log u| 7.4e-2, cutoff distance 7.6e-3, max |Im E_nl| 3.5
+    'lih_twist': (12, 0.1, 2, 1),
+    # 7 accepted, 5 rejected, 2 duplicated, min |A - log u| 0.23, cutoff distance 3.0e-3, max |Im E_nl| 11.3
+    'bcc_li': (6, 0.05, 2, 1),
+}
 
 
 @functools.lru_cache(maxsize=None)
-def replay_reference(seed=None):
-    """The model's run of the replay from state_valid = 0, comb every step, Philox offset 0; e_ref, e_trial and e_cut as
-    dmc_helpers.replay_reference chooses them, from the energies with the pseudopotential."""
-    B, tau, steps, sd = REPLAY
+def replay_reference(name=NAME, seed=None):
+    """The model's run of the replay of case `name` from state_valid = 0, comb every step, Philox offset 0; e_ref, e_trial and e_cut
+    as dmc_helpers.replay_reference chooses them, from the energies with the pseudopotential."""
+    B, tau, steps, sd = REPLAYS[name]
     sd = sd if seed is None else seed
-    ecp = potential()
-    orc = DmcEcpOracle(NAME, ecp, sd)
-    x0 = dh.start_walkers(NAME, B, sd)
+    ecp = potential(name)
+    orc = DmcEcpOracle(name, ecp, sd)
+    x0 = dh.start_walkers(name, B, sd)
     el0 = orc.evaluate(x0, 0)[3]
     e_ref = float(np.round(np.mean(el0), 3))
     e_cut = 0.05 * np.sqrt(orc.n / tau)
     w0 = dh.preset_weights('ramp', B)
     r = run_model(orc, x0, w0, steps, tau, tau, e_ref, e_ref, e_cut, 1, sd, 0)
     r['tau_eff'] = tau
-    r.update(x0=x0, w0=w0, e_ref=e_ref, e_cut=e_cut, tau=tau, seed=sd, B=B, ecp=ecp, cond=conditions(r))
+    r.update(x0=x0, w0=w0, e_ref=e_ref, e_cut=e_cut, tau=tau, seed=sd, B=B, ecp=ecp, name=name, cond=conditions(r, name))
     return r
 
 
-def conditions(r):
-    """`dmc_helpers.conditions` plus: the smallest distance of any visited position's pair from a cutoff, the smallest distance of
-    a clipped-or-not decision from a clip edge in units of the energy tolerance, and the weight tolerance with the pseudopotential's
-    share of the energy tolerance."""
+def conditions(r, name=NAME):
+    """`dmc_helpers.conditions` plus: the smallest distance of any visited position's pair from a cutoff of case `name`, the smallest
+    distance of a clipped-or-not decision from a clip edge in units of the energy tolerance, the weight tolerance with the
+    pseudopotential's share of the energy tolerance, and the largest |Im E_nl| over the start walkers and the proposals."""
     c = dh.conditions(r)
     st = r['steps']
+    c['name'], c['r_cut'] = name, eh.CASES[name][0]
+    c['im_e_nl'] = float(max(np.nanmax(np.abs(e[:, 2])) for e in [r['state0']['epp']] + [s['epp_prop'] for s in st]))
     c['cutoff_distance'] = min([r['aux0']['cutoff_distance']] + [s['aux']['cutoff_distance'] for s in st])
     c['edge'] = min(s['edge'] for s in st)
     tol_e = max(float(np.nanmax(s['tol_prop'])) for s in st)

@@ -1,7 +1,8 @@
 """GPU tests of DMC with a semi-local pseudopotential in the locality approximation: `ds_dmc_step_ecp` (csrc/ds_dmc.h, the algorithm
 as include/deepsolid_hip.h states it) against its parts -- `ds_dmc_step`, `ds_ecp_energy`, `ds_local_energy`, `ds_dmc_branch` --
 bit for bit, against the numpy model of dmc_ecp_helpers.py on the CPU oracle, its refusals, the pair capacity, and
-`inference.run_dmc(..., pseudopotential=...)` end to end.  All on the lih case with the synthetic potential of ecp_helpers."""
+`inference.run_dmc(..., pseudopotential=...)` end to end.  With the synthetic potential of ecp_helpers, on the lih case and, where a
+test names them, on lih_twist and bcc_li, whose wavefunctions are complex: Im E_nl, the third column of epp, is live only there."""
 import ctypes as C
 import re
 
@@ -11,6 +12,7 @@ import torch
 
 import dmc_ecp_helpers as deh
 import dmc_helpers as dh
+import dmc_parts_helpers as ph
 import ecp_helpers as eh
 import sampler_helpers as sh
 from test_gpu_dmc import KEYS, TOL_X, assert_row_close, bits, clone, cu, dev_params, phase_np, same_bits, system
@@ -28,8 +30,20 @@ def tables(sysd, ecp):
     return sysd._ecp_tables(ecp)
 
 
-def start(B, seed, dtype=torch.float64):
-    return cu(dh.start_walkers(NAME, B, seed), dtype)
+def start(B, seed, dtype=torch.float64, name=NAME):
+    return cu(dh.start_walkers(name, B, seed), dtype)
+
+
+def ecp_row_bits(row, st):
+    """A row of out_ecp_stats against dmc_parts_helpers.ecp_stats_from_state of the state it was formed from: bit for bit."""
+    want = ph.ecp_stats_from_state(st['weight'].cpu().numpy(), st['epp'].cpu().numpy())
+    got = row.cpu().numpy()
+    return np.array_equal(got.view(np.int64), want.view(np.int64)), (got, want)
+
+
+# (case, B) of the parts tests: B = 37 is neither a multiple of the wave nor of the four-wave workgroup; bcc_li has 24 electrons and
+# about 15 pairs per walker
+PARTS = [('lih', B37), ('lih_twist', B37), ('bcc_li', 5)]
 
 
 def epp_of(e):
@@ -43,8 +57,9 @@ def plus_ecp(base, e):
 
 
 def raw_step(sysd, ecp, dp, st, steps=1, tau=0.1, seed=0, offset=0, cap=None, state_valid=1, stats=None, ecp_stats=None, skip=None,
-             ecp_handle='tables', branch_every=0, ws_bytes=None):
-    """The raw entry on a seven-array state, Philox mode -> (return code, steps_done, message)."""
+             ecp_handle='tables', branch_every=0, ws_bytes=None, noise=(None, None, None, None)):
+    """The raw entry on a seven-array state, Philox mode or with `noise` = (normals, uniforms, comb_uniforms, rotations) float64
+    -> (return code, steps_done, message)."""
     from deepsolid_amd.device import _ptr, _stream
     B = st['x'].shape[0]
     t = tables(sysd, ecp)
@@ -53,24 +68,26 @@ def raw_step(sysd, ecp, dp, st, steps=1, tau=0.1, seed=0, offset=0, cap=None, st
     done = C.c_int(-1)
     ptrs = [None if k == skip else _ptr(st[k]) for k in KEYS7]
     rc = sysd.lib.ds_dmc_step_ecp(sysd.handle, t.handle if ecp_handle == 'tables' else ecp_handle, _ptr(sysd.pack_params(dp)), *ptrs, B,
-                                  steps, tau, tau, KW['e_trial'], KW['e_ref'], KW['e_cut'], 0, branch_every, seed, offset, None, None, None,
-                                  None, cap, state_valid, _ptr(stats if stats is not None else torch.zeros(steps, 9, **F64)),
+                                  steps, tau, tau, KW['e_trial'], KW['e_ref'], KW['e_cut'], 0, branch_every, seed, offset,
+                                  *[_ptr(t) for t in noise], cap, state_valid, _ptr(stats if stats is not None else torch.zeros(steps, 9, **F64)),
                                   _ptr(ecp_stats), None, None, C.byref(done), _ptr(ws), ws.numel() if ws_bytes is None else ws_bytes,
                                   _stream())
     return rc, done.value, sysd.lib.ds_last_error().decode()
 
 
 # ------------------------------------------------------------------------------------------ 1. the initialisation and its parts
-@pytest.mark.parametrize('dtype', [torch.float64, torch.float32])
-def test_initialisation_has_the_bits_of_its_parts(dtype):
+@pytest.mark.parametrize('name, B37, dtype', [pytest.param(n, b, torch.float64, id=f'{n}-{b}-float64') for n, b in PARTS] +
+                         [pytest.param(n, b, torch.float32, id=f'{n}-{b}-float32') for n, b in (PARTS[0], PARTS[2])])
+def test_initialisation_has_the_bits_of_its_parts(name, B37, dtype):
     """state_valid = 0: eloc = ((the plain initialisation) + E_loc) + Re E_nl of ds_ecp_energy(x, seed, offset), epp = its out_energy,
     out_pairs[0] = its pair total.  A call always takes a step, so the initial state is read off a step whose proposals are all
     refused as non-finite (NaN normals) at tau_eff = 0, as test_gpu_dmc.py reads it; the rotations of that explicit call are the
-    ones the Philox-mode ds_ecp_energy drew.  A Philox-mode call then shows the same initial rows on the walkers it rejects."""
-    sysd, dp = system(NAME, dtype)
-    ecp = deh.potential()
+    ones the Philox-mode ds_ecp_energy drew.  A Philox-mode call then shows the same initial rows on the walkers it rejects.
+    Off lih the third column of epp is live; everywhere the out_ecp_stats row has the bits of the tree of dmc_parts_helpers."""
+    sysd, dp = system(name, dtype)
+    ecp = deh.potential(name)
     seed, off = 11, 5
-    x0 = start(B37, 4, dtype)
+    x0 = start(B37, 4, dtype, name)
     e = sysd.ecp_energy(dp, x0, ecp, seed=seed, offset=off, want_pairs=True, want_rotations=True)
     rot = torch.stack([e['rotations'], e['rotations']])
     nan = torch.full((1, B37, 3 * sysd.n), float('nan'), dtype=dtype, device='cuda')
@@ -85,6 +102,9 @@ def test_initialisation_has_the_bits_of_its_parts(dtype):
     assert torch.equal(bits(st['epp']), bits(epp_of(e)))
     assert int(out['pairs'][0]) == int(e['pairs'].sum()) > 0 and int(out['pairs'][1]) == 0
     assert bool((e['e_nl'].abs() > 0).any()) and bool((e['e_loc'] != 0).any())
+    assert name == NAME or bool((st['epp'][:, 2] != 0).any())
+    same, rows = ecp_row_bits(out['ecp_stats'][0], st)
+    assert same, rows
     # Philox mode: the rejected walkers still show the initialisation
     st2 = sysd.dmc_state(x0, ecp=True)
     out2 = sysd.dmc_step(dp, st2, 1, 0.3, branch_every=0, state_valid=False, ecp=ecp, seed=seed, offset=off, want_pairs=True, **KW)
@@ -94,14 +114,15 @@ def test_initialisation_has_the_bits_of_its_parts(dtype):
 
 
 # ------------------------------------------------------------------------------------------ 2. one forced-accept step
-def test_a_forced_accept_step_equals_the_composition():
+@pytest.mark.parametrize('name, B37', PARTS)
+def test_a_forced_accept_step_equals_the_composition(name, B37):
     """Explicit noise from ds_dmc_noise with the uniforms replaced by 2^-60 (every finite proposal is accepted), rotations replayed
     for the counters o and o + 1, no comb: afterwards epp is ds_ecp_energy(x_after, rotations[1]) bit for bit -- the same call on
     the same array -- and eloc is Re ke + ewald of ds_local_energy(x_after) plus the two terms in the stated order."""
-    sysd, dp = system(NAME)
-    ecp = deh.potential()
+    sysd, dp = system(name)
+    ecp = deh.potential(name)
     seed, o = 7, 20
-    x0 = start(B37, 2)
+    x0 = start(B37, 2, name=name)
     nz, un, xi = sysd.dmc_noise(B37, 1, seed, o)
     un = torch.full_like(un, 2.0 ** -60)
     rot = cu(np.stack([eh.replay_rotations(seed, o, B37), eh.replay_rotations(seed, o + 1, B37)]))
@@ -119,18 +140,25 @@ def test_a_forced_accept_step_equals_the_composition():
     want = (st['weight'][:, None] * st['epp']).sum(0).cpu().numpy()
     mag = (st['weight'][:, None] * st['epp']).abs().sum(0).cpu().numpy()
     assert (np.abs(out['ecp_stats'].cpu().numpy()[0] - want) <= B37 * eh.EPS * mag).all()
+    # ... and to the bit in the order the kernels add them; off lih the third column is live
+    same, rows = ecp_row_bits(out['ecp_stats'][0], st)
+    assert same, rows
+    assert name == NAME or bool((st['epp'][:, 2] != 0).any())
 
 
 # ------------------------------------------------------------------------------------------ 3. replay against the model
-def test_replay_against_the_model():
-    """B = 12, 2 steps, tau = 0.1, comb every step, Philox mode from state_valid = 0 against dmc_ecp_helpers.run_model on the CPU
-    oracle: decisions, parents and the integer columns are equal; positions, log|psi|, phase and drift within the tolerances of
-    test_gpu_dmc.py; eloc within eloc_bound(ke) + TOL_Q e_nl_scale + the E_loc bound; weights, rows and ecp_stats within what
-    those imply."""
-    ref = deh.replay_reference()
+@pytest.mark.parametrize('name', list(deh.REPLAYS))
+def test_replay_against_the_model(name):
+    """The replays of dmc_ecp_helpers.REPLAYS (lih: B = 12, 2 steps, tau = 0.1), comb every step, Philox mode from state_valid = 0
+    against dmc_ecp_helpers.run_model on the CPU oracle: decisions, parents and the integer columns are equal; positions, log|psi|,
+    phase and drift within the tolerances of test_gpu_dmc.py; eloc within eloc_bound(ke) + TOL_Q e_nl_scale + the E_loc bound;
+    weights, rows and ecp_stats within what those imply.  lih_twist and bcc_li have a complex wavefunction: the third column of epp
+    and of ecp_stats is compared against a model value that is not zero."""
+    ref = deh.replay_reference(name)
     deh.assert_conditions(ref['cond'])
-    B, tau, steps, seed = deh.REPLAY
-    sysd, dp = system(NAME)
+    assert name == NAME or ref['cond']['im_e_nl'] > 0
+    B, tau, steps, seed = deh.REPLAYS[name]
+    sysd, dp = system(name)
     kw = dict(e_trial=ref['e_ref'], e_ref=ref['e_ref'], e_cut=ref['e_cut'], seed=seed, ecp=ref['ecp'])
     st = sysd.dmc_state(cu(ref['x0']), cu(ref['w0']), ecp=True)
     out = sysd.dmc_step(dp, st, steps, tau, branch_every=1, offset=0, state_valid=False, want_parents=True, want_pairs=True, **kw)
@@ -309,6 +337,136 @@ def test_capacity_overflow_fails_before_the_acceptance_and_keeps_the_state():
     torch.cuda.synchronize()
     assert rc != 0 and done == 0 and f'the walkers have {p0} pairs' in msg
     assert same_bits(before, fresh, KEYS7) == []
+
+
+# ------------------------------------------------------------------------------------------ 7b. two stats groups
+def test_two_stats_groups_with_a_pseudopotential():
+    """lih, B = 300 (two rows of stats partials, the second of 44 walkers; two blocks of k_dmc_gather_epp), 2 steps in Philox mode
+    with the comb every step, against the same steps taken one by one without the fused comb and `dmc_branch` after each: every
+    ecp_stats row has the bits of dmc_parts_helpers.ecp_stats_from_state of the state before that step's comb, epp after the comb
+    is before[parents], and stats, parents and pairs agree between the two paths."""
+    sysd, dp = system(NAME)
+    ecp = deh.potential()
+    B, steps, tau, seed, o = 300, 2, 0.1, 3, 9
+    x0, w0 = start(B, 3), cu(dh.preset_weights('ramp', B))
+    kw = dict(seed=seed, ecp=ecp, want_parents=True, want_pairs=True, **KW)
+    fused, split = sysd.dmc_state(x0, w0, ecp=True), sysd.dmc_state(x0, w0, ecp=True)
+    rf = sysd.dmc_step(dp, fused, steps, tau, offset=o, state_valid=False, branch_every=1, **kw)
+    pairs = []
+    for i in range(steps):
+        r = sysd.dmc_step(dp, split, 1, tau, offset=o + i, state_valid=i > 0, branch_every=0, **kw)
+        before = clone(split)
+        for row in (rf['ecp_stats'][i], r['ecp_stats'][0]):
+            same, rows = ecp_row_bits(row, before)
+            assert same, (i, rows)
+        xi = float(sysd.dmc_noise(B, 1, seed, o + i)[2][0])
+        par = sysd.dmc_branch(split, xi)
+        assert torch.equal(par, rf['parents'][i]) and len(torch.unique(par)) < B
+        assert torch.equal(bits(split['epp']), bits(before['epp'][par.long()]))
+        assert torch.equal(bits(r['stats'][0, :8]), bits(rf['stats'][i, :8])) and float(r['stats'][0, 8]) == B
+        assert float(rf['stats'][i, 8]) == len(torch.unique(par))
+        pairs += r['pairs'].tolist() if i == 0 else r['pairs'].tolist()[1:]
+    assert same_bits(fused, split, KEYS7) == [] and pairs == rf['pairs'].tolist()
+    assert 0 < float(rf['stats'][:, 3].sum()) < steps * B and bool((rf['ecp_stats'][:, :2] != 0).all())
+
+
+# ------------------------------------------------------------------------------------------ 7c. the wrapper's continuation
+def midpoint_walkers():
+    """The three walkers of test_gpu_ecp.test_wrapper_retries_once_with_the_needed_capacity: all four electrons near the midpoint of
+    Li and H, 8 pairs each, 24 > B N = 12."""
+    ecp = deh.potential()
+    rng = np.random.default_rng(4)
+    mid = np.asarray([0.5 * ecp.atoms[1][0], 0.0, 0.0])
+    x = (mid[None, None, :] + rng.uniform(-0.15, 0.15, (3, 4, 3))).reshape(3, 12)
+    assert eh.pair_list(ecp, x)['counts'].tolist() == [8, 8, 8]
+    return x
+
+
+def assert_same_call(a, ra, b, rb):
+    assert same_bits(a, b, KEYS7) == []
+    for k in ('stats', 'ecp_stats'):
+        assert torch.equal(bits(ra[k]), bits(rb[k])), k
+    assert torch.equal(ra['parents'], rb['parents']) and torch.equal(ra['pairs'], rb['pairs'])
+
+
+@pytest.mark.parametrize('mode', ['philox', 'explicit'])
+def test_default_capacity_overflow_at_the_initialisation_is_retried(monkeypatch, mode):
+    """With the pair budget at 0 the default capacity is B N = 12; the midpoint walkers have 24 pairs, so the initialisation overflows:
+    the wrapper repeats the whole call (nothing was done) with the capacity the message names, and arrays and outputs have the bits
+    of a call that was given it -- in Philox mode with the same offset, in explicit mode with the same rotations."""
+    sysd, dp = system(NAME)
+    ecp = deh.potential()
+    monkeypatch.setattr(sysd, 'ECP_PAIR_BUDGET', 0)
+    x0 = cu(midpoint_walkers())
+    B, steps, tau, seed, o = 3, 2, 0.01, 5, 40
+    kw = dict(seed=seed, offset=o, branch_every=1, state_valid=False, ecp=ecp, want_parents=True, want_pairs=True, **KW)
+    if mode == 'explicit':
+        nz, un, xi = sysd.dmc_noise(B, steps, seed + 1, 3)
+        kw.update(normals=nz, uniforms=un, comb_uniforms=xi, rotations=cu(np.stack([eh.replay_rotations(seed, 7 + j, B) for j in range(steps + 1)])))
+    a, b = sysd.dmc_state(x0, ecp=True), sysd.dmc_state(x0, ecp=True)
+    ra = sysd.dmc_step(dp, a, steps, tau, **kw)
+    rb = sysd.dmc_step(dp, b, steps, tau, pair_capacity=24, **kw)
+    assert ra['pair_capacity'] == 24 and rb['pair_capacity'] == 24 and int(ra['pairs'][0]) == 24
+    assert_same_call(a, ra, b, rb)
+    assert bool((a['x'] != x0).any()) and bool(torch.isfinite(ra['stats']).all())
+
+
+def overflow_inside(sysd, dp, ecp, branch_every):
+    """B = 3 on the lih fixture walkers 2, 3, 4 (11 pairs, every electron-ion distance at least 0.5 Bohr from the non-local cutoff; a
+    drift move is shorter than sqrt(2 tau) = 0.14), tau = 0.01, two steps of explicit noise.  Step 0 has zero normals: the pair total
+    stays 11 whether or not it accepts.  Step 1's normals are chi = (target - x_1 - tau vbar_1) / sqrt(tau) with (x_1, drift_1) read
+    off a clone that took step 0 alone with capacity 24 and target the midpoint walkers: its proposal has 24 pairs.
+    -> (start state, noise dict, the step-0 clone)."""
+    B, tau, seed, o = 3, 0.01, 5, 40
+    x0 = np.asarray(sh.case(NAME)[0]['x'], dtype=np.float64)[2:5]
+    r = eh.min_image(x0, ecp.atoms, ecp.a)[0]
+    assert eh.pair_list(ecp, x0)['counts'].sum() == 11 and np.abs(r - deh.R_CUT).min() >= 0.5
+    rot = cu(np.stack([eh.replay_rotations(seed, o + j, B) for j in range(3)]))
+    un, xi = torch.full((2, B), 0.5, **F64), cu([0.3, 0.6])
+    nz = torch.zeros(2, B, 3 * sysd.n, **F64)
+    first = sysd.dmc_state(cu(x0), ecp=True)
+    sysd.dmc_step(dp, first, 1, tau, branch_every=1 if branch_every == 1 else 0, state_valid=False, ecp=ecp, pair_capacity=24,
+                  normals=nz[:1], uniforms=un[:1], comb_uniforms=xi[:1], rotations=rot[:2], **KW)
+    x1, d1 = first['x'].cpu().numpy(), first['drift'].cpu().numpy()
+    nz[1] = cu((midpoint_walkers() - x1 - tau * dh.limited(d1, tau)) / np.sqrt(tau))
+    return sysd.dmc_state(cu(x0), ecp=True), dict(normals=nz, uniforms=un, comb_uniforms=xi, rotations=rot), first
+
+
+def test_default_capacity_overflow_inside_the_call_continues_from_the_completed_steps(monkeypatch):
+    """The second step's proposal overflows the default capacity of 12: the wrapper continues from the one completed step -- offset,
+    noise, rotations and outputs advanced by one, state_valid set -- and everything has the bits of the call given capacity 24.
+    The raw entry with capacity 12 stops with steps_done = 1, the state that of the step-0 clone and row 1 of the stats untouched."""
+    sysd, dp = system(NAME)
+    ecp = deh.potential()
+    monkeypatch.setattr(sysd, 'ECP_PAIR_BUDGET', 0)
+    tau, seed, o = 0.01, 5, 40
+    st, noise, first = overflow_inside(sysd, dp, ecp, 1)
+    kw = dict(seed=seed, offset=o, branch_every=1, state_valid=False, ecp=ecp, want_parents=True, want_pairs=True, **noise, **KW)
+    a, b, c = clone(st), clone(st), clone(st)
+    ra = sysd.dmc_step(dp, a, 2, tau, **kw)
+    rb = sysd.dmc_step(dp, b, 2, tau, pair_capacity=24, **kw)
+    assert ra['pair_capacity'] == 24 and ra['pairs'].tolist() == [11, 11, 24] and rb['pairs'].tolist() == [11, 11, 24]
+    assert_same_call(a, ra, b, rb)
+    stats = torch.full((2, 9), -7.0, **F64)
+    rc, done, msg = raw_step(sysd, ecp, dp, c, steps=2, tau=tau, seed=seed, offset=o, cap=12, state_valid=0, stats=stats, branch_every=1,
+                             noise=tuple(noise[k] for k in ('normals', 'uniforms', 'comb_uniforms', 'rotations')))
+    torch.cuda.synchronize()
+    assert rc != 0 and done == 1 and 'pair capacity exceeded' in msg and 'the walkers have 24 pairs' in msg
+    assert same_bits(first, c, KEYS7) == []
+    assert bool((stats[1] == -7.0).all()) and torch.equal(bits(stats[0]), bits(rb['stats'][0]))
+
+
+def test_no_continuation_off_the_combs_schedule(monkeypatch):
+    """branch_every = 2: a continuation from one completed step would shift the comb's schedule, so the overflow is raised, and the
+    state is that after the one completed step."""
+    sysd, dp = system(NAME)
+    ecp = deh.potential()
+    monkeypatch.setattr(sysd, 'ECP_PAIR_BUDGET', 0)
+    st, noise, first = overflow_inside(sysd, dp, ecp, 2)
+    with pytest.raises(RuntimeError, match='pair capacity exceeded: the walkers have 24 pairs'):
+        sysd.dmc_step(dp, st, 2, 0.01, seed=5, offset=40, branch_every=2, state_valid=False, ecp=ecp, **noise, **KW)
+    torch.cuda.synchronize()
+    assert same_bits(first, st, KEYS7) == [] and bool((st['eloc'] != 0).all())
 
 
 # ------------------------------------------------------------------------------------------ 8. non-finite input

@@ -4,7 +4,7 @@ the replay fixture of tests/test_gpu_dmc_ecp.py for a range of seeds and print w
 find_dmc_seeds.py, the smallest distance of a pair from a cutoff over all visited positions, the smallest distance of an energy
 from a clip edge in units of its tolerance, and whether it meets the conditions the tests assert.
 
-    python tools/find_dmc_ecp_seeds.py [--seeds 1 2 3]
+    python tools/find_dmc_ecp_seeds.py [--case lih_twist] [--seeds 1 2 3]
 """
 import argparse
 import os
@@ -20,10 +20,11 @@ import dmc_ecp_helpers as deh  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--seeds', type=int, nargs='*', default=[1, 2, 3])
+    ap.add_argument('--case', default=deh.NAME, choices=sorted(deh.REPLAYS), help='the replay of dmc_ecp_helpers.REPLAYS')
     a = ap.parse_args()
     for seed in a.seeds:
         t0 = time.time()
-        c = deh.replay_reference(seed)['cond']
+        c = deh.replay_reference(a.case, seed)['cond']
         try:
             deh.assert_conditions(c)
             ok = 'meets the conditions'
