@@ -128,6 +128,10 @@ SIGNATURES = {
     'ds_dmc_step_ecp': (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int, C.c_double, C.c_double,
                                  C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _VP, _VP, _VP, _VP,
                                  C.c_int64, C.c_int, _VP, _VP, _VP, _VP, C.POINTER(C.c_int), _VP, C.c_int64, _VP]),
+    'ds_dmc_tmove_workspace_bytes': (C.c_int64, [_VP, _VP, C.c_int64, C.c_int64]),
+    'ds_dmc_step_tmove': (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int, C.c_double, C.c_double,
+                                   C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _VP, _VP, _VP, _VP, _VP,
+                                   C.c_int64, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_int), _VP, C.c_int64, _VP]),
     'ds_dmc_noise': (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, _VP, _VP, _VP, _VP]),
     'ds_dmc_branch_workspace_bytes':(C.c_int64, [C.c_int, C.c_int, C.c_int64]),
     'ds_dmc_branch': (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),

@@ -9,7 +9,8 @@
 //   k_dmc_stats_final  adds the rows in workgroup order: one row of out_stats
 // With a pseudopotential (ds_dmc_step_ecp, locality approximation) ds_ecp_energy's launches follow the chain pass at x', the ECP
 // instances of k_dmc_init / k_dmc_accept take its float64 triple, k_dmc_ecp_stats / k_dmc_ecp_stats_final form the row of
-// out_ecp_stats, and k_dmc_gather_epp follows the comb.
+// out_ecp_stats, and k_dmc_gather_epp follows the comb.  With T-moves (ds_dmc_step_tmove) the pseudopotential is evaluated after
+// the decision: the kernels at the end of this file.
 // and on a branching step the comb (k_dmc_scan_chunks, k_dmc_scan_offsets, k_dmc_select, k_dmc_gather, k_dmc_copy_back).
 //
 // Prefix sums of the weights, the order the numpy model reproduces bit for bit (DMC_CHUNK = 256):
@@ -417,6 +418,149 @@ __global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_copy_back(long long B, i
         logabs[k] = bla[k]; phase[2 * k] = bph[2 * k]; phase[2 * k + 1] = bph[2 * k + 1]; eloc[k] = bel[k];
         weight[k] = tot[1];
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ T-moves
+// ds_dmc_step_tmove evaluates the pseudopotential AFTER the decision, at the position the walker then has, so k_dmc_accept splits:
+//   k_dmc_tm_decide    one wave per walker: the decision of k_dmc_accept with E_c' = Re ke' + ewald' for E'; (p, flags) and the
+//                      selected position x_cur go to the workspace, the state is only read
+//   (ds_ecp_energy's launches on x_cur; a pair total above the capacity ends the call here with the state untouched)
+//   k_dmc_tm_commit    one wave per walker: selects the rows, E = ((E_c + E_loc) + Re E_nl), the one-point weight, epp, E
+//   (k_ecp_tmove of ds_ecp.h: the heat-bath move of one electron; the stats rows)
+//   (energy chain at x)
+//   k_dmc_tm_refresh   one wave per walker: a walker that made a T-move takes logabs, phase, drift, eloc of that pass
+template <typename T>
+__global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_tm_decide(DmcArgs A, const T* __restrict__ x, const T* __restrict__ logabs,
+                                                                  const T* __restrict__ phase, const T* __restrict__ drift,
+                                                                  const T* __restrict__ x2, const T* __restrict__ la2,
+                                                                  const T* __restrict__ ph2, const T* __restrict__ gc2,
+                                                                  const T* __restrict__ ke2, const T* __restrict__ ew2,
+                                                                  const T* __restrict__ chi, const T* __restrict__ uniform, PhiloxKey key,
+                                                                  unsigned long long step, double* __restrict__ pacc, int* __restrict__ flags,
+                                                                  T* __restrict__ xcur) {
+    const long long w = (long long)blockIdx.x * DMC_WAVES + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (w >= A.B) return;
+    const int n3 = 3 * A.N;
+    const size_t row = (size_t)w * n3;
+    double s1 = 0.0, s2 = 0.0;
+    for (int e = lane; e < A.N; e += 64) {
+        const size_t o = row + 3 * e;
+        const T g1[3] = {drift[o], drift[o + 1], drift[o + 2]}, g2[3] = {gc2[2 * o], gc2[2 * (o + 1)], gc2[2 * (o + 2)]};
+        const T f1 = dmc_limiter(g1, (T)A.tau), f2 = dmc_limiter(g2, (T)A.tau);
+        for (int c = 0; c < 3; ++c) {
+            const double ch = (double)chi[o + c];
+            const double bk = ch + A.sqrt_tau * ((double)(f1 * g1[c]) + (double)(f2 * g2[c]));
+            s1 += ch * ch; s2 += bk * bk;
+        }
+    }
+    s1 = wave_sum(s1); s2 = wave_sum(s2);
+    const double a_log = 2.0 * ((double)la2[w] - (double)logabs[w]) + 0.5 * (s1 - s2);
+    const double e_prop = dmc_energy(ke2, ew2, w);
+    const double u = uniform ? (double)uniform[w] : philox_uniform(key, step, (unsigned long long)w);
+    const bool finite = isfinite(a_log) && isfinite(e_prop);
+    const double overlap = (double)ph2[2 * w] * (double)phase[2 * w] + (double)ph2[2 * w + 1] * (double)phase[2 * w + 1];
+    const bool node_ok = A.node_mode == 0 || overlap > 0.0;
+    const bool acc = finite && node_ok && a_log > log(u);
+    const T* src = acc ? x2 : x;
+    for (int c = lane; c < n3; c += 64) xcur[row + c] = src[row + c];
+    if (lane == 0) {
+        int fl = 0;
+        if (acc) fl |= DMC_ACCEPTED;
+        if (!finite) fl |= DMC_NONFINITE;
+        else if (!node_ok) fl |= DMC_NODE;
+        pacc[w] = (finite && node_ok) ? (a_log < 0.0 ? exp(a_log) : 1.0) : 0.0;
+        flags[w] = fl;
+    }
+}
+
+// epp2: the triple at x_cur; etot: E per walker for the stats row and the T-move (out_energy: a copy for the caller)
+template <typename T>
+__global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_tm_commit(DmcArgs A, T* __restrict__ x, T* __restrict__ logabs, T* __restrict__ phase,
+                                                                  T* __restrict__ drift, double* __restrict__ eloc,
+                                                                  double* __restrict__ weight, double* __restrict__ epp,
+                                                                  const T* __restrict__ x2, const T* __restrict__ la2,
+                                                                  const T* __restrict__ ph2, const T* __restrict__ gc2,
+                                                                  const T* __restrict__ ke2, const T* __restrict__ ew2,
+                                                                  const double* __restrict__ epp2, int* __restrict__ flags,
+                                                                  double* __restrict__ etot, double* __restrict__ out_energy) {
+    const long long w = (long long)blockIdx.x * DMC_WAVES + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (w >= A.B) return;
+    const int n3 = 3 * A.N;
+    const size_t row = (size_t)w * n3;
+    const int fl = flags[w];
+    const bool acc = (fl & DMC_ACCEPTED) != 0;
+    if (acc)
+        for (int c = lane; c < n3; c += 64) { x[row + c] = x2[row + c]; drift[row + c] = gc2[2 * (row + c)]; }
+    if (lane == 0) {
+        const double e_c = acc ? dmc_energy(ke2, ew2, w) : eloc[w];
+        const double e = dmc_energy_ecp(e_c, epp2, w);
+        bool clipped;
+        const double ce = dmc_clip(e, A.e_ref, A.e_cut, &clipped);
+        double factor;
+        {
+#pragma clang fp contract(off)
+            factor = exp(-A.tau_eff * (ce - A.e_trial));
+        }
+        const double wn = weight[w] * factor;
+        weight[w] = isfinite(wn) ? wn : 0.0;              // an energy that is not finite kills the walker
+        if (acc) { logabs[w] = la2[w]; phase[2 * w] = ph2[2 * w]; phase[2 * w + 1] = ph2[2 * w + 1]; eloc[w] = e_c; }
+        for (int c = 0; c < 3; ++c) epp[3 * w + c] = epp2[3 * w + c];
+        if (clipped) flags[w] = fl | DMC_CLIPPED;
+        etot[w] = e;
+        if (out_energy) out_energy[w] = e;
+    }
+}
+
+// after the chain pass at the positions that follow the T-moves: gc / la2 / ph2 / ke2 / ew2 are that pass's outputs
+template <typename T>
+__global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_tm_refresh(long long B, int n3, const int* __restrict__ choice,
+                                                                   const T* __restrict__ gc, const T* __restrict__ la2,
+                                                                   const T* __restrict__ ph2, const T* __restrict__ ke2,
+                                                                   const T* __restrict__ ew2, T* __restrict__ logabs, T* __restrict__ phase,
+                                                                   T* __restrict__ drift, double* __restrict__ eloc,
+                                                                   double* __restrict__ weight) {
+    const long long w = (long long)blockIdx.x * DMC_WAVES + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (w >= B || choice[w] < 0) return;
+    for (int c = lane; c < n3; c += 64) drift[(size_t)w * n3 + c] = gc[2 * ((size_t)w * n3 + c)];
+    if (lane == 0) {
+        const double e = dmc_energy(ke2, ew2, w);
+        logabs[w] = la2[w]; phase[2 * w] = ph2[2 * w]; phase[2 * w + 1] = ph2[2 * w + 1]; eloc[w] = e;
+        if (!isfinite(e) || !isfinite((double)la2[w])) weight[w] = 0.0;
+    }
+}
+
+// out_ecp_stats of ds_dmc_step_tmove: the three sums of k_dmc_ecp_stats in its order, and the number of walkers that made a T-move
+// (an exact count) as the fourth column
+__global__ void __launch_bounds__(DMC_GROUP) k_dmc_tm_stats(long long B, const double* __restrict__ weight, const double* __restrict__ epp,
+                                                            const int* __restrict__ choice, double* __restrict__ part) {
+    __shared__ double sh[4][DMC_GROUP];
+    const long long w = (long long)blockIdx.x * DMC_GROUP + threadIdx.x;
+    double v[4] = {0, 0, 0, 0};
+    if (w < B) {
+        const double wt = weight[w];
+        if (wt != 0.0)
+            for (int j = 0; j < 3; ++j) v[j] = wt * epp[3 * w + j];
+        v[3] = choice[w] >= 0 ? 1.0 : 0.0;
+    }
+    for (int j = 0; j < 4; ++j) sh[j][threadIdx.x] = v[j];
+    __syncthreads();
+    for (int s = DMC_GROUP / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+            for (int j = 0; j < 4; ++j) sh[j][threadIdx.x] += sh[j][threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x < 4) part[(long long)blockIdx.x * 4 + threadIdx.x] = sh[threadIdx.x][0];
+}
+
+__global__ void __launch_bounds__(64) k_dmc_tm_stats_final(const double* __restrict__ part, long long n_groups, double* __restrict__ out) {
+    const int j = threadIdx.x;
+    if (j >= 4) return;
+    double s = 0.0;
+    for (long long g = 0; g < n_groups; ++g) s += part[g * 4 + j];
+    out[j] = s;
 }
 
 }  // namespace ds

@@ -83,6 +83,52 @@ inline int64_t dmc_ecp_bytes(const ds_system* s, int64_t B, int64_t nw, int64_t 
     return (int64_t)measure([&](Arena<double>& a) { carve_dmc_ecp<double>(s, a, B, nw, cap, nq, ng); }) * (s->dtype == 0 ? 8 : 4);
 }
 
+// Workspace of ds_dmc_step_tmove: that of ds_dmc_step_ecp (EPP2: the triple at x_cur), then x_cur (B,3N), in 8-byte elements E per
+// walker and the partials of the four columns of out_ecp_stats, as ints the choice.  (The decision lives in the flags.)
+template <typename T> struct DmcTmWs {
+    DmcEcpWs<T> ecp;
+    T* XCUR;
+    double *ETOT, *PART4;
+    int* CHOICE;
+};
+template <typename T>
+DmcTmWs<T> carve_dmc_tmove(const ds_system* s, Arena<T>& a, int64_t B, int64_t nw, int64_t cap, int nq, int64_t ng) {
+    const size_t b = (size_t)B;
+    DmcTmWs<T> w{};
+    w.ecp = carve_dmc_ecp<T>(s, a, B, nw, cap, nq, ng);
+    w.XCUR = a.take(b * 3 * (size_t)s->sd.N);
+    a.align(2);
+    w.ETOT = (double*)a.take(2 * b);
+    w.PART4 = (double*)a.take(2 * 4 * (size_t)((B + ds::DMC_GROUP - 1) / ds::DMC_GROUP));
+    w.CHOICE = (int*)a.take(2 * ((b + 1) / 2));
+    return w;
+}
+inline int64_t dmc_tmove_bytes(const ds_system* s, int64_t B, int64_t nw, int64_t cap, int nq, int64_t ng) {
+    return (int64_t)measure([&](Arena<double>& a) { carve_dmc_tmove<double>(s, a, B, nw, cap, nq, ng); }) * (s->dtype == 0 ? 8 : 4);
+}
+
+// The split of a workspace between the chain and the pseudopotential (ds_dmc_step_ecp, ds_dmc_step_tmove); bytes(nw, ng) = the
+// layout's extent.  One chain walker and one group must fit (false otherwise).  Beside one chain walker the pseudopotential keeps
+// room for up to ECP_RESERVE groups (what ds_ecp_workspace_bytes provides at most); then the chain's chunk takes what fits; then
+// the groups follow from what is left, as ds_ecp_energy derives them.  (Serving the chain first instead lets a workspace that the
+// byte budget cut short run the pseudopotential in chunks of one group: measured 7 x the time of a step.)
+template <typename F>
+bool split_dmc_ecp(const F& bytes, int64_t ws_bytes, int64_t B, int64_t cap, int nq, int64_t* nw_out, int64_t* ng_out) {
+    const int64_t ng_max = std::min<int64_t>(OB_MAX_GROUPS, (cap * nq + ds::PV - 1) / ds::PV);
+    const auto fits = [&](int64_t nw_, int64_t ng_) { return bytes(nw_, ng_) <= ws_bytes; };
+    const auto largest = [](int64_t hi, const auto& ok) {      // the largest n in 1..hi with ok(n); ok(1) holds and ok is monotone
+        int64_t lo = 1;
+        while (lo < hi) { const int64_t mid = (lo + hi + 1) / 2; if (ok(mid)) lo = mid; else hi = mid - 1; }
+        return lo;
+    };
+    if (!fits(1, 1)) return false;
+    const int64_t ng0 = largest(std::min<int64_t>(ECP_RESERVE, ng_max), [&](int64_t n) { return fits(1, n); });
+    const int64_t nw = largest(std::min<int64_t>(B, 65535), [&](int64_t n) { return fits(n, ng0); });
+    *nw_out = nw;
+    *ng_out = largest(ng_max, [&](int64_t n) { return n <= ng0 || fits(nw, n); });
+    return true;
+}
+
 // the comb on the six state arrays: five launches, no host synchronisation.  xi_dev != nullptr: xi is read from the device.
 template <typename T>
 void launch_comb(const CombWs<T>& c, int64_t B, int n3, double xi, const double* xi_dev, T* x, T* logabs, T* phase, T* drift, double* eloc,
@@ -130,25 +176,12 @@ int dmc_step_impl(ds_system* s, const void* params, void* x_, void* logabs_, voi
                         (long long)ws_bytes, (long long)dmc_bytes(s, B, 1));
         we.dmc = carve_dmc<T>(s, a, B, nw);
     } else {
-        // The split of the workspace.  One chain walker and one group must fit.  Beside one chain walker the pseudopotential keeps
-        // room for up to ECP_RESERVE groups (what ds_ecp_workspace_bytes provides at most); then the chain's chunk takes what fits;
-        // then the groups follow from what is left, as ds_ecp_energy derives them.  (Serving the chain first instead lets a workspace
-        // that the byte budget cut short run the pseudopotential in chunks of one group: measured 7 x the time of a step.)
         const int nq = ecp_n_quad(p.e);
-        const int64_t ng_max = std::min<int64_t>(OB_MAX_GROUPS, (p.cap * nq + ds::PV - 1) / ds::PV);
-        const auto fits = [&](int64_t nw_, int64_t ng_) { return dmc_ecp_bytes(s, B, nw_, p.cap, nq, ng_) <= ws_bytes; };
-        const auto largest = [](int64_t hi, const auto& ok) {      // the largest n in 1..hi with ok(n); ok(1) holds and ok is monotone
-            int64_t lo = 1;
-            while (lo < hi) { const int64_t mid = (lo + hi + 1) / 2; if (ok(mid)) lo = mid; else hi = mid - 1; }
-            return lo;
-        };
-        if (!fits(1, 1))
+        int64_t nw, ng;
+        if (!split_dmc_ecp([&](int64_t nw_, int64_t ng_) { return dmc_ecp_bytes(s, B, nw_, p.cap, nq, ng_); }, ws_bytes, B, p.cap, nq, &nw, &ng))
             return fail("workspace too small for ds_dmc_step_ecp: %lld bytes < %lld for one chain chunk of one walker and one group of %d "
                         "configurations (see ds_dmc_ecp_workspace_bytes)", (long long)ws_bytes,
                         (long long)dmc_ecp_bytes(s, B, 1, p.cap, nq, 1), ds::PV);
-        const int64_t ng0 = largest(std::min<int64_t>(ECP_RESERVE, ng_max), [&](int64_t n) { return fits(1, n); });
-        const int64_t nw = largest(std::min<int64_t>(B, 65535), [&](int64_t n) { return fits(n, ng0); });
-        const int64_t ng = largest(ng_max, [&](int64_t n) { return n <= ng0 || fits(nw, n); });
         we = carve_dmc_ecp<T>(s, a, B, nw, p.cap, nq, ng);
     }
     if (!a.ok) return carve_fail("DMC step");
@@ -219,6 +252,102 @@ int dmc_step_impl(ds_system* s, const void* params, void* x_, void* logabs_, voi
             if (p.e)
                 hipLaunchKernelGGL(ds::k_dmc_gather_epp, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, (long long)B,
                                    (const double*)w.comb.TOT, (const int*)w.comb.PAR, (const double*)we.EPP2, p.epp);
+        } else if (par) {
+            hipLaunchKernelGGL(ds::k_dmc_identity, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, (long long)B, par);
+        }
+        if (p.steps_done) *p.steps_done = i + 1;
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// what ds_dmc_step_tmove adds to a ds_dmc_step_ecp call
+struct DmcTmCall {
+    const double* tmove_uniforms; int* out_tmove; double* out_energy;
+};
+
+// ds_dmc_step_tmove: the pseudopotential is evaluated after the decision, at the position the walker then has
+template <typename T>
+int dmc_tmove_impl(ds_system* s, const void* params, void* x_, void* logabs_, void* phase_, void* drift_, double* eloc, double* weight,
+                   const DmcCall& q, const DmcEcpCall& p, const DmcTmCall& m, void* ws, int64_t ws_bytes, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const int64_t B = q.B;
+    const int n3 = 3 * S.N, nq = ecp_n_quad(p.e);
+    T *x = (T*)x_, *logabs = (T*)logabs_, *phase = (T*)phase_, *drift = (T*)drift_;
+    int64_t nw, ng;
+    if (!split_dmc_ecp([&](int64_t nw_, int64_t ng_) { return dmc_tmove_bytes(s, B, nw_, p.cap, nq, ng_); }, ws_bytes, B, p.cap, nq, &nw, &ng))
+        return fail("workspace too small for ds_dmc_step_tmove: %lld bytes < %lld for one chain chunk of one walker and one group of %d "
+                    "configurations (see ds_dmc_tmove_workspace_bytes)", (long long)ws_bytes,
+                    (long long)dmc_tmove_bytes(s, B, 1, p.cap, nq, 1), ds::PV);
+    Arena<T> a = arena_of<T>(ws, ws_bytes);
+    const DmcTmWs<T> wt = carve_dmc_tmove<T>(s, a, B, nw, p.cap, nq, ng);
+    if (!a.ok) return carve_fail("DMC step with T-moves");
+    const DmcEcpWs<T>& we = wt.ecp;
+    const DmcWs<T>& w = we.dmc;
+    const size_t ne = (size_t)B * S.N;
+    const dim3 gw((unsigned)((B + ds::DMC_WAVES - 1) / ds::DMC_WAVES)), bw(64 * ds::DMC_WAVES);
+    const int64_t ngroups = (B + ds::DMC_GROUP - 1) / ds::DMC_GROUP;
+    if (p.steps_done) *p.steps_done = 0;
+    if (!q.state_valid) {
+        // (what ds_dmc_step's initialisation does: no pseudopotential is evaluated, eloc is the chain part)
+        if (int rc = energy_grad_forward(s, params, x, B, w.KE2, w.EW3, logabs, phase, w.GC, w.wsc, w.wsc_bytes, st)) return rc;
+        hipLaunchKernelGGL((ds::k_dmc_init<T>), gw, bw, 0, st, (long long)B, n3, (const T*)w.GC, (const T*)w.KE2, (const T*)w.EW3,
+                           (const T*)logabs, drift, eloc, weight, (const double*)nullptr, (double*)nullptr);
+        HIP_OK(hipMemsetAsync(p.epp, 0, sizeof(double) * 3 * (size_t)B, st));
+    }
+    ds::DmcArgs A{q.tau, std::sqrt(q.tau), q.tau_eff, q.e_trial, q.e_ref, q.e_cut, q.node_mode, S.N, (long long)B};
+    const ds::PhiloxKey key{q.seed, q.offset};
+    const T* normals = (const T*)q.normals; const T* uniforms = (const T*)q.uniforms;
+    for (int i = 0; i < q.steps; ++i) {
+        const T* nz = normals ? normals + (size_t)i * B * n3 : (const T*)nullptr;
+        const T* un = uniforms ? uniforms + (size_t)i * B : (const T*)nullptr;
+        hipLaunchKernelGGL((ds::k_dmc_propose<T>), dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, S.sim_a, S.sim_ainv, (const T*)x,
+                           (const T*)drift, nz, key, (unsigned long long)i, (T)q.tau, (T)A.sqrt_tau, ne, w.X2, w.NZ);
+        if (int rc = energy_grad_forward(s, params, w.X2, B, w.KE2, w.EW3, w.LA2, w.PH2, w.GC, w.wsc, w.wsc_bytes, st)) return rc;
+        hipLaunchKernelGGL((ds::k_dmc_tm_decide<T>), gw, bw, 0, st, A, (const T*)x, (const T*)logabs, (const T*)phase, (const T*)drift,
+                           (const T*)w.X2, (const T*)w.LA2, (const T*)w.PH2, (const T*)w.GC, (const T*)w.KE2, (const T*)w.EW3,
+                           nz ? nz : (const T*)w.NZ, un, key, (unsigned long long)i, w.PACC, w.FLAGS, wt.XCUR);
+        // the pseudopotential at x_cur, exactly as ds_ecp_energy(x_cur, seed, offset + 1 + i) forms it (one host synchronisation: the
+        // pair total).  A total above the capacity fails the call here: nothing of step i is committed, the state is that after i steps
+        EcpWs<T> view{};
+        if (int rc = ecp_energy_forward(s, p.e, params, wt.XCUR, B, q.seed, q.offset + 1 + (uint64_t)i,
+                                        p.rotations ? p.rotations + (size_t)i * 9 * B : nullptr, p.cap, we.EPP2, nullptr, nullptr, nullptr,
+                                        we.wse, we.wse_bytes, st, nullptr, p.out_pairs ? p.out_pairs + i : nullptr, &view))
+            return rc;
+        hipLaunchKernelGGL((ds::k_dmc_tm_commit<T>), gw, bw, 0, st, A, x, logabs, phase, drift, eloc, weight, p.epp, (const T*)w.X2,
+                           (const T*)w.LA2, (const T*)w.PH2, (const T*)w.GC, (const T*)w.KE2, (const T*)w.EW3, (const double*)we.EPP2,
+                           w.FLAGS, wt.ETOT, m.out_energy ? m.out_energy + (size_t)i * B : nullptr);
+        if (int rc = ecp_tmove(s, p.e, &view, x, B, q.tau, weight, wt.ETOT, m.tmove_uniforms ? m.tmove_uniforms + (size_t)i * B : nullptr,
+                               q.seed, q.offset, (uint64_t)i, wt.CHOICE, m.out_tmove ? m.out_tmove + (size_t)i * B : nullptr, st))
+            return rc;
+        // the rows: the weights and E of the commit (the second chain pass may still zero a weight)
+        double* row = q.out_stats + (size_t)i * ds::DMC_ROW;
+        hipLaunchKernelGGL(ds::k_dmc_stats, dim3((unsigned)ngroups), dim3(ds::DMC_GROUP), 0, st, (long long)B, (const double*)weight,
+                           (const double*)wt.ETOT, (const double*)w.PACC, (const int*)w.FLAGS, w.PART);
+        hipLaunchKernelGGL(ds::k_dmc_stats_final, dim3(1), dim3(64), 0, st, (const double*)w.PART, (long long)ngroups, (long long)B, row);
+        if (p.out_ecp_stats) {
+            hipLaunchKernelGGL(ds::k_dmc_tm_stats, dim3((unsigned)ngroups), dim3(ds::DMC_GROUP), 0, st, (long long)B, (const double*)weight,
+                               (const double*)p.epp, (const int*)wt.CHOICE, wt.PART4);
+            hipLaunchKernelGGL(ds::k_dmc_tm_stats_final, dim3(1), dim3(64), 0, st, (const double*)wt.PART4, (long long)ngroups,
+                               p.out_ecp_stats + (size_t)i * 4);
+        }
+        // the chain at x (all B walkers); only the walkers that moved take its outputs
+        if (int rc = energy_grad_forward(s, params, x, B, w.KE2, w.EW3, w.LA2, w.PH2, w.GC, w.wsc, w.wsc_bytes, st)) return rc;
+        hipLaunchKernelGGL((ds::k_dmc_tm_refresh<T>), gw, bw, 0, st, (long long)B, n3, (const int*)wt.CHOICE, (const T*)w.GC, (const T*)w.LA2,
+                           (const T*)w.PH2, (const T*)w.KE2, (const T*)w.EW3, logabs, phase, drift, eloc, weight);
+        int* par = q.out_parents ? q.out_parents + (size_t)i * B : nullptr;
+        if (q.branch_every > 0 && (i + 1) % q.branch_every == 0) {
+            double xi = 0.0;
+            if (!q.comb_uniforms) {                       // stream 2 at index B, one past the walkers
+                uint32_t r[4];
+                ds_philox_host(q.seed, q.offset, (uint64_t)i, (uint64_t)B, 2, r);
+                xi = ds::u53_co(r[0], r[1]);
+            }
+            launch_comb<T>(w.comb, B, n3, xi, q.comb_uniforms ? q.comb_uniforms + i : nullptr, x, logabs, phase, drift, eloc, weight, par,
+                           row + ds::DMC_ROW - 1, st);
+            // (the commit left epp equal to EPP2, the source of the gather)
+            hipLaunchKernelGGL(ds::k_dmc_gather_epp, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, (long long)B,
+                               (const double*)w.comb.TOT, (const int*)w.comb.PAR, (const double*)we.EPP2, p.epp);
         } else if (par) {
             hipLaunchKernelGGL(ds::k_dmc_identity, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, (long long)B, par);
         }
@@ -335,6 +464,55 @@ int ds_dmc_step_ecp(ds_system* s, const ds_ecp* ecp, const void* params, void* x
     p.steps_done = steps_done;
     hipStream_t st = (hipStream_t)stream;
     return DS_BY_DTYPE(s->dtype, dmc_step_impl, s, params, x, logabs, phase, drift, eloc, weight, q, p, ws, ws_bytes, st);
+}
+
+int64_t ds_dmc_tmove_workspace_bytes(const ds_system* s, const ds_ecp* e, int64_t B, int64_t pair_capacity) {
+    if (!s || !e) { fail("null argument"); return -1; }
+    if (B > ds::DMC_MAX_B || ecp_check(s, e, B, pair_capacity)) return -1;
+    // the shares of ds_dmc_ecp_workspace_bytes
+    const int64_t esz = s->dtype == 0 ? 8 : 4;
+    int64_t chunk = std::min<int64_t>(B, s->chunk_cap);
+    chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, workspace_budget() / ((int64_t)s->ws.per_walker * esz)));
+    const int nq = ecp_n_quad(e);
+    return dmc_tmove_bytes(s, B, chunk, pair_capacity, nq, ecp_default_groups(s, B, pair_capacity, nq));
+}
+
+int ds_dmc_step_tmove(ds_system* s, const ds_ecp* ecp, const void* params, void* x, void* logabs, void* phase, void* drift, double* eloc,
+                      double* weight, double* epp, int64_t B, int steps, double tau, double tau_eff, double e_trial, double e_ref,
+                      double e_cut, int node_mode, int branch_every, uint64_t philox_seed, uint64_t philox_offset, const void* normals,
+                      const void* uniforms, const double* comb_uniforms, const double* rotations, const double* tmove_uniforms,
+                      int64_t pair_capacity, int state_valid, double* out_stats, double* out_ecp_stats, int32_t* out_parents,
+                      int64_t* out_pairs, int32_t* out_tmove, double* out_energy, int* steps_done, void* ws, int64_t ws_bytes,
+                      void* stream) {
+    if (steps_done) *steps_done = 0;
+    if (s) ++s->call_seq;
+    if (!s || !params || !ws) return fail("ds_dmc_step_tmove: null argument");
+    if (!x || !logabs || !phase || !drift || !eloc || !weight) return fail("ds_dmc_step_tmove: null state pointer");
+    if (!epp) return fail("ds_dmc_step_tmove: epp is null (the seventh state array)");
+    if (!out_stats) return fail("ds_dmc_step_tmove: out_stats is null");
+    if (B < 1 || B > ds::DMC_MAX_B) return fail("ds_dmc_step_tmove: B must be in 1..%lld (got %lld)", (long long)ds::DMC_MAX_B, (long long)B);
+    if (steps < 1) return fail("ds_dmc_step_tmove: steps must be >= 1 (got %d)", steps);
+    if (!std::isfinite(tau) || !std::isfinite(tau_eff) || !std::isfinite(e_trial) || !std::isfinite(e_ref) || !std::isfinite(e_cut))
+        return fail("ds_dmc_step_tmove: tau, tau_eff, e_trial, e_ref and e_cut must be finite");
+    if (!(tau > 0.0)) return fail("ds_dmc_step_tmove: tau must be > 0 (got %g)", tau);
+    if (tau_eff < 0.0) return fail("ds_dmc_step_tmove: tau_eff must be >= 0 (got %g)", tau_eff);
+    if (node_mode != 0 && node_mode != 1)
+        return fail("ds_dmc_step_tmove: node_mode must be 0 (fixed phase) or 1 (fixed node) (got %d)", node_mode);
+    if (branch_every < 0) return fail("ds_dmc_step_tmove: branch_every must be >= 0 (got %d)", branch_every);
+    const int given = (normals ? 1 : 0) + (uniforms ? 1 : 0) + (comb_uniforms ? 1 : 0) + (rotations ? 1 : 0) + (tmove_uniforms ? 1 : 0);
+    if (given != 0 && given != 5)
+        return fail("ds_dmc_step_tmove: normals, uniforms, comb_uniforms, rotations and tmove_uniforms must be given together (or all NULL)");
+    if (philox_offset >= (1ull << 61) || philox_offset + (uint64_t)steps >= (1ull << 61))
+        return fail("ds_dmc_step_tmove: philox_offset + steps must be below 2^61 (the rotations' stream 4 lies above)");
+    if (int rc = ecp_check(s, ecp, B, pair_capacity)) return rc;
+    const DmcCall q{B, steps, tau, tau_eff, e_trial, e_ref, e_cut, node_mode, branch_every, philox_seed, philox_offset, normals, uniforms,
+                    comb_uniforms, state_valid, out_stats, (int*)out_parents};
+    DmcEcpCall p;
+    p.e = ecp; p.cap = pair_capacity; p.rotations = rotations; p.epp = epp; p.out_ecp_stats = out_ecp_stats; p.out_pairs = out_pairs;
+    p.steps_done = steps_done;
+    const DmcTmCall m{tmove_uniforms, (int*)out_tmove, out_energy};
+    hipStream_t st = (hipStream_t)stream;
+    return DS_BY_DTYPE(s->dtype, dmc_tmove_impl, s, params, x, logabs, phase, drift, eloc, weight, q, p, m, ws, ws_bytes, st);
 }
 
 int ds_dmc_noise(int dtype, int n_elec, int64_t B, int steps, uint64_t philox_seed, uint64_t philox_offset, void* normals, void* uniforms,

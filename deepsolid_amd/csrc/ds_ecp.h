@@ -288,4 +288,63 @@ __global__ void __launch_bounds__(64 * ECP_WAVES) k_ecp_walker(const double* __r
     }
 }
 
+// The heat-bath T-move of ds_dmc_step_tmove (Casula 2006; include/deepsolid_hip.h has the normative text), on what an evaluation of
+// the walkers at x left in its workspace.  One thread per walker walks the walker's terms twice, in configuration order:
+//   t_c = -tau min(Re term_c, 0);  r_{-1} = 1, r_c = r_{c-1} + t_c (one rounded float64 addition each);  Z = r_last;
+//   theta = u Z;  theta < 1 (or no t_c > 0): no move;  else c = #{c: r_c <= theta}, clamped to the last c with t_c > 0.
+// Only a walker of positive weight and finite energy with at least one pair moves.  The electron of the chosen pair goes to the
+// quadrature point by the arithmetic of k_ecp_propose and is wrapped as k_dmc_propose wraps; nothing else of the row changes.
+// choice[w] (and out_choice[w]) = the walker-local configuration pair_local * N_q + q, or -1.  A few hundred terms per walker: the
+// sequential walk is the normative order and costs nothing beside the evaluation.
+template <typename T>
+__global__ void __launch_bounds__(64) k_ecp_tmove(EcpDev E, const T* __restrict__ a, const T* __restrict__ ainv, T* __restrict__ x, long long B,
+                                                  int N, double tau, const double* __restrict__ rot, const long long* __restrict__ off,
+                                                  const int* __restrict__ pi, const double* __restrict__ pr,
+                                                  const double* __restrict__ term, const double* __restrict__ weight,
+                                                  const double* __restrict__ energy, const double* __restrict__ uniform, PhiloxKey key,
+                                                  unsigned long long step, int* __restrict__ choice, int* __restrict__ out_choice) {
+    const long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= B) return;
+    const long long p0 = off[w], n = (off[w + 1] - p0) * E.n_quad;
+    long long ch = -1;
+    if (weight[w] > 0.0 && isfinite(energy[w]) && n > 0) {
+        const double* t = term + 2 * p0 * E.n_quad;
+        double r = 1.0, theta;
+        long long last = -1;
+        {
+#pragma clang fp contract(off)
+            for (long long c = 0; c < n; ++c) {
+                const double re = t[2 * c], tc = -tau * (re < 0.0 ? re : 0.0);
+                r = r + tc;
+                if (tc > 0.0) last = c;
+            }
+            const double u = uniform ? uniform[w] : philox_uniform(key, step, (unsigned long long)(B + 1 + w));
+            theta = u * r;
+        }
+        if (!(theta < 1.0) && last >= 0) {
+#pragma clang fp contract(off)
+            long long c = 0;
+            r = 1.0;
+            for (; c < n; ++c) {                       // (the r_c do not decrease: the count is the first c with r_c > theta)
+                const double re = t[2 * c];
+                r = r + -tau * (re < 0.0 ? re : 0.0);
+                if (!(r <= theta)) break;
+            }
+            ch = c < last ? c : last;
+        }
+    }
+    choice[w] = (int)ch;
+    if (out_choice) out_choice[w] = (int)ch;
+    if (ch < 0) return;
+    const long long p = p0 + ch / E.n_quad;
+    T* xe = x + (w * N + pi[2 * p]) * 3;
+    double U[3];
+    ecp_point(E, rot + 9 * w, (int)(ch % E.n_quad), U);
+    const double rr = pr[4 * p];
+    T pos[3], o[3], wr[3];
+    for (int k = 0; k < 3; ++k) pos[k] = (T)(((double)xe[k] - rr * pr[4 * p + 1 + k]) + rr * U[k]);
+    wrap_point(pos, a, ainv, o, wr);
+    for (int k = 0; k < 3; ++k) xe[k] = o[k];
+}
+
 }  // namespace ds

@@ -293,11 +293,15 @@ void launch_layer_res_add(dim3 grid, hipStream_t st, const T* Xin, size_t x_ws, 
 // ds_sample.hip: the pseudopotential energy (ds_ecp.h) on a workspace of its own layout (carve_ecp): the body of ds_ecp_energy, which
 // the DMC step runs on a sub-range of its workspace.  Arguments as ds_ecp_energy's; *pairs_total (host, optional) receives the pair
 // total that the call reads back -- also when it fails because the total exceeds `cap` -- and pairs_total_dev (device, optional) a
-// copy of it.  ecp_check: what ds_ecp_workspace_bytes and ds_ecp_energy refuse alike (also a null descriptor); ecp_n_quad: N_q;
-// ecp_default_groups: the groups per chunk that ds_ecp_workspace_bytes provides
+// copy of it; *view (optional) the carved EcpWs<T> of the system's element type: the offsets, the pair records, the rotations and
+// the term buffer that the evaluation leaves in `ws`.  ecp_tmove: the heat-bath T-move of the DMC step (k_ecp_tmove) on such a
+// view, for the walkers in x that were just evaluated.  ecp_check: what ds_ecp_workspace_bytes and ds_ecp_energy refuse alike (also
+// a null descriptor); ecp_n_quad: N_q; ecp_default_groups: the groups per chunk that ds_ecp_workspace_bytes provides
 int ecp_energy_forward(ds_system* s, const ds_ecp* e, const void* params, const void* x, int64_t B, uint64_t seed, uint64_t offset,
                        const double* rotations, int64_t cap, double* out_energy, int64_t* out_pairs, void* out_ratio, double* out_rotation,
-                       void* ws, int64_t ws_bytes, hipStream_t st, int64_t* pairs_total, int64_t* pairs_total_dev);
+                       void* ws, int64_t ws_bytes, hipStream_t st, int64_t* pairs_total, int64_t* pairs_total_dev, void* view = nullptr);
+int ecp_tmove(ds_system* s, const ds_ecp* e, const void* view, void* x, int64_t B, double tau, const double* weight, const double* energy,
+              const double* uniforms, uint64_t seed, uint64_t offset, uint64_t step, int* choice, int* out_choice, hipStream_t st);
 int ecp_check(const ds_system* s, const ds_ecp* e, int64_t B, int64_t pair_capacity);
 int ecp_n_quad(const ds_ecp* e);
 int64_t ecp_default_groups(const ds_system* s, int64_t B, int64_t pair_capacity, int nq);

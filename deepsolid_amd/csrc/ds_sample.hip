@@ -211,7 +211,7 @@ int spin_exchange_impl(ds_system* s, const void* params, const void* x_, int64_t
 template <typename T>
 int ecp_energy_impl(ds_system* s, const ds_ecp* e, const void* params, const void* x_, int64_t B, uint64_t seed, uint64_t offset,
                     const double* rotations, int64_t cap, double* out_energy, int64_t* out_pairs, void* out_ratio, double* out_rotation,
-                    void* ws, int64_t ws_bytes, hipStream_t st, int64_t* pairs_total, int64_t* pairs_total_dev) {
+                    void* ws, int64_t ws_bytes, hipStream_t st, int64_t* pairs_total, int64_t* pairs_total_dev, void* view) {
     const ds::SysDev<T>& S = dev<T>(s);
     const ds::EcpDev& E = e->D;
     const T* x = (const T*)x_;
@@ -225,6 +225,7 @@ int ecp_energy_impl(ds_system* s, const ds_ecp* e, const void* params, const voi
     Arena<T> a = arena_of<T>(ws, ws_bytes);
     const EcpWs<T> w = carve_ecp<T>(s, a, B, cap, nq, ng);
     if (!a.ok) return carve_fail("pseudopotential energy");
+    if (view) *(EcpWs<T>*)view = w;
     const dim3 gw((unsigned)((B + 63) / 64)), bw(64);
     hipLaunchKernelGGL((ds::k_ecp_scan<T>), gw, bw, 0, st, E, x, (long long)B, S.N, ds::PhiloxKey{seed, offset}, rotations, w.ROT, w.ELOC,
                        w.CNT, w.BAD, out_rotation);
@@ -263,9 +264,26 @@ int ecp_energy_impl(ds_system* s, const ds_ecp* e, const void* params, const voi
 
 int ecp_energy_forward(ds_system* s, const ds_ecp* e, const void* params, const void* x, int64_t B, uint64_t seed, uint64_t offset,
                        const double* rotations, int64_t cap, double* out_energy, int64_t* out_pairs, void* out_ratio, double* out_rotation,
-                       void* ws, int64_t ws_bytes, hipStream_t st, int64_t* pairs_total, int64_t* pairs_total_dev) {
+                       void* ws, int64_t ws_bytes, hipStream_t st, int64_t* pairs_total, int64_t* pairs_total_dev, void* view) {
     return DS_BY_DTYPE(s->dtype, ecp_energy_impl, s, e, params, x, B, seed, offset, rotations, cap, out_energy, out_pairs, out_ratio,
-                       out_rotation, ws, ws_bytes, st, pairs_total, pairs_total_dev);
+                       out_rotation, ws, ws_bytes, st, pairs_total, pairs_total_dev, view);
+}
+
+template <typename T>
+int ecp_tmove_impl(ds_system* s, const ds_ecp* e, const void* view, void* x, int64_t B, double tau, const double* weight,
+                   const double* energy, const double* uniforms, uint64_t seed, uint64_t offset, uint64_t step, int* choice, int* out_choice,
+                   hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const EcpWs<T>& w = *(const EcpWs<T>*)view;
+    hipLaunchKernelGGL((ds::k_ecp_tmove<T>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, e->D, S.sim_a, S.sim_ainv, (T*)x, (long long)B,
+                       S.N, tau, (const double*)w.ROT, (const long long*)w.OFF, (const int*)w.PI, (const double*)w.PR, (const double*)w.TERM,
+                       weight, energy, uniforms, ds::PhiloxKey{seed, offset}, (unsigned long long)step, choice, out_choice);
+    return 0;
+}
+
+int ecp_tmove(ds_system* s, const ds_ecp* e, const void* view, void* x, int64_t B, double tau, const double* weight, const double* energy,
+              const double* uniforms, uint64_t seed, uint64_t offset, uint64_t step, int* choice, int* out_choice, hipStream_t st) {
+    return DS_BY_DTYPE(s->dtype, ecp_tmove_impl, s, e, view, x, B, tau, weight, energy, uniforms, seed, offset, step, choice, out_choice, st);
 }
 
 int ecp_n_quad(const ds_ecp* e) { return e->D.n_quad; }

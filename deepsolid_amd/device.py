@@ -611,7 +611,8 @@ class DeviceSystem:
 
     def dmc_step(self, params, state, steps, tau, tau_eff=None, e_trial=0.0, e_ref=0.0, e_cut=0.0, node_mode=0, branch_every=1,
                  seed=0, offset=0, normals=None, uniforms=None, comb_uniforms=None, state_valid=True, want_parents=False,
-                 max_bytes=None, ecp=None, pair_capacity=None, rotations=None, want_pairs=False):
+                 max_bytes=None, ecp=None, pair_capacity=None, rotations=None, want_pairs=False, tmoves=False, tmove_uniforms=None,
+                 want_tmoves=False):
         """`ds_dmc_step`: `steps` fixed-phase DMC steps on the walker state IN PLACE (dict of x, logabs, phase, drift, eloc, weight:
         `dmc_state`), enqueued without a host synchronisation; the algorithm is stated in include/deepsolid_hip.h.  Noise from
         the in-kernel Philox stream (seed, offset) or replayed from `normals` (steps,B,3N), `uniforms` (steps,B) and
@@ -625,11 +626,22 @@ class DeviceSystem:
         has a non-local channel), which cannot overflow; where the pair records of that bound exceed `ECP_PAIR_BUDGET` bytes the
         default is B * N, and on overflow the call is repeated once with the number the library reports, continuing from the
         steps that were completed.  The dict gains ecp_stats (steps, 3) float64 = per step sum w E_loc, sum w Re E_nl, sum w Im E_nl,
-        pairs (steps + 1,) int64 with `want_pairs` (entry 0: the initialisation), and pair_capacity."""
+        pairs (steps + 1,) int64 with `want_pairs` (entry 0: the initialisation), and pair_capacity.
+
+        `tmoves=True` (with `ecp`): `ds_dmc_step_tmove`, Casula's T-moves.  The pseudopotential is evaluated after the decision, at
+        the position the walker then has; 'eloc' is the chain part alone and 'epp' the triple of the walker's last evaluation.
+        `tmove_uniforms` (steps, B) float64 joins the explicit noise (all five or none), `rotations` is (steps, B, 3, 3) and the
+        initialisation evaluates no pseudopotential.  ecp_stats is (steps, 4): the fourth column counts the walkers that made a
+        T-move; pairs is (steps,); the dict gains energy (steps, B) float64, the branching energy of every walker, and tmoves
+        (steps, B) int32 with `want_tmoves`: the walker-local configuration pair * N_q + q of the move taken, or -1."""
+        if tmoves and ecp is None:
+            raise ValueError('tmoves=True needs a pseudopotential (ecp=...)')
+        if (tmove_uniforms is not None or want_tmoves) and not tmoves:
+            raise ValueError('tmove_uniforms and want_tmoves go with tmoves=True')
         if ecp is not None:
             return self._dmc_step_ecp(params, state, int(steps), tau, tau_eff, e_trial, e_ref, e_cut, node_mode, branch_every, seed,
                                       offset, normals, uniforms, comb_uniforms, state_valid, want_parents, max_bytes, ecp,
-                                      pair_capacity, rotations, want_pairs)
+                                      pair_capacity, rotations, want_pairs, bool(tmoves), tmove_uniforms, want_tmoves)
         if rotations is not None or pair_capacity is not None or want_pairs:
             raise ValueError('rotations, pair_capacity and want_pairs go with a pseudopotential (ecp=...)')
         B = self._check_dmc_state(state)
@@ -664,21 +676,27 @@ class DeviceSystem:
         return ecp
 
     def _dmc_step_ecp(self, params, state, steps, tau, tau_eff, e_trial, e_ref, e_cut, node_mode, branch_every, seed, offset, normals,
-                      uniforms, comb_uniforms, state_valid, want_parents, max_bytes, ecp, pair_capacity, rotations, want_pairs):
+                      uniforms, comb_uniforms, state_valid, want_parents, max_bytes, ecp, pair_capacity, rotations, want_pairs,
+                      tmoves=False, tmove_uniforms=None, want_tmoves=False):
         import re
         B = self._check_dmc_state(state, ecp=True)
         ecp = self._ecp_tables(ecp)
         p = self.pack_params(params)
-        given = [t is not None for t in (normals, uniforms, comb_uniforms, rotations)]
+        lead = 0 if tmoves else 1                          # entries of rotations / pairs for an initialisation
+        given = [t is not None for t in (normals, uniforms, comb_uniforms, rotations) + ((tmove_uniforms,) if tmoves else ())]
         if all(given):
             normals = normals.to(device=self.device, dtype=self.dtype).contiguous()
             uniforms = uniforms.to(device=self.device, dtype=self.dtype).contiguous()
             comb_uniforms = comb_uniforms.to(device=self.device, dtype=torch.float64).contiguous()
             rotations = rotations.to(device=self.device, dtype=torch.float64).contiguous()
             if tuple(normals.shape) != (steps, B, 3 * self.n) or tuple(uniforms.shape) != (steps, B) or \
-                    tuple(comb_uniforms.shape) != (steps,) or tuple(rotations.shape) != (steps + 1, B, 3, 3):
+                    tuple(comb_uniforms.shape) != (steps,) or tuple(rotations.shape) != (steps + lead, B, 3, 3):
                 raise ValueError('explicit noise must be normals (steps, B, 3N), uniforms (steps, B), comb_uniforms (steps,) and '
-                                 'rotations (steps + 1, B, 3, 3)')
+                                 f'rotations (steps{" + 1" if lead else ""}, B, 3, 3)')
+            if tmoves:
+                tmove_uniforms = tmove_uniforms.to(device=self.device, dtype=torch.float64).contiguous()
+                if tuple(tmove_uniforms.shape) != (steps, B):
+                    raise ValueError('tmove_uniforms must be (steps, B)')
         if pair_capacity is None:
             src = ecp.ecp
             n_nl = int(np.count_nonzero(np.asarray(src.n_l)[np.asarray(src.atom_species)] > 0))
@@ -688,24 +706,33 @@ class DeviceSystem:
         else:
             cap = int(pair_capacity)
         stats = torch.zeros(max(steps, 1), 9, dtype=torch.float64, device=self.device)
-        ecp_stats = torch.zeros(max(steps, 1), 3, dtype=torch.float64, device=self.device)
+        ecp_stats = torch.zeros(max(steps, 1), 4 if tmoves else 3, dtype=torch.float64, device=self.device)
         parents = torch.empty(max(steps, 1), B, dtype=torch.int32, device=self.device) if want_parents else None
-        pairs = torch.zeros(max(steps, 1) + 1, dtype=torch.int64, device=self.device) if want_pairs else None
+        pairs = torch.zeros(max(steps, 1) + lead, dtype=torch.int64, device=self.device) if want_pairs else None
+        choice = torch.full((max(steps, 1), B), -1, dtype=torch.int32, device=self.device) if tmoves and want_tmoves else None
+        energy = torch.zeros(max(steps, 1), B, dtype=torch.float64, device=self.device) if tmoves else None
+        name = 'ds_dmc_step_tmove' if tmoves else 'ds_dmc_step_ecp'
         done, valid = 0, bool(state_valid)
         for attempt in range(2):
             k, left = done, steps - done
-            ws = self._workspace('ds_dmc_ecp_workspace_bytes', ecp.handle, int(B), cap, max_bytes=max_bytes) \
+            ws = self._workspace('ds_dmc_tmove_workspace_bytes' if tmoves else 'ds_dmc_ecp_workspace_bytes', ecp.handle, int(B), cap,
+                                 max_bytes=max_bytes) \
                 if 1 <= B <= 2 ** 20 and cap >= 1 else self.workspace(1)         # (the library refuses such a B or capacity itself)
             n_done = C.c_int(0)
-            rc = self.lib.ds_dmc_step_ecp(
-                self.handle, ecp.handle, _ptr(p), _ptr(state['x']), _ptr(state['logabs']), _ptr(state['phase']), _ptr(state['drift']),
-                _ptr(state['eloc']), _ptr(state['weight']), _ptr(state['epp']), B, left, float(tau),
-                float(tau if tau_eff is None else tau_eff), float(e_trial), float(e_ref), float(e_cut), int(node_mode), int(branch_every),
-                int(seed) & (2 ** 64 - 1), (int(offset) + k) & (2 ** 64 - 1), _ptr(normals[k:] if all(given) else normals),
-                _ptr(uniforms[k:] if all(given) else uniforms), _ptr(comb_uniforms[k:] if all(given) else comb_uniforms),
-                _ptr(rotations[k:] if all(given) else rotations), cap, int(valid), _ptr(stats[k:]), _ptr(ecp_stats[k:]),
-                _ptr(parents[k:] if parents is not None else None), _ptr(pairs[k:] if pairs is not None else None), C.byref(n_done),
-                _ptr(ws), ws.numel(), _stream())
+            cut = (lambda t: t[k:]) if all(given) else (lambda t: t)
+            head = (self.handle, ecp.handle, _ptr(p), _ptr(state['x']), _ptr(state['logabs']), _ptr(state['phase']), _ptr(state['drift']),
+                    _ptr(state['eloc']), _ptr(state['weight']), _ptr(state['epp']), B, left, float(tau),
+                    float(tau if tau_eff is None else tau_eff), float(e_trial), float(e_ref), float(e_cut), int(node_mode), int(branch_every),
+                    int(seed) & (2 ** 64 - 1), (int(offset) + k) & (2 ** 64 - 1), _ptr(cut(normals)), _ptr(cut(uniforms)),
+                    _ptr(cut(comb_uniforms)), _ptr(cut(rotations)))
+            outs = (_ptr(stats[k:]), _ptr(ecp_stats[k:]), _ptr(parents[k:] if parents is not None else None),
+                    _ptr(pairs[k:] if pairs is not None else None))
+            tail = (C.byref(n_done), _ptr(ws), ws.numel(), _stream())
+            if tmoves:
+                rc = self.lib.ds_dmc_step_tmove(*head, _ptr(cut(tmove_uniforms)), cap, int(valid), *outs,
+                                                _ptr(choice[k:] if choice is not None else None), _ptr(energy[k:]), *tail)
+            else:
+                rc = self.lib.ds_dmc_step_ecp(*head, cap, int(valid), *outs, *tail)
             if rc != 0 and attempt == 0 and pair_capacity is None:
                 m = re.search(r'pair capacity exceeded: the walkers have (\d+) pairs', self.lib.ds_last_error().decode())
                 # (the comb's schedule counts the steps of a call: a continuation keeps it only from a multiple of branch_every)
@@ -714,9 +741,12 @@ class DeviceSystem:
                     done += n_done.value
                     valid = valid or done > 0
                     continue
-            _lib.check(rc, 'ds_dmc_step_ecp')
+            _lib.check(rc, name)
             break
-        return dict(stats=stats, parents=parents, ecp_stats=ecp_stats, pairs=pairs, pair_capacity=cap)
+        out = dict(stats=stats, parents=parents, ecp_stats=ecp_stats, pairs=pairs, pair_capacity=cap)
+        if tmoves:
+            out.update(tmoves=choice, energy=energy)
+        return out
 
     def dmc_noise(self, B, steps, seed=0, offset=0):
         """`ds_dmc_noise`: what `dmc_step` draws in Philox mode for (seed, offset), as the arrays its explicit mode takes

@@ -3,7 +3,7 @@ in include/deepsolid_hip.h and DESIGN.md section 19).  The reference has no DMC;
 
 `make_dmc_step` returns the block function (one C-ABI call per block of steps; no host synchronisation inside WITHOUT a
 pseudopotential -- with one, `ds_dmc_step_ecp` synchronises the stream once per step and once more for the initialisation, to
-read the pair total of every pseudopotential evaluation), `DmcState` holds
+read the pair total of every pseudopotential evaluation; `ds_dmc_step_tmove`, the same with T-moves, once per step), `DmcState` holds
 the six walker arrays (seven with a pseudopotential: 'epp') with the scalars a run carries between blocks (`save` / `load`: one .npz of numbers; a resumed run continues
 bit-identically), `reblock` is the blocking error bar of a correlated series.  The driver loop is `inference.run_dmc`.
 """
@@ -47,18 +47,23 @@ class DmcState:
                        float(f['sum_w']), float(f['sum_we']))
 
 
-def make_dmc_step(logdet_net, simulation_cell, tau, steps, e_cut=None, node_mode=0, branch_every=1, seed=0, pseudopotential=None):
+def make_dmc_step(logdet_net, simulation_cell, tau, steps, e_cut=None, node_mode=0, branch_every=1, seed=0, pseudopotential=None,
+                  tmoves=False):
     """-> block(params, state) -> stats (steps, 9) float64 device tensor: `steps` DMC steps on `state` (a `DmcState`) in place as ONE
     `ds_dmc_step` call, with the state's e_trial, e_ref and tau_eff; the state's Philox offset advances by `steps`.  `e_cut`
     defaults to `default_e_cut`; 0 switches the clip off.  `seed`: the Philox seed (fold the rank into it).
     `pseudopotential` (a `pseudopotential.SemiLocalECP`): the locality approximation, ONE `ds_dmc_step_ecp` call per block, which
     synchronises the stream once per step (and once for the initialisation); the state needs 'epp' (`DmcState.fresh(...,
     ecp=True)`), and the block's `ecp_stats` (steps, 3) = per step sum w E_loc, sum w Re E_nl, sum w Im E_nl stay on
-    `block.ecp_stats`.  Any other form of potential is refused."""
+    `block.ecp_stats`.  Any other form of potential is refused.
+    `tmoves=True` (needs a `pseudopotential`): Casula's T-moves, ONE `ds_dmc_step_tmove` call per block (DESIGN.md section 19.2);
+    `block.ecp_stats` is then (steps, 4), the fourth column the number of walkers that made a T-move."""
     from .pseudopotential import SemiLocalECP
     if pseudopotential is not None and not isinstance(pseudopotential, SemiLocalECP):
         raise NotImplementedError('DMC with this form of pseudopotential is not provided: only a pseudopotential.SemiLocalECP in the '
                                   'locality approximation is (no T-moves: DESIGN.md section 19)')
+    if tmoves and pseudopotential is None:
+        raise ValueError('tmoves=True needs a pseudopotential')
     system = logdet_net.apply.system
     tau = float(tau)
     e_cut = default_e_cut(system.n, tau) if e_cut is None else float(e_cut)
@@ -67,7 +72,8 @@ def make_dmc_step(logdet_net, simulation_cell, tau, steps, e_cut=None, node_mode
     def block(params, state):
         out = system.dmc_step(params, state.arrays, steps, tau, tau_eff=state.tau_eff, e_trial=state.e_trial, e_ref=state.e_ref,
                               e_cut=e_cut, node_mode=node_mode, branch_every=branch_every, seed=seed, offset=state.offset,
-                              state_valid=state.valid, **({} if pseudopotential is None else {'ecp': pseudopotential}))
+                              state_valid=state.valid, **({} if pseudopotential is None else {'ecp': pseudopotential}),
+                              **({'tmoves': True} if tmoves else {}))
         state.valid = True
         state.offset += steps
         block.ecp_stats = out.get('ecp_stats')

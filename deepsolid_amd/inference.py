@@ -188,7 +188,7 @@ DMC_SCHEMA = ['block', 'energy', 'variance', 'acceptance', 'tau_eff', 'e_trial',
 
 def run_dmc(slog_net, logdet_net, params, data, simulation_cell, blocks, steps_per_block, tau, key=0, move_width=0.02, mcmc_steps=20,
             burn_in=100, vmc_iterations=20, branch_every=1, e_cut=None, node_mode=0, feedback=10.0, save_path=None,
-            stats_file_name='dmc_stats', accumulators=(), pseudopotential=None, state=None):
+            stats_file_name='dmc_stats', accumulators=(), pseudopotential=None, state=None, tmoves=False):
     """Fixed-phase diffusion Monte Carlo of a fixed wavefunction (`deepsolid_amd.dmc`).
     Returns (state, rows, info).  Equilibrate `data` (B, 3N) with the existing `qmc.make_mcmc_step` (`burn_in` iterations), take
     the VMC energy over `vmc_iterations` more (info['vmc_energy'], info['vmc_error']: reblocked batch means, per primitive cell;
@@ -205,7 +205,10 @@ def run_dmc(slog_net, logdet_net, params, data, simulation_cell, blocks, steps_p
     synchronises once per step).  The VMC energy that seeds e_ref goes through `train.make_loss(..., pseudopotential=...)`;
     rows and the CSV carry a 'pseudopotential' column: the mixed estimate sum w (E_loc + E_nl) / sum w of the block, complex, per
     primitive cell, from the block's ecp_stats, which cross the ranks in the same packed all-reduce as the stats rows.  Any
-    other form of potential is refused (`dmc.make_dmc_step`)."""
+    other form of potential is refused (`dmc.make_dmc_step`).
+    `tmoves=True` (with a `pseudopotential`): Casula's T-moves (`ds_dmc_step_tmove`) in place of the
+    locality approximation; rows and the CSV gain a 'tmoves' column, the T-moves per walker and step of the block, whose sum is
+    the fourth ecp_stats column in the same packed all-reduce."""
     from . import constants, dmc
     accumulators = tuple(accumulators)
     from .pseudopotential import SemiLocalECP
@@ -238,10 +241,10 @@ def run_dmc(slog_net, logdet_net, params, data, simulation_cell, blocks, steps_p
         info.update(vmc_energy=e_vmc / scale, vmc_error=err_vmc / scale, vmc_series=np.asarray(series) / scale)
         state = dmc.DmcState.fresh(system, data, tau, e_vmc, ecp=pseudopotential is not None)
     block_fn = dmc.make_dmc_step(logdet_net, simulation_cell, tau, steps_per_block, e_cut=e_cut, node_mode=node_mode,
-                                 branch_every=branch_every, seed=seed, pseudopotential=pseudopotential)
+                                 branch_every=branch_every, seed=seed, pseudopotential=pseudopotential, tmoves=tmoves)
     w_target = float(batch * max(1, constants.world_size()))
     rows = []
-    schema = DMC_SCHEMA + (['pseudopotential'] if pseudopotential is not None else [])
+    schema = DMC_SCHEMA + (['pseudopotential'] if pseudopotential is not None else []) + (['tmoves'] if tmoves else [])
     writer = Writer(stats_file_name, schema, save_path) if save_path else None
     if writer:
         writer.__enter__()
@@ -249,7 +252,7 @@ def run_dmc(slog_net, logdet_net, params, data, simulation_cell, blocks, steps_p
         for b in range(blocks):
             tau_eff, e_trial = state.tau_eff, state.e_trial
             st = block_fn(params, state)
-            if pseudopotential is not None:                # (the three ecp_stats columns ride behind the nine of the stats rows)
+            if pseudopotential is not None:                # (the ecp_stats columns -- three, four with T-moves -- ride behind the nine of the stats rows)
                 st = torch.cat([st, block_fn.ecp_stats], dim=1)
             st = constants.psum_if_pmap(st).cpu().numpy()                               # ONE packed all-reduce per block
             w, we, we2 = st[:, 0].sum(), st[:, 1].sum(), st[:, 2].sum()
@@ -261,6 +264,8 @@ def run_dmc(slog_net, logdet_net, params, data, simulation_cell, blocks, steps_p
                    'weight': float(st[-1, 0]), 'killed': int((w_target - st[combed, 8]).sum()) if branch_every > 0 else 0}
             if pseudopotential is not None:
                 row['pseudopotential'] = complex(st[:, 9].sum() + st[:, 10].sum(), st[:, 11].sum()) / w / scale
+            if tmoves:
+                row['tmoves'] = float(st[:, 12].sum()) / (w_target * steps_per_block)
             rows.append(row)
             if writer:
                 writer.write(b, **row)

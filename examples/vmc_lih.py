@@ -20,7 +20,9 @@ THIS cell) to the local energy of training and evaluation: the r
 cell of this example is all-electron, so with a real potential the numbers mean nothing: the point is the call sequence);
 --dmc BLOCKS [--dmc-tau TAU]: after the evaluation, BLOCKS blocks of 20 steps of fixed-phase diffusion Monte Carlo at time step TAU
 (default 0.01) from the evaluation's walkers, through deepsolid_amd.inference.run_dmc; with --ecp in the locality
-approximation, the rows then carrying the mixed estimate of E_loc + E_nl)"""
+approximation, the rows then carrying the mixed estimate of E_loc + E_nl;
+--tmoves: with --ecp and --dmc, Casula's T-moves in place of the locality approximation: the energy is then
+an upper bound, and the rows carry the T-moves per walker and step)"""
 import os
 import sys
 
@@ -81,11 +83,16 @@ if '--dmc' in sys.argv:
     i = sys.argv.index('--dmc')
     dmc_blocks = int(sys.argv[i + 1])
     del sys.argv[i:i + 2]
+tmoves = '--tmoves' in sys.argv
+if tmoves:
+    sys.argv.remove('--tmoves')
 ecp_file = None
 if '--ecp' in sys.argv:
     i = sys.argv.index('--ecp')
     ecp_file = sys.argv[i + 1]
     del sys.argv[i:i + 2]
+if tmoves and (ecp_file is None or dmc_blocks <= 0):
+    sys.exit('--tmoves needs --ecp FILE.npz and --dmc BLOCKS')
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 batch = int(sys.argv[2]) if len(sys.argv) > 2 else 1024
 cell, klist = systems.build('lih')
@@ -153,12 +160,14 @@ for acc in accumulators:
 if dmc_blocks > 0:
     from deepsolid_amd import dmc
     state, dmc_rows, info = inference.run_dmc(slogdet, logdet, params, data, cell, blocks=dmc_blocks, steps_per_block=20, tau=dmc_tau,
-                                              move_width=width, burn_in=10, pseudopotential=ecp)
+                                              move_width=width, burn_in=10, pseudopotential=ecp, tmoves=tmoves)
     e, err, length = dmc.reblock([r['energy'] for r in dmc_rows[len(dmc_rows) // 4:]])
     print('VMC:        E = %.4f +- %.4f Ha' % (info['vmc_energy'], info['vmc_error']))
     print('DMC:        E = %.4f +- %.4f Ha (tau = %g, %d blocks of 20 steps, the first quarter left out; acceptance %.4f, '
           'tau_eff %.5f, %d walkers killed)' % (e, err, dmc_tau, dmc_blocks, sum(r['acceptance'] for r in dmc_rows) / len(dmc_rows),
                                                 dmc_rows[-1]['tau_eff'], sum(r['killed'] for r in dmc_rows)))
     if ecp is not None:
-        print('            locality approximation: mixed <E_loc + E_nl> = %.4f Ha'
-              % (sum(r['pseudopotential'].real for r in dmc_rows) / len(dmc_rows)))
+        print('            %s: mixed <E_loc + E_nl> = %.4f Ha'
+              % ('T-moves' if tmoves else 'locality approximation', sum(r['pseudopotential'].real for r in dmc_rows) / len(dmc_rows)))
+    if tmoves:
+        print('            %.4f T-moves per walker and step' % (sum(r['tmoves'] for r in dmc_rows) / len(dmc_rows)))

@@ -618,8 +618,8 @@ int ds_ecp_energy(ds_system* sys, const ds_ecp* ecp, const void* params, const v
  * Refused with a ds_last_error message before any launch: null state pointers or out_stats; B < 1 or B > 2^20 (the chunk offsets
  * of the scan are kept in one workgroup's LDS); steps < 1; tau <= 0, tau_eff < 0 or a non-finite scalar; node_mode outside
  * {0, 1}; branch_every < 0; noise arrays given in part; a workspace below one chain chunk ("workspace too small").
- * Out of scope: T-moves (ds_dmc_step_ecp below is the locality approximation; ds_dmc_step itself takes no ds_ecp and adds no ECP
- * term), electron-by-electron moves, forward walking and pure estimators, weighted accumulators, cross-rank walker exchange
+ * Out of scope: a pseudopotential in ds_dmc_step itself (it takes no ds_ecp and adds no ECP term: ds_dmc_step_ecp below is the
+ * locality approximation, ds_dmc_step_tmove below it adds T-moves), electron-by-electron moves, forward walking and pure estimators, weighted accumulators, cross-rank walker exchange
  * (ranks keep fixed populations with their own total weights, which is unbiased).
  *
  * ds_dmc_branch is the comb of step 8 alone with a given xi in [0, 1); it needs no handle (dtype: 0 float64, else float32) and is
@@ -632,7 +632,8 @@ int ds_dmc_step(ds_system* sys, const void* params, void* x, void* logabs, void*
                 void* stream);
 /* DMC with a semi-local pseudopotential in the LOCALITY APPROXIMATION: the branching energy is
  *   E = ((Re E_kin + E_ewald) + E_loc) + Re E_nl,
- * with E_loc and E_nl projected on the trial function exactly as ds_ecp_energy defines them.  No T-moves.
+ * with E_loc and E_nl projected on the trial function exactly as ds_ecp_energy defines them.  T-moves: ds_dmc_step_tmove below
+ * (DESIGN.md section 19.2).
  * ds_dmc_step_ecp takes every argument of ds_dmc_step, plus:
  *   ecp             the descriptor's handle (ds_ecp_create)
  *   pair_capacity   as in ds_ecp_energy, for ONE evaluation (all B walkers at one position each)
@@ -683,6 +684,73 @@ int ds_dmc_step_ecp(ds_system* sys, const ds_ecp* ecp, const void* params, void*
                     const void* normals, const void* uniforms, const double* comb_uniforms, const double* rotations,
                     int64_t pair_capacity, int state_valid, double* out_stats, double* out_ecp_stats, int32_t* out_parents,
                     int64_t* out_pairs, int* steps_done, void* ws, int64_t ws_bytes, void* stream);
+/* DMC with a semi-local pseudopotential and T-MOVES (Casula, Phys. Rev. B 74, 161102 (2006)): the terms of
+ * E_nl with a negative real part become heat-bath moves of one electron to a quadrature point, so that the mixed energy is an upper
+ * bound.  The pseudopotential is evaluated AFTER the accept/reject decision, at the position the walker then has: a rejected
+ * walker is evaluated where it stands, the term list is used within the step and discarded, and a step costs one pseudopotential
+ * evaluation, as in ds_dmc_step_ecp, plus one more chain pass.  The price is Casula's one-point branching weight.
+ * ds_dmc_step_tmove takes every argument of ds_dmc_step_ecp, with these differences:
+ *   tmove_uniforms  NULL, or (steps, B) float64 [device]: joins the explicit inputs (normals, uniforms, comb_uniforms, rotations,
+ *                   tmove_uniforms), which come all together or not at all
+ *   rotations       NULL, or (steps, B, 3, 3) float64 [device]: slot i for step i (the initialisation evaluates no pseudopotential)
+ *   out_ecp_stats   NULL, or (steps, 4) float64 [device]: the three columns of ds_dmc_step_ecp and the number of walkers that made
+ *                   a T-move in the step (an exact count)
+ *   out_pairs       NULL, or (steps,) int64 [device]: the pair total of every step's evaluation
+ *   out_tmove       NULL, or (steps, B) int32 [device]: the walker-local configuration pair_local * N_q + q of the move taken (pairs
+ *                   of the walker in (i, I) order, as ds_ecp_energy orders them), or -1 for none
+ *   out_energy      NULL, or (steps, B) float64 [device]: E of step 5 below for every walker
+ * State: the seven arrays of ds_dmc_step_ecp with these meanings:
+ *   eloc = Re E_kin + E_ewald at the walker's CURRENT position (the meaning it has in ds_dmc_step: without the pseudopotential);
+ *   epp  = (E_loc, Re E_nl, Im E_nl) of the walker's LAST EVALUATION, that is at its position before its T-move.  It is reported
+ *          only and never an input.
+ * With state_valid = 0 the call does exactly what ds_dmc_step's initialisation does, and sets epp to 0.
+ * Step i of a call:
+ *   1. Limited drift and proposal: steps 1 and 2 of ds_dmc_step, with the same kernels.
+ *   2. One chain pass at x' with both outputs, plus Ewald.  E_c' = Re ke' + ewald' in float64, as ds_dmc_step forms E'.
+ *   3. Decision: step 4 of ds_dmc_step with "E' finite" read as "E_c' finite".  Nothing is committed yet: the decision, p and the
+ *      flags go to the workspace, and the selected position x_cur (x' if accepted, else x) is gathered into a workspace buffer.
+ *   4. The pseudopotential at x_cur, exactly as ds_ecp_energy(x_cur, philox_seed, philox_offset + 1 + i) evaluates it: the triple
+ *      (E_loc, Re E_nl, Im E_nl), and in the workspace the pair offsets, the pair records and the terms (W / N_q) q of every
+ *      configuration.  A pair total above pair_capacity fails the call here, with ds_ecp_energy's message: the state is exactly
+ *      that after i steps and *steps_done = i.
+ *   5. Commit.  x, logabs, phase, drift and eloc (= E_c' or the old eloc) are selected.  E = ((E_c + E_loc) + Re E_nl), each
+ *      addition rounded in float64, in that order.  weight <- weight * exp(-tau_eff (clip(E) - e_trial)) with the clip of
+ *      ds_dmc_step: the ONE-POINT weight; a result that is not finite becomes 0.  epp <- the triple.  Flag "clipped" from clip(E).
+ *   6. T-move, only for a walker of positive weight and finite E that has at least one pair.  Its configurations are
+ *      c = 0 .. n_w N_q - 1 in (pair, q) order, term_c the complex (W / N_q) q of step 4.
+ *        t_c = -tau min(Re term_c, 0)          (tau, not tau_eff; for a complex wavefunction the real part decides)
+ *        r_{-1} = 1,  r_c = r_{c-1} + t_c      (one rounded float64 addition each, in this order);  Z = r_last
+ *        u = the stream-2 uniform at index B + 1 + w, counter philox_offset + i, as a 53-bit uniform in [0, 1) (index w is the
+ *            acceptance uniform, index B the comb's), or tmove_uniforms[i, w]
+ *        theta = u Z                            (one rounded product)
+ *        theta < 1: no move.  Otherwise the chosen c = the number of c with r_c <= theta, clamped to the last c with t_c > 0
+ *        (no t_c > 0: no move).  This sequential order is normative.
+ *      The electron of the chosen pair moves to the quadrature point by the arithmetic of ds_ecp_energy's displaced rows,
+ *      (r_i - r dhat) + r U_q from the same pair record and rotation, rounded to T, and is wrapped as step 2 wraps.  Nothing else
+ *      in the row changes.  There is no node test on a T-move (node_mode governs the diffusion move only): the terms with
+ *      Re term < 0 are exactly those the effective Hamiltonian keeps, whatever the sign of the ratio.
+ *   7. One chain pass at x (all B walkers), plus Ewald.  For the walkers that made a T-move only, logabs, phase, drift and eloc are
+ *      replaced by its outputs; a logabs or eloc that is not finite there sets the weight to 0.  The others keep their rows.
+ *   8. The out_stats row: the nine columns of ds_dmc_step in its fixed order, from the weights after step 5 and E of step 5
+ *      (column [6] counts the non-finite proposals as before).  out_ecp_stats is taken at the same point with the same tree.
+ *   9. The comb, as in ds_dmc_step_ecp, epp gathered from the same parents.
+ * Rotations: stream 4 with the counter philox_offset + 1 + i, the counter step i of ds_dmc_step_ecp uses.  `steps` steps in one call
+ * equal `steps` calls of one step with the offset advanced and state_valid = 1 (branch_every 0 or 1).
+ * Synchronisation, capacity, the split of a smaller workspace and bit-identity for any split are those of ds_dmc_step_ecp, with one
+ * synchronisation per step and none for the initialisation.  Workspace: ds_dmc_tmove_workspace_bytes = the layout of
+ * ds_dmc_step_ecp followed by x_cur, E, the partials of out_ecp_stats and the choice.
+ * Refused with a ds_last_error message before any launch: everything ds_dmc_step_ecp refuses, with the five explicit inputs given in
+ * part in place of its four.  Every other entry point is unchanged.
+ * Out of scope: the size-consistent per-electron T-moves of Casula, Moroni, Sorella and Filippi (2010), a symmetric weight with
+ * T-moves, T-moves in ds_dmc_branch, a synchronisation-free evaluation. */
+int64_t ds_dmc_tmove_workspace_bytes(const ds_system* sys, const ds_ecp* ecp, int64_t B, int64_t pair_capacity);
+int ds_dmc_step_tmove(ds_system* sys, const ds_ecp* ecp, const void* params, void* x, void* logabs, void* phase, void* drift,
+                      double* eloc, double* weight, double* epp, int64_t B, int steps, double tau, double tau_eff, double e_trial,
+                      double e_ref, double e_cut, int node_mode, int branch_every, uint64_t philox_seed, uint64_t philox_offset,
+                      const void* normals, const void* uniforms, const double* comb_uniforms, const double* rotations,
+                      const double* tmove_uniforms, int64_t pair_capacity, int state_valid, double* out_stats,
+                      double* out_ecp_stats, int32_t* out_parents, int64_t* out_pairs, int32_t* out_tmove, double* out_energy,
+                      int* steps_done, void* ws, int64_t ws_bytes, void* stream);
 /* What a Philox-mode ds_dmc_step call of `steps` steps draws, written out in the layout of its explicit mode: normals
  * (steps, B, 3N) and uniforms (steps, B) of dtype T, comb_uniforms (steps,) float64 [device].  The normals are the device's own
  * Box-Muller values (a host model agrees with them to a few ulp, not to the bit), so a float64 call that replays these arrays

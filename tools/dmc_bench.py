@@ -5,12 +5,15 @@
 Prints one JSON line: ms per DMC step with the comb on every step and without any, ms per `ds_local_energy`, ms per importance
 move, the ratio step / local_energy, `outside_chain` = 1 - local_energy / step (the share of a step that the chain pass does not
 account for: the kernels of ds_dmc.h, the gradient half of k_combine, launch gaps) and ms of the comb alone (`ds_dmc_branch`).
-usage: python tools/dmc_bench.py [--reps R] [--steps S] [--batch B] [--once] [--ecp [FILE.npz]] [--r-cut-nl R]
+usage: python tools/dmc_bench.py [--reps R] [--steps S] [--batch B] [--once] [--ecp [FILE.npz]] [--r-cut-nl R] [--tmoves]
 `--once`: one call and no timing -- the run to put under a kernel trace for the share of the k_dmc_* kernels.
 `--ecp`: the cost of the locality approximation instead, one JSON line: (a) ms per `ds_dmc_step` step, (b) ms per stand-alone
 `ds_ecp_energy` call on the same walkers, (c) ms per `ds_dmc_step_ecp` step, and (c) / ((a) + (b)); all with the comb on every
 step.  The potential is the one saved in FILE.npz (`SemiLocalECP.save`, built for the bcc-Li cell) or, without a file, the
-synthetic species of tools/ecp_bench.py on all 8 atoms with the non-local cutoff `--r-cut-nl` (default 2.747 Bohr), N_q = 12."""
+synthetic species of tools/ecp_bench.py on all 8 atoms with the non-local cutoff `--r-cut-nl` (default 2.747 Bohr), N_q = 12.
+`--tmoves` (with `--ecp`): also (d) ms per `ds_dmc_step_tmove` step from the same walkers with the same potential, (d) / (c), the
+excess (d) - (c) beside ms per `ds_local_energy` (one chain pass, what the cost model says the excess is), and the T-moves per
+walker and step."""
 import argparse
 import json
 import os
@@ -59,21 +62,42 @@ def bench_ecp(args, cell, sysd, params, x):
     def ecp_alone():
         offset[0] += 1
         return sysd.ecp_energy(params, x, ecp, offset=offset[0], pair_capacity=cap)
+    state_t, moves = None, [0.0, 0]
+    if args.tmoves:
+        state_t = sysd.dmc_state(x, ecp=True)
+        sysd.dmc_step(params, state_t, 1, args.tau, branch_every=0, state_valid=False, ecp=ecp, pair_capacity=cap, tmoves=True)
+
+    def step_tmove():
+        offset[0] += S
+        out = sysd.dmc_step(params, state_t, S, args.tau, ecp=ecp, pair_capacity=cap, offset=offset[0], tmoves=True, **kw)
+        moves[0] += float(out['ecp_stats'][:, 3].sum())
+        moves[1] += S
+        return out
     if args.once:                                      # (the run to put under a kernel trace: one call of each kind)
         sysd.dmc_step(params, plain, S, args.tau, **kw)
         ecp_alone()
         step_ecp()
+        if args.tmoves:
+            step_tmove()
         torch.cuda.synchronize()
         return
     ms_a = timed(lambda: sysd.dmc_step(params, plain, S, args.tau, **kw), args.reps) / S
     ms_b = timed(ecp_alone, args.reps)
     ms_c = timed(step_ecp, args.reps) / S
     pairs = first['pairs'].cpu().numpy()
+    extra = {}
+    if args.tmoves:
+        ms_d = timed(step_tmove, args.reps) / S
+        ms_e = timed(lambda: sysd.local_energy(params, x), args.reps)
+        extra = {'dmc_step_tmove_ms': round(ms_d, 3), 'ratio_d_over_c': round(ms_d / ms_c, 4), 'excess_ms': round(ms_d - ms_c, 3),
+                 'local_energy_ms': round(ms_e, 3), 'tmoves_per_walker_step': moves[0] / (moves[1] * B),
+                 'tmove_workspace_bytes': int(sysd.lib.ds_dmc_tmove_workspace_bytes(sysd.handle, ecp.handle, B, cap)),
+                 'total_weight_tmove': float(state_t['weight'].sum())}
     print(json.dumps({'case': 'bcc_li', 'electrons': sysd.n, 'B': B, 'steps_per_call': S, 'tau': args.tau, 'n_quad': pot.n_quad,
                       'r_cut_nl': pot.r_cut_nl.tolist(), 'pair_capacity': cap, 'pairs_per_walker': float(pairs[0]) / B,
                       'workspace_bytes': int(sysd.lib.ds_dmc_ecp_workspace_bytes(sysd.handle, ecp.handle, B, cap)),
                       'dmc_step_ms': round(ms_a, 3), 'ecp_energy_ms': round(ms_b, 3), 'dmc_step_ecp_ms': round(ms_c, 3),
-                      'ratio_c_over_a_plus_b': round(ms_c / (ms_a + ms_b), 4), 'total_weight': float(state['weight'].sum())}))
+                      'ratio_c_over_a_plus_b': round(ms_c / (ms_a + ms_b), 4), 'total_weight': float(state['weight'].sum()), **extra}))
 
 
 def main():
@@ -85,7 +109,10 @@ def main():
     ap.add_argument('--once', action='store_true')
     ap.add_argument('--ecp', nargs='?', const='', default=None)
     ap.add_argument('--r-cut-nl', type=float, default=2.747)
+    ap.add_argument('--tmoves', action='store_true')
     args = ap.parse_args()
+    if args.tmoves and args.ecp is None:
+        ap.error('--tmoves needs --ecp')
     cell, klist = systems.build('bcc_li')
     net = network.make_solid_fermi_net(klist=klist, simulation_cell=cell, method_name='eval_logdet', **systems.DETNET_DEFAULTS)
     params = net.init(0)
