@@ -135,6 +135,12 @@ SIGNATURES = {
     'ds_dmc_noise': (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, _VP, _VP, _VP, _VP]),
     'ds_dmc_branch_workspace_bytes':(C.c_int64, [C.c_int, C.c_int, C.c_int64]),
     'ds_dmc_branch': (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    'ds_dmc_ancestry_workspace_bytes': (C.c_int64, [C.c_int64, C.c_int]),
+    'ds_dmc_ancestry': (C.c_int, [C.c_int64, C.c_int, _VP, C.c_int, _VP, _VP, _VP, C.c_int64, _VP]),
+    'ds_realspace_counts_w': (C.c_int, [_PD, C.POINTER(C.c_int32), _PD, _PD, C.c_double, C.c_int, C.c_int, _VP, C.c_int64, C.c_int64,
+                                        C.c_int64, _VP, _VP, C.c_int64, _VP, _VP, C.c_double, _VP, _VP, _VP]),
+    'ds_dmc_fw_sums_workspace_bytes': (C.c_int64, [C.c_int64, C.c_int]),
+    'ds_dmc_fw_sums': (C.c_int, [C.c_int64, C.c_int, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     'ds_philox_host': (None,[C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_uint32)]),
     'ds_energy_stats': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP]),
     'ds_debug_stage': (C.c_int64, [_VP, _VP, _VP, C.c_int64, C.c_char_p, _VP, C.c_int64, _VP, C.c_int64, _VP]),

@@ -1,8 +1,10 @@
 // ds_observe.hip -- observables of a batch of walkers that need no wave function (ds_obs.h, ds_realspace.h): structure factor and
-// polarization sums, electron density and pair-correlation counts.
+// polarization sums, electron density and pair-correlation counts; and forward walking for the DMC (ds_fw.h): ancestor tables, the
+// counts with a weight and a source row per walker, weighted sums of per-walker values.
 #include "ds_host.h"
 #include "ds_obs.h"
 #include "ds_realspace.h"
+#include "ds_fw.h"
 
 namespace ds {
 namespace host {
@@ -28,6 +30,57 @@ template <typename T>
 void realspace_counts(const ds::RealSpaceArgs& A, const void* x, size_t off, long long nb, int N, int64_t* dens, int64_t* pair, hipStream_t st) {
     hipLaunchKernelGGL((ds::k_realspace_counts<T>), dim3((unsigned)ds::rs_groups(nb)), dim3(ds::RS_THREADS), 0, st, A, (const T*)x + off, nb, N,
                        (unsigned long long*)dens, (unsigned long long*)pair);
+}
+
+// what ds_realspace_counts and ds_realspace_counts_w check alike, and the kernel arguments they share
+static int realspace_args(const char* who, const double* fold_inv, const int32_t* grid, const double* latvec, const double* latvec_inv,
+                          double r_max, int n_r, int dtype, const void* x, int64_t B, int64_t n_elec, int64_t n_up, const int64_t* dens,
+                          const int64_t* pair, ds::RealSpaceArgs& A) {
+    if (!x) return fail("null argument");
+    if (!dens && !pair) return fail("%s: dens and pair are both null, nothing to count", who);
+    if (dtype != 0 && dtype != 1) return fail("dtype must be 0 or 1");
+    if (B < 1) return fail("B must be >= 1 (got %lld)", (long long)B);
+    if (n_elec < 1 || n_elec > ds::RS_MAX_N) return fail("n_elec must be in 1..%d (got %lld)", ds::RS_MAX_N, (long long)n_elec);
+    if (n_up < 0 || n_up > n_elec) return fail("n_up must be in 0..n_elec = %lld (got %lld)", (long long)n_elec, (long long)n_up);
+    std::memset(&A, 0, sizeof(A));
+    A.n_up = (int)n_up;
+    A.do_dens = dens != nullptr;
+    A.do_pair = pair != nullptr;
+    if (dens) {
+        if (!fold_inv || !grid) return fail("%s: the density needs fold_inv and grid", who);
+        long long cells = 1;
+        for (int j = 0; j < 3; ++j) {
+            if (grid[j] < 1 || grid[j] > ds::RS_MAX_G) return fail("grid[%d] must be in 1..%d (got %d)", j, ds::RS_MAX_G, (int)grid[j]);
+            A.g[j] = grid[j];
+            cells *= grid[j];
+        }
+        if (cells > ds::RS_MAX_BINS) return fail("grid has %lld points, at most %lld are supported", cells, ds::RS_MAX_BINS);
+        for (int i = 0; i < 9; ++i) {
+            if (!std::isfinite(fold_inv[i])) return fail("fold_inv[%d] is not finite", i);
+            A.fold_inv[i] = fold_inv[i];
+        }
+    }
+    if (pair) {
+        if (!latvec || !latvec_inv) return fail("%s: the pair counts need latvec and latvec_inv", who);
+        if (n_r < 1 || n_r > ds::RS_MAX_NR) return fail("n_r must be in 1..%d (got %d)", ds::RS_MAX_NR, n_r);
+        if (!(r_max > 0.0) || !std::isfinite(r_max)) return fail("r_max must be positive and finite (got %g)", r_max);
+        for (int i = 0; i < 9; ++i) {
+            if (!std::isfinite(latvec[i]) || !std::isfinite(latvec_inv[i])) return fail("latvec / latvec_inv [%d] is not finite", i);
+            A.a[i] = latvec[i];
+            A.a_inv[i] = latvec_inv[i];
+        }
+        A.n_r = n_r;
+        A.r_max = r_max;
+    }
+    return 0;
+}
+
+template <typename T>
+void realspace_counts_w(const ds::RealSpaceArgs& A, const void* x, long long nb, int N, long long B_src, const int32_t* index,
+                        const double* weight, double scale, int64_t* dens, int64_t* pair, int64_t* q_sum, int64_t* n_bad, hipStream_t st) {
+    hipLaunchKernelGGL((ds::k_realspace_counts_w<T>), dim3((unsigned)ds::rs_groups(nb)), dim3(ds::RS_THREADS), 0, st, A, (const T*)x, nb, N,
+                       B_src, (const int*)index, weight, scale, (unsigned long long*)dens, (unsigned long long*)pair, (unsigned long long*)q_sum,
+                       (unsigned long long*)n_bad);
 }
 
 }  // namespace host
@@ -83,43 +136,9 @@ int ds_observables(const double* recvec, int dtype, const void* x, int64_t B, in
 int ds_realspace_counts(const double* fold_inv, const int32_t* grid, const double* latvec, const double* latvec_inv, double r_max,
                         int n_r, int dtype, const void* x, int64_t B, int64_t n_elec, int64_t n_up, int64_t* dens, int64_t* pair,
                         void* stream) {
-    if (!x) return fail("null argument");
-    if (!dens && !pair) return fail("ds_realspace_counts: dens and pair are both null, nothing to count");
-    if (dtype != 0 && dtype != 1) return fail("dtype must be 0 or 1");
-    if (B < 1) return fail("B must be >= 1 (got %lld)", (long long)B);
-    if (n_elec < 1 || n_elec > ds::RS_MAX_N) return fail("n_elec must be in 1..%d (got %lld)", ds::RS_MAX_N, (long long)n_elec);
-    if (n_up < 0 || n_up > n_elec) return fail("n_up must be in 0..n_elec = %lld (got %lld)", (long long)n_elec, (long long)n_up);
     ds::RealSpaceArgs A;
-    std::memset(&A, 0, sizeof(A));
-    A.n_up = (int)n_up;
-    A.do_dens = dens != nullptr;
-    A.do_pair = pair != nullptr;
-    if (dens) {
-        if (!fold_inv || !grid) return fail("ds_realspace_counts: the density needs fold_inv and grid");
-        long long cells = 1;
-        for (int j = 0; j < 3; ++j) {
-            if (grid[j] < 1 || grid[j] > ds::RS_MAX_G) return fail("grid[%d] must be in 1..%d (got %d)", j, ds::RS_MAX_G, (int)grid[j]);
-            A.g[j] = grid[j];
-            cells *= grid[j];
-        }
-        if (cells > ds::RS_MAX_BINS) return fail("grid has %lld points, at most %lld are supported", cells, ds::RS_MAX_BINS);
-        for (int i = 0; i < 9; ++i) {
-            if (!std::isfinite(fold_inv[i])) return fail("fold_inv[%d] is not finite", i);
-            A.fold_inv[i] = fold_inv[i];
-        }
-    }
-    if (pair) {
-        if (!latvec || !latvec_inv) return fail("ds_realspace_counts: the pair counts need latvec and latvec_inv");
-        if (n_r < 1 || n_r > ds::RS_MAX_NR) return fail("n_r must be in 1..%d (got %d)", ds::RS_MAX_NR, n_r);
-        if (!(r_max > 0.0) || !std::isfinite(r_max)) return fail("r_max must be positive and finite (got %g)", r_max);
-        for (int i = 0; i < 9; ++i) {
-            if (!std::isfinite(latvec[i]) || !std::isfinite(latvec_inv[i])) return fail("latvec / latvec_inv [%d] is not finite", i);
-            A.a[i] = latvec[i];
-            A.a_inv[i] = latvec_inv[i];
-        }
-        A.n_r = n_r;
-        A.r_max = r_max;
-    }
+    if (int rc = realspace_args("ds_realspace_counts", fold_inv, grid, latvec, latvec_inv, r_max, n_r, dtype, x, B, n_elec, n_up, dens, pair, A))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     // pieces of at most RS_MAX_LAUNCH_WALKERS walkers: the bound behind the uint32 LDS bins (ds_realspace.h)
     for (int64_t b0 = 0; b0 < B; b0 += ds::RS_MAX_LAUNCH_WALKERS) {
@@ -128,6 +147,89 @@ int ds_realspace_counts(const double* fold_inv, const int32_t* grid, const doubl
         DS_BY_DTYPE(dtype, realspace_counts, A, x, off, nb, (int)n_elec, dens, pair, st);
         HIP_OK(hipGetLastError());
     }
+    return 0;
+}
+
+int ds_realspace_counts_w(const double* fold_inv, const int32_t* grid, const double* latvec, const double* latvec_inv, double r_max,
+                          int n_r, int dtype, const void* x, int64_t B, int64_t n_elec, int64_t n_up, int64_t* dens, int64_t* pair,
+                          int64_t B_src, const int32_t* index, const double* weight, double weight_scale, int64_t* q_sum,
+                          int64_t* n_bad, void* stream) {
+    ds::RealSpaceArgs A;
+    if (int rc = realspace_args("ds_realspace_counts_w", fold_inv, grid, latvec, latvec_inv, r_max, n_r, dtype, x, B, n_elec, n_up, dens, pair, A))
+        return rc;
+    if (!q_sum || !n_bad) return fail("ds_realspace_counts_w: null q_sum or n_bad");
+    if (B_src < 1 || B_src > INT32_MAX) return fail("ds_realspace_counts_w: B_src must be in 1..2^31 - 1 (got %lld)", (long long)B_src);
+    if (!index && B > B_src) return fail("ds_realspace_counts_w: without an index B = %lld walkers need B_src >= B (got %lld)", (long long)B, (long long)B_src);
+    if (weight && !(weight_scale > 0.0 && std::isfinite(weight_scale)))
+        return fail("ds_realspace_counts_w: weight_scale must be positive and finite (got %g)", weight_scale);
+    hipStream_t st = (hipStream_t)stream;
+    // pieces of at most RS_MAX_LAUNCH_WALKERS walkers: the bound behind the LDS bins (ds_fw.h); the source rows are those of all of x.
+    // Without an index walker w reads row w: the piece's rows then start at its own first walker.
+    for (int64_t b0 = 0; b0 < B; b0 += ds::RS_MAX_LAUNCH_WALKERS) {
+        const long long nb = (long long)std::min<int64_t>(B - b0, ds::RS_MAX_LAUNCH_WALKERS);
+        const size_t off = index ? 0 : (size_t)b0 * 3 * (size_t)n_elec;
+        const void* xp = dtype == 0 ? (const void*)((const double*)x + off) : (const void*)((const float*)x + off);
+        DS_BY_DTYPE(dtype, realspace_counts_w, A, xp, nb, (int)n_elec, (long long)(index ? B_src : B_src - b0), index ? index + b0 : nullptr,
+                    weight ? weight + b0 : nullptr, weight_scale, dens, pair, q_sum, n_bad, st);
+        HIP_OK(hipGetLastError());
+    }
+    return 0;
+}
+
+int64_t ds_dmc_ancestry_workspace_bytes(int64_t B, int n_slots) {
+    if (B < 1 || B > INT32_MAX || n_slots < 0) return -1;
+    return (int64_t)sizeof(int32_t) * B * (1 + (int64_t)n_slots);
+}
+
+int ds_dmc_ancestry(int64_t B, int steps, const int32_t* parents, int n_slots, int32_t* anc, int32_t* out_block, void* ws, int64_t ws_bytes,
+                    void* stream) {
+    if (B < 1 || B > INT32_MAX) return fail("ds_dmc_ancestry: B must be in 1..2^31 - 1 (got %lld)", (long long)B);
+    if (steps < 0 || n_slots < 0) return fail("ds_dmc_ancestry: steps and n_slots must be >= 0 (got %d, %d)", steps, n_slots);
+    if (steps > 0 && !parents) return fail("ds_dmc_ancestry: null parents with steps = %d", steps);
+    if (n_slots > 0 && !anc) return fail("ds_dmc_ancestry: null anc with n_slots = %d", n_slots);
+    if (!ws) return fail("ds_dmc_ancestry: null workspace");
+    const int64_t need = ds_dmc_ancestry_workspace_bytes(B, n_slots);
+    if (ws_bytes < need)
+        return fail("workspace too small for ds_dmc_ancestry: %lld bytes < %lld (see ds_dmc_ancestry_workspace_bytes)", (long long)ws_bytes,
+                    (long long)need);
+    hipStream_t st = (hipStream_t)stream;
+    int* P = (int*)ws;
+    int* old = P + B;
+    const unsigned groups = (unsigned)((B + 255) / 256);
+    hipLaunchKernelGGL(ds::k_fw_compose, dim3(groups), dim3(256), 0, st, (long long)B, steps, (const int*)parents, P);
+    HIP_OK(hipGetLastError());
+    if (n_slots > 0) {
+        HIP_OK(hipMemcpyAsync(old, anc, sizeof(int32_t) * (size_t)B * (size_t)n_slots, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(ds::k_fw_apply, dim3(groups), dim3(256), 0, st, (long long)B, n_slots, (const int*)P, (const int*)old, (int*)anc);
+        HIP_OK(hipGetLastError());
+    }
+    if (out_block) HIP_OK(hipMemcpyAsync(out_block, P, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+int64_t ds_dmc_fw_sums_workspace_bytes(int64_t B, int K) {
+    if (B < 1 || B > INT32_MAX || K < 1 || K > ds::FW_MAX_K) return -1;
+    return (int64_t)sizeof(double) * 2 * K * ((B + ds::FW_GROUP - 1) / ds::FW_GROUP);
+}
+
+int ds_dmc_fw_sums(int64_t B, int K, const double* values, int64_t B_src, const int32_t* index, const double* weight, double* out,
+                   int64_t* n_bad, void* ws, int64_t ws_bytes, void* stream) {
+    if (!values || !out || !n_bad || !ws) return fail("ds_dmc_fw_sums: null argument");
+    if (B < 1 || B > INT32_MAX) return fail("ds_dmc_fw_sums: B must be in 1..2^31 - 1 (got %lld)", (long long)B);
+    if (K < 1 || K > ds::FW_MAX_K) return fail("ds_dmc_fw_sums: K must be in 1..%d (got %d)", ds::FW_MAX_K, K);
+    if (B_src < 1 || B_src > INT32_MAX) return fail("ds_dmc_fw_sums: B_src must be in 1..2^31 - 1 (got %lld)", (long long)B_src);
+    if (!index && B > B_src) return fail("ds_dmc_fw_sums: without an index B = %lld walkers need B_src >= B (got %lld)", (long long)B, (long long)B_src);
+    const int64_t need = ds_dmc_fw_sums_workspace_bytes(B, K);
+    if (ws_bytes < need)
+        return fail("workspace too small for ds_dmc_fw_sums: %lld bytes < %lld (see ds_dmc_fw_sums_workspace_bytes)", (long long)ws_bytes,
+                    (long long)need);
+    hipStream_t st = (hipStream_t)stream;
+    const long long groups = (B + ds::FW_GROUP - 1) / ds::FW_GROUP;
+    hipLaunchKernelGGL(ds::k_fw_sums, dim3((unsigned)groups), dim3(ds::FW_GROUP), 0, st, (long long)B, K, values, (long long)B_src,
+                       (const int*)index, weight, (double*)ws, (unsigned long long*)n_bad);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(ds::k_fw_sums_final, dim3(1), dim3(2 * ds::FW_MAX_K), 0, st, (const double*)ws, groups, K, out);
+    HIP_OK(hipGetLastError());
     return 0;
 }
 

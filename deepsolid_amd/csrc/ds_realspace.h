@@ -62,6 +62,54 @@ __device__ inline void rs_pair_of(int p, int& lo, int& hi) {
     lo = p - h * (h - 1) / 2;
 }
 
+// The flat density bin of an electron at (r0, r1, r2): the folding rule above.  Shared by every kernel that counts densities
+// (k_realspace_counts here, k_realspace_counts_w in ds_fw.h), so that their binning cannot drift apart.
+__device__ __forceinline__ long long rs_density_bin(const RealSpaceArgs& A, double r0, double r1, double r2) {
+    long long bin = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        double f = r0 * A.fold_inv[c] + r1 * A.fold_inv[3 + c] + r2 * A.fold_inv[6 + c];
+        f -= floor(f);
+        // min(int(f g), g - 1), taken in double so that the conversion is defined for every input (a NaN lands in bin 0)
+        const double t = fmin(fmax(f * (double)A.g[c], 0.0), (double)(A.g[c] - 1));
+        bin = bin * A.g[c] + (int)t;
+    }
+    return bin;
+}
+
+// The radial bin of the pair (lo, hi), lo < hi, of the staged walker `pos`, or -1 if its minimum-image distance is not below
+// r_max; ch receives the channel.  Shared like rs_density_bin.
+__device__ __forceinline__ int rs_pair_bin(const RealSpaceArgs& A, const double* pos, int lo, int hi, int& ch) {
+    const int n_r = A.n_r;
+    const double d0 = pos[3 * lo] - pos[3 * hi], d1 = pos[3 * lo + 1] - pos[3 * hi + 1], d2 = pos[3 * lo + 2] - pos[3 * hi + 2];
+    double f0 = d0 * A.a_inv[0] + d1 * A.a_inv[3] + d2 * A.a_inv[6];
+    double f1 = d0 * A.a_inv[1] + d1 * A.a_inv[4] + d2 * A.a_inv[7];
+    double f2 = d0 * A.a_inv[2] + d1 * A.a_inv[5] + d2 * A.a_inv[8];
+    f0 -= floor(f0 + 0.5);
+    f1 -= floor(f1 + 0.5);
+    f2 -= floor(f2 + 0.5);
+    double best = INFINITY;
+#pragma unroll
+    for (int s0 = -1; s0 <= 1; ++s0) {
+#pragma unroll
+        for (int s1 = -1; s1 <= 1; ++s1) {
+#pragma unroll
+            for (int s2 = -1; s2 <= 1; ++s2) {
+                const double u0 = f0 + s0, u1 = f1 + s1, u2 = f2 + s2;
+                const double v0 = u0 * A.a[0] + u1 * A.a[3] + u2 * A.a[6];
+                const double v1 = u0 * A.a[1] + u1 * A.a[4] + u2 * A.a[7];
+                const double v2 = u0 * A.a[2] + u1 * A.a[5] + u2 * A.a[8];
+                best = fmin(best, v0 * v0 + v1 * v1 + v2 * v2);
+            }
+        }
+    }
+    const double r = sqrt(best);
+    ch = hi < A.n_up ? 0 : (lo < A.n_up ? 1 : 2);
+    if (!(r < A.r_max)) return -1;     // (also for a NaN)
+    const int k = (int)(r * (double)n_r / A.r_max);
+    return k < n_r ? k : n_r - 1;      // r < r_max, so only a rounding of the quotient could reach n_r
+}
+
 template <typename T>
 __global__ __launch_bounds__(RS_THREADS) void k_realspace_counts(RealSpaceArgs A, const T* __restrict__ x, long long B, int N,
                                                                  unsigned long long* __restrict__ dens,
@@ -83,15 +131,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_realspace_counts(RealSpaceArgs A
 
         if (A.do_dens && tid < N) {
             const double r0 = pos[3 * tid], r1 = pos[3 * tid + 1], r2 = pos[3 * tid + 2];
-            long long bin = 0;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                double f = r0 * A.fold_inv[c] + r1 * A.fold_inv[3 + c] + r2 * A.fold_inv[6 + c];
-                f -= floor(f);
-                // min(int(f g), g - 1), taken in double so that the conversion is defined for every input (a NaN lands in bin 0)
-                const double t = fmin(fmax(f * (double)A.g[c], 0.0), (double)(A.g[c] - 1));
-                bin = bin * A.g[c] + (int)t;
-            }
+            const long long bin = rs_density_bin(A, r0, r1, r2);
             const long long cells = (long long)A.g[0] * A.g[1] * A.g[2];
             atomicAdd(dens + (tid < A.n_up ? 0 : cells) + bin, 1ull);
         }
@@ -100,34 +140,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_realspace_counts(RealSpaceArgs A
             for (int p = tid; p < n_pairs; p += RS_THREADS) {
                 int lo, hi;
                 rs_pair_of(p, lo, hi);
-                const double d0 = pos[3 * lo] - pos[3 * hi], d1 = pos[3 * lo + 1] - pos[3 * hi + 1],
-                             d2 = pos[3 * lo + 2] - pos[3 * hi + 2];
-                double f0 = d0 * A.a_inv[0] + d1 * A.a_inv[3] + d2 * A.a_inv[6];
-                double f1 = d0 * A.a_inv[1] + d1 * A.a_inv[4] + d2 * A.a_inv[7];
-                double f2 = d0 * A.a_inv[2] + d1 * A.a_inv[5] + d2 * A.a_inv[8];
-                f0 -= floor(f0 + 0.5);
-                f1 -= floor(f1 + 0.5);
-                f2 -= floor(f2 + 0.5);
-                double best = INFINITY;
-#pragma unroll
-                for (int s0 = -1; s0 <= 1; ++s0) {
-#pragma unroll
-                    for (int s1 = -1; s1 <= 1; ++s1) {
-#pragma unroll
-                        for (int s2 = -1; s2 <= 1; ++s2) {
-                            const double u0 = f0 + s0, u1 = f1 + s1, u2 = f2 + s2;
-                            const double v0 = u0 * A.a[0] + u1 * A.a[3] + u2 * A.a[6];
-                            const double v1 = u0 * A.a[1] + u1 * A.a[4] + u2 * A.a[7];
-                            const double v2 = u0 * A.a[2] + u1 * A.a[5] + u2 * A.a[8];
-                            best = fmin(best, v0 * v0 + v1 * v1 + v2 * v2);
-                        }
-                    }
-                }
-                const double r = sqrt(best);
-                if (r < A.r_max) {     // false for a NaN
-                    int k = (int)(r * (double)n_r / A.r_max);
-                    k = k < n_r ? k : n_r - 1;     // r < r_max, so only a rounding of the quotient could reach n_r
-                    const int ch = hi < A.n_up ? 0 : (lo < A.n_up ? 1 : 2);
+                int ch;
+                const int k = rs_pair_bin(A, pos, lo, hi, ch);
+                if (k >= 0) {
                     atomicAdd(&hist[ch * n_r + k], 1u);
                 }
             }

@@ -895,6 +895,50 @@ def observable_sums(recvec, x, q_int, pol_direction):
     return out
 
 
+def _realspace_setup(who, x, dens, fold_lattice, pair, latvec, r_max, min_rows='B'):
+    """What `realspace_counts` and `realspace_counts_w` check alike -> (x contiguous, the host arguments of the C entry in its
+    order: fold_inv, grid, latvec, latvec_inv, r_max, n_r)."""
+    _require_gpu()
+    if not x.is_cuda:
+        raise RuntimeError(f'{who}: walkers must live on the ROCm device (no CPU path)')
+    if x.dtype not in _DTYPES:
+        raise TypeError(f'{who}: walkers must be float64 or float32, got {x.dtype}')
+    if x.dim() != 2 or x.shape[1] % 3:
+        raise ValueError(f'{who}: walkers must have shape ({min_rows}, 3N), got {tuple(x.shape)}')
+    if x.shape[0] < 1:
+        raise ValueError(f'{who}: empty walker batch')
+    if dens is None and pair is None:
+        raise ValueError(f'{who}: neither a density nor a pair buffer was given')
+    for name, buf, lead in (('dens', dens, 2), ('pair', pair, 3)):
+        if buf is None:
+            continue
+        if not (isinstance(buf, torch.Tensor) and buf.dtype == torch.int64 and buf.is_contiguous()):
+            raise TypeError(f'{who}: {name} must be a contiguous int64 tensor')
+        if buf.device != x.device:
+            raise RuntimeError(f'{who}: {name} lives on {buf.device}, the walkers on {x.device}')
+        if buf.dim() != (4 if lead == 2 else 2) or buf.shape[0] != lead:
+            raise ValueError(f'{who}: {name} must have shape ' + ('(2, g0, g1, g2)' if lead == 2 else '(3, n_r)')
+                             + f', got {tuple(buf.shape)}')
+    f8 = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(3, 3))
+    fold_inv = grid = a = a_inv = None
+    n_r, rm = 0, 0.0
+    if dens is not None:
+        if fold_lattice is None:
+            raise ValueError(f'{who}: the density needs fold_lattice')
+        fold_inv = np.ascontiguousarray(np.linalg.inv(f8(fold_lattice)))
+        grid = np.asarray(dens.shape[1:], dtype=np.int32)
+    if pair is not None:
+        if latvec is None or r_max is None:
+            raise ValueError(f'{who}: the pair counts need latvec and r_max')
+        a = f8(latvec)
+        a_inv = np.ascontiguousarray(np.linalg.inv(a))
+        n_r, rm = int(pair.shape[1]), float(r_max)
+    keep = (fold_inv, grid, a, a_inv)                      # (the host arrays must outlive the call: the caller holds the tuple)
+    args = (_pd(fold_inv) if fold_inv is not None else None, grid.ctypes.data_as(C.POINTER(C.c_int32)) if grid is not None else None,
+            _pd(a) if a is not None else None, _pd(a_inv) if a_inv is not None else None, rm, n_r)
+    return x.contiguous(), args, keep
+
+
 def realspace_counts(x, n_up, dens=None, fold_lattice=None, pair=None, latvec=None, r_max=None):
     """Add the real-space counts of the walkers x to caller-owned int64 device buffers (`ds_realspace_counts`,
     csrc/ds_realspace.h); needs no handle, returns nothing and copies nothing to the host.
@@ -903,48 +947,97 @@ def realspace_counts(x, n_up, dens=None, fold_lattice=None, pair=None, latvec=No
     or None.  pair: int64 device tensor (3, n_r), the up-up / up-down / down-down histogram of minimum-image distances below
     `r_max` in the simulation cell `latvec` (3, 3), or None.  The caller guarantees r_max <= half the shortest lattice vector and
     r_max < 1.5 x the smallest plane spacing (`estimator.RealSpaceAccumulator` checks both)."""
+    x, args, keep = _realspace_setup('realspace_counts', x, dens, fold_lattice, pair, latvec, r_max)
+    _lib.check(_lib.load().ds_realspace_counts(*args, _DTYPES[x.dtype], _ptr(x), x.shape[0], x.shape[1] // 3, int(n_up), _ptr(dens),
+                                               _ptr(pair), _stream()), 'ds_realspace_counts')
+    del keep
+
+
+# ------------------------------------------------------------------ forward walking (csrc/ds_fw.h, DESIGN.md section 19.3)
+def _fw_array(name, t, dtype, shape, device):
+    if t is None:
+        return None
+    if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f'{name} must be a contiguous {dtype} tensor of shape {tuple(shape)}')
+    if t.device != device:
+        raise RuntimeError(f'{name} lives on {t.device}, expected {device}')
+    return t
+
+
+def dmc_ancestry(parents, anc=None, want_block=False, B=None):
+    """`ds_dmc_ancestry`: carry the ancestor tables `anc` (n_slots, B) int32 through one block IN PLACE, given the block's
+    `parents` (steps, B) int32 as the DMC step entries write them (None, with `B`: no steps, the identity).  An entry of
+    `parents` outside [0, B) loses the lineage: -1, which stays -1.  `anc` None: no tables (only the block map).
+    -> the block map P (B,) int32 with `want_block`, else None."""
     _require_gpu()
-    if not x.is_cuda:
-        raise RuntimeError('realspace_counts: walkers must live on the ROCm device (no CPU path)')
-    if x.dtype not in _DTYPES:
-        raise TypeError(f'realspace_counts: walkers must be float64 or float32, got {x.dtype}')
-    if x.dim() != 2 or x.shape[1] % 3:
-        raise ValueError(f'realspace_counts: walkers must have shape (B, 3N), got {tuple(x.shape)}')
-    if x.shape[0] < 1:
-        raise ValueError('realspace_counts: empty walker batch')
-    if dens is None and pair is None:
-        raise ValueError('realspace_counts: neither a density nor a pair buffer was given')
-    for name, buf, lead in (('dens', dens, 2), ('pair', pair, 3)):
-        if buf is None:
-            continue
-        if not (isinstance(buf, torch.Tensor) and buf.dtype == torch.int64 and buf.is_contiguous()):
-            raise TypeError(f'realspace_counts: {name} must be a contiguous int64 tensor')
-        if buf.device != x.device:
-            raise RuntimeError(f'realspace_counts: {name} lives on {buf.device}, the walkers on {x.device}')
-        if buf.dim() != (4 if lead == 2 else 2) or buf.shape[0] != lead:
-            raise ValueError(f'realspace_counts: {name} must have shape ' + ('(2, g0, g1, g2)' if lead == 2 else '(3, n_r)')
-                             + f', got {tuple(buf.shape)}')
+    ref = parents if parents is not None else anc
+    if ref is None:
+        if B is None:
+            raise ValueError('dmc_ancestry: without parents and tables the number of walkers B is needed')
+        dev = torch.device('cuda', torch.cuda.current_device())
+    else:
+        if not ref.is_cuda:
+            raise RuntimeError('dmc_ancestry: parents / anc must live on the ROCm device (no CPU path)')
+        if ref.dim() != 2:
+            raise ValueError(f'dmc_ancestry: parents must be (steps, B) and anc (n_slots, B), got {tuple(ref.shape)}')
+        dev = ref.device
+    B = int(ref.shape[1]) if B is None else int(B)
+    steps = 0 if parents is None else int(parents.shape[0])
+    n_slots = 0 if anc is None else int(anc.shape[0])
+    _fw_array('dmc_ancestry: parents', parents, torch.int32, (steps, B), dev)
+    _fw_array('dmc_ancestry: anc', anc, torch.int32, (n_slots, B), dev)
     lib = _lib.load()
-    x = x.contiguous()
-    f8 = lambda v: np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(3, 3))
-    fold_inv = grid = a = a_inv = None
-    n_r, rm = 0, 0.0
-    if dens is not None:
-        if fold_lattice is None:
-            raise ValueError('realspace_counts: the density needs fold_lattice')
-        fold_inv = np.ascontiguousarray(np.linalg.inv(f8(fold_lattice)))
-        grid = np.asarray(dens.shape[1:], dtype=np.int32)
-    if pair is not None:
-        if latvec is None or r_max is None:
-            raise ValueError('realspace_counts: the pair counts need latvec and r_max')
-        a = f8(latvec)
-        a_inv = np.ascontiguousarray(np.linalg.inv(a))
-        n_r, rm = int(pair.shape[1]), float(r_max)
-    _lib.check(lib.ds_realspace_counts(_pd(fold_inv) if fold_inv is not None else None,
-                                       grid.ctypes.data_as(C.POINTER(C.c_int32)) if grid is not None else None,
-                                       _pd(a) if a is not None else None, _pd(a_inv) if a_inv is not None else None, rm, n_r,
-                                       _DTYPES[x.dtype], _ptr(x), x.shape[0], x.shape[1] // 3, int(n_up), _ptr(dens), _ptr(pair),
-                                       _stream()), 'ds_realspace_counts')
+    need = int(lib.ds_dmc_ancestry_workspace_bytes(B, n_slots))
+    ws = torch.empty(max(need, 4) // 4, dtype=torch.int32, device=dev)
+    block = torch.empty(B, dtype=torch.int32, device=dev) if want_block else None
+    _lib.check(lib.ds_dmc_ancestry(B, steps, _ptr(parents), n_slots, _ptr(anc), _ptr(block), _ptr(ws), ws.numel() * 4, _stream()),
+               'ds_dmc_ancestry')
+    return block
+
+
+def realspace_counts_w(x, n_up, q_sum, n_bad, index=None, weight=None, weight_scale=1.0, dens=None, fold_lattice=None, pair=None,
+                       latvec=None, r_max=None):
+    """`ds_realspace_counts_w`: `realspace_counts` with a source row and an integer weight per walker.  Walker w adds the
+    positions of row `index[w]` (int32 (B,); None: row w) of x (B_src, 3N) with the weight q = rint(weight[w] * weight_scale)
+    (`weight` float64 (B,); None: 1) to the int64 buffers `dens` / `pair`; q_sum (1,) int64 += sum q; n_bad (2,) int64 += the
+    walkers skipped for their index / for their weight (not finite, negative, q > 2^24).  Nothing is zeroed or copied to the host."""
+    x, args, keep = _realspace_setup('realspace_counts_w', x, dens, fold_lattice, pair, latvec, r_max, min_rows='B_src')
+    B = int(index.shape[0]) if index is not None else (int(weight.shape[0]) if weight is not None else int(x.shape[0]))
+    if q_sum is None or n_bad is None:
+        raise ValueError('realspace_counts_w: q_sum and n_bad are needed')
+    _fw_array('realspace_counts_w: index', index, torch.int32, (B,), x.device)
+    _fw_array('realspace_counts_w: weight', weight, torch.float64, (B,), x.device)
+    _fw_array('realspace_counts_w: q_sum', q_sum, torch.int64, (1,), x.device)
+    _fw_array('realspace_counts_w: n_bad', n_bad, torch.int64, (2,), x.device)
+    _lib.check(_lib.load().ds_realspace_counts_w(*args, _DTYPES[x.dtype], _ptr(x), B, x.shape[1] // 3, int(n_up), _ptr(dens), _ptr(pair),
+                                                 int(x.shape[0]), _ptr(index), _ptr(weight), float(weight_scale), _ptr(q_sum),
+                                                 _ptr(n_bad), _stream()), 'ds_realspace_counts_w')
+    del keep
+
+
+def dmc_fw_sums(values, index=None, weight=None, n_bad=None):
+    """`ds_dmc_fw_sums`: out[k] = (sum_w weight[w] values[index[w], k], sum_w weight[w]) over the walkers with a valid index, a
+    finite weight > 0 and a finite value, in the fixed summation order of the DMC stats rows.  values (B_src, K) float64; index
+    (B,) int32 or None (row w); weight (B,) float64 or None (1); n_bad (2,) int64, added to (None: a fresh one).
+    -> (out (K, 2) float64 device tensor, n_bad)."""
+    _require_gpu()
+    if not (isinstance(values, torch.Tensor) and values.is_cuda and values.dtype == torch.float64 and values.dim() == 2):
+        raise ValueError('dmc_fw_sums: values must be a (B_src, K) float64 tensor on the ROCm device (no CPU path)')
+    values = values.contiguous()
+    B_src, K = (int(v) for v in values.shape)
+    B = int(index.shape[0]) if index is not None else (int(weight.shape[0]) if weight is not None else B_src)
+    _fw_array('dmc_fw_sums: index', index, torch.int32, (B,), values.device)
+    _fw_array('dmc_fw_sums: weight', weight, torch.float64, (B,), values.device)
+    if n_bad is None:
+        n_bad = torch.zeros(2, dtype=torch.int64, device=values.device)
+    _fw_array('dmc_fw_sums: n_bad', n_bad, torch.int64, (2,), values.device)
+    lib = _lib.load()
+    need = int(lib.ds_dmc_fw_sums_workspace_bytes(B, K))
+    ws = torch.empty(max(need, 8) // 8, dtype=torch.float64, device=values.device)
+    out = torch.empty(max(K, 1), 2, dtype=torch.float64, device=values.device)
+    _lib.check(lib.ds_dmc_fw_sums(B, K, _ptr(values), B_src, _ptr(index), _ptr(weight), _ptr(out), _ptr(n_bad), _ptr(ws),
+                                  ws.numel() * 8, _stream()), 'ds_dmc_fw_sums')
+    return out, n_bad
 
 
 class HfOrbitalTables:

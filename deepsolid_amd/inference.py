@@ -188,7 +188,7 @@ DMC_SCHEMA = ['block', 'energy', 'variance', 'acceptance', 'tau_eff', 'e_trial',
 
 def run_dmc(slog_net, logdet_net, params, data, simulation_cell, blocks, steps_per_block, tau, key=0, move_width=0.02, mcmc_steps=20,
             burn_in=100, vmc_iterations=20, branch_every=1, e_cut=None, node_mode=0, feedback=10.0, save_path=None,
-            stats_file_name='dmc_stats', accumulators=(), pseudopotential=None, state=None, tmoves=False):
+            stats_file_name='dmc_stats', accumulators=(), pseudopotential=None, state=None, tmoves=False, forward_walking=None):
     """Fixed-phase diffusion Monte Carlo of a fixed wavefunction (`deepsolid_amd.dmc`).
     Returns (state, rows, info).  Equilibrate `data` (B, 3N) with the existing `qmc.make_mcmc_step` (`burn_in` iterations), take
     the VMC energy over `vmc_iterations` more (info['vmc_energy'], info['vmc_error']: reblocked batch means, per primitive cell;
@@ -208,7 +208,12 @@ def run_dmc(slog_net, logdet_net, params, data, simulation_cell, blocks, steps_p
     other form of potential is refused (`dmc.make_dmc_step`).
     `tmoves=True` (with a `pseudopotential`): Casula's T-moves (`ds_dmc_step_tmove`) in place of the
     locality approximation; rows and the CSV gain a 'tmoves' column, the T-moves per walker and step of the block, whose sum is
-    the fourth ecp_stats column in the same packed all-reduce."""
+    the fourth ecp_stats column in the same packed all-reduce.
+    `forward_walking` (a `dmc.ForwardWalking`): pure estimators by forward walking.  The blocks are then
+    built with `want_parents=True` and `forward_walking.update` runs after EVERY block, whatever `branch_every` is (its weights are
+    the walkers' own); `reduce()` runs at the end, and with a `save_path` every rank has written its tracker, before the
+    reduction, to <save_path>/forward_walking.npz (forward_walking_rank<r>.npz with several ranks, named as the DMC state
+    file is).  A `state=` resume continues it with the same bits when the caller passes a tracker that has loaded that file."""
     from . import constants, dmc
     accumulators = tuple(accumulators)
     from .pseudopotential import SemiLocalECP
@@ -241,7 +246,8 @@ def run_dmc(slog_net, logdet_net, params, data, simulation_cell, blocks, steps_p
         info.update(vmc_energy=e_vmc / scale, vmc_error=err_vmc / scale, vmc_series=np.asarray(series) / scale)
         state = dmc.DmcState.fresh(system, data, tau, e_vmc, ecp=pseudopotential is not None)
     block_fn = dmc.make_dmc_step(logdet_net, simulation_cell, tau, steps_per_block, e_cut=e_cut, node_mode=node_mode,
-                                 branch_every=branch_every, seed=seed, pseudopotential=pseudopotential, tmoves=tmoves)
+                                 branch_every=branch_every, seed=seed, pseudopotential=pseudopotential, tmoves=tmoves,
+                                 want_parents=forward_walking is not None)
     w_target = float(batch * max(1, constants.world_size()))
     rows = []
     schema = DMC_SCHEMA + (['pseudopotential'] if pseudopotential is not None else []) + (['tmoves'] if tmoves else [])
@@ -274,6 +280,8 @@ def run_dmc(slog_net, logdet_net, params, data, simulation_cell, blocks, steps_p
             state.e_trial = state.e_ref - float(np.log(st[-1, 0] / w_target)) / (float(feedback) * float(tau) * steps_per_block)
             for acc in accumulators:
                 acc.update(state.arrays['x'])
+            if forward_walking is not None:
+                forward_walking.update(system, state, block_fn.parents)
     finally:
         if writer:
             writer.__exit__(None, None, None)
@@ -281,6 +289,11 @@ def run_dmc(slog_net, logdet_net, params, data, simulation_cell, blocks, steps_p
         acc.reduce()
         if save_path and constants.rank() == 0:
             acc.save(os.path.join(save_path, 'realspace.npz' if i == 0 else f'realspace_{i}.npz'), results=True)
+    if forward_walking is not None:
+        if save_path:
+            forward_walking.save(os.path.join(save_path, f'forward_walking_rank{constants.rank()}.npz' if constants.world_size() > 1
+                                              else 'forward_walking.npz'))
+        forward_walking.reduce()
     if save_path:
         state.save(os.path.join(save_path, f'dmc_state_rank{constants.rank()}.npz' if constants.world_size() > 1 else 'dmc_state.npz'))
     series = np.asarray([r['energy'] for r in rows])

@@ -21,6 +21,9 @@ cell of this example is all-electron, so with a real potential the numbers mean 
 --dmc BLOCKS [--dmc-tau TAU]: after the evaluation, BLOCKS blocks of 20 steps of fixed-phase diffusion Monte Carlo at time step TAU
 (default 0.01) from the evaluation's walkers, through deepsolid_amd.inference.run_dmc; with --ecp in the locality
 approximation, the rows then carrying the mixed estimate of E_loc + E_nl;
+--dmc-pure LAG[,LAG...]: with --dmc, pure estimators by forward walking at these lags, counted in blocks (deepsolid_amd.dmc.ForwardWalking,
+DESIGN.md section 19.3): for every lag the pure potential, kinetic and total energy and the largest density difference to lag 0
+(the properly weighted mixed estimate, which is always tracked);
 --tmoves: with --ecp and --dmc, Casula's T-moves in place of the locality approximation: the energy is then
 an upper bound, and the rows carry the T-moves per walker and step)"""
 import os
@@ -79,6 +82,11 @@ if '--dmc-tau' in sys.argv:
     i = sys.argv.index('--dmc-tau')
     dmc_tau = float(sys.argv[i + 1])
     del sys.argv[i:i + 2]
+dmc_pure = None
+if '--dmc-pure' in sys.argv:
+    i = sys.argv.index('--dmc-pure')
+    dmc_pure = tuple(sorted({0} | {int(v) for v in sys.argv[i + 1].split(',')}))
+    del sys.argv[i:i + 2]
 if '--dmc' in sys.argv:
     i = sys.argv.index('--dmc')
     dmc_blocks = int(sys.argv[i + 1])
@@ -91,6 +99,8 @@ if '--ecp' in sys.argv:
     i = sys.argv.index('--ecp')
     ecp_file = sys.argv[i + 1]
     del sys.argv[i:i + 2]
+if dmc_pure is not None and dmc_blocks <= 0:
+    sys.exit('--dmc-pure needs --dmc BLOCKS')
 if tmoves and (ecp_file is None or dmc_blocks <= 0):
     sys.exit('--tmoves needs --ecp FILE.npz and --dmc BLOCKS')
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 20
@@ -159,8 +169,10 @@ for acc in accumulators:
               % (pair_bins, acc.r_max, g[0, -1], g[1, -1], g[2, -1]))
 if dmc_blocks > 0:
     from deepsolid_amd import dmc
+    tracker = None if dmc_pure is None else dmc.ForwardWalking(cell, lags=dmc_pure, density_grid=16, pair_bins=32)
     state, dmc_rows, info = inference.run_dmc(slogdet, logdet, params, data, cell, blocks=dmc_blocks, steps_per_block=20, tau=dmc_tau,
-                                              move_width=width, burn_in=10, pseudopotential=ecp, tmoves=tmoves)
+                                              move_width=width, burn_in=10, pseudopotential=ecp, tmoves=tmoves,
+                                              forward_walking=tracker)
     e, err, length = dmc.reblock([r['energy'] for r in dmc_rows[len(dmc_rows) // 4:]])
     print('VMC:        E = %.4f +- %.4f Ha' % (info['vmc_energy'], info['vmc_error']))
     print('DMC:        E = %.4f +- %.4f Ha (tau = %g, %d blocks of 20 steps, the first quarter left out; acceptance %.4f, '
@@ -171,3 +183,10 @@ if dmc_blocks > 0:
               % ('T-moves' if tmoves else 'locality approximation', sum(r['pseudopotential'].real for r in dmc_rows) / len(dmc_rows)))
     if tmoves:
         print('            %.4f T-moves per walker and step' % (sum(r['tmoves'] for r in dmc_rows) / len(dmc_rows)))
+    if tracker is not None:
+        skip = dmc_blocks // 4
+        for lag in dmc_pure:
+            (e, err, _), (v, _, _), (k, _, _) = (tracker.scalar(n, lag, skip=skip) for n in ('energy', 'potential', 'kinetic'))
+            diff = abs(tracker.density(lag) - tracker.density(0)).max()
+            print('pure, lag %2d blocks: V = %.4f  T = %.4f  E = %.4f +- %.4f Ha per simulation cell; largest density difference to '
+                  'lag 0: %.3e e/Bohr^3' % (lag, v, k, e, err, diff))

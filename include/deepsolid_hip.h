@@ -619,8 +619,9 @@ int ds_ecp_energy(ds_system* sys, const ds_ecp* ecp, const void* params, const v
  * of the scan are kept in one workgroup's LDS); steps < 1; tau <= 0, tau_eff < 0 or a non-finite scalar; node_mode outside
  * {0, 1}; branch_every < 0; noise arrays given in part; a workspace below one chain chunk ("workspace too small").
  * Out of scope: a pseudopotential in ds_dmc_step itself (it takes no ds_ecp and adds no ECP term: ds_dmc_step_ecp below is the
- * locality approximation, ds_dmc_step_tmove below it adds T-moves), electron-by-electron moves, forward walking and pure estimators, weighted accumulators, cross-rank walker exchange
- * (ranks keep fixed populations with their own total weights, which is unbiased).
+ * locality approximation, ds_dmc_step_tmove below it adds T-moves), electron-by-electron moves, cross-rank walker exchange
+ * (ranks keep fixed populations with their own total weights, which is unbiased).  Forward walking and the weighted estimators
+ * built on out_parents: ds_dmc_ancestry, ds_realspace_counts_w and ds_dmc_fw_sums below.
  *
  * ds_dmc_branch is the comb of step 8 alone with a given xi in [0, 1); it needs no handle (dtype: 0 float64, else float32) and is
  * the code ds_dmc_step runs.  Workspace: ds_dmc_branch_workspace_bytes.  The caller's buffers may alias nothing else. */
@@ -760,6 +761,65 @@ int ds_dmc_noise(int dtype, int n_elec, int64_t B, int steps, uint64_t philox_se
 int64_t ds_dmc_branch_workspace_bytes(int dtype, int n_elec, int64_t B);
 int ds_dmc_branch(int dtype, int n_elec, int64_t B, double xi, void* x, void* logabs, void* phase, void* drift, double* eloc,
                   double* weight, int32_t* out_parents, void* ws, int64_t ws_bytes, void* stream);
+
+/* Forward walking for the DMC above (csrc/ds_fw.h): pure estimators from the parents that every DMC entry
+ * can write.  The pure estimate of an observable O at a lag of L blocks is
+ *   sum_w w_w(t + L) O(x_anc(w)(t)) / sum_w w_w(t + L),
+ * the snapshot taken L blocks ago weighted with what its descendants weigh now; anc(w) is the walker of the snapshot from which
+ * walker w descends.  The three entries need no ds_system, use no floating-point atomics and are bit-identical from run to run.
+ * An index read from a caller's array is range-checked in the kernel before it is used as an address: garbage in `parents` or
+ * `index` gives counted skips, never a fault.  All pointers are device arrays unless marked HOST.
+ *
+ * ds_dmc_ancestry carries ancestor tables through one block of `steps` steps.
+ *   parents (steps, B) int32: parents[k][w] is the walker before step k from which walker w after step k descends.  This is
+ *     exactly what the step entries write to out_parents: the identity for a step without a comb.  NULL with steps = 0.
+ *   Block map: P[w] = parents[0][parents[1][... parents[steps-1][w]]].  An entry outside [0, B) anywhere in the chain gives
+ *     P[w] = -1.  steps = 0 gives the identity.
+ *   anc (n_slots, B) int32, updated in place: for every slot s, anc_s[w] <- anc_s_old[P[w]], and -1 where P[w] = -1.  The old
+ *     table is read out of place (a copy in the workspace).  A value of the old table is copied as it is, never used as an address:
+ *     anc_old = -1 stays -1, "-1 means the lineage is lost" propagates.  NULL with n_slots = 0.
+ *   out_block (B,) int32, or NULL: receives P.
+ *   steps = 0 or n_slots = 0 is valid.  Workspace: ds_dmc_ancestry_workspace_bytes(B, n_slots) = 4 B (1 + n_slots) bytes; a
+ *   smaller ws_bytes is refused ("workspace too small").  Refused too: B < 1 or B > 2^31 - 1, negative steps or n_slots, a null
+ *   array that the call would read or write.
+ *
+ * ds_realspace_counts_w is ds_realspace_counts with a source row and an integer weight per walker.  It takes the arguments of
+ * ds_realspace_counts, with the same meaning, limits and binning rules (the two kernels share the binning code), and then:
+ *   B_src: x has shape (B_src, 3 n_elec); B is the number of walkers, the length of index and weight.
+ *   index (B,) int32, or NULL: walker w contributes the positions of source row src = index ? index[w] : w of x.
+ *   weight (B,) float64, or NULL, and weight_scale: the walker contributes with the integer weight
+ *     q = weight ? llrint(weight[w] * weight_scale) : 1   (round to nearest, ties to even).
+ *   Skipped and counted in n_bad[0]: src outside [0, B_src).  Skipped and counted in n_bad[1]: a weight that is not finite, a
+ *     negative weight, or q > 2^24.  A walker with both counts under n_bad[0] alone.  q = 0 contributes nothing and is not bad.
+ *   Every density bin and pair bin that ds_realspace_counts would increment by 1 for that row is incremented by q.
+ *   q_sum int64[1]: q_sum += the sum of q over the contributing walkers.  n_bad int64[2]: added to, as above.  Neither is zeroed.
+ *   All additions are integer atomics, so the buffers do not depend on the order of the additions.  The pair bins in LDS are
+ *   64-bit: one workgroup adds at most 2^18 walkers x 8128 pairs x 2^24 < 2^55 to a bin.  Overflow of the global int64 buffers is the
+ *   caller's: a call adds at most B n_elec 2^24 to a density bin and B n_elec (n_elec - 1) / 2 x 2^24 to a pair bin.
+ *   Refused too: null q_sum or n_bad, B_src < 1, B > B_src without an index, a weight_scale that is not positive and finite (with
+ *   a weight).
+ *
+ * ds_dmc_fw_sums forms weighted sums of per-walker values.
+ *   values (B_src, K) float64, 1 <= K <= 64; index, weight as above (weight = NULL means 1; there is no scale: the weight enters
+ *   as the float64 it is).
+ *   out (K, 2) float64, overwritten: out[k] = (sum_w w_w v[src_w, k], sum_w w_w).  The sum runs over the walkers with a valid src, a
+ *     finite weight > 0 and a finite v[src, k].
+ *   n_bad int64[2], added to: [0] walkers whose src is outside [0, B_src); [1] walkers whose weight is not finite or negative,
+ *     plus every (walker, column) whose value is not finite.  A weight of 0 is skipped and not bad.
+ *   Summation order: that of out_stats in ds_dmc_step.  One row of partials per 256 consecutive walkers (thread t holds walker t, a
+ *     skipped one holds 0; a tree adds t and t + s for s = 128, 64, .., 1), then the rows are added in order onto 0.  Each product
+ *     w v is rounded once before it is added.
+ *   Workspace: ds_dmc_fw_sums_workspace_bytes(B, K) = 16 K ceil(B / 256) bytes. */
+int64_t ds_dmc_ancestry_workspace_bytes(int64_t B, int n_slots);
+int ds_dmc_ancestry(int64_t B, int steps, const int32_t* parents, int n_slots, int32_t* anc, int32_t* out_block, void* ws,
+                    int64_t ws_bytes, void* stream);
+int ds_realspace_counts_w(const double* fold_inv, const int32_t* grid, const double* latvec, const double* latvec_inv, double r_max,
+                          int n_r, int dtype, const void* x, int64_t B, int64_t n_elec, int64_t n_up, int64_t* dens, int64_t* pair,
+                          int64_t B_src, const int32_t* index, const double* weight, double weight_scale, int64_t* q_sum,
+                          int64_t* n_bad, void* stream);
+int64_t ds_dmc_fw_sums_workspace_bytes(int64_t B, int K);
+int ds_dmc_fw_sums(int64_t B, int K, const double* values, int64_t B_src, const int32_t* index, const double* weight, double* out,
+                   int64_t* n_bad, void* ws, int64_t ws_bytes, void* stream);
 
 /* Packed batch statistics of train.make_loss.total_energy (train.py:74-82) in one deterministic reduction:
  * out_stats (8,) float64 on the device =

@@ -6,6 +6,7 @@ Prints one JSON line: ms per DMC step with the comb on every step and without an
 move, the ratio step / local_energy, `outside_chain` = 1 - local_energy / step (the share of a step that the chain pass does not
 account for: the kernels of ds_dmc.h, the gradient half of k_combine, launch gaps) and ms of the comb alone (`ds_dmc_branch`).
 usage: python tools/dmc_bench.py [--reps R] [--steps S] [--batch B] [--once] [--ecp [FILE.npz]] [--r-cut-nl R] [--tmoves]
+                                 [--forward-walking [LAG,LAG,...]]
 `--once`: one call and no timing -- the run to put under a kernel trace for the share of the k_dmc_* kernels.
 `--ecp`: the cost of the locality approximation instead, one JSON line: (a) ms per `ds_dmc_step` step, (b) ms per stand-alone
 `ds_ecp_energy` call on the same walkers, (c) ms per `ds_dmc_step_ecp` step, and (c) / ((a) + (b)); all with the comb on every
@@ -13,7 +14,10 @@ step.  The potential is the one saved in FILE.npz (`SemiLocalECP.save`, built fo
 synthetic species of tools/ecp_bench.py on all 8 atoms with the non-local cutoff `--r-cut-nl` (default 2.747 Bohr), N_q = 12.
 `--tmoves` (with `--ecp`): also (d) ms per `ds_dmc_step_tmove` step from the same walkers with the same potential, (d) / (c), the
 excess (d) - (c) beside ms per `ds_local_energy` (one chain pass, what the cost model says the excess is), and the T-moves per
-walker and step."""
+walker and step.
+`--forward-walking` (without `--ecp`): one JSON line with ms per `dmc.ForwardWalking.update` (lags 0, 4, 16 unless given; density
+grid 32^3 on the primitive cell, 128 radial bins, the three built-in scalars) once the ring is full, beside ms per `ds_dmc_step`
+step with the comb on every step from the same process, their ratio per block of `--steps` steps, and the bytes the ring holds."""
 import argparse
 import json
 import os
@@ -110,6 +114,7 @@ def main():
     ap.add_argument('--ecp', nargs='?', const='', default=None)
     ap.add_argument('--r-cut-nl', type=float, default=2.747)
     ap.add_argument('--tmoves', action='store_true')
+    ap.add_argument('--forward-walking', nargs='?', const='0,4,16', default=None)
     args = ap.parse_args()
     if args.tmoves and args.ecp is None:
         ap.error('--tmoves needs --ecp')
@@ -126,6 +131,28 @@ def main():
     e0 = float(state['eloc'][torch.isfinite(state['eloc'])].mean())
     kw = dict(e_trial=e0, e_ref=e0, e_cut=0.2 * (sysd.n / args.tau) ** 0.5)
     step = lambda every: sysd.dmc_step(params, state, S, args.tau, branch_every=every, **kw)
+    if args.forward_walking is not None:
+        from deepsolid_amd import dmc
+        lags = tuple(int(v) for v in args.forward_walking.split(','))
+        tracker = dmc.ForwardWalking(cell, lags=lags, density_grid=32, pair_bins=128)
+        parents = [None]
+
+        def block():
+            parents[0] = sysd.dmc_step(params, state, S, args.tau, branch_every=1, want_parents=True, **kw)['parents']
+        block()
+        for _ in range(max(lags) + 1):                     # fill the ring: every lag's slot exists from here on
+            tracker.update(sysd, state, parents[0])
+        if args.once:
+            torch.cuda.synchronize()
+            return
+        ms_step = timed(block, args.reps) / S
+        ms_update = timed(lambda: tracker.update(sysd, state, parents[0]), args.reps)
+        ring = sum(t.numel() * t.element_size() for t in (tracker.ring_x, tracker.ring_v, tracker.anc))
+        print(json.dumps({'case': 'bcc_li', 'electrons': sysd.n, 'B': B, 'steps_per_call': S, 'tau': args.tau, 'lags': list(lags),
+                          'dmc_step_ms': round(ms_step, 3), 'fw_update_ms': round(ms_update, 3),
+                          'update_over_block': round(ms_update / (ms_step * S), 5), 'ring_bytes': ring,
+                          'q_sum': [int(v) for v in tracker.q_sum], 'lost': [tracker.lost(l) for l in lags]}))
+        return
     if args.once:
         step(1)
         torch.cuda.synchronize()
