@@ -89,6 +89,14 @@ SIGNATURES = {
     'ds_kfac_inverses_sized_workspace_bytes': (C.c_int64, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     'ds_kfac_inverses_sized': (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _VP,
                                         C.c_double, C.c_double, _VP, _VP, C.c_int64, _VP]),
+    'ds_jacobian_workspace_bytes': (C.c_int64, [_VP, C.c_int64]),
+    'ds_logpsi_jacobian': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP]),
+    'ds_minsr_gram_workspace_bytes': (C.c_int64, [C.c_int64, C.c_int64]),
+    'ds_minsr_gram': (C.c_int, [C.c_int, _VP, C.c_int64, C.c_int64, C.c_int64, _VP, _VP, C.c_int64, _VP]),
+    'ds_minsr_matvec_workspace_bytes': (C.c_int64, [C.c_int, C.c_int64, C.c_int64]),
+    'ds_minsr_matvec': (C.c_int, [C.c_int, C.c_int, _VP, C.c_int64, C.c_int64, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP]),
+    'ds_minsr_solve_workspace_bytes': (C.c_int64, [C.c_int64, C.c_int64]),
+    'ds_minsr_solve': (C.c_int, [C.c_int64, C.c_int64, C.c_double, C.c_double, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     'ds_orbitals': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP]),
     'ds_ewald': (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP]),
     'ds_local_energy': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),

@@ -1,9 +1,10 @@
 // ds_gradpass.hip -- the gradient passes (ds_grad.h) and the KFAC optimizer (ds_kfac.h): the reverse sweep behind ds_logpsi_vjp,
-// ds_kfac_factors and ds_pretrain_loss_vjp, the Kronecker-factor pass that rides on it, and the KFAC step (damped inverses,
-// preconditioner).  The forward of a pass is the value chain of ds_value.hip.
+// ds_kfac_factors, ds_pretrain_loss_vjp and ds_logpsi_jacobian, the Kronecker-factor pass and the per-walker emission (ds_jac.h)
+// that ride on it, and the KFAC step (damped inverses, preconditioner).  The forward of a pass is the value chain of ds_value.hip.
 #include "ds_host.h"
 #include "ds_grad.h"
 #include "ds_kfac.h"
+#include "ds_jac.h"
 
 namespace ds {
 namespace host {
@@ -299,12 +300,21 @@ void kfac_emit(ds_system* s, const KfacSink<T>& ks, const KfacBlockPlan& b, cons
                        b.nparam, (const T*)ks.P3, (long)(ng * nsplit), scale, ks.first ? 1 : 0, ks.factors + b.pub.g_offset);
 }
 
+// The per-walker sink of the sweep (ds_logpsi_jacobian, ds_jac.h): row w of `rows` (leading dimension ld) receives walker w's own
+// gradient of every parameter block, from the operands the batch-summed gradient is formed from
+template <typename T> struct JacSink {
+    T* rows;
+    size_t ld;
+};
+
 // PHIBAR / QBAR of a chunk -> parameter gradient: grad = (first ? 0 : grad) + this chunk's sums
 template <typename T>
 int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, const T* params, const T* WT, const T* x, int64_t Bc,
-                    bool first, T* grad, hipStream_t st, const KfacSink<T>* ks = nullptr) {
+                    bool first, T* grad, hipStream_t st, const KfacSink<T>* ks = nullptr, const JacSink<T>* js = nullptr) {
     // ks: the KFAC factor pass (ds_kfac_factors) -- every tagged layer's A and G from the operands of its weight gradient;
     // grad may then be null (no packed gradient wanted)
+    // js: the per-walker emission (ds_logpsi_jacobian).  The batch-summed contractions are then not launched at all (grad is null:
+    // nobody reads PART); the cotangent chain itself is the same.  With js null nothing below differs from the plain sweep.
     const ds::SysDev<T>& S = dev<T>(s);
     const int PV = ds::PV;
     const int64_t ng = (Bc + PV - 1) / PV;
@@ -319,8 +329,16 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
     {
         HIP_OK(hipMemsetAsync(PART, 0, np * ng * sizeof(T), st));
         const size_t gws = (size_t)S.N * S.ldk * PV, gts = (size_t)S.ldk * PV;
+        // per-walker emission of one block: the operands of `outer` (X null: a row of ones); pair: the pair layout of k_two_bwd
+        auto emit = [&](const T* X, size_t xg, size_t xt, int ldx, const T* Z, size_t zg, size_t zt, int ldz, int nt, int K, int Nc,
+                        size_t off, bool pair) {
+            const unsigned nblk = (unsigned)(((K + 31) / 32) * ((Nc + 63) / 64));
+            hipLaunchKernelGGL((ds::k_jac_outer<T>), dim3(nblk, (unsigned)Bc), dim3(256), 0, st, X, xg, xt, ldx, Z, zg, zt, ldz, nt, K, Nc,
+                               pair ? S.NP : 0, S.N * S.N, (long)Bc, js->rows, js->ld, off);
+        };
         auto outer = [&](const T* X, size_t xg, size_t xt, int ldx, const T* Z, size_t zg, size_t zt, int ldz, int nt, int J, int K,
                          int Nc, size_t off, int nsplit = 1) {
+            if (js) { emit(X, xg, xt, ldx, Z, zg, zt, ldz, nt, K, Nc, off, nsplit > 1); return; }      // (only the pair layers split)
             const int nwt = ((K + 31) / 32) * ((Nc + 31) / 32) * nsplit;
             T* dst = nsplit == 1 ? PART + off : W2S;
             hipLaunchKernelGGL((ds::k_outer_gemm<T>), dim3((unsigned)((nwt + 3) / 4), (unsigned)ng), dim3(256), 0, st, X, xg, xt, ldx, Z, zg,
@@ -340,7 +358,10 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
                 o.Gaux = vb.Gl[L]; o.e0 = i0; o.ne = ns;
                 kfac_emit<T>(s, *ks, ks->kp->blocks[L + S.n_double + sp], o, 1, Bc, st);
             }
-            if (S.bias_orb)
+            if (S.bias_orb && js)
+                hipLaunchKernelGGL((ds::k_jac_orb_bias<T>), dim3((unsigned)Bc), dim3(256), 0, st, PB[sp], pgs, ns, OC, S.nparam[sp], (long)Bc,
+                                   js->rows, js->ld, boff(s->i_borb[sp]));
+            else if (S.bias_orb)
                 hipLaunchKernelGGL((ds::k_orb_bias_grad<T>), dim3(2 * S.nparam[sp], (unsigned)ng), dim3(256), 0, st, PB[sp], pgs, ns, OC,
                                    S.nparam[sp], PART + boff(s->i_borb[sp]), np);
             const int Kop = gp.korb_pad;
@@ -363,9 +384,14 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
                                    (size_t)Ksh * PV, (size_t)0, Ksh, PV, (const T*)nullptr, (const T*)nullptr, ds::OrbEpi<T>{});
             }
         }
-        hipLaunchKernelGGL((ds::k_env_grad<T>), dim3((unsigned)ng, S.nch), dim3(256), 0, st, S, x, (long)Bc, vb.Gl[0], QBAR,
-                           blk(s->i_pi[0]), blk(s->i_sg[0]), blk(s->i_pi[S.nch - 1]), blk(s->i_sg[S.nch - 1]), PART, np,
-                           (long)boff(s->i_pi[0]), (long)boff(s->i_sg[0]), (long)boff(s->i_pi[S.nch - 1]), (long)boff(s->i_sg[S.nch - 1]));
+        if (js)
+            hipLaunchKernelGGL((ds::k_jac_env<T>), dim3((unsigned)Bc, S.nch), dim3(256), 0, st, S, x, (long)Bc, vb.Gl[0], QBAR,
+                               blk(s->i_pi[0]), blk(s->i_sg[0]), blk(s->i_pi[S.nch - 1]), blk(s->i_sg[S.nch - 1]), js->rows, js->ld,
+                               (long)boff(s->i_pi[0]), (long)boff(s->i_sg[0]), (long)boff(s->i_pi[S.nch - 1]), (long)boff(s->i_sg[S.nch - 1]));
+        else
+            hipLaunchKernelGGL((ds::k_env_grad<T>), dim3((unsigned)ng, S.nch), dim3(256), 0, st, S, x, (long)Bc, vb.Gl[0], QBAR,
+                               blk(s->i_pi[0]), blk(s->i_sg[0]), blk(s->i_pi[S.nch - 1]), blk(s->i_sg[S.nch - 1]), PART, np,
+                               (long)boff(s->i_pi[0]), (long)boff(s->i_sg[0]), (long)boff(s->i_pi[S.nch - 1]), (long)boff(s->i_sg[S.nch - 1]));
         // ---- layers, last to first
         const T* D1 = GBAR; int ld1 = gp.korb_pad; const T* MB = s->use_last ? MEANBAR : nullptr; const T* CARRY = nullptr;
         const T* MB2 = s->use_last && S.nch > 1 ? MEANBAR2 : nullptr;
@@ -383,6 +409,8 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
             else
                 hipLaunchKernelGGL((ds::k_layer_bwd_prep<T, false>), dim3(Nout / 4, (unsigned)ng), dim3(4 * PV), 0, st, S, D1, ld1, MB, MB2, CARRY,
                                    vb.Gl[l + 1], vb.Gl[l], Nout, HBc, ZBAR, SBAR, PART + boff(s->i_b[l]), np);
+            if (js)      // b[l]: the walker's row sums of ZBAR over the electrons
+                emit(nullptr, 0, 0, 0, ZBAR, (size_t)S.N * Nout * PV, (size_t)Nout * PV, PV, S.N, 1, Nout, boff(s->i_b[l]), false);
             outer(vb.Gl[l], gws, gts, PV, ZBAR, (size_t)S.N * Nout * PV, (size_t)Nout * PV, PV, S.N, PV, Kloc, Nout, boff(s->i_wloc[l]));
             if (ks) {
                 KfacOperands<T> o;
@@ -442,8 +470,11 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
                     o.Z = pair_tiles<T>(Z2BAR, K2o, S.N, S.NP);
                     kfac_emit<T>(s, *ks, ks->kp->blocks[L + l], o, ks->kp->nsplit2, Bc, st);
                 }
-                hipLaunchKernelGGL((ds::k_row_sums<T>), dim3(K2o, (unsigned)ng), dim3(256), 0, st, Z2BAR, (size_t)(PV / 5) * K2o * J,
-                                   (size_t)K2o * J, J, PV / 5, J, PART + boff(s->i_b2[l]), np);
+                if (js)  // b2[l]: the walker's row sums of Z2BAR over its pairs
+                    emit(nullptr, 0, 0, 0, Z2BAR, (size_t)(PV / 5) * K2o * J, (size_t)K2o * J, J, PV / 5, 1, K2o, boff(s->i_b2[l]), true);
+                else
+                    hipLaunchKernelGGL((ds::k_row_sums<T>), dim3(K2o, (unsigned)ng), dim3(256), 0, st, Z2BAR, (size_t)(PV / 5) * K2o * J,
+                                       (size_t)K2o * J, J, PV / 5, J, PART + boff(s->i_b2[l]), np);
                 h2i ^= 1;
             }
             D1 = GBAR; ld1 = Kpad; MB = MEANBAR; MB2 = nullptr; CARRY = res ? HBc : nullptr;
@@ -467,10 +498,12 @@ template <typename T> struct GradWs {
 };
 
 template <typename T>
-GradWs<T> carve_grad_pass(const ds_system* s, const GradPlan& gp, const KfacPlan* kp, bool dets, Arena<T>& a, int64_t ng) {
+GradWs<T> carve_grad_pass(const ds_system* s, const GradPlan& gp, const KfacPlan* kp, bool dets, Arena<T>& a, int64_t ng,
+                          bool seedbuf = false) {
     GradWs<T> w{};
     w.WT = a.take(gp.wt_total);
     w.gb = carve_grad<T>(s, gp, a, ng);
+    if (seedbuf && !kp) w.cot = a.take((size_t)2 * ds::PV * ng);      // the Jacobian pass: its one-hot seeds
     if (kp) {
         a.align(4);                  // k_syrk reads its operands as 4-element vectors
         w.P1 = a.take(kp->p1 * ng);
@@ -486,8 +519,8 @@ GradWs<T> carve_grad_pass(const ds_system* s, const GradPlan& gp, const KfacPlan
     return w;
 }
 
-inline PassSize grad_pass_size(const ds_system* s, const GradPlan& gp, const KfacPlan* kp) {
-    auto extent = [&](int64_t ng) { return measure([&](Arena<double>& a) { carve_grad_pass<double>(s, gp, kp, true, a, ng); }); };
+inline PassSize grad_pass_size(const ds_system* s, const GradPlan& gp, const KfacPlan* kp, bool seedbuf = false) {
+    auto extent = [&](int64_t ng) { return measure([&](Arena<double>& a) { carve_grad_pass<double>(s, gp, kp, true, a, ng, seedbuf); }); };
     return PassSize{extent(0), extent(1) - extent(0)};
 }
 
@@ -538,6 +571,57 @@ int logpsi_vjp_impl(ds_system* s, const void* params, const void* x, int64_t B, 
                         true, ws, ws_bytes, st, [&](const GradPlan& gp, const GradWs<T>& w, int64_t b0, int64_t Bc, bool) {
                             return seed_logdet<T>(s, gp, w.gb, (const T*)params, (const T*)cot + 2 * b0, Bc, st);
                         });
+}
+
+// Per-walker Jacobian (ds_jac.h): per chunk the value chain once, then two reverse sweeps with the per-walker sink -- the seed
+// (1, 0) on every walker fills the rows b (d log|psi_b|), the seed (0, 1) the rows B + b (d arg psi_b).  The sweep writes only
+// its own cotangent buffers (and MEANL, the value chain's scratch): every activation the second sweep reads is still what the
+// value chain left, so the chain is not rerun.  A chunk holds at most JAC_MAX_GROUPS groups (its walkers are a grid dimension).
+constexpr int64_t JAC_MAX_GROUPS = 512;
+
+int64_t jacobian_bytes(const ds_system* s, int64_t B) {
+    GradPlan gp;
+    if (grad_plan(s, &gp)) return -1;
+    const int64_t esz = s->dtype == 0 ? 8 : 4;
+    const int64_t groups = groups_per_pass(B, esz, grad_pass_size(s, gp, nullptr, true), (int64_t)32 << 30);
+    return (int64_t)measure([&](Arena<double>& a) { carve_grad_pass<double>(s, gp, nullptr, true, a, groups, true); }) * esz + 256;
+}
+
+template <typename T>
+int logpsi_jacobian_impl(ds_system* s, const void* params_, const void* x_, int64_t B, void* jac_, int64_t ld, void* out_logabs_,
+                         void* out_phase_, void* ws, int64_t ws_bytes, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const int PV = ds::PV;
+    const T* params = (const T*)params_;
+    T *jac = (T*)jac_, *out_logabs = (T*)out_logabs_, *out_phase = (T*)out_phase_;
+    GradPlan gp;
+    if (int rc = grad_plan(s, &gp)) return rc;
+    int64_t cg = groups_that_fit(ws_bytes, sizeof(T), grad_pass_size(s, gp, nullptr, true));
+    if (cg < 1) return fail("workspace too small for the per-walker Jacobian: %lld bytes", (long long)ws_bytes);
+    cg = std::min(cg, JAC_MAX_GROUPS);
+    bool first = true;
+    for (int64_t b0 = 0; b0 < B; b0 += cg * PV) {
+        const int64_t Bc = std::min<int64_t>(cg * PV, B - b0);
+        const T* x = (const T*)x_ + b0 * 3 * S.N;
+        Arena<T> a = arena_of<T>(ws, ws_bytes);
+        const GradWs<T> w = carve_grad_pass<T>(s, gp, nullptr, true, a, (Bc + PV - 1) / PV, true);
+        if (!a.ok) return carve_fail("the per-walker Jacobian");
+        if (first) grad_transposes<T>(s, gp, params, w.WT, st);
+        if (int rc = run_value_chain<T>(s, params, x, Bc, w.gb.vb, st, out_logabs ? out_logabs + b0 : nullptr,
+                                        out_phase ? out_phase + 2 * b0 : nullptr)) return rc;
+        for (int half = 0; half < 2; ++half) {
+            T* rows = jac + (size_t)(half * B + b0) * (size_t)ld;
+            hipLaunchKernelGGL((ds::k_jac_zero<T>), dim3((unsigned)((s->nparams + 255) / 256), (unsigned)Bc), dim3(256), 0, st, rows, (size_t)ld,
+                               (long)s->nparams, (long)Bc);
+            hipLaunchKernelGGL((ds::k_jac_seed<T>), dim3((unsigned)((Bc + 255) / 256)), dim3(256), 0, st, w.cot, (long)Bc, half);
+            if (int rc = seed_logdet<T>(s, gp, w.gb, params, w.cot, Bc, st)) return rc;
+            const JacSink<T> js{rows, (size_t)ld};
+            if (int rc = sweep_from_seed<T>(s, gp, w.gb, params, w.WT, x, Bc, true, (T*)nullptr, st, nullptr, &js)) return rc;
+        }
+        first = false;
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
 }
 
 // KFAC factor pass: the value chain, the seed (sqrt2, 0) on every walker, one reverse sweep.
@@ -700,6 +784,21 @@ int ds_logpsi_vjp(ds_system* s, const void* params, const void* x, int64_t B, co
         return 0;
     }
     return DS_BY_DTYPE(s->dtype, logpsi_vjp_impl, s, params, x, B, cot, grad, out_logabs, out_phase, ws, ws_bytes, st);
+}
+
+int64_t ds_jacobian_workspace_bytes(const ds_system* s, int64_t B) {
+    if (!s) return -1;
+    return jacobian_bytes(s, B);
+}
+
+int ds_logpsi_jacobian(ds_system* s, const void* params, const void* x, int64_t B, void* jac, int64_t ld, void* out_logabs,
+                       void* out_phase, void* ws, int64_t ws_bytes, void* stream) {
+    if (s) ++s->call_seq;
+    if (!s || !params) return fail("null argument");
+    if (B <= 0) return 0;                               // the empty batch has no rows
+    if (!x || !jac || !ws) return fail("null argument");
+    if (ld < s->nparams) return fail("ds_logpsi_jacobian: ld = %lld is smaller than the parameter count %lld", (long long)ld, (long long)s->nparams);
+    return DS_BY_DTYPE(s->dtype, logpsi_jacobian_impl, s, params, x, B, jac, ld, out_logabs, out_phase, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int ds_kfac_block_count(const ds_system* s) {

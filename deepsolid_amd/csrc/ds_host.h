@@ -1,5 +1,5 @@
 // ds_host.h -- what the host units of libdeepsolid_hip.so share (ds_api.hip, ds_chain.hip, ds_det.hip, ds_value.hip,
-// ds_gradpass.hip, ds_sample.hip, ds_dmc.hip, ds_observe.hip) on top of ds_base.h: the workspace arena, the handle, the workspace layouts of the
+// ds_gradpass.hip, ds_minsr.hip, ds_sample.hip, ds_dmc.hip, ds_observe.hip) on top of ds_base.h: the workspace arena, the handle, the workspace layouts of the
 // two chains and the few functions that one unit calls in another.  Internal to the library.
 #pragma once
 #include "ds_base.h"

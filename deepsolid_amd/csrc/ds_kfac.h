@@ -262,8 +262,9 @@ __global__ void __launch_bounds__(256) k_kinv_prep(KfacMats M, const T* __restri
 //   k_kinv_panel   C[i] = W[i][K] (saved: the update below overwrites it),  W[K][j] = P W[K][j]     for the blocks i, j != k
 //   k_kinv_update  W[i][j] -= C[i] W[K][j],  W[i][K] = -C[i] P,  W[K][K] = P                       for i != k
 // After the last step W is the inverse.  Edge blocks are handled by index: nothing beyond row / column n is read or written.
+// (The kernels that are no templates are `static`: two units include this header, ds_gradpass.hip and ds_minsr.hip.)
 // grid (2 nb), block 256
-__global__ void __launch_bounds__(256) k_kinv_diag(KfacMats M, const double* __restrict__ W, double* __restrict__ P, int k) {
+static __global__ void __launch_bounds__(256) k_kinv_diag(KfacMats M, const double* __restrict__ W, double* __restrict__ P, int k) {
     __shared__ double S[32][33];
     const int m = blockIdx.x, n = M.n[m], k0 = 32 * k;
     if (k0 >= n) return;
@@ -312,7 +313,7 @@ __device__ __forceinline__ void kinv_mma(const double* Ap, size_t lda, int ra, c
 }
 
 // grid (ceil(nbmax / 4), 2 nb), block 256: a wave per 32-wide block j of the pivot row panel
-__global__ void __launch_bounds__(256) k_kinv_panel(KfacMats M, double* __restrict__ W, const double* __restrict__ P,
+static __global__ void __launch_bounds__(256) k_kinv_panel(KfacMats M, double* __restrict__ W, const double* __restrict__ P,
                                                     double* __restrict__ Cs, int k) {
     const int m = blockIdx.y, n = M.n[m], k0 = 32 * k, nbm = (n + 31) / 32;
     const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, lr = lane & 15;
@@ -336,7 +337,7 @@ __global__ void __launch_bounds__(256) k_kinv_panel(KfacMats M, double* __restri
 }
 
 // grid (ceil(nbmax^2 / 4), 2 nb), block 256: a wave per 32 x 32 block (i, j)
-__global__ void __launch_bounds__(256) k_kinv_update(KfacMats M, double* __restrict__ W, const double* __restrict__ P,
+static __global__ void __launch_bounds__(256) k_kinv_update(KfacMats M, double* __restrict__ W, const double* __restrict__ P,
                                                      const double* __restrict__ Cs, int k) {
     const int m = blockIdx.y, n = M.n[m], k0 = 32 * k, nbm = (n + 31) / 32;
     const int wt = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, lr = lane & 15;
@@ -494,7 +495,7 @@ __global__ void __launch_bounds__(256) k_kprec_gemm(KfacMats M, const T* __restr
 }
 
 // sq[b] = the block's tile partials added in index order.  grid (nb), block 64
-__global__ void k_kprec_final(KfacMats M, const double* __restrict__ part, double* __restrict__ sq) {
+static __global__ void k_kprec_final(KfacMats M, const double* __restrict__ part, double* __restrict__ sq) {
     if (threadIdx.x != 0) return;
     const int b = blockIdx.x;
     double v = 0;

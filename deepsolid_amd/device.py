@@ -297,6 +297,87 @@ class DeviceSystem:
                                           ws.numel(), _stream()), 'ds_logpsi_vjp')
         return grad, la, torch.view_as_complex(ph)
 
+    def logpsi_jacobian(self, params, x, out=None, max_bytes=None):
+        """Per-walker Jacobian of log psi = log|psi| + i arg psi in the packed parameters (`ds_logpsi_jacobian`):
+        -> (J (2B, param_count): row b = d log|psi_b| / d theta, row B + b = d arg psi_b / d theta; log|psi| (B,); phase (B,)
+        complex).  `out`: a (2B, ld) tensor of the system's dtype with unit column stride and ld >= param_count to write into (J is
+        then its first param_count columns; the others are not touched).  `max_bytes` caps the workspace: the library then walks
+        the batch in more chunks, with the same bits."""
+        x = self._check_x(x)
+        B = x.shape[0]
+        p = self.pack_params(params)
+        P = self.param_count
+        if out is None:
+            out = torch.empty(2 * B, P, dtype=self.dtype, device=self.device)
+        if (out.dtype != self.dtype or not out.is_cuda or out.dim() != 2 or out.shape[0] != 2 * B or out.shape[1] < P
+                or (B > 0 and (out.stride(1) != 1 or out.stride(0) < out.shape[1]))):
+            raise ValueError(f'out must be a ({2 * B}, >= {P}) {self.dtype} device tensor with contiguous rows')
+        la = torch.empty(B, dtype=self.dtype, device=self.device)
+        ph = torch.empty(B, 2, dtype=self.dtype, device=self.device)
+        if B > 0:
+            ws = self._workspace('ds_jacobian_workspace_bytes', int(B), max_bytes=max_bytes)
+            _lib.check(self.lib.ds_logpsi_jacobian(self.handle, _ptr(p), _ptr(x), B, _ptr(out), int(out.stride(0)), _ptr(la), _ptr(ph),
+                                                   _ptr(ws), ws.numel(), _stream()), 'ds_logpsi_jacobian')
+        return out[:, :P], la, torch.view_as_complex(ph)
+
+    # Linear algebra on a Jacobian (`ds_minsr_*`): no system handle, any (R, P).  jac: (R, >= P) float64 / float32 device tensor
+    # with contiguous rows, of which the first P columns count; vectors and G are float64.
+    @staticmethod
+    def _minsr_jac(jac, P=None):
+        if not jac.is_cuda or jac.dim() != 2 or jac.dtype not in _DTYPES or jac.stride(1) != 1:
+            raise ValueError('jac must be a 2-d float64 / float32 device tensor with contiguous rows')
+        P = jac.shape[1] if P is None else int(P)
+        if not 0 < P <= jac.shape[1] or jac.shape[0] < 1:
+            raise ValueError(f'jac is {tuple(jac.shape)}: P = {P} columns do not fit')
+        return _lib.load(), int(jac.shape[0]), P, int(jac.stride(0))
+
+    @staticmethod
+    def _minsr_ws(lib, device, fn, *args):
+        need = int(getattr(lib, fn)(*args))
+        if need < 0:
+            _lib.check(1, fn)
+        return torch.empty(max(need, 8), dtype=torch.uint8, device=device)
+
+    @staticmethod
+    def minsr_gram(jac, P=None):
+        """G = J J^T (R, R) float64, exactly symmetric (`ds_minsr_gram`)."""
+        lib, R, P, ld = DeviceSystem._minsr_jac(jac, P)
+        ws = DeviceSystem._minsr_ws(lib, jac.device, 'ds_minsr_gram_workspace_bytes', R, P)
+        G = torch.empty(R, R, dtype=torch.float64, device=jac.device)
+        _lib.check(lib.ds_minsr_gram(_DTYPES[jac.dtype], _ptr(jac), R, P, ld, _ptr(G), _ptr(ws), ws.numel(), _stream()), 'ds_minsr_gram')
+        return G
+
+    @staticmethod
+    def minsr_matvec(jac, v, transpose=False, P=None):
+        """J v (R,) or, with `transpose`, J^T v (P,), float64 (`ds_minsr_matvec`)."""
+        lib, R, P, ld = DeviceSystem._minsr_jac(jac, P)
+        n_in, n_out = (R, P) if transpose else (P, R)
+        v = v.to(device=jac.device, dtype=torch.float64).contiguous()
+        if v.numel() != n_in:
+            raise ValueError(f'v must hold {n_in} entries, got {v.numel()}')
+        out = torch.empty(n_out, dtype=torch.float64, device=jac.device)
+        _lib.check(lib.ds_minsr_matvec(_DTYPES[jac.dtype], 1 if transpose else 0, _ptr(jac), R, P, ld, _ptr(v), _ptr(out), _ptr(None), 0,
+                                       _stream()), 'ds_minsr_matvec')
+        return out
+
+    @staticmethod
+    def minsr_solve(G, rhs, scale=1.0, damping=1e-3, block=0):
+        """zeta of (scale H G H + damping I) zeta = rhs in float64; H centres each consecutive `block` rows and columns
+        (0: no centring) (`ds_minsr_solve`)."""
+        if not G.is_cuda or G.dim() != 2 or G.shape[0] != G.shape[1] or G.dtype != torch.float64:
+            raise ValueError('G must be a square float64 device tensor')
+        lib, R = _lib.load(), int(G.shape[0])
+        G = G.contiguous()
+        rhs = rhs.to(device=G.device, dtype=torch.float64).contiguous()
+        if rhs.numel() != R:
+            raise ValueError(f'rhs must hold {R} entries, got {rhs.numel()}')
+        need = int(lib.ds_minsr_solve_workspace_bytes(R, int(block)))
+        ws = torch.empty(max(need, 8), dtype=torch.uint8, device=G.device)       # (a refused shape: the call below names the reason)
+        zeta = torch.empty(R, dtype=torch.float64, device=G.device)
+        _lib.check(lib.ds_minsr_solve(R, int(block), float(scale), float(damping), _ptr(G), _ptr(rhs), _ptr(zeta), _ptr(ws), ws.numel(),
+                                      _stream()), 'ds_minsr_solve')
+        return zeta
+
     def pretrain_loss_vjp(self, params, x, targets, max_bytes=None):
         """Orbital-matching loss of pretrain.py:70-94 and its packed parameter gradient (`ds_pretrain_loss_vjp`).
         `targets`: the reference's list, one complex (B, n_s, n_s) tensor [walker, electron, orbital] per spin with

@@ -313,7 +313,7 @@ def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations
                  save_path=None, save_every=None, stats_file_name='train_stats', laplacian_mode='for',
                  partition_number=3, t_init=0, opt_state=None, check_nan=True, max_rejected=20, complex_polarization=False,
                  structure_factor=False, structure_factor_nq=4, pretrain_iterations=0, pretrain_lr=5e-3, scf_approx=None,
-                 optimizer='adam', kfac=None, pretrain_method='net', pretrain_steps=1, pseudopotential=None):
+                 optimizer='adam', kfac=None, pretrain_method='net', pretrain_steps=1, pseudopotential=None, spring=None):
     """The `optimizer='adam'` branch of the reference driver (process.py:204-219, 256-383): burn-in, then per iteration
     ``mcmc_step -> value_and_grad(total_energy) -> gradient pmean -> Adam -> CSV row -> width adaptation``, with
     checkpoints in the reference's layout (`deepsolid_amd.checkpoint.save`) every `save_every` iterations.
@@ -342,13 +342,19 @@ def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations
     (invert_every, damping, cov_ema_decay, norm_constraint, l2_reg; momentum must be 0, register_only_generic False); `learning_rate`
     is then the schedule of the optimizer's own step count.  `opt_state` of a resumed run is the dict `checkpoint.restore` returns
     (through `checkpoint.opt_state_to_single_device`).
-    `pseudopotential`: as in `run_inference`; both optimizers take their energies from `aux.local_energy` of the same
+    `optimizer='spring'`: SPRING on the per-walker Jacobian (`deepsolid_amd.spring`; beyond the reference): Jacobian pass, Gram
+    matrix, solve and the two matrix-vector products on the GPU every iteration; one rank only.  `spring`: dict of the keys
+    damping (1e-3), mu (0.99; 0 is MinSR), norm_constraint (1e-3); `learning_rate` is the schedule of the optimizer's own step
+    count.  `opt_state` of a resumed run as for kfac.
+    `pseudopotential`: as in `run_inference`; all optimizers take their energies from `aux.local_energy` of the same
     `total_energy`, so the gradient follows without another change."""
     from . import checkpoint
-    if optimizer not in ('adam', 'kfac'):
-        raise ValueError(f"optimizer must be 'adam' or 'kfac', got {optimizer!r}")
+    if optimizer not in ('adam', 'kfac', 'spring'):
+        raise ValueError(f"optimizer must be 'adam', 'kfac' or 'spring', got {optimizer!r}")
     if kfac is not None and optimizer != 'kfac':
         raise ValueError("the `kfac` settings need optimizer='kfac'")
+    if spring is not None and optimizer != 'spring':
+        raise ValueError("the `spring` settings need optimizer='spring'")
     if pretrain_method not in ('net', 'hf'):
         raise ValueError(f"pretrain_method must be 'net' or 'hf', got {pretrain_method!r}")
     if pretrain_method == 'hf' and scf_approx is None:
@@ -393,6 +399,18 @@ def run_training(slog_net, logdet_net, params, data, simulation_cell, iterations
         if opt_state is None:
             opt_state = kfac_opt[0](params)
         step = kfac_mod.make_kfac_training_step(mcmc_step, total_energy, kfac_opt, check_nan=check_nan)
+    elif optimizer == 'spring':
+        from . import spring as spring_mod
+        cfg = dict(spring or {})
+        known = {'damping': 1e-3, 'mu': 0.99, 'norm_constraint': 1e-3}
+        unknown = sorted(set(cfg) - set(known))
+        if unknown:
+            raise ValueError(f'unknown spring settings {unknown} (known: {sorted(known)})')
+        cfg = {**known, **cfg}
+        spring_opt = spring_mod.spring(schedule, damping=cfg['damping'], mu=cfg['mu'], norm_constraint=cfg['norm_constraint'])
+        if opt_state is None:
+            opt_state = spring_opt[0](params)
+        step = spring_mod.make_spring_training_step(mcmc_step, total_energy, spring_opt, check_nan=check_nan)
     else:
         opt_init, opt_update = train.adam(schedule)
         if opt_state is None:

@@ -91,11 +91,16 @@ def make_loss(network, batch_network, simulation_cell, clip_local_energy=5.0, cl
         return re, AuxiliaryLossData(variance=var, local_energy=e_l, imaginary=im, kinetic=ke, ewald=ew, n_nonfinite=bad,
                                      pseudopotential=pp)
 
-    def value_and_grad_packed(params, data):
-        """-> ((loss, aux), packed gradient of this rank's walkers)."""
+    def value_and_clip_diff(params, data):
+        """-> ((loss, aux), clip_diff (B,) complex): the numerator of the gradient's cotangent, clip(E_L - loss).  The packed
+        gradient below and the sample-space optimizers (`spring`) both start from it."""
         loss, aux = total_energy(params, data)
         diff = aux.local_energy - loss                                 # :101
-        clip_diff = clip_difference(diff, clip_local_energy, clip_type)
+        return (loss, aux), clip_difference(diff, clip_local_energy, clip_type)
+
+    def value_and_grad_packed(params, data):
+        """-> ((loss, aux), packed gradient of this rank's walkers)."""
+        (loss, aux), clip_diff = value_and_clip_diff(params, data)
         cot = clip_diff / data.shape[0]                                # :136 mean over the batch
         flat, _, _ = system.logpsi_vjp(params, data, cot)
         return (loss, aux), flat
@@ -106,6 +111,7 @@ def make_loss(network, batch_network, simulation_cell, clip_local_energy=5.0, cl
 
     total_energy.value_and_grad = value_and_grad
     total_energy.value_and_grad_packed = value_and_grad_packed
+    total_energy.value_and_clip_diff = value_and_clip_diff
     total_energy.system = system
     total_energy.pseudopotential_energy = pp_fun
     return total_energy

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """End-to-end example on one MI355X: variational Monte Carlo of the 4-electron LiH cell with the reference's default
-network -- a few Adam (or KFAC) iterations (train.py / process.py), then an energy evaluation of the result
+network -- a few Adam (or KFAC, or SPRING) iterations (train.py / process.py), then an energy evaluation of the result
 (process.py `optimizer='none'`).  Synthetic start (random parameters, uniform walkers): the numbers are not physics,
-the point is the call sequence.  usage: python examples/vmc_lih.py [iterations] [batch] [--pretrain N] [--optimizer adam|kfac]   (N iterations of orbital-matching pretraining against
+the point is the call sequence.  usage: python examples/vmc_lih.py [iterations] [batch] [--pretrain N] [--optimizer adam|kfac|spring]   (N iterations of orbital-matching pretraining against
 the plane waves of the network's own k list first, process.py:148-177; --optimizer kfac: the reference's default optimizer,
-process.py:209-228, with the learning-rate schedule of base_config.py:46-51;
+process.py:209-228, with the learning-rate schedule of base_config.py:46-51; --optimizer spring: SPRING on the per-walker Jacobian,
+deepsolid_amd.spring, with the same schedule;
 --hf FILE.npz: pretrain against the Hartree-Fock orbitals dumped into FILE.npz (deepsolid_amd.hf.GaussianOrbitals, INTEGRATION.md:
 a calculation of THIS 4-electron cell) instead of plane waves, the network taking the file's k list; --pretrain-method net|hf:
 move the pretraining walkers on the network's density or on the Hartree-Fock density, process.py:148,164; hf needs --hf;

@@ -237,6 +237,40 @@ int ds_kfac_inverses_sized(int dtype, int n_blocks, const int32_t* d_in, const i
                            const void* factors, double ema_weight, double damping, void* inverses, void* ws, int64_t ws_bytes,
                            void* stream);
 
+/* Per-walker Jacobian of log psi_b = u_b + i phi_b (u = log|psi|, phi = arg psi) with respect to the packed parameters: the
+ * primitive of the sample-space optimizers (MinSR, SPRING; deepsolid_amd/spring.py).  jac is (2B, ld) row-major in the system's
+ * dtype, ld >= ds_param_count(): row b = d u_b / d theta, row B + b = d phi_b / d theta, in the packed layout of
+ * ds_param_layout -- the gradient ds_logpsi_vjp returns for a cotangent that is (1, 0), resp. (0, 1), on walker b and zero
+ * elsewhere.  Every column in [0, ds_param_count()) of every row is written, padding columns with exact zeros; columns beyond
+ * are not touched.  out_logabs / out_phase optional, as in ds_logpsi_vjp.  Per chunk of the batch that fits ws the value chain
+ * runs once and the reverse sweep twice (seed (1, 0), then (0, 1), on every walker; the sweep leaves the chain's buffers
+ * intact), with the per-walker kernels of csrc/ds_jac.h in place of the batch-summed contractions.  Nothing is allocated or
+ * synchronised.  All sums run in a fixed order without atomics: two calls give the same bits, a capped workspace gives the
+ * same bits as an uncapped one.  B = 0 succeeds and writes nothing.  Every network option of ds_system_desc is supported. */
+int64_t ds_jacobian_workspace_bytes(const ds_system* sys, int64_t B);
+int ds_logpsi_jacobian(ds_system* sys, const void* params, const void* x, int64_t B, void* jac, int64_t ld, void* out_logabs,
+                       void* out_phase, void* ws, int64_t ws_bytes, void* stream);
+
+/* Linear algebra on such a Jacobian (csrc/ds_minsr.h), without a system handle: jac is (R, ld) row-major, P <= ld columns count.
+ * dtype 0: float64 operands, 1: float32 (converted on load).  All accumulation is float64; no atomics: two calls give the same
+ * bits.  Each call enqueues on `stream`, allocates nothing and reads nothing back; ws: what its *_workspace_bytes reports.
+ * ds_minsr_gram:   G = J J^T (R x R float64).  Only the 128 x 128 tiles on and above the diagonal are computed, on
+ *   v_mfma_f64_16x16x4_f64 from LDS-staged row panels; both triangles are written from them: symmetric to the bit.  For small R
+ *   the P axis is split over workgroups and the partials are added in index order (the split depends on the shape alone).
+ * ds_minsr_matvec: mode 0: out = J v (R,), mode 1: out = J^T v (P,); v and out float64.  One pass over J, fixed-order sums.
+ * ds_minsr_solve:  (scale H G H + lambda I) zeta = rhs in float64.  H centres each consecutive `block` rows and columns
+ *   (block = 0: no centring); R % block == 0 and lambda > 0 are checked before any launch.  The matrix is formed exactly
+ *   symmetric from the upper triangle of G, inverted by the blocked Gauss-Jordan elimination and Newton step of the KFAC
+ *   inverses (csrc/ds_kfac.h), and zeta = X rhs takes one step of iterative refinement against the matrix itself. */
+int64_t ds_minsr_gram_workspace_bytes(int64_t R, int64_t P);
+int ds_minsr_gram(int dtype, const void* jac, int64_t R, int64_t P, int64_t ld, double* G, void* ws, int64_t ws_bytes, void* stream);
+int64_t ds_minsr_matvec_workspace_bytes(int mode, int64_t R, int64_t P);
+int ds_minsr_matvec(int dtype, int mode, const void* jac, int64_t R, int64_t P, int64_t ld, const double* v, double* out, void* ws,
+                    int64_t ws_bytes, void* stream);
+int64_t ds_minsr_solve_workspace_bytes(int64_t R, int64_t block);
+int ds_minsr_solve(int64_t R, int64_t block, double scale, double lambda, const double* G, const double* rhs, double* zeta, void* ws,
+                   int64_t ws_bytes, void* stream);
+
 /* network.eval_func method 'eval_mats' (network.py:601): out_up (B, n_det, n_up, n_up, 2),
  * out_dn (B, n_det, n_dn, n_dn, 2), complex as (Re, Im) pairs. */
 int ds_orbitals(ds_system* sys, const void* params, const void* x, int64_t B,
