@@ -63,6 +63,17 @@ class EcpDesc(C.Structure):
 
 # name -> (restype, argtypes); every symbol declared in include/deepsolid_hip.h
 _VP = C.c_void_p
+
+
+def _dmc_step_sig(n_lead, n_noise, n_out, ecp):
+    """The three DMC step entries share their argument list: `n_lead` pointers (handles, params, the state arrays), B, steps, tau,
+    tau_eff, e_trial, e_ref, e_cut, node_mode, branch_every, seed, offset, `n_noise` explicit noise arrays, (with `ecp`:
+    pair_capacity,) state_valid, `n_out` output arrays, (with `ecp`: steps_done,) then ws, ws_bytes, stream."""
+    step = [C.c_int64, C.c_int] + [C.c_double] * 5 + [C.c_int, C.c_int, C.c_uint64, C.c_uint64]
+    return (C.c_int, [_VP] * n_lead + step + [_VP] * n_noise + ([C.c_int64] if ecp else []) + [C.c_int] + [_VP] * n_out +
+            ([C.POINTER(C.c_int)] if ecp else []) + [_VP, C.c_int64, _VP])
+
+
 SIGNATURES = {
     'ds_device_widths': (C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -130,16 +141,11 @@ SIGNATURES = {
     'ds_ecp_energy': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_uint64, C.c_uint64, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP,
                                C.c_int64, _VP]),
     'ds_dmc_workspace_bytes': (C.c_int64, [_VP, C.c_int64]),
-    'ds_dmc_step': (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
-                             C.c_double, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _VP, _VP, _VP, C.c_int, _VP, _VP, _VP, C.c_int64, _VP]),
+    'ds_dmc_step': _dmc_step_sig(8, 3, 2, ecp=False),
     'ds_dmc_ecp_workspace_bytes': (C.c_int64, [_VP, _VP, C.c_int64, C.c_int64]),
-    'ds_dmc_step_ecp': (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int, C.c_double, C.c_double,
-                                 C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _VP, _VP, _VP, _VP,
-                                 C.c_int64, C.c_int, _VP, _VP, _VP, _VP, C.POINTER(C.c_int), _VP, C.c_int64, _VP]),
+    'ds_dmc_step_ecp': _dmc_step_sig(10, 4, 4, ecp=True),
     'ds_dmc_tmove_workspace_bytes': (C.c_int64, [_VP, _VP, C.c_int64, C.c_int64]),
-    'ds_dmc_step_tmove': (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, C.c_int, C.c_double, C.c_double,
-                                   C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _VP, _VP, _VP, _VP, _VP,
-                                   C.c_int64, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(C.c_int), _VP, C.c_int64, _VP]),
+    'ds_dmc_step_tmove': _dmc_step_sig(10, 5, 6, ecp=True),
     'ds_dmc_noise': (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int, C.c_uint64, C.c_uint64, _VP, _VP, _VP, _VP]),
     'ds_dmc_branch_workspace_bytes':(C.c_int64, [C.c_int, C.c_int, C.c_int64]),
     'ds_dmc_branch': (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),

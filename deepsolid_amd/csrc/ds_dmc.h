@@ -7,11 +7,12 @@
 //   k_dmc_accept       one wave per walker: the two squared norms, the decision, the weight, the selected rows, (p, flags)
 //   k_dmc_stats        one workgroup per DMC_GROUP consecutive walkers: one row of float64 partials
 //   k_dmc_stats_final  adds the rows in workgroup order: one row of out_stats
-// With a pseudopotential (ds_dmc_step_ecp, locality approximation) ds_ecp_energy's launches follow the chain pass at x', the ECP
-// instances of k_dmc_init / k_dmc_accept take its float64 triple, k_dmc_ecp_stats / k_dmc_ecp_stats_final form the row of
-// out_ecp_stats, and k_dmc_gather_epp follows the comb.  With T-moves (ds_dmc_step_tmove) the pseudopotential is evaluated after
-// the decision: the kernels at the end of this file.
 // and on a branching step the comb (k_dmc_scan_chunks, k_dmc_scan_offsets, k_dmc_select, k_dmc_gather, k_dmc_copy_back).
+// With a pseudopotential (ds_dmc_step_ecp, locality approximation) ds_ecp_energy's launches follow the chain pass at x', the ECP
+// instances of k_dmc_init / k_dmc_accept take its float64 triple, k_dmc_col_stats<3> / k_dmc_col_stats_final<3> form the row of
+// out_ecp_stats, and k_dmc_gather_epp follows the comb.  With T-moves (ds_dmc_step_tmove) the pseudopotential is evaluated after
+// the decision: the kernels at the end of this file.  All three steps take the decision of dmc_decide and set a walker's chain
+// scalars with dmc_set_walker; every stats row goes through the one LDS tree of dmc_group_tree.
 //
 // Prefix sums of the weights, the order the numpy model reproduces bit for bit (DMC_CHUNK = 256):
 //   chunk c holds walkers 256 c .. 256 c + 255;  r_0 = w_first, r_i = r_{i-1} + w_i  (sequential inside the chunk);
@@ -87,47 +88,54 @@ __device__ __forceinline__ double dmc_energy_ecp(double e, const double* __restr
     return (e + epp[3 * w]) + epp[3 * w + 1];
 }
 
-// state_valid = 0: drift = Re grad, eloc = Re ke + ewald; a walker whose log|psi| or E_L is not finite gets weight 0.  ECP: the
-// triple epp2 enters E_L and becomes the walker's epp
-template <typename T, bool ECP = false>
-__global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_init(long long B, int n3, const T* __restrict__ gc, const T* __restrict__ ke,
-                                                             const T* __restrict__ ew3, const T* __restrict__ logabs,
-                                                             T* __restrict__ drift, double* __restrict__ eloc, double* __restrict__ weight,
-                                                             const double* __restrict__ epp2 = nullptr, double* __restrict__ epp = nullptr) {
-    const long long w = (long long)blockIdx.x * DMC_WAVES + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (w >= B) return;
+// One wave on walker w after a chain pass (gc, ke, ew3, la: its outputs): drift = Re grad, eloc = Re ke + ewald (ECP: with the triple
+// epp2); a walker whose log|psi| or E_L is not finite gets weight 0
+template <typename T, bool ECP>
+__device__ __forceinline__ void dmc_set_walker(long long w, int lane, int n3, const T* __restrict__ gc, const T* __restrict__ ke,
+                                               const T* __restrict__ ew3, const T* __restrict__ la, const double* __restrict__ epp2,
+                                               T* __restrict__ drift, double* __restrict__ eloc, double* __restrict__ weight) {
     for (int c = lane; c < n3; c += 64) drift[(size_t)w * n3 + c] = gc[2 * ((size_t)w * n3 + c)];
     if (lane == 0) {
         double e = dmc_energy(ke, ew3, w);
-        if constexpr (ECP) {
-            e = dmc_energy_ecp(e, epp2, w);
-            for (int c = 0; c < 3; ++c) epp[3 * w + c] = epp2[3 * w + c];
-        }
+        if constexpr (ECP) e = dmc_energy_ecp(e, epp2, w);
         eloc[w] = e;
-        if (!isfinite(e) || !isfinite((double)logabs[w])) weight[w] = 0.0;
+        if (!isfinite(e) || !isfinite((double)la[w])) weight[w] = 0.0;
     }
 }
 
-// One wave per walker.  Lanes stride the electrons for |chi|^2 and |chi + sqrt(tau) (vbar + vbar')|^2 (float64 sums; the butterfly
-// adds them in a fixed order), every lane then holds the same decision, lane 0 updates the scalars, the wave copies the rows.
-// ECP: the triple epp2 at x' enters E' and is selected into epp with the other rows; epp2 then holds the walker's selected triple
-// too (the source of the comb's gather, k_dmc_gather_epp).
-template <typename T, bool ECP = false>
-__global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_accept(DmcArgs A, T* __restrict__ x, T* __restrict__ logabs, T* __restrict__ phase,
-                                                               T* __restrict__ drift, double* __restrict__ eloc,
-                                                               double* __restrict__ weight, const T* __restrict__ x2,
-                                                               const T* __restrict__ la2, const T* __restrict__ ph2,
-                                                               const T* __restrict__ gc2, const T* __restrict__ ke2,
-                                                               const T* __restrict__ ew2, const T* __restrict__ chi,
-                                                               const T* __restrict__ uniform, PhiloxKey key, unsigned long long step,
-                                                               double* __restrict__ pacc, int* __restrict__ flags,
-                                                               double* __restrict__ epp2 = nullptr, double* __restrict__ epp = nullptr) {
+// state_valid = 0: dmc_set_walker on the chain pass at x.  ECP: the triple epp2 enters E_L and becomes the walker's epp
+template <typename T, bool ECP>
+__global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_init(long long B, int n3, const T* __restrict__ gc, const T* __restrict__ ke,
+                                                             const T* __restrict__ ew3, const T* __restrict__ logabs,
+                                                             T* __restrict__ drift, double* __restrict__ eloc, double* __restrict__ weight,
+                                                             const double* __restrict__ epp2, double* __restrict__ epp) {
     const long long w = (long long)blockIdx.x * DMC_WAVES + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    if (w >= A.B) return;
-    const int n3 = 3 * A.N;
-    const size_t row = (size_t)w * n3;
+    if (w >= B) return;
+    dmc_set_walker<T, ECP>(w, lane, n3, gc, ke, ew3, logabs, epp2, drift, eloc, weight);
+    if constexpr (ECP)
+        if (lane == 0)
+            for (int c = 0; c < 3; ++c) epp[3 * w + c] = epp2[3 * w + c];
+}
+
+// The decision of one wave on walker w, the same in the three steps.  Lanes stride the electrons for |chi|^2 and
+// |chi + sqrt(tau) (vbar + vbar')|^2 (float64 sums; the butterfly adds them in a fixed order); every lane then holds the same
+// decision.  e_prop_of() is the caller's energy at x', whose finiteness the decision asks for: the chain part, to which the locality
+// step adds the triple.  It is a callable so that it is evaluated behind the wave sums, where both kernels had it: evaluated in
+// front of them, k_dmc_tm_decide<double> takes 66 VGPRs instead of 58 and loses a wave of occupancy.
+// flags: DMC_ACCEPTED, DMC_NONFINITE, DMC_NODE (the caller adds DMC_CLIPPED); pacc(): min(1, exp A), 0 for a refused proposal.
+struct DmcDecision {
+    double a_log, e_prop;
+    bool open, acc;                                    // open: the proposal is finite and on the allowed side of the node
+    int flags;
+    __device__ __forceinline__ double pacc() const { return open ? (a_log < 0.0 ? exp(a_log) : 1.0) : 0.0; }
+};
+template <typename T, typename F>
+__device__ __forceinline__ DmcDecision dmc_decide(const DmcArgs& A, long long w, int lane, const T* __restrict__ logabs,
+                                                  const T* __restrict__ phase, const T* __restrict__ drift, const T* __restrict__ la2,
+                                                  const T* __restrict__ ph2, const T* __restrict__ gc2, const T* __restrict__ chi,
+                                                  const T* __restrict__ uniform, PhiloxKey key, unsigned long long step, const F& e_prop_of) {
+    const size_t row = (size_t)w * 3 * A.N;
     double s1 = 0.0, s2 = 0.0;
     for (int e = lane; e < A.N; e += 64) {
         const size_t o = row + 3 * e;
@@ -142,9 +150,7 @@ __global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_accept(DmcArgs A, T* __r
     s1 = wave_sum(s1); s2 = wave_sum(s2);
     const double la_new = (double)la2[w], la_old = (double)logabs[w];
     const double a_log = 2.0 * (la_new - la_old) + 0.5 * (s1 - s2);
-    double e_prop = dmc_energy(ke2, ew2, w);
-    if constexpr (ECP) e_prop = dmc_energy_ecp(e_prop, epp2, w);
-    const double e_old = eloc[w];
+    const double e_prop = e_prop_of();
     const double u = uniform ? (double)uniform[w] : philox_uniform(key, step, (unsigned long long)w);
     const bool finite = isfinite(a_log) && isfinite(e_prop);
     const double overlap = (double)ph2[2 * w] * (double)phase[2 * w] + (double)ph2[2 * w + 1] * (double)phase[2 * w + 1];
@@ -154,6 +160,36 @@ __global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_accept(DmcArgs A, T* __r
     if (acc) fl |= DMC_ACCEPTED;
     if (!finite) fl |= DMC_NONFINITE;
     else if (!node_ok) fl |= DMC_NODE;
+    return DmcDecision{a_log, e_prop, finite && node_ok, acc, fl};
+}
+
+// One wave per walker: the decision, then lane 0 updates the scalars and the wave copies the rows.
+// ECP: the triple epp2 at x' enters E' and is selected into epp with the other rows; epp2 then holds the walker's selected triple
+// too (the source of the comb's gather, k_dmc_gather_epp).
+template <typename T, bool ECP>
+__global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_accept(DmcArgs A, T* __restrict__ x, T* __restrict__ logabs, T* __restrict__ phase,
+                                                               T* __restrict__ drift, double* __restrict__ eloc,
+                                                               double* __restrict__ weight, const T* __restrict__ x2,
+                                                               const T* __restrict__ la2, const T* __restrict__ ph2,
+                                                               const T* __restrict__ gc2, const T* __restrict__ ke2,
+                                                               const T* __restrict__ ew2, const T* __restrict__ chi,
+                                                               const T* __restrict__ uniform, PhiloxKey key, unsigned long long step,
+                                                               double* __restrict__ pacc, int* __restrict__ flags,
+                                                               double* __restrict__ epp2, double* __restrict__ epp) {
+    const long long w = (long long)blockIdx.x * DMC_WAVES + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (w >= A.B) return;
+    const int n3 = 3 * A.N;
+    const size_t row = (size_t)w * n3;
+    const DmcDecision d = dmc_decide(A, w, lane, logabs, phase, drift, la2, ph2, gc2, chi, uniform, key, step, [&] {
+        const double e = dmc_energy(ke2, ew2, w);
+        if constexpr (ECP) return dmc_energy_ecp(e, epp2, w);
+        else return e;
+    });
+    const bool acc = d.acc;
+    const double e_prop = d.e_prop;
+    int fl = d.flags;
+    const double e_old = eloc[w];
     const double e_new = acc ? e_prop : e_old;
     bool c_new, c_old;
     const double cn = dmc_clip(e_new, A.e_ref, A.e_cut, &c_new), co = dmc_clip(e_old, A.e_ref, A.e_cut, &c_old);
@@ -170,7 +206,7 @@ __global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_accept(DmcArgs A, T* __r
         const double wn = weight[w] * factor;
         weight[w] = isfinite(wn) ? wn : 0.0;              // an energy that is not finite kills the walker
         if (acc) { logabs[w] = la2[w]; phase[2 * w] = ph2[2 * w]; phase[2 * w + 1] = ph2[2 * w + 1]; eloc[w] = e_prop; }
-        pacc[w] = (finite && node_ok) ? (a_log < 0.0 ? exp(a_log) : 1.0) : 0.0;
+        pacc[w] = d.pacc();
         flags[w] = fl;
         if constexpr (ECP) {
             for (int c = 0; c < 3; ++c) {
@@ -181,34 +217,44 @@ __global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_accept(DmcArgs A, T* __r
     }
 }
 
-// ds_dmc_step_ecp: one row of partials per DMC_GROUP walkers, [sum w E_loc, sum w Re E_nl, sum w Im E_nl] over the walkers of
-// non-zero weight, in the order of k_dmc_stats (thread t takes walker g0 + t; the tree adds t and t + s) ...
-__global__ void __launch_bounds__(DMC_GROUP) k_dmc_ecp_stats(long long B, const double* __restrict__ weight, const double* __restrict__ epp,
-                                                             double* __restrict__ part) {
-    __shared__ double sh[3][DMC_GROUP];
+// The column sums of one workgroup of DMC_GROUP threads in LDS: thread t brings v[0..NC), the tree adds t and t + s, and row
+// blockIdx.x of `part` takes the NC sums.  Every stats row of this file is formed here, so its order of additions is one.
+template <int NC> __device__ __forceinline__ void dmc_group_tree(const double (&v)[NC], double* __restrict__ part) {
+    __shared__ double sh[NC][DMC_GROUP];
+    for (int j = 0; j < NC; ++j) sh[j][threadIdx.x] = v[j];
+    __syncthreads();
+    for (int s = DMC_GROUP / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s)
+            for (int j = 0; j < NC; ++j) sh[j][threadIdx.x] += sh[j][threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x < NC) part[(long long)blockIdx.x * NC + threadIdx.x] = sh[threadIdx.x][0];
+}
+
+// out_ecp_stats: one row of partials per DMC_GROUP walkers, [sum w E_loc, sum w Re E_nl, sum w Im E_nl] over the walkers of non-zero
+// weight (thread t takes walker g0 + t).  NC = 3: ds_dmc_step_ecp, choice is not read.  NC = 4: ds_dmc_step_tmove, the fourth
+// column is the number of walkers that made a T-move (choice >= 0; an exact count) ...
+template <int NC>
+__global__ void __launch_bounds__(DMC_GROUP) k_dmc_col_stats(long long B, const double* __restrict__ weight, const double* __restrict__ epp,
+                                                             const int* __restrict__ choice, double* __restrict__ part) {
     const long long w = (long long)blockIdx.x * DMC_GROUP + threadIdx.x;
-    double v[3] = {0, 0, 0};
+    double v[NC] = {};
     if (w < B) {
         const double wt = weight[w];
         if (wt != 0.0)
             for (int j = 0; j < 3; ++j) v[j] = wt * epp[3 * w + j];
+        if constexpr (NC > 3) v[3] = choice[w] >= 0 ? 1.0 : 0.0;
     }
-    for (int j = 0; j < 3; ++j) sh[j][threadIdx.x] = v[j];
-    __syncthreads();
-    for (int s = DMC_GROUP / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s)
-            for (int j = 0; j < 3; ++j) sh[j][threadIdx.x] += sh[j][threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x < 3) part[(long long)blockIdx.x * 3 + threadIdx.x] = sh[threadIdx.x][0];
+    dmc_group_tree<NC>(v, part);
 }
 
 // ... and the rows added in workgroup order: one row of out_ecp_stats
-__global__ void __launch_bounds__(64) k_dmc_ecp_stats_final(const double* __restrict__ part, long long n_groups, double* __restrict__ out) {
+template <int NC>
+__global__ void __launch_bounds__(64) k_dmc_col_stats_final(const double* __restrict__ part, long long n_groups, double* __restrict__ out) {
     const int j = threadIdx.x;
-    if (j >= 3) return;
+    if (j >= NC) return;
     double s = 0.0;
-    for (long long g = 0; g < n_groups; ++g) s += part[g * 3 + j];
+    for (long long g = 0; g < n_groups; ++g) s += part[g * NC + j];
     out[j] = s;
 }
 
@@ -227,7 +273,6 @@ __global__ void __launch_bounds__(256) k_dmc_gather_epp(long long B, const doubl
 __global__ void __launch_bounds__(DMC_GROUP) k_dmc_stats(long long B, const double* __restrict__ weight, const double* __restrict__ eloc,
                                                          const double* __restrict__ pacc, const int* __restrict__ flags,
                                                          double* __restrict__ part) {
-    __shared__ double sh[DMC_ROW - 1][DMC_GROUP];
     const long long w = (long long)blockIdx.x * DMC_GROUP + threadIdx.x;
     double v[DMC_ROW - 1] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (w < B) {
@@ -238,14 +283,7 @@ __global__ void __launch_bounds__(DMC_GROUP) k_dmc_stats(long long B, const doub
         v[3] = (fl & DMC_ACCEPTED) ? 1.0 : 0.0; v[4] = pacc[w];
         v[5] = (fl & DMC_CLIPPED) ? 1.0 : 0.0; v[6] = (fl & DMC_NONFINITE) ? 1.0 : 0.0;
     }
-    for (int j = 0; j < DMC_ROW - 1; ++j) sh[j][threadIdx.x] = v[j];
-    __syncthreads();
-    for (int s = DMC_GROUP / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s)
-            for (int j = 0; j < DMC_ROW - 1; ++j) sh[j][threadIdx.x] += sh[j][threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x < DMC_ROW - 1) part[(long long)blockIdx.x * (DMC_ROW - 1) + threadIdx.x] = sh[threadIdx.x][0];
+    dmc_group_tree<DMC_ROW - 1>(v, part);
 }
 
 // out[j] = the rows added in workgroup order; out[8] = B (a comb that follows overwrites it)
@@ -422,7 +460,7 @@ __global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_copy_back(long long B, i
 
 // ------------------------------------------------------------------------------------------------------------------ T-moves
 // ds_dmc_step_tmove evaluates the pseudopotential AFTER the decision, at the position the walker then has, so k_dmc_accept splits:
-//   k_dmc_tm_decide    one wave per walker: the decision of k_dmc_accept with E_c' = Re ke' + ewald' for E'; (p, flags) and the
+//   k_dmc_tm_decide    one wave per walker: the decision (dmc_decide) with E_c' = Re ke' + ewald' for E'; (p, flags) and the
 //                      selected position x_cur go to the workspace, the state is only read
 //   (ds_ecp_energy's launches on x_cur; a pair total above the capacity ends the call here with the state untouched)
 //   k_dmc_tm_commit    one wave per walker: selects the rows, E = ((E_c + E_loc) + Re E_nl), the one-point weight, epp, E
@@ -443,35 +481,11 @@ __global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_tm_decide(DmcArgs A, con
     if (w >= A.B) return;
     const int n3 = 3 * A.N;
     const size_t row = (size_t)w * n3;
-    double s1 = 0.0, s2 = 0.0;
-    for (int e = lane; e < A.N; e += 64) {
-        const size_t o = row + 3 * e;
-        const T g1[3] = {drift[o], drift[o + 1], drift[o + 2]}, g2[3] = {gc2[2 * o], gc2[2 * (o + 1)], gc2[2 * (o + 2)]};
-        const T f1 = dmc_limiter(g1, (T)A.tau), f2 = dmc_limiter(g2, (T)A.tau);
-        for (int c = 0; c < 3; ++c) {
-            const double ch = (double)chi[o + c];
-            const double bk = ch + A.sqrt_tau * ((double)(f1 * g1[c]) + (double)(f2 * g2[c]));
-            s1 += ch * ch; s2 += bk * bk;
-        }
-    }
-    s1 = wave_sum(s1); s2 = wave_sum(s2);
-    const double a_log = 2.0 * ((double)la2[w] - (double)logabs[w]) + 0.5 * (s1 - s2);
-    const double e_prop = dmc_energy(ke2, ew2, w);
-    const double u = uniform ? (double)uniform[w] : philox_uniform(key, step, (unsigned long long)w);
-    const bool finite = isfinite(a_log) && isfinite(e_prop);
-    const double overlap = (double)ph2[2 * w] * (double)phase[2 * w] + (double)ph2[2 * w + 1] * (double)phase[2 * w + 1];
-    const bool node_ok = A.node_mode == 0 || overlap > 0.0;
-    const bool acc = finite && node_ok && a_log > log(u);
-    const T* src = acc ? x2 : x;
+    const DmcDecision d = dmc_decide(A, w, lane, logabs, phase, drift, la2, ph2, gc2, chi, uniform, key, step,
+                                     [&] { return dmc_energy(ke2, ew2, w); });
+    const T* src = d.acc ? x2 : x;
     for (int c = lane; c < n3; c += 64) xcur[row + c] = src[row + c];
-    if (lane == 0) {
-        int fl = 0;
-        if (acc) fl |= DMC_ACCEPTED;
-        if (!finite) fl |= DMC_NONFINITE;
-        else if (!node_ok) fl |= DMC_NODE;
-        pacc[w] = (finite && node_ok) ? (a_log < 0.0 ? exp(a_log) : 1.0) : 0.0;
-        flags[w] = fl;
-    }
+    if (lane == 0) { pacc[w] = d.pacc(); flags[w] = d.flags; }
 }
 
 // epp2: the triple at x_cur; etot: E per walker for the stats row and the T-move (out_energy: a copy for the caller)
@@ -524,43 +538,8 @@ __global__ void __launch_bounds__(64 * DMC_WAVES) k_dmc_tm_refresh(long long B, 
     const long long w = (long long)blockIdx.x * DMC_WAVES + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (w >= B || choice[w] < 0) return;
-    for (int c = lane; c < n3; c += 64) drift[(size_t)w * n3 + c] = gc[2 * ((size_t)w * n3 + c)];
-    if (lane == 0) {
-        const double e = dmc_energy(ke2, ew2, w);
-        logabs[w] = la2[w]; phase[2 * w] = ph2[2 * w]; phase[2 * w + 1] = ph2[2 * w + 1]; eloc[w] = e;
-        if (!isfinite(e) || !isfinite((double)la2[w])) weight[w] = 0.0;
-    }
-}
-
-// out_ecp_stats of ds_dmc_step_tmove: the three sums of k_dmc_ecp_stats in its order, and the number of walkers that made a T-move
-// (an exact count) as the fourth column
-__global__ void __launch_bounds__(DMC_GROUP) k_dmc_tm_stats(long long B, const double* __restrict__ weight, const double* __restrict__ epp,
-                                                            const int* __restrict__ choice, double* __restrict__ part) {
-    __shared__ double sh[4][DMC_GROUP];
-    const long long w = (long long)blockIdx.x * DMC_GROUP + threadIdx.x;
-    double v[4] = {0, 0, 0, 0};
-    if (w < B) {
-        const double wt = weight[w];
-        if (wt != 0.0)
-            for (int j = 0; j < 3; ++j) v[j] = wt * epp[3 * w + j];
-        v[3] = choice[w] >= 0 ? 1.0 : 0.0;
-    }
-    for (int j = 0; j < 4; ++j) sh[j][threadIdx.x] = v[j];
-    __syncthreads();
-    for (int s = DMC_GROUP / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s)
-            for (int j = 0; j < 4; ++j) sh[j][threadIdx.x] += sh[j][threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x < 4) part[(long long)blockIdx.x * 4 + threadIdx.x] = sh[threadIdx.x][0];
-}
-
-__global__ void __launch_bounds__(64) k_dmc_tm_stats_final(const double* __restrict__ part, long long n_groups, double* __restrict__ out) {
-    const int j = threadIdx.x;
-    if (j >= 4) return;
-    double s = 0.0;
-    for (long long g = 0; g < n_groups; ++g) s += part[g * 4 + j];
-    out[j] = s;
+    dmc_set_walker<T, false>(w, lane, n3, gc, ke2, ew2, la2, nullptr, drift, eloc, weight);
+    if (lane == 0) { logabs[w] = la2[w]; phase[2 * w] = ph2[2 * w]; phase[2 * w + 1] = ph2[2 * w + 1]; }
 }
 
 }  // namespace ds

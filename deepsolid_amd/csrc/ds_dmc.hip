@@ -146,7 +146,9 @@ void launch_comb(const CombWs<T>& c, int64_t B, int n3, double xi, const double*
                        eloc, weight, stat_distinct);
 }
 
+// what the three step entries share: the six state arrays, the step, the noise, the outputs
 struct DmcCall {
+    void *x, *logabs, *phase, *drift; double *eloc, *weight;
     int64_t B; int steps; double tau, tau_eff, e_trial, e_ref, e_cut; int node_mode, branch_every;
     uint64_t seed, offset; const void *normals, *uniforms; const double* comb_uniforms; int state_valid;
     double* out_stats; int* out_parents;
@@ -157,13 +159,127 @@ struct DmcEcpCall {
     int64_t* out_pairs = nullptr; int* steps_done = nullptr;
 };
 
-template <typename T>
-int dmc_step_impl(ds_system* s, const void* params, void* x_, void* logabs_, void* phase_, void* drift_, double* eloc, double* weight,
-                  const DmcCall& q, const DmcEcpCall& p, void* ws, int64_t ws_bytes, hipStream_t st) {
+// What the three step entries refuse, in this order, before anything is launched.  name: the entry; p: what a pseudopotential adds
+// (nullptr: ds_dmc_step); given / expected: how many of the entry's explicit noise arrays are not NULL, and how many it takes.
+inline int dmc_check(const char* name, ds_system* s, const void* params, const void* ws, const DmcCall& q, const DmcEcpCall* p, int given,
+                     int expected) {
+    static const char* const noise[] = {"normals, uniforms and comb_uniforms", "normals, uniforms, comb_uniforms and rotations",
+                                        "normals, uniforms, comb_uniforms, rotations and tmove_uniforms"};
+    if (p && p->steps_done) *p->steps_done = 0;
+    if (s) ++s->call_seq;
+    if (!s || !params || !ws) return fail("%s: null argument", name);
+    if (!q.x || !q.logabs || !q.phase || !q.drift || !q.eloc || !q.weight) return fail("%s: null state pointer", name);
+    if (p && !p->epp) return fail("%s: epp is null (the seventh state array)", name);
+    if (!q.out_stats) return fail("%s: out_stats is null", name);
+    if (q.B < 1 || q.B > ds::DMC_MAX_B) return fail("%s: B must be in 1..%lld (got %lld)", name, (long long)ds::DMC_MAX_B, (long long)q.B);
+    if (q.steps < 1) return fail("%s: steps must be >= 1 (got %d)", name, q.steps);
+    if (!std::isfinite(q.tau) || !std::isfinite(q.tau_eff) || !std::isfinite(q.e_trial) || !std::isfinite(q.e_ref) || !std::isfinite(q.e_cut))
+        return fail("%s: tau, tau_eff, e_trial, e_ref and e_cut must be finite", name);
+    if (!(q.tau > 0.0)) return fail("%s: tau must be > 0 (got %g)", name, q.tau);
+    if (q.tau_eff < 0.0) return fail("%s: tau_eff must be >= 0 (got %g)", name, q.tau_eff);
+    if (q.node_mode != 0 && q.node_mode != 1)
+        return fail("%s: node_mode must be 0 (fixed phase) or 1 (fixed node) (got %d)", name, q.node_mode);
+    if (q.branch_every < 0) return fail("%s: branch_every must be >= 0 (got %d)", name, q.branch_every);
+    if (given != 0 && given != expected) return fail("%s: %s must be given together (or all NULL)", name, noise[expected - 3]);
+    if (!p) return 0;
+    if (q.offset >= (1ull << 61) || q.offset + (uint64_t)q.steps >= (1ull << 61))
+        return fail("%s: philox_offset + steps must be below 2^61 (the rotations' stream 4 lies above)", name);
+    return ecp_check(s, p->e, q.B, p->cap);
+}
+
+// the chain's chunk that the *_workspace_bytes entries provide: what ds_workspace_bytes gives the energy chain of B walkers
+inline int64_t dmc_default_chunk(const ds_system* s, int64_t B) {
+    const int64_t esz = s->dtype == 0 ? 8 : 4;
+    const int64_t chunk = std::min<int64_t>(B, s->chunk_cap);
+    return std::max<int64_t>(1, std::min<int64_t>(chunk, workspace_budget() / ((int64_t)s->ws.per_walker * esz)));
+}
+
+// What both step loops work with, built once per call behind the workspace: the typed state, the geometry of the per-walker kernels
+// and of the stats rows, the kernels' arguments, the explicit noise of step i (nullptr in Philox mode), and the launches they share.
+template <typename T> struct DmcCtx {
+    ds_system* s; const void* params; const DmcCall& q; const DmcWs<T>& w; hipStream_t st;
     const ds::SysDev<T>& S = dev<T>(s);
-    const int64_t B = q.B, esz = (int64_t)sizeof(T);
+    const int64_t B = q.B, ngroups = (B + ds::DMC_GROUP - 1) / ds::DMC_GROUP;
     const int n3 = 3 * S.N;
-    T *x = (T*)x_, *logabs = (T*)logabs_, *phase = (T*)phase_, *drift = (T*)drift_;
+    const size_t ne = (size_t)B * S.N;
+    T *x = (T*)q.x, *logabs = (T*)q.logabs, *phase = (T*)q.phase, *drift = (T*)q.drift;
+    double *eloc = q.eloc, *weight = q.weight;
+    const dim3 gw = dim3((unsigned)((B + ds::DMC_WAVES - 1) / ds::DMC_WAVES)), bw = dim3(64 * ds::DMC_WAVES);
+    const ds::DmcArgs A{q.tau, std::sqrt(q.tau), q.tau_eff, q.e_trial, q.e_ref, q.e_cut, q.node_mode, S.N, (long long)B};
+    const ds::PhiloxKey key{q.seed, q.offset};
+    const T* nz(int i) const { return q.normals ? (const T*)q.normals + (size_t)i * B * n3 : nullptr; }
+    const T* un(int i) const { return q.uniforms ? (const T*)q.uniforms + (size_t)i * B : nullptr; }
+
+    // the energy chain with both outputs at xe: KE2, EW3 and GC, log|psi| and the phase into la and ph
+    int chain(const T* xe, T* la, T* ph) const {
+        return energy_grad_forward(s, params, xe, B, w.KE2, w.EW3, la, ph, w.GC, w.wsc, w.wsc_bytes, st);
+    }
+    // state_valid = 0: the chain at x, then k_dmc_init; with epp its ECP instance, which takes the triple epp2
+    int init(const double* epp2, double* epp) const {
+        if (int rc = chain(x, logabs, phase)) return rc;
+        const auto k = epp ? ds::k_dmc_init<T, true> : ds::k_dmc_init<T, false>;
+        hipLaunchKernelGGL(k, gw, bw, 0, st, (long long)B, n3, (const T*)w.GC, (const T*)w.KE2, (const T*)w.EW3, (const T*)logabs, drift, eloc,
+                           weight, epp2, epp);
+        return 0;
+    }
+    // step i: the proposal x' into X2 (the noise that was used into NZ), then the chain at x'
+    int propose(int i) const {
+        hipLaunchKernelGGL((ds::k_dmc_propose<T>), dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, S.sim_a, S.sim_ainv, (const T*)x,
+                           (const T*)drift, nz(i), key, (unsigned long long)i, (T)q.tau, (T)A.sqrt_tau, ne, w.X2, w.NZ);
+        return chain(w.X2, w.LA2, w.PH2);
+    }
+    // row i of out_stats from the weights, the energies e and the (p, flags) of the decision -> the row
+    double* stats_row(int i, const double* e) const {
+        double* row = q.out_stats + (size_t)i * ds::DMC_ROW;
+        hipLaunchKernelGGL(ds::k_dmc_stats, dim3((unsigned)ngroups), dim3(ds::DMC_GROUP), 0, st, (long long)B, (const double*)weight, e,
+                           (const double*)w.PACC, (const int*)w.FLAGS, w.PART);
+        hipLaunchKernelGGL(ds::k_dmc_stats_final, dim3(1), dim3(64), 0, st, (const double*)w.PART, (long long)ngroups, (long long)B, row);
+        return row;
+    }
+    // one row of out_ecp_stats: NC = 3 columns from epp, with NC = 4 the count of choice >= 0
+    template <int NC> void ecp_row(const double* epp, const int* choice, double* part, double* out) const {
+        hipLaunchKernelGGL(ds::k_dmc_col_stats<NC>, dim3((unsigned)ngroups), dim3(ds::DMC_GROUP), 0, st, (long long)B, (const double*)weight,
+                           epp, choice, part);
+        hipLaunchKernelGGL(ds::k_dmc_col_stats_final<NC>, dim3(1), dim3(64), 0, st, (const double*)part, (long long)ngroups, out);
+    }
+    // The end of step i.  On a branching step the comb, which puts the distinct parents into the row (xi: comb_uniforms or stream 2
+    // at index B, one past the walkers), and with a pseudopotential the gather of epp from epp2, which the step left equal to it.
+    // Otherwise every walker is its own parent.
+    void branch(int i, double* row, const double* epp2, double* epp, int* steps_done) const {
+        int* par = q.out_parents ? q.out_parents + (size_t)i * B : nullptr;
+        if (q.branch_every > 0 && (i + 1) % q.branch_every == 0) {
+            double xi = 0.0;
+            if (!q.comb_uniforms) {
+                uint32_t r[4];
+                ds_philox_host(q.seed, q.offset, (uint64_t)i, (uint64_t)B, 2, r);
+                xi = ds::u53_co(r[0], r[1]);
+            }
+            launch_comb<T>(w.comb, B, n3, xi, q.comb_uniforms ? q.comb_uniforms + i : nullptr, x, logabs, phase, drift, eloc, weight, par,
+                           row + ds::DMC_ROW - 1, st);
+            if (epp)
+                hipLaunchKernelGGL(ds::k_dmc_gather_epp, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, (long long)B,
+                                   (const double*)w.comb.TOT, (const int*)w.comb.PAR, epp2, epp);
+        } else if (par) {
+            hipLaunchKernelGGL(ds::k_dmc_identity, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, (long long)B, par);
+        }
+        if (steps_done) *steps_done = i + 1;
+    }
+};
+
+// The pseudopotential triple of the walkers at xe into EPP2, exactly as ds_ecp_energy(xe, seed, counter) forms it (one host
+// synchronisation: the pair total, which above the capacity fails the call); slot: its entry of `rotations` and of out_pairs;
+// view: the term buffer that the evaluation leaves in the workspace (ecp_tmove)
+template <typename T>
+int dmc_ecp_eval(const DmcCtx<T>& c, const DmcEcpCall& p, const DmcEcpWs<T>& we, const T* xe, uint64_t counter, int slot, void* view = nullptr) {
+    return ecp_energy_forward(c.s, p.e, c.params, xe, c.B, c.q.seed, counter, p.rotations ? p.rotations + (size_t)slot * 9 * c.B : nullptr,
+                              p.cap, we.EPP2, nullptr, nullptr, nullptr, we.wse, we.wse_bytes, c.st, nullptr,
+                              p.out_pairs ? p.out_pairs + slot : nullptr, view);
+}
+
+// ds_dmc_step and ds_dmc_step_ecp (the locality approximation: the pseudopotential at x' enters the decision's E')
+template <typename T>
+int dmc_step_impl(ds_system* s, const void* params, const DmcCall& q, const DmcEcpCall& p, void* ws, int64_t ws_bytes, hipStream_t st) {
+    const int64_t B = q.B, esz = (int64_t)sizeof(T);
     DmcEcpWs<T> we{};
     Arena<T> a = arena_of<T>(ws, ws_bytes);
     if (!p.e) {
@@ -186,76 +302,26 @@ int dmc_step_impl(ds_system* s, const void* params, void* x_, void* logabs_, voi
     }
     if (!a.ok) return carve_fail("DMC step");
     const DmcWs<T>& w = we.dmc;
-    const size_t ne = (size_t)B * S.N;
-    const dim3 gw((unsigned)((B + ds::DMC_WAVES - 1) / ds::DMC_WAVES)), bw(64 * ds::DMC_WAVES);
-    const int64_t ngroups = (B + ds::DMC_GROUP - 1) / ds::DMC_GROUP;
-    if (p.steps_done) *p.steps_done = 0;
-    // the pseudopotential triple of the walkers at xe into EPP2, exactly as ds_ecp_energy(xe, seed, counter) forms it (one host
-    // synchronisation: the pair total); slot: its entry of `rotations` and of out_pairs
-    auto ecp_eval = [&](const T* xe, uint64_t counter, int slot) {
-        return ecp_energy_forward(s, p.e, params, xe, B, q.seed, counter, p.rotations ? p.rotations + (size_t)slot * 9 * B : nullptr, p.cap,
-                                  we.EPP2, nullptr, nullptr, nullptr, we.wse, we.wse_bytes, st, nullptr,
-                                  p.out_pairs ? p.out_pairs + slot : nullptr);
-    };
+    const DmcCtx<T> c{s, params, q, w, st};
     if (!q.state_valid) {
         // (the pseudopotential first: a pair total above the capacity then fails the call with the state untouched)
         if (p.e)
-            if (int rc = ecp_eval(x, q.offset, 0)) return rc;
-        if (int rc = energy_grad_forward(s, params, x, B, w.KE2, w.EW3, logabs, phase, w.GC, w.wsc, w.wsc_bytes, st)) return rc;
-        if (p.e)
-            hipLaunchKernelGGL((ds::k_dmc_init<T, true>), gw, bw, 0, st, (long long)B, n3, (const T*)w.GC, (const T*)w.KE2, (const T*)w.EW3,
-                               (const T*)logabs, drift, eloc, weight, (const double*)we.EPP2, p.epp);
-        else
-            hipLaunchKernelGGL((ds::k_dmc_init<T>), gw, bw, 0, st, (long long)B, n3, (const T*)w.GC, (const T*)w.KE2, (const T*)w.EW3,
-                               (const T*)logabs, drift, eloc, weight, (const double*)nullptr, (double*)nullptr);
+            if (int rc = dmc_ecp_eval(c, p, we, (const T*)c.x, q.offset, 0)) return rc;
+        if (int rc = c.init(we.EPP2, p.epp)) return rc;
     }
-    ds::DmcArgs A{q.tau, std::sqrt(q.tau), q.tau_eff, q.e_trial, q.e_ref, q.e_cut, q.node_mode, S.N, (long long)B};
-    const ds::PhiloxKey key{q.seed, q.offset};
-    const T* normals = (const T*)q.normals; const T* uniforms = (const T*)q.uniforms;
+    const auto accept = p.e ? ds::k_dmc_accept<T, true> : ds::k_dmc_accept<T, false>;
     for (int i = 0; i < q.steps; ++i) {
-        const T* nz = normals ? normals + (size_t)i * B * n3 : (const T*)nullptr;
-        hipLaunchKernelGGL((ds::k_dmc_propose<T>), dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, S.sim_a, S.sim_ainv, (const T*)x,
-                           (const T*)drift, nz, key, (unsigned long long)i, (T)q.tau, (T)A.sqrt_tau, ne, w.X2, w.NZ);
-        if (int rc = energy_grad_forward(s, params, w.X2, B, w.KE2, w.EW3, w.LA2, w.PH2, w.GC, w.wsc, w.wsc_bytes, st)) return rc;
-        const T* un = uniforms ? uniforms + (size_t)i * B : (const T*)nullptr;
-        if (p.e) {
-            // (a pair total above the capacity fails the call here: the state is that after i steps)
-            if (int rc = ecp_eval(w.X2, q.offset + 1 + (uint64_t)i, i + 1)) return rc;
-            hipLaunchKernelGGL((ds::k_dmc_accept<T, true>), gw, bw, 0, st, A, x, logabs, phase, drift, eloc, weight, (const T*)w.X2,
-                               (const T*)w.LA2, (const T*)w.PH2, (const T*)w.GC, (const T*)w.KE2, (const T*)w.EW3, nz ? nz : (const T*)w.NZ,
-                               un, key, (unsigned long long)i, w.PACC, w.FLAGS, we.EPP2, p.epp);
-        } else {
-            hipLaunchKernelGGL((ds::k_dmc_accept<T>), gw, bw, 0, st, A, x, logabs, phase, drift, eloc, weight, (const T*)w.X2,
-                               (const T*)w.LA2, (const T*)w.PH2, (const T*)w.GC, (const T*)w.KE2, (const T*)w.EW3, nz ? nz : (const T*)w.NZ,
-                               un, key, (unsigned long long)i, w.PACC, w.FLAGS, (double*)nullptr, (double*)nullptr);
-        }
-        double* row = q.out_stats + (size_t)i * ds::DMC_ROW;
-        hipLaunchKernelGGL(ds::k_dmc_stats, dim3((unsigned)ngroups), dim3(ds::DMC_GROUP), 0, st, (long long)B, (const double*)weight,
-                           (const double*)eloc, (const double*)w.PACC, (const int*)w.FLAGS, w.PART);
-        hipLaunchKernelGGL(ds::k_dmc_stats_final, dim3(1), dim3(64), 0, st, (const double*)w.PART, (long long)ngroups, (long long)B, row);
-        if (p.e && p.out_ecp_stats) {
-            hipLaunchKernelGGL(ds::k_dmc_ecp_stats, dim3((unsigned)ngroups), dim3(ds::DMC_GROUP), 0, st, (long long)B, (const double*)weight,
-                               (const double*)p.epp, we.PART3);
-            hipLaunchKernelGGL(ds::k_dmc_ecp_stats_final, dim3(1), dim3(64), 0, st, (const double*)we.PART3, (long long)ngroups,
-                               p.out_ecp_stats + (size_t)i * 3);
-        }
-        int* par = q.out_parents ? q.out_parents + (size_t)i * B : nullptr;
-        if (q.branch_every > 0 && (i + 1) % q.branch_every == 0) {
-            double xi = 0.0;
-            if (!q.comb_uniforms) {                       // stream 2 at index B, one past the walkers
-                uint32_t r[4];
-                ds_philox_host(q.seed, q.offset, (uint64_t)i, (uint64_t)B, 2, r);
-                xi = ds::u53_co(r[0], r[1]);
-            }
-            launch_comb<T>(w.comb, B, n3, xi, q.comb_uniforms ? q.comb_uniforms + i : nullptr, x, logabs, phase, drift, eloc, weight, par,
-                           row + ds::DMC_ROW - 1, st);
-            if (p.e)
-                hipLaunchKernelGGL(ds::k_dmc_gather_epp, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, (long long)B,
-                                   (const double*)w.comb.TOT, (const int*)w.comb.PAR, (const double*)we.EPP2, p.epp);
-        } else if (par) {
-            hipLaunchKernelGGL(ds::k_dmc_identity, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, (long long)B, par);
-        }
-        if (p.steps_done) *p.steps_done = i + 1;
+        if (int rc = c.propose(i)) return rc;
+        // (a pair total above the capacity fails the call here: the state is that after i steps)
+        if (p.e)
+            if (int rc = dmc_ecp_eval(c, p, we, (const T*)w.X2, q.offset + 1 + (uint64_t)i, i + 1)) return rc;
+        const T* nz = c.nz(i);
+        hipLaunchKernelGGL(accept, c.gw, c.bw, 0, st, c.A, c.x, c.logabs, c.phase, c.drift, c.eloc, c.weight, (const T*)w.X2, (const T*)w.LA2,
+                           (const T*)w.PH2, (const T*)w.GC, (const T*)w.KE2, (const T*)w.EW3, nz ? nz : (const T*)w.NZ, c.un(i), c.key,
+                           (unsigned long long)i, w.PACC, w.FLAGS, we.EPP2, p.epp);
+        double* row = c.stats_row(i, c.eloc);
+        if (p.e && p.out_ecp_stats) c.template ecp_row<3>(p.epp, nullptr, we.PART3, p.out_ecp_stats + (size_t)i * 3);
+        c.branch(i, row, we.EPP2, p.epp, p.steps_done);
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -268,12 +334,10 @@ struct DmcTmCall {
 
 // ds_dmc_step_tmove: the pseudopotential is evaluated after the decision, at the position the walker then has
 template <typename T>
-int dmc_tmove_impl(ds_system* s, const void* params, void* x_, void* logabs_, void* phase_, void* drift_, double* eloc, double* weight,
-                   const DmcCall& q, const DmcEcpCall& p, const DmcTmCall& m, void* ws, int64_t ws_bytes, hipStream_t st) {
-    const ds::SysDev<T>& S = dev<T>(s);
+int dmc_tmove_impl(ds_system* s, const void* params, const DmcCall& q, const DmcEcpCall& p, const DmcTmCall& m, void* ws, int64_t ws_bytes,
+                   hipStream_t st) {
     const int64_t B = q.B;
-    const int n3 = 3 * S.N, nq = ecp_n_quad(p.e);
-    T *x = (T*)x_, *logabs = (T*)logabs_, *phase = (T*)phase_, *drift = (T*)drift_;
+    const int nq = ecp_n_quad(p.e);
     int64_t nw, ng;
     if (!split_dmc_ecp([&](int64_t nw_, int64_t ng_) { return dmc_tmove_bytes(s, B, nw_, p.cap, nq, ng_); }, ws_bytes, B, p.cap, nq, &nw, &ng))
         return fail("workspace too small for ds_dmc_step_tmove: %lld bytes < %lld for one chain chunk of one walker and one group of %d "
@@ -284,74 +348,37 @@ int dmc_tmove_impl(ds_system* s, const void* params, void* x_, void* logabs_, vo
     if (!a.ok) return carve_fail("DMC step with T-moves");
     const DmcEcpWs<T>& we = wt.ecp;
     const DmcWs<T>& w = we.dmc;
-    const size_t ne = (size_t)B * S.N;
-    const dim3 gw((unsigned)((B + ds::DMC_WAVES - 1) / ds::DMC_WAVES)), bw(64 * ds::DMC_WAVES);
-    const int64_t ngroups = (B + ds::DMC_GROUP - 1) / ds::DMC_GROUP;
-    if (p.steps_done) *p.steps_done = 0;
+    const DmcCtx<T> c{s, params, q, w, st};
     if (!q.state_valid) {
         // (what ds_dmc_step's initialisation does: no pseudopotential is evaluated, eloc is the chain part)
-        if (int rc = energy_grad_forward(s, params, x, B, w.KE2, w.EW3, logabs, phase, w.GC, w.wsc, w.wsc_bytes, st)) return rc;
-        hipLaunchKernelGGL((ds::k_dmc_init<T>), gw, bw, 0, st, (long long)B, n3, (const T*)w.GC, (const T*)w.KE2, (const T*)w.EW3,
-                           (const T*)logabs, drift, eloc, weight, (const double*)nullptr, (double*)nullptr);
+        if (int rc = c.init(nullptr, nullptr)) return rc;
         HIP_OK(hipMemsetAsync(p.epp, 0, sizeof(double) * 3 * (size_t)B, st));
     }
-    ds::DmcArgs A{q.tau, std::sqrt(q.tau), q.tau_eff, q.e_trial, q.e_ref, q.e_cut, q.node_mode, S.N, (long long)B};
-    const ds::PhiloxKey key{q.seed, q.offset};
-    const T* normals = (const T*)q.normals; const T* uniforms = (const T*)q.uniforms;
     for (int i = 0; i < q.steps; ++i) {
-        const T* nz = normals ? normals + (size_t)i * B * n3 : (const T*)nullptr;
-        const T* un = uniforms ? uniforms + (size_t)i * B : (const T*)nullptr;
-        hipLaunchKernelGGL((ds::k_dmc_propose<T>), dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, S.sim_a, S.sim_ainv, (const T*)x,
-                           (const T*)drift, nz, key, (unsigned long long)i, (T)q.tau, (T)A.sqrt_tau, ne, w.X2, w.NZ);
-        if (int rc = energy_grad_forward(s, params, w.X2, B, w.KE2, w.EW3, w.LA2, w.PH2, w.GC, w.wsc, w.wsc_bytes, st)) return rc;
-        hipLaunchKernelGGL((ds::k_dmc_tm_decide<T>), gw, bw, 0, st, A, (const T*)x, (const T*)logabs, (const T*)phase, (const T*)drift,
-                           (const T*)w.X2, (const T*)w.LA2, (const T*)w.PH2, (const T*)w.GC, (const T*)w.KE2, (const T*)w.EW3,
-                           nz ? nz : (const T*)w.NZ, un, key, (unsigned long long)i, w.PACC, w.FLAGS, wt.XCUR);
-        // the pseudopotential at x_cur, exactly as ds_ecp_energy(x_cur, seed, offset + 1 + i) forms it (one host synchronisation: the
-        // pair total).  A total above the capacity fails the call here: nothing of step i is committed, the state is that after i steps
+        if (int rc = c.propose(i)) return rc;
+        const T* nz = c.nz(i);
+        hipLaunchKernelGGL((ds::k_dmc_tm_decide<T>), c.gw, c.bw, 0, st, c.A, (const T*)c.x, (const T*)c.logabs, (const T*)c.phase,
+                           (const T*)c.drift, (const T*)w.X2, (const T*)w.LA2, (const T*)w.PH2, (const T*)w.GC, (const T*)w.KE2,
+                           (const T*)w.EW3, nz ? nz : (const T*)w.NZ, c.un(i), c.key, (unsigned long long)i, w.PACC, w.FLAGS, wt.XCUR);
+        // the pseudopotential at x_cur.  A pair total above the capacity fails the call here: nothing of step i is committed, the
+        // state is that after i steps
         EcpWs<T> view{};
-        if (int rc = ecp_energy_forward(s, p.e, params, wt.XCUR, B, q.seed, q.offset + 1 + (uint64_t)i,
-                                        p.rotations ? p.rotations + (size_t)i * 9 * B : nullptr, p.cap, we.EPP2, nullptr, nullptr, nullptr,
-                                        we.wse, we.wse_bytes, st, nullptr, p.out_pairs ? p.out_pairs + i : nullptr, &view))
-            return rc;
-        hipLaunchKernelGGL((ds::k_dmc_tm_commit<T>), gw, bw, 0, st, A, x, logabs, phase, drift, eloc, weight, p.epp, (const T*)w.X2,
-                           (const T*)w.LA2, (const T*)w.PH2, (const T*)w.GC, (const T*)w.KE2, (const T*)w.EW3, (const double*)we.EPP2,
-                           w.FLAGS, wt.ETOT, m.out_energy ? m.out_energy + (size_t)i * B : nullptr);
-        if (int rc = ecp_tmove(s, p.e, &view, x, B, q.tau, weight, wt.ETOT, m.tmove_uniforms ? m.tmove_uniforms + (size_t)i * B : nullptr,
+        if (int rc = dmc_ecp_eval(c, p, we, (const T*)wt.XCUR, q.offset + 1 + (uint64_t)i, i, &view)) return rc;
+        hipLaunchKernelGGL((ds::k_dmc_tm_commit<T>), c.gw, c.bw, 0, st, c.A, c.x, c.logabs, c.phase, c.drift, c.eloc, c.weight, p.epp,
+                           (const T*)w.X2, (const T*)w.LA2, (const T*)w.PH2, (const T*)w.GC, (const T*)w.KE2, (const T*)w.EW3,
+                           (const double*)we.EPP2, w.FLAGS, wt.ETOT, m.out_energy ? m.out_energy + (size_t)i * B : nullptr);
+        if (int rc = ecp_tmove(s, p.e, &view, c.x, B, q.tau, c.weight, wt.ETOT, m.tmove_uniforms ? m.tmove_uniforms + (size_t)i * B : nullptr,
                                q.seed, q.offset, (uint64_t)i, wt.CHOICE, m.out_tmove ? m.out_tmove + (size_t)i * B : nullptr, st))
             return rc;
         // the rows: the weights and E of the commit (the second chain pass may still zero a weight)
-        double* row = q.out_stats + (size_t)i * ds::DMC_ROW;
-        hipLaunchKernelGGL(ds::k_dmc_stats, dim3((unsigned)ngroups), dim3(ds::DMC_GROUP), 0, st, (long long)B, (const double*)weight,
-                           (const double*)wt.ETOT, (const double*)w.PACC, (const int*)w.FLAGS, w.PART);
-        hipLaunchKernelGGL(ds::k_dmc_stats_final, dim3(1), dim3(64), 0, st, (const double*)w.PART, (long long)ngroups, (long long)B, row);
-        if (p.out_ecp_stats) {
-            hipLaunchKernelGGL(ds::k_dmc_tm_stats, dim3((unsigned)ngroups), dim3(ds::DMC_GROUP), 0, st, (long long)B, (const double*)weight,
-                               (const double*)p.epp, (const int*)wt.CHOICE, wt.PART4);
-            hipLaunchKernelGGL(ds::k_dmc_tm_stats_final, dim3(1), dim3(64), 0, st, (const double*)wt.PART4, (long long)ngroups,
-                               p.out_ecp_stats + (size_t)i * 4);
-        }
+        double* row = c.stats_row(i, wt.ETOT);
+        if (p.out_ecp_stats) c.template ecp_row<4>(p.epp, wt.CHOICE, wt.PART4, p.out_ecp_stats + (size_t)i * 4);
         // the chain at x (all B walkers); only the walkers that moved take its outputs
-        if (int rc = energy_grad_forward(s, params, x, B, w.KE2, w.EW3, w.LA2, w.PH2, w.GC, w.wsc, w.wsc_bytes, st)) return rc;
-        hipLaunchKernelGGL((ds::k_dmc_tm_refresh<T>), gw, bw, 0, st, (long long)B, n3, (const int*)wt.CHOICE, (const T*)w.GC, (const T*)w.LA2,
-                           (const T*)w.PH2, (const T*)w.KE2, (const T*)w.EW3, logabs, phase, drift, eloc, weight);
-        int* par = q.out_parents ? q.out_parents + (size_t)i * B : nullptr;
-        if (q.branch_every > 0 && (i + 1) % q.branch_every == 0) {
-            double xi = 0.0;
-            if (!q.comb_uniforms) {                       // stream 2 at index B, one past the walkers
-                uint32_t r[4];
-                ds_philox_host(q.seed, q.offset, (uint64_t)i, (uint64_t)B, 2, r);
-                xi = ds::u53_co(r[0], r[1]);
-            }
-            launch_comb<T>(w.comb, B, n3, xi, q.comb_uniforms ? q.comb_uniforms + i : nullptr, x, logabs, phase, drift, eloc, weight, par,
-                           row + ds::DMC_ROW - 1, st);
-            // (the commit left epp equal to EPP2, the source of the gather)
-            hipLaunchKernelGGL(ds::k_dmc_gather_epp, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, (long long)B,
-                               (const double*)w.comb.TOT, (const int*)w.comb.PAR, (const double*)we.EPP2, p.epp);
-        } else if (par) {
-            hipLaunchKernelGGL(ds::k_dmc_identity, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, (long long)B, par);
-        }
-        if (p.steps_done) *p.steps_done = i + 1;
+        if (int rc = c.chain(c.x, w.LA2, w.PH2)) return rc;
+        hipLaunchKernelGGL((ds::k_dmc_tm_refresh<T>), c.gw, c.bw, 0, st, (long long)B, c.n3, (const int*)wt.CHOICE, (const T*)w.GC,
+                           (const T*)w.LA2, (const T*)w.PH2, (const T*)w.KE2, (const T*)w.EW3, c.logabs, c.phase, c.drift, c.eloc, c.weight);
+        // (the commit left epp equal to EPP2, the source of the gather)
+        c.branch(i, row, we.EPP2, p.epp, p.steps_done);
     }
     HIP_OK(hipGetLastError());
     return 0;
@@ -388,46 +415,26 @@ extern "C" {
 
 int64_t ds_dmc_workspace_bytes(const ds_system* s, int64_t B) {
     if (!s || B < 1 || B > ds::DMC_MAX_B) return -1;
-    // the chain's share is what ds_workspace_bytes gives the energy chain of B walkers
-    const int64_t esz = s->dtype == 0 ? 8 : 4;
-    int64_t chunk = std::min<int64_t>(B, s->chunk_cap);
-    chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, workspace_budget() / ((int64_t)s->ws.per_walker * esz)));
-    return dmc_bytes(s, B, chunk);
+    return dmc_bytes(s, B, dmc_default_chunk(s, B));
 }
 
 int ds_dmc_step(ds_system* s, const void* params, void* x, void* logabs, void* phase, void* drift, double* eloc, double* weight, int64_t B,
                 int steps, double tau, double tau_eff, double e_trial, double e_ref, double e_cut, int node_mode, int branch_every,
                 uint64_t philox_seed, uint64_t philox_offset, const void* normals, const void* uniforms, const double* comb_uniforms,
                 int state_valid, double* out_stats, int32_t* out_parents, void* ws, int64_t ws_bytes, void* stream) {
-    if (s) ++s->call_seq;
-    if (!s || !params || !ws) return fail("ds_dmc_step: null argument");
-    if (!x || !logabs || !phase || !drift || !eloc || !weight) return fail("ds_dmc_step: null state pointer");
-    if (!out_stats) return fail("ds_dmc_step: out_stats is null");
-    if (B < 1 || B > ds::DMC_MAX_B) return fail("ds_dmc_step: B must be in 1..%lld (got %lld)", (long long)ds::DMC_MAX_B, (long long)B);
-    if (steps < 1) return fail("ds_dmc_step: steps must be >= 1 (got %d)", steps);
-    if (!std::isfinite(tau) || !std::isfinite(tau_eff) || !std::isfinite(e_trial) || !std::isfinite(e_ref) || !std::isfinite(e_cut))
-        return fail("ds_dmc_step: tau, tau_eff, e_trial, e_ref and e_cut must be finite");
-    if (!(tau > 0.0)) return fail("ds_dmc_step: tau must be > 0 (got %g)", tau);
-    if (tau_eff < 0.0) return fail("ds_dmc_step: tau_eff must be >= 0 (got %g)", tau_eff);
-    if (node_mode != 0 && node_mode != 1) return fail("ds_dmc_step: node_mode must be 0 (fixed phase) or 1 (fixed node) (got %d)", node_mode);
-    if (branch_every < 0) return fail("ds_dmc_step: branch_every must be >= 0 (got %d)", branch_every);
+    const DmcCall q{x, logabs, phase, drift, eloc, weight, B, steps, tau, tau_eff, e_trial, e_ref, e_cut, node_mode, branch_every, philox_seed,
+                    philox_offset, normals, uniforms, comb_uniforms, state_valid, out_stats, (int*)out_parents};
     const int given = (normals ? 1 : 0) + (uniforms ? 1 : 0) + (comb_uniforms ? 1 : 0);
-    if (given != 0 && given != 3) return fail("ds_dmc_step: normals, uniforms and comb_uniforms must be given together (or all NULL)");
-    const DmcCall q{B, steps, tau, tau_eff, e_trial, e_ref, e_cut, node_mode, branch_every, philox_seed, philox_offset, normals, uniforms,
-                    comb_uniforms, state_valid, out_stats, (int*)out_parents};
-    hipStream_t st = (hipStream_t)stream;
-    return DS_BY_DTYPE(s->dtype, dmc_step_impl, s, params, x, logabs, phase, drift, eloc, weight, q, DmcEcpCall{}, ws, ws_bytes, st);
+    if (int rc = dmc_check("ds_dmc_step", s, params, ws, q, nullptr, given, 3)) return rc;
+    return DS_BY_DTYPE(s->dtype, dmc_step_impl, s, params, q, DmcEcpCall{}, ws, ws_bytes, (hipStream_t)stream);
 }
 
+// the chain's share as in ds_dmc_workspace_bytes, the pseudopotential's as in ds_ecp_workspace_bytes
 int64_t ds_dmc_ecp_workspace_bytes(const ds_system* s, const ds_ecp* e, int64_t B, int64_t pair_capacity) {
     if (!s || !e) { fail("null argument"); return -1; }
     if (B > ds::DMC_MAX_B || ecp_check(s, e, B, pair_capacity)) return -1;
-    // the chain's share as in ds_dmc_workspace_bytes, the pseudopotential's as in ds_ecp_workspace_bytes
-    const int64_t esz = s->dtype == 0 ? 8 : 4;
-    int64_t chunk = std::min<int64_t>(B, s->chunk_cap);
-    chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, workspace_budget() / ((int64_t)s->ws.per_walker * esz)));
     const int nq = ecp_n_quad(e);
-    return dmc_ecp_bytes(s, B, chunk, pair_capacity, nq, ecp_default_groups(s, B, pair_capacity, nq));
+    return dmc_ecp_bytes(s, B, dmc_default_chunk(s, B), pair_capacity, nq, ecp_default_groups(s, B, pair_capacity, nq));
 }
 
 int ds_dmc_step_ecp(ds_system* s, const ds_ecp* ecp, const void* params, void* x, void* logabs, void* phase, void* drift, double* eloc,
@@ -436,45 +443,20 @@ int ds_dmc_step_ecp(ds_system* s, const ds_ecp* ecp, const void* params, void* x
                     const double* comb_uniforms, const double* rotations, int64_t pair_capacity, int state_valid, double* out_stats,
                     double* out_ecp_stats, int32_t* out_parents, int64_t* out_pairs, int* steps_done, void* ws, int64_t ws_bytes,
                     void* stream) {
-    if (steps_done) *steps_done = 0;
-    if (s) ++s->call_seq;
-    if (!s || !params || !ws) return fail("ds_dmc_step_ecp: null argument");
-    if (!x || !logabs || !phase || !drift || !eloc || !weight) return fail("ds_dmc_step_ecp: null state pointer");
-    if (!epp) return fail("ds_dmc_step_ecp: epp is null (the seventh state array)");
-    if (!out_stats) return fail("ds_dmc_step_ecp: out_stats is null");
-    if (B < 1 || B > ds::DMC_MAX_B) return fail("ds_dmc_step_ecp: B must be in 1..%lld (got %lld)", (long long)ds::DMC_MAX_B, (long long)B);
-    if (steps < 1) return fail("ds_dmc_step_ecp: steps must be >= 1 (got %d)", steps);
-    if (!std::isfinite(tau) || !std::isfinite(tau_eff) || !std::isfinite(e_trial) || !std::isfinite(e_ref) || !std::isfinite(e_cut))
-        return fail("ds_dmc_step_ecp: tau, tau_eff, e_trial, e_ref and e_cut must be finite");
-    if (!(tau > 0.0)) return fail("ds_dmc_step_ecp: tau must be > 0 (got %g)", tau);
-    if (tau_eff < 0.0) return fail("ds_dmc_step_ecp: tau_eff must be >= 0 (got %g)", tau_eff);
-    if (node_mode != 0 && node_mode != 1)
-        return fail("ds_dmc_step_ecp: node_mode must be 0 (fixed phase) or 1 (fixed node) (got %d)", node_mode);
-    if (branch_every < 0) return fail("ds_dmc_step_ecp: branch_every must be >= 0 (got %d)", branch_every);
+    const DmcCall q{x, logabs, phase, drift, eloc, weight, B, steps, tau, tau_eff, e_trial, e_ref, e_cut, node_mode, branch_every, philox_seed,
+                    philox_offset, normals, uniforms, comb_uniforms, state_valid, out_stats, (int*)out_parents};
+    const DmcEcpCall p{ecp, pair_capacity, rotations, epp, out_ecp_stats, out_pairs, steps_done};
     const int given = (normals ? 1 : 0) + (uniforms ? 1 : 0) + (comb_uniforms ? 1 : 0) + (rotations ? 1 : 0);
-    if (given != 0 && given != 4)
-        return fail("ds_dmc_step_ecp: normals, uniforms, comb_uniforms and rotations must be given together (or all NULL)");
-    if (philox_offset >= (1ull << 61) || philox_offset + (uint64_t)steps >= (1ull << 61))
-        return fail("ds_dmc_step_ecp: philox_offset + steps must be below 2^61 (the rotations' stream 4 lies above)");
-    if (int rc = ecp_check(s, ecp, B, pair_capacity)) return rc;
-    const DmcCall q{B, steps, tau, tau_eff, e_trial, e_ref, e_cut, node_mode, branch_every, philox_seed, philox_offset, normals, uniforms,
-                    comb_uniforms, state_valid, out_stats, (int*)out_parents};
-    DmcEcpCall p;
-    p.e = ecp; p.cap = pair_capacity; p.rotations = rotations; p.epp = epp; p.out_ecp_stats = out_ecp_stats; p.out_pairs = out_pairs;
-    p.steps_done = steps_done;
-    hipStream_t st = (hipStream_t)stream;
-    return DS_BY_DTYPE(s->dtype, dmc_step_impl, s, params, x, logabs, phase, drift, eloc, weight, q, p, ws, ws_bytes, st);
+    if (int rc = dmc_check("ds_dmc_step_ecp", s, params, ws, q, &p, given, 4)) return rc;
+    return DS_BY_DTYPE(s->dtype, dmc_step_impl, s, params, q, p, ws, ws_bytes, (hipStream_t)stream);
 }
 
+// the shares of ds_dmc_ecp_workspace_bytes
 int64_t ds_dmc_tmove_workspace_bytes(const ds_system* s, const ds_ecp* e, int64_t B, int64_t pair_capacity) {
     if (!s || !e) { fail("null argument"); return -1; }
     if (B > ds::DMC_MAX_B || ecp_check(s, e, B, pair_capacity)) return -1;
-    // the shares of ds_dmc_ecp_workspace_bytes
-    const int64_t esz = s->dtype == 0 ? 8 : 4;
-    int64_t chunk = std::min<int64_t>(B, s->chunk_cap);
-    chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, workspace_budget() / ((int64_t)s->ws.per_walker * esz)));
     const int nq = ecp_n_quad(e);
-    return dmc_tmove_bytes(s, B, chunk, pair_capacity, nq, ecp_default_groups(s, B, pair_capacity, nq));
+    return dmc_tmove_bytes(s, B, dmc_default_chunk(s, B), pair_capacity, nq, ecp_default_groups(s, B, pair_capacity, nq));
 }
 
 int ds_dmc_step_tmove(ds_system* s, const ds_ecp* ecp, const void* params, void* x, void* logabs, void* phase, void* drift, double* eloc,
@@ -484,35 +466,13 @@ int ds_dmc_step_tmove(ds_system* s, const ds_ecp* ecp, const void* params, void*
                       int64_t pair_capacity, int state_valid, double* out_stats, double* out_ecp_stats, int32_t* out_parents,
                       int64_t* out_pairs, int32_t* out_tmove, double* out_energy, int* steps_done, void* ws, int64_t ws_bytes,
                       void* stream) {
-    if (steps_done) *steps_done = 0;
-    if (s) ++s->call_seq;
-    if (!s || !params || !ws) return fail("ds_dmc_step_tmove: null argument");
-    if (!x || !logabs || !phase || !drift || !eloc || !weight) return fail("ds_dmc_step_tmove: null state pointer");
-    if (!epp) return fail("ds_dmc_step_tmove: epp is null (the seventh state array)");
-    if (!out_stats) return fail("ds_dmc_step_tmove: out_stats is null");
-    if (B < 1 || B > ds::DMC_MAX_B) return fail("ds_dmc_step_tmove: B must be in 1..%lld (got %lld)", (long long)ds::DMC_MAX_B, (long long)B);
-    if (steps < 1) return fail("ds_dmc_step_tmove: steps must be >= 1 (got %d)", steps);
-    if (!std::isfinite(tau) || !std::isfinite(tau_eff) || !std::isfinite(e_trial) || !std::isfinite(e_ref) || !std::isfinite(e_cut))
-        return fail("ds_dmc_step_tmove: tau, tau_eff, e_trial, e_ref and e_cut must be finite");
-    if (!(tau > 0.0)) return fail("ds_dmc_step_tmove: tau must be > 0 (got %g)", tau);
-    if (tau_eff < 0.0) return fail("ds_dmc_step_tmove: tau_eff must be >= 0 (got %g)", tau_eff);
-    if (node_mode != 0 && node_mode != 1)
-        return fail("ds_dmc_step_tmove: node_mode must be 0 (fixed phase) or 1 (fixed node) (got %d)", node_mode);
-    if (branch_every < 0) return fail("ds_dmc_step_tmove: branch_every must be >= 0 (got %d)", branch_every);
-    const int given = (normals ? 1 : 0) + (uniforms ? 1 : 0) + (comb_uniforms ? 1 : 0) + (rotations ? 1 : 0) + (tmove_uniforms ? 1 : 0);
-    if (given != 0 && given != 5)
-        return fail("ds_dmc_step_tmove: normals, uniforms, comb_uniforms, rotations and tmove_uniforms must be given together (or all NULL)");
-    if (philox_offset >= (1ull << 61) || philox_offset + (uint64_t)steps >= (1ull << 61))
-        return fail("ds_dmc_step_tmove: philox_offset + steps must be below 2^61 (the rotations' stream 4 lies above)");
-    if (int rc = ecp_check(s, ecp, B, pair_capacity)) return rc;
-    const DmcCall q{B, steps, tau, tau_eff, e_trial, e_ref, e_cut, node_mode, branch_every, philox_seed, philox_offset, normals, uniforms,
-                    comb_uniforms, state_valid, out_stats, (int*)out_parents};
-    DmcEcpCall p;
-    p.e = ecp; p.cap = pair_capacity; p.rotations = rotations; p.epp = epp; p.out_ecp_stats = out_ecp_stats; p.out_pairs = out_pairs;
-    p.steps_done = steps_done;
+    const DmcCall q{x, logabs, phase, drift, eloc, weight, B, steps, tau, tau_eff, e_trial, e_ref, e_cut, node_mode, branch_every, philox_seed,
+                    philox_offset, normals, uniforms, comb_uniforms, state_valid, out_stats, (int*)out_parents};
+    const DmcEcpCall p{ecp, pair_capacity, rotations, epp, out_ecp_stats, out_pairs, steps_done};
     const DmcTmCall m{tmove_uniforms, (int*)out_tmove, out_energy};
-    hipStream_t st = (hipStream_t)stream;
-    return DS_BY_DTYPE(s->dtype, dmc_tmove_impl, s, params, x, logabs, phase, drift, eloc, weight, q, p, m, ws, ws_bytes, st);
+    const int given = (normals ? 1 : 0) + (uniforms ? 1 : 0) + (comb_uniforms ? 1 : 0) + (rotations ? 1 : 0) + (tmove_uniforms ? 1 : 0);
+    if (int rc = dmc_check("ds_dmc_step_tmove", s, params, ws, q, &p, given, 5)) return rc;
+    return DS_BY_DTYPE(s->dtype, dmc_tmove_impl, s, params, q, p, m, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int ds_dmc_noise(int dtype, int n_elec, int64_t B, int steps, uint64_t philox_seed, uint64_t philox_offset, void* normals, void* uniforms,

@@ -7,6 +7,8 @@ results are torch tensors on the ROCm device -- torch is used for memory,
 streams and (elsewhere) torch.distributed, nothing else.
 """
 import ctypes as C
+import re
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -27,6 +29,30 @@ def _ptr(t):
 
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+class _DmcVariant(NamedTuple):
+    """One of the three step entries behind `DeviceSystem.dmc_step`.  noise: the explicit noise arrays in the entry's order, each
+    (keyword, float64 (else the system's dtype), shape behind the leading `steps` as a function of (B, 3N)); lead: the entries of
+    rotations and pairs that an initialisation takes; columns: of ecp_stats."""
+    entry: str
+    ws_entry: str
+    noise: tuple
+    lead: int
+    columns: int
+    noise_message: str
+
+
+_DMC_NOISE = (('normals', False, lambda B, n3: (B, n3)), ('uniforms', False, lambda B, n3: (B,)), ('comb_uniforms', True, lambda B, n3: ()))
+_DMC_ROTATIONS = ('rotations', True, lambda B, n3: (B, 3, 3))
+_DMC_MESSAGE = 'explicit noise must be normals (steps, B, 3N), uniforms (steps, B)'
+_DMC_VARIANTS = dict(
+    plain=_DmcVariant('ds_dmc_step', 'ds_dmc_workspace_bytes', _DMC_NOISE, 0, 0, _DMC_MESSAGE + ' and comb_uniforms (steps,)'),
+    ecp=_DmcVariant('ds_dmc_step_ecp', 'ds_dmc_ecp_workspace_bytes', _DMC_NOISE + (_DMC_ROTATIONS,), 1, 3,
+                    _DMC_MESSAGE + ', comb_uniforms (steps,) and rotations (steps + 1, B, 3, 3)'),
+    tmove=_DmcVariant('ds_dmc_step_tmove', 'ds_dmc_tmove_workspace_bytes',
+                      _DMC_NOISE + (_DMC_ROTATIONS, ('tmove_uniforms', True, lambda B, n3: (B,))), 0, 4,
+                      _DMC_MESSAGE + ', comb_uniforms (steps,) and rotations (steps, B, 3, 3)'))
 
 
 def _require_gpu():
@@ -719,32 +745,76 @@ class DeviceSystem:
             raise ValueError('tmoves=True needs a pseudopotential (ecp=...)')
         if (tmove_uniforms is not None or want_tmoves) and not tmoves:
             raise ValueError('tmove_uniforms and want_tmoves go with tmoves=True')
-        if ecp is not None:
-            return self._dmc_step_ecp(params, state, int(steps), tau, tau_eff, e_trial, e_ref, e_cut, node_mode, branch_every, seed,
-                                      offset, normals, uniforms, comb_uniforms, state_valid, want_parents, max_bytes, ecp,
-                                      pair_capacity, rotations, want_pairs, bool(tmoves), tmove_uniforms, want_tmoves)
-        if rotations is not None or pair_capacity is not None or want_pairs:
+        if ecp is None and (rotations is not None or pair_capacity is not None or want_pairs):
             raise ValueError('rotations, pair_capacity and want_pairs go with a pseudopotential (ecp=...)')
-        B = self._check_dmc_state(state)
-        steps = int(steps)
+        v = _DMC_VARIANTS['plain' if ecp is None else 'tmove' if tmoves else 'ecp']
+        B = self._check_dmc_state(state, ecp=ecp is not None)
+        steps, n, tmoves = int(steps), max(int(steps), 1), bool(tmoves)
+        if ecp is not None:
+            ecp = self._ecp_tables(ecp)
         p = self.pack_params(params)
-        given = [t is not None for t in (normals, uniforms, comb_uniforms)]
-        if all(given):
-            normals = normals.to(device=self.device, dtype=self.dtype).contiguous()
-            uniforms = uniforms.to(device=self.device, dtype=self.dtype).contiguous()
-            comb_uniforms = comb_uniforms.to(device=self.device, dtype=torch.float64).contiguous()
-            if tuple(normals.shape) != (steps, B, 3 * self.n) or tuple(uniforms.shape) != (steps, B) or tuple(comb_uniforms.shape) != (steps,):
-                raise ValueError('explicit noise must be normals (steps, B, 3N), uniforms (steps, B) and comb_uniforms (steps,)')
-        stats = torch.zeros(max(steps, 1), 9, dtype=torch.float64, device=self.device)
-        parents = torch.empty(max(steps, 1), B, dtype=torch.int32, device=self.device) if want_parents else None
-        ws = self._workspace('ds_dmc_workspace_bytes', int(B), max_bytes=max_bytes) if 1 <= B <= 2 ** 20 else self.workspace(1)
-        _lib.check(self.lib.ds_dmc_step(
-            self.handle, _ptr(p), _ptr(state['x']), _ptr(state['logabs']), _ptr(state['phase']), _ptr(state['drift']),
-            _ptr(state['eloc']), _ptr(state['weight']), B, steps, float(tau), float(tau if tau_eff is None else tau_eff),
-            float(e_trial), float(e_ref), float(e_cut), int(node_mode), int(branch_every), int(seed) & (2 ** 64 - 1),
-            int(offset) & (2 ** 64 - 1), _ptr(normals), _ptr(uniforms), _ptr(comb_uniforms), int(bool(state_valid)), _ptr(stats),
-            _ptr(parents), _ptr(ws), ws.numel(), _stream()), 'ds_dmc_step')
-        return dict(stats=stats, parents=parents)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        # the explicit noise in the entry's order: all of it or none (the library refuses a part of it)
+        noise = dict(normals=normals, uniforms=uniforms, comb_uniforms=comb_uniforms, rotations=rotations, tmove_uniforms=tmove_uniforms)
+        noise = {k: noise[k] for k, _, _ in v.noise}
+        explicit = all(t is not None for t in noise.values())
+        if explicit:
+            bad = []
+            for k, is_f64, shape in v.noise:
+                noise[k] = noise[k].to(device=self.device, dtype=torch.float64 if is_f64 else self.dtype).contiguous()
+                if tuple(noise[k].shape) != (steps + (v.lead if k == 'rotations' else 0),) + shape(B, 3 * self.n):
+                    bad.append(k)
+            if bad:
+                raise ValueError('tmove_uniforms must be (steps, B)' if bad == ['tmove_uniforms'] else v.noise_message)
+        if ecp is None:
+            cap = None
+        elif pair_capacity is None:
+            src = ecp.ecp
+            n_nl = int(np.count_nonzero(np.asarray(src.n_l)[np.asarray(src.atom_species)] > 0))
+            cap = B * self.n * max(n_nl, 1)
+            if cap * (72 + 16 * ecp.n_quad) > self.ECP_PAIR_BUDGET:
+                cap = B * self.n
+        else:
+            cap = int(pair_capacity)
+        stats = torch.zeros(n, 9, **f64)
+        parents = torch.empty(n, B, dtype=torch.int32, device=self.device) if want_parents else None
+        ecp_stats = torch.zeros(n, v.columns, **f64) if ecp is not None else None
+        pairs = torch.zeros(n + v.lead, dtype=torch.int64, device=self.device) if want_pairs else None
+        choice = torch.full((n, B), -1, dtype=torch.int32, device=self.device) if want_tmoves else None
+        energy = torch.zeros(n, B, **f64) if tmoves else None
+        outs = [stats] + ([ecp_stats] if ecp is not None else []) + [parents] + ([pairs] if ecp is not None else []) + \
+            ([choice, energy] if tmoves else [])
+        keys = ('x', 'logabs', 'phase', 'drift', 'eloc', 'weight') + (('epp',) if ecp is not None else ())
+        done, valid = 0, bool(state_valid)
+        for attempt in range(2):                           # (a second time only after a pair capacity overflow)
+            k, left = done, steps - done
+            size_args = (int(B),) if ecp is None else (ecp.handle, int(B), cap)
+            ws = self._workspace(v.ws_entry, *size_args, max_bytes=max_bytes) if 1 <= B <= 2 ** 20 and (ecp is None or cap >= 1) \
+                else self.workspace(1)                     # (the library refuses such a B or capacity itself)
+            n_done = C.c_int(0)
+            cut = (lambda t: t[k:]) if explicit else (lambda t: t)
+            rc = getattr(self.lib, v.entry)(
+                self.handle, *((ecp.handle,) if ecp is not None else ()), _ptr(p), *[_ptr(state[key]) for key in keys], B, left, float(tau),
+                float(tau if tau_eff is None else tau_eff), float(e_trial), float(e_ref), float(e_cut), int(node_mode), int(branch_every),
+                int(seed) & (2 ** 64 - 1), (int(offset) + k) & (2 ** 64 - 1), *[_ptr(cut(t)) for t in noise.values()],
+                *((cap,) if ecp is not None else ()), int(valid), *[_ptr(t[k:] if t is not None else None) for t in outs],
+                *((C.byref(n_done),) if ecp is not None else ()), _ptr(ws), ws.numel(), _stream())
+            if rc != 0 and attempt == 0 and ecp is not None and pair_capacity is None:
+                m = re.search(r'pair capacity exceeded: the walkers have (\d+) pairs', self.lib.ds_last_error().decode())
+                # (the comb's schedule counts the steps of a call: a continuation keeps it only from a multiple of branch_every)
+                if m and (branch_every <= 1 or n_done.value % int(branch_every) == 0):
+                    cap = int(m.group(1))
+                    done += n_done.value
+                    valid = valid or done > 0
+                    continue
+            _lib.check(rc, v.entry)
+            break
+        out = dict(stats=stats, parents=parents)
+        if ecp is not None:
+            out.update(ecp_stats=ecp_stats, pairs=pairs, pair_capacity=cap)
+        if tmoves:
+            out.update(tmoves=choice, energy=energy)
+        return out
 
     ECP_PAIR_BUDGET = 1 << 30              # bytes of pair records up to which dmc_step's default capacity is the hard bound
 
@@ -755,79 +825,6 @@ class DeviceSystem:
                 tables = ecp.__dict__['_ds_tables'] = EcpTables(ecp, device=self.device)
             ecp = tables
         return ecp
-
-    def _dmc_step_ecp(self, params, state, steps, tau, tau_eff, e_trial, e_ref, e_cut, node_mode, branch_every, seed, offset, normals,
-                      uniforms, comb_uniforms, state_valid, want_parents, max_bytes, ecp, pair_capacity, rotations, want_pairs,
-                      tmoves=False, tmove_uniforms=None, want_tmoves=False):
-        import re
-        B = self._check_dmc_state(state, ecp=True)
-        ecp = self._ecp_tables(ecp)
-        p = self.pack_params(params)
-        lead = 0 if tmoves else 1                          # entries of rotations / pairs for an initialisation
-        given = [t is not None for t in (normals, uniforms, comb_uniforms, rotations) + ((tmove_uniforms,) if tmoves else ())]
-        if all(given):
-            normals = normals.to(device=self.device, dtype=self.dtype).contiguous()
-            uniforms = uniforms.to(device=self.device, dtype=self.dtype).contiguous()
-            comb_uniforms = comb_uniforms.to(device=self.device, dtype=torch.float64).contiguous()
-            rotations = rotations.to(device=self.device, dtype=torch.float64).contiguous()
-            if tuple(normals.shape) != (steps, B, 3 * self.n) or tuple(uniforms.shape) != (steps, B) or \
-                    tuple(comb_uniforms.shape) != (steps,) or tuple(rotations.shape) != (steps + lead, B, 3, 3):
-                raise ValueError('explicit noise must be normals (steps, B, 3N), uniforms (steps, B), comb_uniforms (steps,) and '
-                                 f'rotations (steps{" + 1" if lead else ""}, B, 3, 3)')
-            if tmoves:
-                tmove_uniforms = tmove_uniforms.to(device=self.device, dtype=torch.float64).contiguous()
-                if tuple(tmove_uniforms.shape) != (steps, B):
-                    raise ValueError('tmove_uniforms must be (steps, B)')
-        if pair_capacity is None:
-            src = ecp.ecp
-            n_nl = int(np.count_nonzero(np.asarray(src.n_l)[np.asarray(src.atom_species)] > 0))
-            cap = B * self.n * max(n_nl, 1)
-            if cap * (72 + 16 * ecp.n_quad) > self.ECP_PAIR_BUDGET:
-                cap = B * self.n
-        else:
-            cap = int(pair_capacity)
-        stats = torch.zeros(max(steps, 1), 9, dtype=torch.float64, device=self.device)
-        ecp_stats = torch.zeros(max(steps, 1), 4 if tmoves else 3, dtype=torch.float64, device=self.device)
-        parents = torch.empty(max(steps, 1), B, dtype=torch.int32, device=self.device) if want_parents else None
-        pairs = torch.zeros(max(steps, 1) + lead, dtype=torch.int64, device=self.device) if want_pairs else None
-        choice = torch.full((max(steps, 1), B), -1, dtype=torch.int32, device=self.device) if tmoves and want_tmoves else None
-        energy = torch.zeros(max(steps, 1), B, dtype=torch.float64, device=self.device) if tmoves else None
-        name = 'ds_dmc_step_tmove' if tmoves else 'ds_dmc_step_ecp'
-        done, valid = 0, bool(state_valid)
-        for attempt in range(2):
-            k, left = done, steps - done
-            ws = self._workspace('ds_dmc_tmove_workspace_bytes' if tmoves else 'ds_dmc_ecp_workspace_bytes', ecp.handle, int(B), cap,
-                                 max_bytes=max_bytes) \
-                if 1 <= B <= 2 ** 20 and cap >= 1 else self.workspace(1)         # (the library refuses such a B or capacity itself)
-            n_done = C.c_int(0)
-            cut = (lambda t: t[k:]) if all(given) else (lambda t: t)
-            head = (self.handle, ecp.handle, _ptr(p), _ptr(state['x']), _ptr(state['logabs']), _ptr(state['phase']), _ptr(state['drift']),
-                    _ptr(state['eloc']), _ptr(state['weight']), _ptr(state['epp']), B, left, float(tau),
-                    float(tau if tau_eff is None else tau_eff), float(e_trial), float(e_ref), float(e_cut), int(node_mode), int(branch_every),
-                    int(seed) & (2 ** 64 - 1), (int(offset) + k) & (2 ** 64 - 1), _ptr(cut(normals)), _ptr(cut(uniforms)),
-                    _ptr(cut(comb_uniforms)), _ptr(cut(rotations)))
-            outs = (_ptr(stats[k:]), _ptr(ecp_stats[k:]), _ptr(parents[k:] if parents is not None else None),
-                    _ptr(pairs[k:] if pairs is not None else None))
-            tail = (C.byref(n_done), _ptr(ws), ws.numel(), _stream())
-            if tmoves:
-                rc = self.lib.ds_dmc_step_tmove(*head, _ptr(cut(tmove_uniforms)), cap, int(valid), *outs,
-                                                _ptr(choice[k:] if choice is not None else None), _ptr(energy[k:]), *tail)
-            else:
-                rc = self.lib.ds_dmc_step_ecp(*head, cap, int(valid), *outs, *tail)
-            if rc != 0 and attempt == 0 and pair_capacity is None:
-                m = re.search(r'pair capacity exceeded: the walkers have (\d+) pairs', self.lib.ds_last_error().decode())
-                # (the comb's schedule counts the steps of a call: a continuation keeps it only from a multiple of branch_every)
-                if m and (branch_every <= 1 or n_done.value % int(branch_every) == 0):
-                    cap = int(m.group(1))
-                    done += n_done.value
-                    valid = valid or done > 0
-                    continue
-            _lib.check(rc, name)
-            break
-        out = dict(stats=stats, parents=parents, ecp_stats=ecp_stats, pairs=pairs, pair_capacity=cap)
-        if tmoves:
-            out.update(tmoves=choice, energy=energy)
-        return out
 
     def dmc_noise(self, B, steps, seed=0, offset=0):
         """`ds_dmc_noise`: what `dmc_step` draws in Philox mode for (seed, offset), as the arrays its explicit mode takes

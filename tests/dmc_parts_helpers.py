@@ -103,7 +103,7 @@ def longest_cell_vector(cell):
 
 
 def log_ratio(la, la2, drift, drift2, chi, tau, dtype=np.float64):
-    """k_dmc_accept's A = 2 (la2 - la) + 0.5 (|chi|^2 - |chi + sqrt(tau) (f1 v1 + f2 v2)|^2) per walker -> (A (B,), tol_A (B,)).
+    """The A of dmc_decide (k_dmc_accept, k_dmc_tm_decide) = 2 (la2 - la) + 0.5 (|chi|^2 - |chi + sqrt(tau) (f1 v1 + f2 v2)|^2) per walker -> (A (B,), tol_A (B,)).
     The limiter and the products f v are formed in `dtype`, everything else in float64.
 
     tol_A bounds |A_device - A_host| a priori.  Float64 part: the two sums have 3N terms each, added in another order than here and

@@ -329,6 +329,37 @@ def test_two_stats_groups():
     assert np.array_equal(got.view(np.int64), want.view(np.int64)), (got, want)
 
 
+# ------------------------------------------------------------------------------------------ 6b. one decision in three entries
+@pytest.mark.parametrize('B, dtype', [(B37, torch.float64), (B37, torch.float32), (300, torch.float64)], ids=['37-float64', '37-float32', '300-float64'])
+def test_the_three_entries_take_the_same_decision(B, dtype):
+    """lih, one state initialised by the plain call (its first step included), then the same single step at tau = 0.1 without a
+    comb or a clip through ds_dmc_step, ds_dmc_step_ecp and ds_dmc_step_tmove on the same explicit normals and uniforms.  The
+    decision reads logabs, phase, drift and the noise alone, so the accepted count, sum p and the non-finite count (columns 3, 4
+    and 6 of the stats row) have the same bits in the three calls, and x after the plain and the locality step is the same (the
+    T-move step may move an electron afterwards).  A third of the uniforms forces acceptance (2^-60), a third are the Philox
+    draws, a third are 1 (accepted only where A > 0): both outcomes occur.  B = 300: two stats groups, the second of 44."""
+    sysd, dp = system(NAME, dtype)
+    ecp = deh.potential()
+    seed, o, tau = 11, 30, 0.1
+    kw = dict(branch_every=0, e_cut=0.0)
+    init = sysd.dmc_state(start(B, 4, dtype), ecp=True)
+    sysd.dmc_step(dp, init, 1, tau, seed=seed, offset=o, state_valid=False, **kw)
+    nz, un, xi = sysd.dmc_noise(B, 1, seed, o + 1)
+    un[0, 0::3] = 2.0 ** -60
+    un[0, 2::3] = 1.0
+    noise = dict(normals=nz, uniforms=un, comb_uniforms=xi)
+    rot = cu(eh.replay_rotations(seed, o + 2, B))[None]
+    plain, loc, tm = clone(init), clone(init), clone(init)
+    rows = [sysd.dmc_step(dp, plain, 1, tau, **noise, **kw)['stats'],
+            sysd.dmc_step(dp, loc, 1, tau, ecp=ecp, rotations=torch.cat([rot, rot]), **noise, **kw)['stats'],
+            sysd.dmc_step(dp, tm, 1, tau, ecp=ecp, tmoves=True, rotations=rot, tmove_uniforms=cu(th.tmove_uniforms(seed, o + 1, 1, B)),
+                          **noise, **kw)['stats']]
+    for r in rows[1:]:
+        assert torch.equal(bits(r[0, [3, 4, 6]]), bits(rows[0][0, [3, 4, 6]])), (r, rows[0])
+    assert torch.equal(bits(plain['x']), bits(loc['x']))
+    assert 0 < float(rows[0][0, 3]) < B
+
+
 # ------------------------------------------------------------------------------------------ 7. robustness
 def test_a_walker_with_a_nan_coordinate_dies_and_disturbs_nobody():
     sysd, dp = system(NAME)
