@@ -1,10 +1,12 @@
 // ds_observe.hip -- observables of a batch of walkers that need no wave function (ds_obs.h, ds_realspace.h): structure factor and
 // polarization sums, electron density and pair-correlation counts; and forward walking for the DMC (ds_fw.h): ancestor tables, the
-// counts with a weight and a source row per walker, weighted sums of per-walker values.
+// counts with a weight and a source row per walker, weighted sums of per-walker values; and the ionic forces (ds_force.h), which need
+// the handle's Ewald tables and the caller's drift but no forward of their own.
 #include "ds_host.h"
 #include "ds_obs.h"
 #include "ds_realspace.h"
 #include "ds_fw.h"
+#include "ds_force.h"
 
 namespace ds {
 namespace host {
@@ -82,6 +84,48 @@ void realspace_counts_w(const ds::RealSpaceArgs& A, const void* x, long long nb,
                        B_src, (const int*)index, weight, scale, (unsigned long long*)dens, (unsigned long long*)pair, (unsigned long long*)q_sum,
                        (unsigned long long*)n_bad);
 }
+
+// the smallest distance between neighbouring lattice planes (estimator.plane_spacings)
+static double min_plane_spacing(const double* a) {
+    double inv[9], best = INFINITY;
+    inv3(a, inv);
+    for (int j = 0; j < 3; ++j) best = std::min(best, 1.0 / std::sqrt(inv[j] * inv[j] + inv[3 + j] * inv[3 + j] + inv[6 + j] * inv[6 + j]));
+    return best;
+}
+
+// ionic forces (ds_force.h): the walkers [b0, b0 + nb) of the batch; rows: of this launch
+template <typename T>
+void ion_forces(ds_system* s, const void* x, const void* drift, int64_t b0, int64_t nb, double r_c, const double* ion_ion, double* out_hf,
+                double* out_zv, double* rows, int64_t* n_bad, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const int tables = ds::force_table_flags(S);      // (>= 0: checked by ds_ion_forces)
+    const size_t n3 = 3 * (size_t)S.N, a3 = 3 * (size_t)S.As;
+    hipLaunchKernelGGL((ds::k_ion_forces<T>), dim3((unsigned)nb), dim3(256), ds::force_lds_doubles(S, tables) * sizeof(double), st, S,
+                       (const T*)x + b0 * n3, drift ? (const T*)drift + b0 * n3 : nullptr, r_c, 0.5 * min_plane_spacing(s->d.sim_a), ion_ion, tables,
+                       out_hf ? out_hf + b0 * a3 : nullptr, out_zv ? out_zv + b0 * a3 : nullptr, rows, (unsigned long long*)n_bad);
+}
+
+// half the length of the shortest non-zero lattice vector with coefficients in -3..3 (estimator.wigner_seitz_radius)
+static double wigner_seitz_radius(const double* a) {
+    double best = INFINITY;
+    for (int i = -3; i <= 3; ++i)
+        for (int j = -3; j <= 3; ++j)
+            for (int k = -3; k <= 3; ++k) {
+                if (!i && !j && !k) continue;
+                double v2 = 0;
+                for (int c = 0; c < 3; ++c) {
+                    const double v = i * a[c] + j * a[3 + c] + k * a[6 + c];
+                    v2 += v * v;
+                }
+                best = std::min(best, v2);
+            }
+    return 0.5 * std::sqrt(best);
+}
+
+template <typename T> int force_tables(ds_system* s) { return ds::force_table_flags(dev<T>(s)); }
+
+// doubles of workspace per group of FORCE_GROUP walkers: their rows and the group's partial sums
+static int64_t force_group_doubles(const ds_system* s) { return (int64_t)ds::FORCE_GROUP * 6 * s->sd.As + 12 * s->sd.As + 1; }
 
 }  // namespace host
 }  // namespace ds
@@ -230,6 +274,62 @@ int ds_dmc_fw_sums(int64_t B, int K, const double* values, int64_t B_src, const 
     HIP_OK(hipGetLastError());
     hipLaunchKernelGGL(ds::k_fw_sums_final, dim3(1), dim3(2 * ds::FW_MAX_K), 0, st, (const double*)ws, groups, K, out);
     HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int64_t ds_ion_forces_workspace_bytes(const ds_system* s, int64_t B) {
+    if (!s || B < 1) return -1;
+    const int64_t per = force_group_doubles(s) * (int64_t)sizeof(double);
+    const int64_t groups = (B + ds::FORCE_GROUP - 1) / ds::FORCE_GROUP;
+    return per * std::max<int64_t>(1, std::min<int64_t>(groups, workspace_budget() / per));
+}
+
+int ds_ion_forces(ds_system* s, const void* x, const void* drift, int64_t B, double r_c, const double* ion_ion, double* out_hf,
+                  double* out_zv, double* sums, int64_t* n_bad, void* ws, int64_t ws_bytes, void* stream) {
+    if (!s || !x) return fail("ds_ion_forces: null argument");
+    if (B < 1) return fail("ds_ion_forces: B must be >= 1 (got %lld)", (long long)B);
+    if (!out_hf && !out_zv && !sums) return fail("ds_ion_forces: out_hf, out_zv and sums are all null, nothing to write");
+    if ((out_zv || sums) && !drift) return fail("ds_ion_forces: out_zv and sums need the drift (got a null drift)");
+    const double r_ws = wigner_seitz_radius(s->d.sim_a);
+    if (!(r_c > 0.0) || !std::isfinite(r_c) || r_c > r_ws * (1.0 + 1e-12))
+        return fail("ds_ion_forces: the cutoff r_c = %g must be positive and at most the Wigner-Seitz radius %.17g of the simulation cell", r_c, r_ws);
+    // the nearest image of the zero-variance term is looked for one cell around the wrapped one (ds_force.h)
+    if ((out_zv || sums) && !(r_c < min_plane_spacing(s->d.sim_a)))
+        return fail("ds_ion_forces: the cutoff r_c = %g is not below the smallest plane spacing %g of the simulation cell: the lattice "
+                    "vectors are too skewed for the nearest-image search (use a reduced cell or a smaller cutoff)", r_c, min_plane_spacing(s->d.sim_a));
+    if (DS_BY_DTYPE(s->dtype, force_tables, s) < 0)
+        return fail("ds_ion_forces: %d ions need more than %d KB of LDS per walker: not supported", s->sd.As, (int)(ds::FORCE_LDS_MAX / 1024));
+    const int A = s->sd.As;
+    const int64_t per = force_group_doubles(s) * (int64_t)sizeof(double);
+    int64_t fit = 0;
+    if (sums) {
+        fit = ws ? ws_bytes / per : 0;
+        if (fit < 1)
+            return fail("workspace too small for ds_ion_forces: %lld bytes < %lld for one group of %d walkers (see ds_ion_forces_workspace_bytes)",
+                        (long long)(ws ? ws_bytes : 0), (long long)per, ds::FORCE_GROUP);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (!sums) {
+        DS_BY_DTYPE(s->dtype, ion_forces, s, x, drift, (int64_t)0, B, r_c, ion_ion, out_hf, out_zv, (double*)nullptr, n_bad, st);
+        HIP_OK(hipGetLastError());
+        return 0;
+    }
+    // passes of `fit` groups: a pass starts at a multiple of FORCE_GROUP walkers of the batch, so the groups -- and with them the
+    // order of every addition -- are those of one pass over everything
+    const int K = 12 * A + 1;
+    fit = std::min<int64_t>(fit, (B + ds::FORCE_GROUP - 1) / ds::FORCE_GROUP);
+    double* rows = (double*)ws;
+    double* part = rows + (size_t)fit * ds::FORCE_GROUP * 6 * A;
+    for (int64_t b0 = 0; b0 < B; b0 += fit * ds::FORCE_GROUP) {
+        const int64_t nb = std::min<int64_t>(B - b0, fit * ds::FORCE_GROUP);
+        const int64_t groups = (nb + ds::FORCE_GROUP - 1) / ds::FORCE_GROUP;
+        DS_BY_DTYPE(s->dtype, ion_forces, s, x, drift, b0, nb, r_c, ion_ion, out_hf, out_zv, rows, n_bad, st);
+        HIP_OK(hipGetLastError());
+        hipLaunchKernelGGL(ds::k_force_part, dim3((unsigned)groups), dim3(ds::FORCE_GROUP), 0, st, (const double*)rows, (long long)nb, A, part);
+        HIP_OK(hipGetLastError());
+        hipLaunchKernelGGL(ds::k_force_final, dim3((K + 255) / 256), dim3(256), 0, st, (const double*)part, (long long)groups, K, sums);
+        HIP_OK(hipGetLastError());
+    }
     return 0;
 }
 

@@ -686,6 +686,52 @@ class DeviceSystem:
         return dict(sums=sums, n_bad=n_bad, ratios=torch.view_as_complex(ratios) if ratios is not None else None,
                     walker=torch.view_as_complex(walker) if want_walker else None)
 
+    def force_cutoff(self, cutoff=None):
+        """The cutoff r_c of the zero-variance force term (`estimator.force_cutoff` on the simulation cell): `cutoff`, or by default
+        the Wigner-Seitz radius, which is also the largest value accepted (the same check the library makes)."""
+        from .estimator import force_cutoff
+        return force_cutoff(self.cell.a, cutoff)
+
+    def ion_forces(self, x, drift=None, cutoff=None, sums=None, want_walker=True, max_bytes=None):
+        """`ds_ion_forces` (csrc/ds_force.h): per walker and ion of the simulation cell the Hellmann-Feynman
+        force of the Ewald energy, hf = -d(E_ei + E_ii)/dR_a, and with `drift` (B, 3N) = Re grad log psi (`logpsi_grad(...)[1].real`)
+        the zero-variance force zv = hf + dF of Assaraf and Caffarel with the cutoff `cutoff` (default and maximum: the Wigner-Seitz
+        radius).  NOT the full force: the Pulay term is missing, so hf and zv are exact only for an exact psi (bias first order in
+        the error of psi); all-electron ions only.  `sums`: float64 device tensor (12 A + 1,) that is ADDED to = per (a, c)
+        [sum hf, sum hf^2, sum zv, sum zv^2] over the good walkers, then their number; it needs the drift.  A walker with a
+        non-finite coordinate, drift or result is NaN, left out and counted.  `max_bytes` caps the workspace of `sums`: more
+        passes, bit-identical results.  The ion-ion force is computed once on the host and cached on the system.
+        -> dict(hf (B, A, 3) float64 or None without `want_walker`, zv likewise or None without a drift, n_bad (1,) int64 device
+        tensor, sums).  No host synchronisation."""
+        x = self._check_x(x)
+        B = x.shape[0]
+        A = int(self.tables.atom_coords.shape[0])
+        r_c = self.force_cutoff(cutoff)
+        if drift is not None:
+            if not (drift.is_cuda and drift.dtype == self.dtype and tuple(drift.shape) == tuple(x.shape)):
+                raise ValueError(f'drift must be a {self.dtype} device tensor of shape {tuple(x.shape)}')
+            drift = drift.contiguous()
+        if sums is not None:
+            if not (sums.is_cuda and sums.dtype == torch.float64 and sums.is_contiguous() and tuple(sums.shape) == (12 * A + 1,)):
+                raise ValueError(f'sums must be a contiguous float64 device tensor of shape ({12 * A + 1},)')
+            if drift is None:
+                raise ValueError('sums hold the zero-variance force too: they need the drift')
+        if not want_walker and sums is None:
+            raise ValueError('nothing to compute: neither the walker forces nor sums are asked for')
+        hf = torch.empty(B, A, 3, dtype=torch.float64, device=self.device) if want_walker else None
+        zv = torch.empty(B, A, 3, dtype=torch.float64, device=self.device) if want_walker and drift is not None else None
+        n_bad = torch.zeros(1, dtype=torch.int64, device=self.device)
+        if B == 0:
+            return dict(hf=hf, zv=zv, n_bad=n_bad, sums=sums)
+        if getattr(self, '_ion_ion_force', None) is None:
+            from .ewaldsum import ion_ion_forces
+            self._ion_ion_force = torch.as_tensor(ion_ion_forces(self.cell, tables=self.tables), dtype=torch.float64, device=self.device)
+        ws = self._workspace('ds_ion_forces_workspace_bytes', int(B), max_bytes=max_bytes) if sums is not None else None
+        _lib.check(self.lib.ds_ion_forces(self.handle, _ptr(x), _ptr(drift), B, r_c, _ptr(self._ion_ion_force), _ptr(hf), _ptr(zv),
+                                          _ptr(sums), _ptr(n_bad), _ptr(ws), ws.numel() if ws is not None else 0, _stream()),
+                   'ds_ion_forces')
+        return dict(hf=hf, zv=zv, n_bad=n_bad, sums=sums)
+
     def dmc_state(self, x, weight=None, ecp=False):
         """Fresh DMC walker state for `dmc_step(..., state_valid=False)`: dict of the six caller-owned device buffers (x is copied;
         logabs, phase, drift and eloc are filled by the first call; weights are 1 or `weight`).  `ecp=True` adds the seventh, 'epp'

@@ -675,3 +675,188 @@ class SpinSquared:
         """The accumulator saved at `path` as a fresh rank-local one without a network (see `from_state_dict`)."""
         with np.load(path) as f:
             return cls.from_state_dict({k: f[k] for k in f.files})
+
+
+# ------------------------------------------------------------------ ionic forces (csrc/ds_force.h)
+# The reference has no force estimator; the conventions of this section are this project's own (DESIGN.md section 21).
+def force_cutoff(a, cutoff=None):
+    """The cutoff r_c of the zero-variance force term for the lattice `a`: `cutoff` in bohr, by default `wigner_seitz_radius(a)`, which
+    is also the largest value accepted; anything <= 0, not finite or larger raises ValueError.  So does a cutoff that is not below
+    the smallest plane spacing (lattice vectors far from reduced: the kernel looks for the nearest image one cell around the
+    wrapped one; no shipped cell comes close)."""
+    r_ws = wigner_seitz_radius(a)
+    cutoff = r_ws if cutoff is None else float(cutoff)
+    if not (np.isfinite(cutoff) and 0.0 < cutoff <= r_ws * (1.0 + 1e-12)):
+        raise ValueError(f'cutoff = {cutoff} must be positive and at most the Wigner-Seitz radius {r_ws} of the simulation cell')
+    if not cutoff < plane_spacings(a).min():
+        raise ValueError(f'cutoff = {cutoff} is not below the smallest plane spacing {plane_spacings(a).min()} of the simulation '
+                         'cell: the lattice vectors are too skewed for the nearest-image search (use a reduced cell)')
+    return cutoff
+
+
+class IonForces:
+    """Forces on the ions of the simulation cell, accumulated on the device over any number of walker batches: an accumulator for
+    `run_inference(accumulators=...)` (VMC) and `run_dmc(accumulators=...)` (the mixed estimate, on comb blocks).  Per ion a:
+
+        hf = < -d(E_ei + E_ii)/dR_a >                 the Hellmann-Feynman force of the Ewald energy (infinite variance at an
+                                                      all-electron nucleus: the integrand goes as 1/r^2)
+        zv = < hf + (H - E_L)(Q_a psi)/psi >          the zero-variance force of Assaraf and Caffarel,
+             Q_a = -Z_a sum_i c(r_ia) v_ia / r_ia,    c(r) = (1 - r^2/r_c^2)^3 inside the cutoff r_c, 0 beyond,
+                                                      v_ia the nearest image of r_i - R_a
+
+    The added term has zero expectation and cancels the 1/r^2 singularity; it needs only the drift Re grad log psi.
+    WHAT IS MISSING: the Pulay term 2 <(E_L - E) d log psi / dR_a> is not evaluated (the walker gradient comes from forward jets:
+    there is no derivative with respect to an ion position).  hf and zv are therefore the force only for an exact psi, and their
+    bias is FIRST ORDER in the error of the wave function.  All-electron ions only: a semi-local pseudopotential has force terms
+    of its own, which are not implemented (`pseudopotential` must be None).
+
+    Every `update` is ONE `ds_logpsi_grad` call and ONE `ds_ion_forces` call that adds to 12 A + 1 float64 numbers; nothing is read
+    back.  `cutoff`: r_c, by default (and at most) `wigner_seitz_radius` of the simulation cell.  `net`: the object
+    `make_solid_fermi_net` returns (or its `.apply`).
+    A pure (forward-walking) DMC estimate of one component goes through `dmc.ForwardWalking` as a callable, for instance
+    `scalars={'f_zv': lambda arrays: system.ion_forces(arrays['x'], arrays['drift'])['zv'].reshape(len(arrays['x']), -1)}`."""
+
+    def __init__(self, net, params, cutoff=None, pseudopotential=None):
+        if pseudopotential is not None:
+            raise NotImplementedError('IonForces: the force terms of a semi-local pseudopotential are not implemented '
+                                      '(all-electron ions only)')
+        self.apply = getattr(net, 'apply', net)
+        self.params = params
+        cell = self.apply.simulation_cell
+        self._setup(np.asarray(cell.atom_coords(), np.float64), np.asarray(cell.atom_charges(), np.float64),
+                    np.asarray(cell.a, np.float64), int(sum(cell.nelec)), cutoff)
+
+    def _setup(self, atoms, charges, latvec, n_elec, cutoff):
+        self.atoms = np.asarray(atoms, np.float64).reshape(-1, 3)
+        self.charges = np.asarray(charges, np.float64).reshape(-1)
+        self.latvec = np.asarray(latvec, np.float64).reshape(3, 3)
+        self.n_elec = int(n_elec)
+        self.cutoff = force_cutoff(self.latvec, cutoff)
+        self.n_atoms = self.atoms.shape[0]
+        self.sums = torch.zeros(12 * self.n_atoms + 1, dtype=torch.float64)     # moved to the walkers' device by the first update
+        self.n_bad = torch.zeros(1, dtype=torch.int64)
+        self.n_walkers = 0
+        self.reduced = False
+
+    # ---- accumulation
+    def update(self, data):
+        """Add the forces of every walker of `data` (B, 3N) to the sums: one `ds_logpsi_grad` and one `ds_ion_forces` call, no
+        device -> host copy."""
+        if self.apply is None:
+            raise RuntimeError('IonForces.update: a loaded accumulator has no network; merge it into one that has')
+        if self.reduced:
+            raise RuntimeError('IonForces.update after reduce(): the sums are already summed over the ranks')
+        if data.shape[-1] != 3 * self.n_elec:
+            raise ValueError(f'walkers have {data.shape[-1]} coordinates, the cell has {self.n_elec} electrons')
+        x = data.reshape(-1, 3 * self.n_elec)
+        if x.shape[0] == 0:
+            return
+        if self.sums.device != x.device:
+            self.sums, self.n_bad = self.sums.to(x.device), self.n_bad.to(x.device)
+        system = self.apply.system
+        drift = system.logpsi_grad(self.params, x)[1].real.contiguous()
+        out = system.ion_forces(x, drift, cutoff=self.cutoff, sums=self.sums, want_walker=False)
+        self.n_bad += out['n_bad']
+        self.n_walkers += int(x.shape[0])           # only now: a call that raised leaves the count with the sums
+
+    def _same_setup(self, other):
+        return (self.atoms.shape == other.atoms.shape and np.array_equal(self.atoms, other.atoms) and
+                np.array_equal(self.charges, other.charges) and np.array_equal(self.latvec, other.latvec) and
+                self.n_elec == other.n_elec and self.cutoff == other.cutoff)
+
+    def merge(self, other):
+        """Add the sums, the bad count and the walker number of another accumulator of the same ions, lattice and cutoff.  Both sides
+        must be in the same state (rank-local or summed over the ranks), as for `SpinSquared.merge`."""
+        if not self._same_setup(other):
+            raise ValueError('IonForces.merge: the two accumulators differ in ions, lattice, electron number or cutoff')
+        if self.reduced != other.reduced and constants.world_size() > 1:
+            raise ValueError('IonForces.merge: one side is summed over the ranks and the other is rank-local')
+        self.sums = self.sums + other.sums.to(self.sums.device)
+        self.n_bad = self.n_bad + other.n_bad.to(self.n_bad.device)
+        self.n_walkers += other.n_walkers
+        return self
+
+    def reduce(self):
+        """Sum the sums, the bad count and the walker number over the ranks in ONE packed float64 all-reduce (counts below 2^53 are
+        exact; the identity at world size 1).  Once per accumulator: a second call raises."""
+        if self.reduced:
+            raise RuntimeError('IonForces.reduce was already called: reducing twice would count every rank again')
+        if constants.world_size() > 1:
+            dev = self.sums.device if self.sums.is_cuda else torch.device('cuda' if torch.cuda.is_available() else 'cpu')
+            k = self.sums.numel()
+            packed = torch.cat([self.sums.to(dev), self.n_bad.to(dev, torch.float64),
+                                torch.tensor([self.n_walkers], dtype=torch.float64, device=dev)])
+            packed = constants.psum_if_pmap(packed)
+            self.sums = packed[:k].clone()
+            self.n_bad = packed[k:k + 1].round().to(torch.int64)
+            self.n_walkers = int(packed[k + 1].round())
+        self.reduced = True                 # only now: a collective that raised leaves the accumulator as it was
+        return self
+
+    # ---- normalisation (host)
+    def forces(self):
+        """-> dict(hf, hf_error, zv, zv_error (each (A, 3) float64, Ha/bohr), n_walkers, n_bad, atoms (A, 3), cutoff):
+        the means over the n_good walkers whose forces were finite, and error = sqrt((sum f^2 / n_good - mean^2) / (n_good - 1)): a
+        NAIVE standard error over walkers -- it takes them as independent and ignores the autocorrelation of the Markov chain, so
+        it is a lower bound on a real run (NaN below two good walkers; of hf it does not even exist in the limit: the variance of
+        the bare Hellmann-Feynman force of an all-electron ion is infinite).  NaN everywhere without a good walker.  The Pulay
+        term is not part of either force (see the class)."""
+        s = self.sums.detach().cpu().numpy()
+        A = self.n_atoms
+        n = float(s[12 * A])
+        q = s[:12 * A].reshape(A, 3, 4)
+        out = dict(n_walkers=self.n_walkers, n_bad=int(self.n_bad.sum()), atoms=self.atoms.copy(), cutoff=self.cutoff)
+        for name, k in (('hf', 0), ('zv', 2)):
+            if n < 1:
+                out[name] = np.full((A, 3), np.nan)
+                out[name + '_error'] = np.full((A, 3), np.nan)
+                continue
+            mean = q[:, :, k] / n
+            var = np.maximum(q[:, :, k + 1] / n - mean * mean, 0.0)
+            out[name] = mean
+            out[name + '_error'] = np.sqrt(var / (n - 1)) if n > 1 else np.full((A, 3), np.nan)
+        return out
+
+    # ---- persistence
+    def state_dict(self):
+        """Plain numpy arrays: the sums and counts and the setup they belong to."""
+        return {'sums': self.sums.detach().cpu().numpy().copy(), 'n_bad': self.n_bad.detach().cpu().numpy().copy(),
+                'n_walkers': np.int64(self.n_walkers), 'atoms': self.atoms.copy(), 'charges': self.charges.copy(),
+                'latvec': self.latvec.copy(), 'n_elec': np.int64(self.n_elec), 'cutoff': np.float64(self.cutoff),
+                'reduced': np.bool_(self.reduced)}
+
+    def load_state_dict(self, sd):
+        """Replace the sums and counts by those of `sd` (same ions, lattice and cutoff); the accumulator is rank-local and open for
+        `update` afterwards."""
+        other = IonForces.from_state_dict(sd)
+        if not self._same_setup(other):
+            raise ValueError('IonForces.load_state_dict: the state belongs to other ions, another lattice or another cutoff')
+        self.sums, self.n_bad = other.sums.to(self.sums.device), other.n_bad.to(self.n_bad.device)
+        self.n_walkers, self.reduced = other.n_walkers, False
+        return self
+
+    @classmethod
+    def from_state_dict(cls, sd):
+        """An accumulator without a network: it can be merged, normalised and saved, not updated."""
+        acc = cls.__new__(cls)
+        acc.apply = acc.params = None
+        acc._setup(sd['atoms'], sd['charges'], sd['latvec'], int(sd['n_elec']), float(sd['cutoff']))
+        acc.sums = torch.as_tensor(np.array(sd['sums'], dtype=np.float64).reshape(12 * acc.n_atoms + 1))
+        acc.n_bad = torch.as_tensor(np.array(sd['n_bad'], dtype=np.int64).reshape(1))
+        acc.n_walkers = int(sd['n_walkers'])
+        return acc                          # reduced stays False: the loaded sums are this rank's contribution from here on
+
+    def save(self, path, results=True):
+        """One .npz of `state_dict()`; `results`: also hf, hf_error, zv and zv_error of `forces()`."""
+        sd = self.state_dict()
+        if results:
+            r = self.forces()
+            sd.update({k: r[k] for k in ('hf', 'hf_error', 'zv', 'zv_error')})
+        with open(path, 'wb') as f:
+            np.savez(f, **sd)
+
+    @classmethod
+    def load(cls, path):
+        """The accumulator saved at `path` as a fresh rank-local one without a network (see `from_state_dict`)."""
+        with np.load(path) as f:
+            return cls.from_state_dict({k: f[k] for k in f.files})

@@ -100,6 +100,35 @@ class EwaldTables:
         return -ne * self.i_sum * self.ijconst                                      # :112-113
 
 
+def ion_ion_forces(cell, ewald_gmax=EWALD_GMAX, tables=None):
+    """(A, 3) float64: -d E_ii / d R_a of the ion-ion Ewald energy `EwaldTables.ion_ion` (reference `_ewald_ion`), the minimal-image
+    choice of every pair held fixed.  A constant of the geometry: the ion-ion part of the Hellmann-Feynman force
+    (`DeviceSystem.ion_forces`).
+      real space:  pair a < b, v = mi(R_a - R_b) + D_s over the 27 cells:  F_a += Z_a Z_b [erfc(alpha r)/r^2 + (2 alpha/sqrt pi)
+                   exp(-alpha^2 r^2)/r] v/r,  F_b -= the same
+      reciprocal:  F_a = 2 Z_a sum_G w_G G (Re S sin(G.R_a) - Im S cos(G.R_a)),  S = sum_b Z_b exp(i G.R_b)
+    The constants of the energy do not depend on the positions."""
+    from scipy.special import erfc
+    t = tables if tables is not None else EwaldTables(cell, ewald_gmax)
+    q, R, al = t.atom_charges, t.atom_coords, t.alpha
+    n = len(q)
+    F = np.zeros((n, 3))
+    shifts = np.stack(np.meshgrid(*[np.arange(-1, 2)] * 3, indexing='ij'), -1).reshape(-1, 3) @ t.latvec
+    for a in range(n):
+        for b in range(a + 1, n):
+            d = distance.minimal_image_host(t.latvec, t.dist_mode, R[a] - R[b])
+            v = d[None, :] + shifts
+            r = np.linalg.norm(v, axis=1)
+            f = (erfc(al * r) / r ** 2 + 2 * al / np.sqrt(np.pi) * np.exp(-(al * r) ** 2) / r) / r
+            pair = q[a] * q[b] * (f[:, None] * v).sum(axis=0)
+            F[a] += pair
+            F[b] -= pair
+    gr = t.gpoints @ R.T                                                           # (NG, A)
+    m = t.gweight[:, None] * (t.ion_exp.real[:, None] * np.sin(gr) - t.ion_exp.imag[:, None] * np.cos(gr))
+    F += 2 * q[:, None] * (m.T @ t.gpoints)
+    return F
+
+
 class EwaldSum(EwaldTables):
     """Reference-shaped class: ``energy(configs)`` -> (ee, ei, ii) on the GPU.
 

@@ -16,6 +16,10 @@ deepsolid_amd.estimator.RealSpaceAccumulator, written to realspace.npz in the wo
 through deepsolid_amd.estimator.MomentumDistribution, written to momentum.npz;
 --spin-squared [PAIRS]: the total spin <S^2> from PAIRS spin-exchange ratios per walker and evaluation step (default: all
 n_up n_dn pairs), through deepsolid_amd.estimator.SpinSquared, written to spin_squared.npz;
+--forces: the forces on the two ions over the evaluation, through deepsolid_amd.estimator.IonForces, written to forces.npz: the
+Hellmann-Feynman force of the Ewald energy and the zero-variance force of Assaraf and Caffarel with the Wigner-Seitz radius as its
+cutoff; --forces-cutoff X: the same with the cutoff X in bohr (at most the Wigner-Seitz radius).  The Pulay term is NOT evaluated,
+so both are the force only for an exact wave function (bias first order in its error); all-electron only: not with --ecp;
 --ecp FILE.npz: add the semi-local pseudopotential saved in FILE.npz (deepsolid_amd.pseudopotential.SemiLocalECP.save, built for
 THIS cell) to the local energy of training and evaluation: the rows then carry its batch mean E_loc + E_nl.  The
 cell of this example is all-electron, so with a real potential the numbers mean nothing: the point is the call sequence);
@@ -78,6 +82,14 @@ if '--spin-squared' in sys.argv:
         spin_pairs = int(sys.argv[i + 1])
         del sys.argv[i + 1]
     del sys.argv[i]
+forces, force_cutoff = False, None
+if '--forces-cutoff' in sys.argv:
+    i = sys.argv.index('--forces-cutoff')
+    forces, force_cutoff = True, float(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
+if '--forces' in sys.argv:
+    forces = True
+    sys.argv.remove('--forces')
 dmc_blocks, dmc_tau = 0, 0.01
 if '--dmc-tau' in sys.argv:
     i = sys.argv.index('--dmc-tau')
@@ -100,6 +112,8 @@ if '--ecp' in sys.argv:
     i = sys.argv.index('--ecp')
     ecp_file = sys.argv[i + 1]
     del sys.argv[i:i + 2]
+if forces and ecp_file is not None:
+    sys.exit('--forces is all-electron only: the force terms of a pseudopotential are not implemented')
 if dmc_pure is not None and dmc_blocks <= 0:
     sys.exit('--dmc-pure needs --dmc BLOCKS')
 if tmoves and (ecp_file is None or dmc_blocks <= 0):
@@ -138,6 +152,11 @@ if spin_squared:
     from deepsolid_amd import estimator
     spin_acc = estimator.SpinSquared(logdet, params, pairs_per_walker=spin_pairs)
     accumulators += (spin_acc,)
+force_acc = None
+if forces:
+    from deepsolid_amd import estimator
+    force_acc = estimator.IonForces(logdet, params, cutoff=force_cutoff)
+    accumulators += (force_acc,)
 data, width, rows = inference.run_inference(slogdet, logdet, params, data, cell, iterations=10, burn_in=10, move_width=width,
                                             accumulators=accumulators, pseudopotential=ecp)
 if ecp is not None:
@@ -150,6 +169,15 @@ for acc in accumulators:
         s2 = acc.spin_squared()
         print('<S^2>:      %.4f +- %.4f (naive error over %d walkers, %d left out; %d of %d pairs per walker; S_z (S_z + 1) = %.2f)'
               % (s2['value'], s2['error'], s2['n_walkers'], s2['n_bad'], acc.pairs_per_walker, acc.n_pairs_total, s2['sz'] * (s2['sz'] + 1)))
+        continue
+    if acc is force_acc:
+        acc.save('forces.npz', results=True)
+        f = acc.forces()
+        print('forces:     cutoff %.4f Bohr, naive errors over %d walkers (%d left out); no Pulay term: exact only for an exact psi'
+              % (f['cutoff'], f['n_walkers'], f['n_bad']))
+        for a in range(len(f['atoms'])):
+            print('            %-2s HF (%9.4f %9.4f %9.4f) +- (%.4f %.4f %.4f)   ZV (%9.4f %9.4f %9.4f) +- (%.4f %.4f %.4f) Ha/Bohr'
+                  % ((cell.atom_symbol(a),) + tuple(f['hf'][a]) + tuple(f['hf_error'][a]) + tuple(f['zv'][a]) + tuple(f['zv_error'][a])))
         continue
     if acc is momentum_acc:
         acc.save('momentum.npz', results=True)

@@ -479,6 +479,40 @@ int ds_spin_exchange_ratios(ds_system* sys, const void* params, const void* x, i
                             double* sums, void* out_ratio, double* out_walker, int64_t* n_bad, void* ws, int64_t ws_bytes,
                             void* stream);
 
+/* Ionic forces of a batch of walkers (csrc/ds_force.h): the Hellmann-Feynman (HF) force of the Ewald energy
+ * and the Assaraf-Caffarel zero-variance (ZV) force.  The reference has no force estimator: the conventions are this library's own.
+ *   Per walker and ion a of the simulation cell (A = n_atoms_sim ions, charges sim_charges):
+ *       F^hf_a = -d(E_ei + E_ii)/dR_a of exactly the Ewald expressions of ds_ewald, the minimal-image choice held fixed
+ *       F^zv_a = F^hf_a + dF_a,   dF_a = -1/2 lap Q_a - grad Q_a . Re grad log psi,
+ *       Q_a(R) = -Z_a sum_i c(r_ia) v_ia / r_ia,   c(r) = (1 - r^2/r_c^2)^3 for r < r_c, 0 beyond,
+ *       v_ia = the NEAREST image of r_i - R_a: not the minimal image of ds_ewald, which on the bcc cells (fractional wrap of a
+ *       non-orthogonal lattice) and for walkers outside the cell is a longer one; the call finds it itself (csrc/ds_force.h)
+ *   dF has zero expectation over |psi|^2 and removes the 1/r^2 singularity (the infinite variance) of F^hf at an all-electron
+ *   nucleus.  NOT included: the Pulay term 2 <(E_L - E) d log psi / dR_a>.  HF + ZV is the force only for an exact psi; its bias is
+ *   first order in the error of the wave function.  All-electron ions only: no pseudopotential term.
+ *   - x (B, 3N) and drift (B, 3N) = Re grad log psi (the real parts of ds_logpsi_grad's out_grad): device arrays of the system's
+ *     dtype.  drift is needed for out_zv and for sums, and may be NULL otherwise.  All arithmetic is float64 for either dtype.
+ *   - r_c: 0 < r_c <= the Wigner-Seitz radius of the simulation cell (half its shortest lattice vector); with out_zv or sums also
+ *     below the smallest plane spacing of the cell (the nearest-image search looks one cell around the wrapped difference; every
+ *     reduced cell meets this with room).
+ *   - ion_ion (A, 3) float64 device array, optional: the ion-ion force, a constant of the geometry, added to both outputs.
+ *   - out_hf, out_zv (B, A, 3) float64, each optional.
+ *   - sums: device float64 [12 A + 1], ADDED to and never zeroed, optional: per (a, c), at 4 (3 a + c),
+ *       [ sum F^hf, sum (F^hf)^2, sum F^zv, sum (F^zv)^2 ]  over the good walkers of the call, then their number.
+ *   - A walker with a non-finite coordinate, drift or result is bad: NaN in all its outputs, left out of sums, counted in n_bad
+ *     (device (1,) int64, ADDED to; optional).
+ *   - ws: needed for sums only: at least one group of 256 walkers (256 x 6 A + 12 A + 1 doubles).
+ * Every addition is made in a fixed order (ds_force.h): the LDS tree over the 256 threads of a walker's workgroup, the same tree over
+ * the 256 walkers of a group, the groups in order onto sums.  Groups are cut at multiples of 256 walkers of the batch whatever the
+ * workspace, so the results are bit-identical from run to run and for ANY workspace size.  No floating-point atomics, no host
+ * synchronisation, no allocation.
+ * Refused with a ds_last_error message before any launch: a null handle or x, B < 1, nothing to write, a null drift with out_zv or
+ * sums, r_c <= 0, not finite, above the Wigner-Seitz radius or (with out_zv or sums) not below the smallest plane spacing, a cell
+ * with so many ions (about a thousand) that the kernel's LDS layout exceeds 64 KB, and with sums a workspace below one group. */
+int64_t ds_ion_forces_workspace_bytes(const ds_system* sys, int64_t B);
+int ds_ion_forces(ds_system* sys, const void* x, const void* drift, int64_t B, double r_c, const double* ion_ion, double* out_hf,
+                  double* out_zv, double* sums, int64_t* n_bad, void* ws, int64_t ws_bytes, void* stream);
+
 /* Semi-local pseudopotential (ECP) energy of a batch of walkers (csrc/ds_ecp.h).  The reference has no
  * pseudopotentials: the conventions are this library's own.
  *
