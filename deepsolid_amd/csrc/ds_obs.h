@@ -13,10 +13,14 @@
 //
 // Layout: one wave per workgroup, walkers b = blockIdx.x, blockIdx.x + G, ... in turn; lane l owns the points q = l + 64 j.
 // Per chunk of 64 electrons each lane computes its electron's z_j and writes the powers z_j^0..z_j^(P-1) to LDS; after the
-// barrier every lane walks the chunk's electrons in order and multiplies its points' three powers out of the table.
-// Reduction order is fixed, so two calls on the same input are bit-identical: electrons in index order inside a walker, the
-// walkers of one workgroup in the order it visits them, then k_obs_final adds the G workgroup partials in workgroup order.
-// No atomics anywhere.
+// barrier every lane walks the chunk's table rows in order and multiplies its points' three powers out of the table.
+// An electron's row is not its index but its slot in the chunk's order by coordinate bit patterns (64 integer comparisons per
+// lane out of LDS): electrons are identical particles, and with the slots the sums of a walker do not depend on how a chunk's
+// electrons are numbered -- permuting them leaves every bit.  (Across chunks the numbering still decides which chunk an
+// electron is in, so there only the rounding bound holds.)  The polarization phase goes through LDS by slot as well.
+// Reduction order is fixed, so two calls on the same input are bit-identical: the chunks in index order, slots in order inside
+// a chunk, the walkers of one workgroup in the order it visits them, then k_obs_final adds the G workgroup partials in
+// workgroup order.  No atomics anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,6 +47,9 @@ template <typename T, int QJ>
 __global__ __launch_bounds__(64) void k_obs_partial(ObsArgs A, const T* __restrict__ x, long long B, int N,
                                                     double* __restrict__ part) {
     __shared__ double2 tab[64][OBS_TAB];
+    __shared__ long long key0[64];     // bit patterns of the chunk's coordinates: the first,
+    __shared__ long long key[64][3];   // and the other two ([1], [2]) for chunks where two first coordinates are equal
+    __shared__ double dps[64];         // polarization phases of the chunk, by slot
     const int lane = threadIdx.x;
     const int G = gridDim.x;
     const int nq = A.n_q;
@@ -68,13 +75,43 @@ __global__ __launch_bounds__(64) void k_obs_partial(ObsArgs A, const T* __restri
         double dpol = 0.0;
         for (int e0 = 0; e0 < N; e0 += 64) {
             const int ne = N - e0 < 64 ? N - e0 : 64;
+            double r0 = 0.0, r1 = 0.0, r2 = 0.0;
             if (lane < ne) {
                 const T* r = xb + 3 * (e0 + lane);
-                const double r0 = (double)r[0], r1 = (double)r[1], r2 = (double)r[2];
+                r0 = (double)r[0], r1 = (double)r[1], r2 = (double)r[2];
+                key[lane][1] = __double_as_longlong(r1);
+                key[lane][2] = __double_as_longlong(r2);
+            }
+            // slot of this electron in the chunk: the number of electrons before it in the lexicographic order of the
+            // coordinates' bit patterns (equal electrons, whose terms are equal too, in lane order): a permutation of 0..ne-1.
+            // The first coordinate decides unless two electrons of the chunk share its bits; lanes without an electron hold
+            // the largest key and come last.
+            const long long k0 = lane < ne ? __double_as_longlong(r0) : 0x7fffffffffffffffLL;
+            key0[lane] = k0;
+            __syncthreads();
+            int slot = 0;
+            bool tie = false;
+#pragma unroll 16
+            for (int m = 0; m < 64; ++m) {
+                const long long m0 = key0[m];
+                slot += (m0 < k0 || (m0 == k0 && m < lane)) ? 1 : 0;
+                tie = tie || (m0 == k0 && m != lane);
+            }
+            if (__any(tie && lane < ne) && lane < ne) {
+                const long long k1 = key[lane][1], k2 = key[lane][2];
+                slot = 0;
+                for (int m = 0; m < ne; ++m) {
+                    const long long m0 = key0[m], m1 = key[m][1], m2 = key[m][2];
+                    const bool same = m0 == k0 && m1 == k1 && m2 == k2;
+                    const bool less = m0 < k0 || (m0 == k0 && (m1 < k1 || (m1 == k1 && m2 < k2)));
+                    slot += (less || (same && m < lane)) ? 1 : 0;
+                }
+            }
+            if (lane < ne) {
                 double d[3];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) d[c] = A.g[3 * c] * r0 + A.g[3 * c + 1] * r1 + A.g[3 * c + 2] * r2;
-                dpol += A.pol == 0 ? d[0] : (A.pol == 1 ? d[1] : (A.pol == 2 ? d[2] : 0.0));
+                dps[slot] = A.pol == 0 ? d[0] : (A.pol == 1 ? d[1] : (A.pol == 2 ? d[2] : 0.0));
                 if (nq > 0) {
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
@@ -82,7 +119,7 @@ __global__ __launch_bounds__(64) void k_obs_partial(ObsArgs A, const T* __restri
                         sincos(d[c], &s, &co);
                         double wr = 1.0, wi = 0.0;
                         for (int p = 0; p < A.n_pow; ++p) {
-                            tab[lane][c * OBS_MAX_POW + p] = make_double2(wr, wi);
+                            tab[slot][c * OBS_MAX_POW + p] = make_double2(wr, wi);
                             const double tr = wr * co - wi * s;
                             wi = wr * s + wi * co;
                             wr = tr;
@@ -91,6 +128,7 @@ __global__ __launch_bounds__(64) void k_obs_partial(ObsArgs A, const T* __restri
                 }
             }
             __syncthreads();
+            if (lane < ne) dpol += dps[lane];
             for (int e = 0; e < ne; ++e) {
 #pragma unroll
                 for (int j = 0; j < QJ; ++j) {

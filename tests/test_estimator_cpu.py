@@ -1,7 +1,9 @@
 """CPU checks of the walker observables (deepsolid_amd/estimator.py, reference DeepSolid/estimator.py): the q-grid order and
 the packed-sum -> (P, S(k)) algebra against tests/golden/estimators.npz (made by tools/make_estimator_golden.py, which
 executes the reference's estimator.py), the 2-rank combination over gloo, the structure_factor.csv row format against pandas,
-and the host side of the `ds_observables` C ABI (symbols, workspace size, argument errors -- all answered before any launch)."""
+and the host side of the `ds_observables` C ABI (symbols, workspace size, argument errors -- all answered before any launch).
+Also the long-double reference, the a-priori error bound and the point lists that tests/test_gpu_estimator.py uses above 64
+electrons, with a float64 replay of the kernel's recurrence that keeps the bound checkable without a GPU."""
 import ctypes as C
 import os
 import subprocess
@@ -41,6 +43,138 @@ def np_sums(x, rv, grid, pol_dir):
         out[2 + Q:2 + 2 * Q] = rho.imag.sum(axis=0)
         out[2 + 2 * Q:] = (np.abs(rho) ** 2).sum(axis=0)
     return out
+
+
+# ----------------------------------------------------------------------------- beyond one 64-electron chunk, general point lists
+TRICLINIC = np.array([[7.0, 0.3, 0.0], [0.2, 8.0, 0.5], [-1.0, 0.4, 9.0]])
+U = 2.0 ** -53
+
+
+def cell_walkers(n_elec, batch, seed=0):
+    """(batch, 3 n_elec) float64 walkers of the triclinic cell, uniform over the cells -3 .. +4 in every direction."""
+    rng = np.random.default_rng(100000 * seed + 1000 * n_elec + batch)
+    return (rng.uniform(-3.0, 4.0, size=(batch, n_elec, 3)) @ TRICLINIC).reshape(batch, 3 * n_elec)
+
+
+def point_lists():
+    """name -> (Q, 3) int32 lattice coordinates:
+    cubic8   the 8^3 grid, 512 points: 8 points per lane;
+    box720   150 points drawn (with repeats) from n1 <= 7, n2 <= 2, n3 = 0: three points per lane (the kernel instance of four),
+             a different largest power in every direction, the table depth 8 set by direction 1 alone;
+    box111   130 points drawn from the eight with all coordinates <= 1: table depth 2;
+    origin   the single point (0, 0, 0): rho = N."""
+    rng = np.random.default_rng(720)
+    box720 = np.stack([rng.integers(0, 8, 150), rng.integers(0, 3, 150), np.zeros(150, np.int64)], axis=1)
+    box720[:3] = [[7, 0, 0], [0, 2, 0], [7, 2, 0]]
+    box111 = rng.integers(0, 2, size=(130, 3))
+    box111[:2] = [[1, 1, 1], [0, 0, 0]]
+    return {'cubic8': estimator.structure_factor_grid(8), 'box720': box720.astype(np.int32), 'box111': box111.astype(np.int32),
+            'origin': np.zeros((1, 3), np.int32)}
+
+
+def ld_sums(x, rv, grid, pol_dir):
+    """`np_sums` in np.longdouble (64-bit significand here), whose own rounding is 2^-11 of float64's -> (packed sums, rho (B, Q)).
+    exp(i q.r) is taken as the product over the three directions of exp(i n_j g_j.r), every factor a direct long-double sincos
+    of n_j (g_j.r): the same number, at 24 sincos per electron instead of Q.  The electron sum runs over every (n1, n2, n3)
+    below the list's largest coordinate as one long-double matrix product, and the list's points are read out of that."""
+    LD = np.longdouble
+    B = x.shape[0]
+    r = np.asarray(x, dtype=np.float64).reshape(B, -1, 3).astype(LD)
+    th = r @ np.asarray(rv, dtype=np.float64).astype(LD).T            # (B, N, 3): g_j . r
+    Q = grid.shape[0]
+    out = np.zeros(2 + 3 * Q, dtype=LD)
+    rho = np.zeros((B, Q), dtype=np.clongdouble)
+    if pol_dir >= 0:
+        ph = th[:, :, pol_dir].sum(axis=1)
+        out[0], out[1] = np.cos(ph).sum(), np.sin(ph).sum()
+    if Q:
+        ang = th[..., None] * np.arange(int(grid.max()) + 1).astype(LD)      # (B, N, 3, n)
+        z = np.cos(ang) + 1j * np.sin(ang)
+        n1, n2, n3 = (int(m) + 1 for m in grid.max(axis=0))
+        for b0 in range(0, B, 64):                                   # every point of the list's box once, then the list's points
+            zb = z[b0:b0 + 64]
+            w = (zb[:, :, 0, :n1, None] * zb[:, :, 1, None, :n2]).reshape(zb.shape[0], -1, n1 * n2)
+            full = np.matmul(w.transpose(0, 2, 1), zb[:, :, 2, :n3])         # (64, n1 n2, n3): the sum over the electrons
+            rho[b0:b0 + 64] = full[:, grid[:, 0] * n2 + grid[:, 1], grid[:, 2]]
+        out[2:2 + Q] = rho.real.sum(axis=0)
+        out[2 + Q:2 + 2 * Q] = rho.imag.sum(axis=0)
+        out[2 + 2 * Q:] = (rho.real ** 2 + rho.imag ** 2).sum(axis=0)
+    return out, rho
+
+
+def sums_bound(x, rv, grid, pol_dir, rho):
+    """A-priori bound on |device - exact| of every packed sum of `ds_observables`, u = 2^-53, A_je = sum_k |g_jk| |r_ek|.
+    One term exp(i q.r_e) of the point (n1, n2, n3):  eps = u (8 sum_j n_j A_je + 64)  -- the three-product dot amplified by n_j,
+    and 64 for the sincos and at most 7 + 2 complex multiplications.
+    Re rho_b, Im rho_b:  d_b = sum_e eps + N^2 u  (any summation order).   Batch sums: sum_b d_b + B u sum_b |rho_b|.
+    |rho|^2:  sum_b (2 |rho_b| d_b + d_b^2) + B u sum_b |rho_b|^2.
+    Polarization: phase error u (N + 4) sum_e A_pe, |dP_b| <= that + 4 u, and B^2 u for the batch sum.
+    `rho` (B, Q): the exact per-walker rho of `ld_sums`."""
+    B = x.shape[0]
+    r = np.abs(np.asarray(x, dtype=np.float64).reshape(B, -1, 3))
+    N, Q = r.shape[1], grid.shape[0]
+    A = (r @ np.abs(np.asarray(rv, dtype=np.float64)).T).sum(axis=1)         # (B, 3): sum_e A_je
+    out = np.zeros(2 + 3 * Q)
+    if pol_dir >= 0:
+        out[0] = out[1] = (U * (N + 4) * A[:, pol_dir] + 4 * U).sum() + B * B * U
+    if Q:
+        mag = np.abs(rho).astype(np.float64)
+        d = U * (8 * A @ grid.T.astype(np.float64) + 64 * N) + N * N * U     # (B, Q)
+        out[2:2 + Q] = out[2 + Q:2 + 2 * Q] = d.sum(axis=0) + B * U * mag.sum(axis=0)
+        out[2 + 2 * Q:] = (2 * mag * d + d * d).sum(axis=0) + B * U * (mag ** 2).sum(axis=0)
+    return out
+
+
+def ratio_to_bound(got, ref, bound):
+    """max |got - ref| / bound over the packed sums; an entry whose bound is 0 (no polarization asked) must be exact."""
+    err = np.abs(np.asarray(got).astype(np.longdouble) - ref).astype(np.float64)
+    assert np.all(err[bound == 0] == 0)
+    return float((err[bound > 0] / bound[bound > 0]).max()) if (bound > 0).any() else 0.0
+
+
+def replay_sums(x, rv, grid, pol_dir):
+    """float64 numpy replay of k_obs_partial's arithmetic: the three-product dot, one sincos per direction, the powers by
+    repeated multiplication, (z1^n1 z2^n2) z3^n3 out of the table, the electrons added one after the other (here in index order; the kernel orders a
+    chunk's electrons by their coordinates, and the bound holds for any order)."""
+    B = x.shape[0]
+    r = np.asarray(x, dtype=np.float64).reshape(B, -1, 3)
+    N, Q = r.shape[1], grid.shape[0]
+    d = np.stack([rv[c, 0] * r[..., 0] + rv[c, 1] * r[..., 1] + rv[c, 2] * r[..., 2] for c in range(3)], axis=-1)
+    out = np.zeros(2 + 3 * Q)
+    if pol_dir >= 0:
+        ph = d[:, :, pol_dir].sum(axis=1)
+        out[0], out[1] = np.cos(ph).sum(), np.sin(ph).sum()
+    if Q:
+        z = np.cos(d) + 1j * np.sin(d)
+        n_pow = int(grid.max()) + 1
+        tab = np.empty((B, N, 3, n_pow), dtype=np.complex128)
+        w = np.ones_like(z)
+        for p in range(n_pow):
+            tab[..., p] = w
+            w = w * z
+        rho = np.zeros((B, Q), dtype=np.complex128)
+        for e in range(N):
+            rho += tab[:, e, 0, grid[:, 0]] * tab[:, e, 1, grid[:, 1]] * tab[:, e, 2, grid[:, 2]]
+        out[2:2 + Q] = rho.real.sum(axis=0)
+        out[2 + Q:2 + 2 * Q] = rho.imag.sum(axis=0)
+        out[2 + 2 * Q:] = (rho.real ** 2 + rho.imag ** 2).sum(axis=0)
+    return out
+
+
+@pytest.mark.parametrize('n_elec', [65, 96, 128])
+def test_sums_bound_holds_for_a_float64_replay(n_elec):
+    """The bound of `sums_bound`, which the GPU tests assert, is checkable without a GPU: a float64 replay of the kernel's
+    recurrence stays inside it against the long-double reference, on every point list and polarization direction.
+    Worst ratio: 8.2e-3 (N = 65, the 8^3 grid), 7.5e-3 on the 150-point list, 4.1e-3 on the 130-point list, 0 on the origin."""
+    rv = recvec(TRICLINIC)
+    x = cell_walkers(n_elec, 5)
+    worst = 0.0
+    for pol_dir, (name, grid) in zip((0, 1, 2, -1), point_lists().items()):
+        ref, rho = ld_sums(x, rv, grid, pol_dir)
+        ratio = ratio_to_bound(replay_sums(x, rv, grid, pol_dir), ref, sums_bound(x, rv, grid, pol_dir, rho))
+        print(f'replay N={n_elec} {name} pol={pol_dir}: max err / bound = {ratio:.3e}')
+        worst = max(worst, ratio)
+    assert worst <= 1.0
 
 
 def test_grid_order_matches_reference_meshgrid():
