@@ -137,6 +137,8 @@ SIGNATURES = {
     'ds_spin_exchange_ratios': (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     'ds_ion_forces_workspace_bytes': (C.c_int64, [_VP, C.c_int64]),
     'ds_ion_forces': (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    'ds_ion_vjp_workspace_bytes': (C.c_int64, [_VP, C.c_int64]),
+    'ds_logpsi_ion_vjp': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     'ds_ecp_create': (C.c_int, [C.POINTER(EcpDesc), C.POINTER(_VP)]),
     'ds_ecp_destroy': (None, [_VP]),
     'ds_ecp_workspace_bytes': (C.c_int64, [_VP, _VP, C.c_int64, C.c_int64]),
@@ -172,7 +174,7 @@ SIGNATURES = {
 }
 
 PROF_KINDS = ('features', 'm2_expand', 'two_layer', 'single_first', 'single_hidden', 'orbital', 'det_inverse',
-              'det_trace', 'combine', 'ewald', 'shared_term', 'single_lr')
+              'det_trace', 'combine', 'ewald', 'shared_term', 'single_lr', 'ion_vjp')
 
 _lib = None
 

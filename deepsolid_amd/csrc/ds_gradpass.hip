@@ -1,10 +1,11 @@
 // ds_gradpass.hip -- the gradient passes (ds_grad.h) and the KFAC optimizer (ds_kfac.h): the reverse sweep behind ds_logpsi_vjp,
-// ds_kfac_factors, ds_pretrain_loss_vjp and ds_logpsi_jacobian, the Kronecker-factor pass and the per-walker emission (ds_jac.h)
-// that ride on it, and the KFAC step (damped inverses, preconditioner).  The forward of a pass is the value chain of ds_value.hip.
+// ds_kfac_factors, ds_pretrain_loss_vjp, ds_logpsi_jacobian and ds_logpsi_ion_vjp, the Kronecker-factor pass, the per-walker emission
+// (ds_jac.h) and the ion sink (ds_iongrad.h) that ride on it, and the KFAC step (damped inverses, preconditioner).  The forward of a pass is the value chain of ds_value.hip.
 #include "ds_host.h"
 #include "ds_grad.h"
 #include "ds_kfac.h"
 #include "ds_jac.h"
+#include "ds_iongrad.h"
 
 namespace ds {
 namespace host {
@@ -70,7 +71,8 @@ template <typename T> struct GradBufs {
 };
 
 template <typename T>
-GradBufs<T> carve_grad(const ds_system* s, const GradPlan& gp, Arena<T>& a, int64_t ng) {
+GradBufs<T> carve_grad(const ds_system* s, const GradPlan& gp, Arena<T>& a, int64_t ng, bool pair_bwd = true) {
+    // pair_bwd false: the ion pass (ds_logpsi_ion_vjp), which runs no pair-stream backward and carves none of its buffers
     const ds::SysDev<double>& S = s->sd;      // (the dims of sd and sf are the same)
     const WsLayout& V = s->wsv;
     const size_t PV = ds::PV;
@@ -97,10 +99,12 @@ GradBufs<T> carve_grad(const ds_system* s, const GradPlan& gp, Arena<T>& a, int6
     for (T*& h : b.HB) h = a.take(gp.hb * ng);
     b.ZBAR = a.take(gp.hb * ng);
     b.SBAR = a.take(gp.sbar * ng);
-    for (T*& h : b.H2BAR) h = a.take(gp.h2 * ng);
-    b.Z2BAR = a.take(gp.h2 * ng);
+    if (pair_bwd) {
+        for (T*& h : b.H2BAR) h = a.take(gp.h2 * ng);
+        b.Z2BAR = a.take(gp.h2 * ng);
+    }
     b.PART = a.take((size_t)s->nparams * ng);
-    b.W2S = a.take(gp.w2s * ng);              // split partials of the pair-stream weight gradients
+    if (pair_bwd) b.W2S = a.take(gp.w2s * ng);              // split partials of the pair-stream weight gradients
     if (s->use_last) {
         b.MEANBAR2 = a.take(V.MEAN * ng);
         for (int c = 0; c < S.nch; ++c) vb.SORB[c] = a.take((size_t)S.ocols[c] * PV * ng);
@@ -307,14 +311,25 @@ template <typename T> struct JacSink {
     size_t ld;
 };
 
+// The ion sink of the sweep (ds_logpsi_ion_vjp, ds_iongrad.h): out (walkers of the chunk, A, 3) receives every walker's own
+// gradient in the positions of the primitive cell's atoms
+struct IonSink {
+    double* out;
+};
+
 // PHIBAR / QBAR of a chunk -> parameter gradient: grad = (first ? 0 : grad) + this chunk's sums
 template <typename T>
 int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, const T* params, const T* WT, const T* x, int64_t Bc,
-                    bool first, T* grad, hipStream_t st, const KfacSink<T>* ks = nullptr, const JacSink<T>* js = nullptr) {
+                    bool first, T* grad, hipStream_t st, const KfacSink<T>* ks = nullptr, const JacSink<T>* js = nullptr,
+                    const IonSink* is = nullptr) {
     // ks: the KFAC factor pass (ds_kfac_factors) -- every tagged layer's A and G from the operands of its weight gradient;
     // grad may then be null (no packed gradient wanted)
     // js: the per-walker emission (ds_logpsi_jacobian).  The batch-summed contractions are then not launched at all (grad is null:
     // nobody reads PART); the cotangent chain itself is the same.  With js null nothing below differs from the plain sweep.
+    // is: the ion sink (ds_logpsi_ion_vjp).  Only the one-electron cotangent chain runs: nothing that forms a parameter sum is
+    // launched (no outer product, row sum, envelope gradient, PART memset or reduction) and the pair-stream backward is left out
+    // altogether -- the pair stream reads neither the ions nor the one-electron stream.  Behind layer 0's element-wise kernel
+    // k_ion_grad takes ZBAR / SBAR / HB / QBAR to the atoms.  With is null nothing below differs from the plain sweep.
     const ds::SysDev<T>& S = dev<T>(s);
     const int PV = ds::PV;
     const int64_t ng = (Bc + PV - 1) / PV;
@@ -327,7 +342,7 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
     T *MEANL = gb.MEANL, *MEANBAR = gb.MEANBAR, *MEANBAR2 = gb.MEANBAR2, *QBAR = gb.QBAR, *GBAR = gb.GBAR, *ZBAR = gb.ZBAR, *SBAR = gb.SBAR,
       *Z2BAR = gb.Z2BAR, *PART = gb.PART, *W2S = gb.W2S;
     {
-        HIP_OK(hipMemsetAsync(PART, 0, np * ng * sizeof(T), st));
+        if (!is) HIP_OK(hipMemsetAsync(PART, 0, np * ng * sizeof(T), st));
         const size_t gws = (size_t)S.N * S.ldk * PV, gts = (size_t)S.ldk * PV;
         // per-walker emission of one block: the operands of `outer` (X null: a row of ones); pair: the pair layout of k_two_bwd
         auto emit = [&](const T* X, size_t xg, size_t xt, int ldx, const T* Z, size_t zg, size_t zt, int ldz, int nt, int K, int Nc,
@@ -338,6 +353,7 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
         };
         auto outer = [&](const T* X, size_t xg, size_t xt, int ldx, const T* Z, size_t zg, size_t zt, int ldz, int nt, int J, int K,
                          int Nc, size_t off, int nsplit = 1) {
+            if (is) return;
             if (js) { emit(X, xg, xt, ldx, Z, zg, zt, ldz, nt, K, Nc, off, nsplit > 1); return; }      // (only the pair layers split)
             const int nwt = ((K + 31) / 32) * ((Nc + 31) / 32) * nsplit;
             T* dst = nsplit == 1 ? PART + off : W2S;
@@ -361,7 +377,7 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
             if (S.bias_orb && js)
                 hipLaunchKernelGGL((ds::k_jac_orb_bias<T>), dim3((unsigned)Bc), dim3(256), 0, st, PB[sp], pgs, ns, OC, S.nparam[sp], (long)Bc,
                                    js->rows, js->ld, boff(s->i_borb[sp]));
-            else if (S.bias_orb)
+            else if (S.bias_orb && !is)
                 hipLaunchKernelGGL((ds::k_orb_bias_grad<T>), dim3(2 * S.nparam[sp], (unsigned)ng), dim3(256), 0, st, PB[sp], pgs, ns, OC,
                                    S.nparam[sp], PART + boff(s->i_borb[sp]), np);
             const int Kop = gp.korb_pad;
@@ -373,7 +389,7 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
             if (s->use_last) {
                 // shared term of the orbital head (network.py:535): S_orb = W_sh^T mean_i h_i, one per spin channel
                 const int Ksh = S.nch * Kl;
-                if (sp == 0)
+                if (sp == 0 && !is)
                     launch_spin_mean<T>(dim3((unsigned)((Ksh * PV + 255) / 256), (unsigned)ng), st, S, vb.Gl[L], Kl, MEANL);
                 hipLaunchKernelGGL((ds::k_sum_tiles<T>), dim3((unsigned)((OC * PV + 255) / 256), (unsigned)ng), dim3(256), 0, st, PB[sp], pgs, ns,
                                    OC * PV, SBAR);
@@ -388,7 +404,7 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
             hipLaunchKernelGGL((ds::k_jac_env<T>), dim3((unsigned)Bc, S.nch), dim3(256), 0, st, S, x, (long)Bc, vb.Gl[0], QBAR,
                                blk(s->i_pi[0]), blk(s->i_sg[0]), blk(s->i_pi[S.nch - 1]), blk(s->i_sg[S.nch - 1]), js->rows, js->ld,
                                (long)boff(s->i_pi[0]), (long)boff(s->i_sg[0]), (long)boff(s->i_pi[S.nch - 1]), (long)boff(s->i_sg[S.nch - 1]));
-        else
+        else if (!is)
             hipLaunchKernelGGL((ds::k_env_grad<T>), dim3((unsigned)ng, S.nch), dim3(256), 0, st, S, x, (long)Bc, vb.Gl[0], QBAR,
                                blk(s->i_pi[0]), blk(s->i_sg[0]), blk(s->i_pi[S.nch - 1]), blk(s->i_sg[S.nch - 1]), PART, np,
                                (long)boff(s->i_pi[0]), (long)boff(s->i_sg[0]), (long)boff(s->i_pi[S.nch - 1]), (long)boff(s->i_sg[S.nch - 1]));
@@ -396,7 +412,7 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
         const T* D1 = GBAR; int ld1 = gp.korb_pad; const T* MB = s->use_last ? MEANBAR : nullptr; const T* CARRY = nullptr;
         const T* MB2 = s->use_last && S.nch > 1 ? MEANBAR2 : nullptr;
         int hbi = 0, h2i = 0;
-        if (s->use_last)       // the last level of the pair stream feeds the orbital head only
+        if (s->use_last && !is)       // the last level of the pair stream feeds the orbital head only
             hipLaunchKernelGGL((ds::k_pair_scatter<T>), dim3((S.NP + 255) / 256, S.h2[L] * 5, (unsigned)(ng * (PV / 5))), dim3(256), 0, st, S, GBAR,
                                gp.korb_pad, Kl, S.h2[L], H2BAR[h2i]);
         for (int l = L - 1; l >= 0; --l) {
@@ -409,6 +425,16 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
             else
                 hipLaunchKernelGGL((ds::k_layer_bwd_prep<T, false>), dim3(Nout / 4, (unsigned)ng), dim3(4 * PV), 0, st, S, D1, ld1, MB, MB2, CARRY,
                                    vb.Gl[l + 1], vb.Gl[l], Nout, HBc, ZBAR, SBAR, PART + boff(s->i_b[l]), np);
+            if (is && l == 0) {
+                const T* carry = res ? (const T*)HBc : (const T*)nullptr;
+                const dim3 igrid((unsigned)S.A, (unsigned)ng), iblock(4 * PV);
+#define DS_IONG(NF) hipLaunchKernelGGL((ds::k_ion_grad<T, NF>), igrid, iblock, 0, st, S, x, (long)Bc, (const T*)ZBAR, (const T*)SBAR, carry, Nout, \
+                                       blk(s->i_wloc[0]), blk(s->i_wsh[0]), (const T*)QBAR, blk(s->i_pi[0]), blk(s->i_sg[0]), blk(s->i_pi[S.nch - 1]),    \
+                                       blk(s->i_sg[S.nch - 1]), is->out)
+                if (S.nf == 4) DS_IONG(4); else DS_IONG(7);
+#undef DS_IONG
+                break;
+            }
             if (js)      // b[l]: the walker's row sums of ZBAR over the electrons
                 emit(nullptr, 0, 0, 0, ZBAR, (size_t)S.N * Nout * PV, (size_t)Nout * PV, PV, S.N, 1, Nout, boff(s->i_b[l]), false);
             outer(vb.Gl[l], gws, gts, PV, ZBAR, (size_t)S.N * Nout * PV, (size_t)Nout * PV, PV, S.N, PV, Kloc, Nout, boff(s->i_wloc[l]));
@@ -420,7 +446,7 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
                 kfac_emit<T>(s, *ks, ks->kp->blocks[l], o, 1, Bc, st);
             }
             const T* MEANl = vb.MEAN0;
-            if (l > 0) {
+            if (l > 0 && !is) {
                 launch_spin_mean<T>(dim3((unsigned)((S.nch * Kh * PV + 255) / 256), (unsigned)ng), st, S, vb.Gl[l], Kh, MEANL);
                 MEANl = MEANL;
             }
@@ -439,7 +465,9 @@ int sweep_from_seed(ds_system* s, const GradPlan& gp, const GradBufs<T>& gb, con
             }
             // pair stream
             const dim3 pgrid((S.NP / 16 + 3) / 4, (unsigned)(ng * (PV / 5)));
-            if (l == S.n_double) {
+            if (is) {
+                // (no pair-stream backward)
+            } else if (l == S.n_double) {
                 if (l > 0)
                     hipLaunchKernelGGL((ds::k_pair_scatter<T>), dim3((S.NP + 255) / 256, K2 * 5, (unsigned)(ng * (PV / 5))), dim3(256), 0, st, S,
                                        GBAR, Kpad, Kh, K2, H2BAR[h2i]);
@@ -571,6 +599,66 @@ int logpsi_vjp_impl(ds_system* s, const void* params, const void* x, int64_t B, 
                         true, ws, ws_bytes, st, [&](const GradPlan& gp, const GradWs<T>& w, int64_t b0, int64_t Bc, bool) {
                             return seed_logdet<T>(s, gp, w.gb, (const T*)params, (const T*)cot + 2 * b0, Bc, st);
                         });
+}
+
+// The ion pass (ds_logpsi_ion_vjp, ds_iongrad.h): the value chain and the seed of ds_logpsi_vjp, then the sweep with the ion sink.
+// Its workspace is that of a gradient pass without the pair-stream cotangents: [transposed weights | ng groups of carve_grad].
+template <typename T> GradWs<T> carve_ion_pass(const ds_system* s, const GradPlan& gp, Arena<T>& a, int64_t ng) {
+    GradWs<T> w{};
+    w.WT = a.take(gp.wt_total);
+    w.gb = carve_grad<T>(s, gp, a, ng, false);
+    return w;
+}
+
+inline PassSize ion_pass_size(const ds_system* s, const GradPlan& gp) {
+    auto extent = [&](int64_t ng) { return measure([&](Arena<double>& a) { carve_ion_pass<double>(s, gp, a, ng); }); };
+    return PassSize{extent(0), extent(1) - extent(0)};
+}
+
+int64_t ion_pass_bytes(const ds_system* s, int64_t B) {
+    GradPlan gp;
+    if (grad_plan(s, &gp)) return -1;
+    const int64_t esz = s->dtype == 0 ? 8 : 4;
+    const int64_t groups = groups_per_pass(B, esz, ion_pass_size(s, gp), (int64_t)32 << 30);
+    return (int64_t)measure([&](Arena<double>& a) { carve_ion_pass<double>(s, gp, a, groups); }) * esz + 256;
+}
+
+// groups of the ion pass that fit ws_bytes (< 1: refused by the entry point before any launch)
+int64_t ion_pass_groups(const ds_system* s, int64_t ws_bytes) {
+    GradPlan gp;
+    if (grad_plan(s, &gp)) return -1;
+    return groups_that_fit(ws_bytes, s->dtype == 0 ? 8 : 4, ion_pass_size(s, gp));
+}
+
+template <typename T>
+int logpsi_ion_vjp_impl(ds_system* s, const void* params_, const void* x_, int64_t B, const void* cot_, double* out, void* out_logabs_,
+                        void* out_phase_, void* ws, int64_t ws_bytes, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const int PV = ds::PV;
+    const T *params = (const T*)params_, *cot = (const T*)cot_;
+    T *out_logabs = (T*)out_logabs_, *out_phase = (T*)out_phase_;
+    GradPlan gp;
+    if (int rc = grad_plan(s, &gp)) return rc;
+    const int64_t cg = groups_that_fit(ws_bytes, sizeof(T), ion_pass_size(s, gp));
+    if (cg < 1) return fail("workspace too small for ds_logpsi_ion_vjp: %lld bytes", (long long)ws_bytes);
+    bool first = true;
+    for (int64_t b0 = 0; b0 < B; b0 += cg * PV) {
+        const int64_t Bc = std::min<int64_t>(cg * PV, B - b0);
+        const T* x = (const T*)x_ + b0 * 3 * S.N;
+        Arena<T> a = arena_of<T>(ws, ws_bytes);
+        const GradWs<T> w = carve_ion_pass<T>(s, gp, a, (Bc + PV - 1) / PV);
+        if (!a.ok) return carve_fail("ds_logpsi_ion_vjp");
+        ProfScope ps(s, DS_PROF_ION_VJP, st);
+        if (first) grad_transposes<T>(s, gp, params, w.WT, st);
+        if (int rc = run_value_chain<T>(s, params, x, Bc, w.gb.vb, st, out_logabs ? out_logabs + b0 : nullptr,
+                                        out_phase ? out_phase + 2 * b0 : nullptr)) return rc;
+        if (int rc = seed_logdet<T>(s, gp, w.gb, params, cot + 2 * b0, Bc, st)) return rc;
+        const IonSink is{out + (size_t)b0 * S.A * 3};
+        if (int rc = sweep_from_seed<T>(s, gp, w.gb, params, w.WT, x, Bc, true, (T*)nullptr, st, nullptr, nullptr, &is)) return rc;
+        first = false;
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
 }
 
 // Per-walker Jacobian (ds_jac.h): per chunk the value chain once, then two reverse sweeps with the per-walker sink -- the seed
@@ -784,6 +872,26 @@ int ds_logpsi_vjp(ds_system* s, const void* params, const void* x, int64_t B, co
         return 0;
     }
     return DS_BY_DTYPE(s->dtype, logpsi_vjp_impl, s, params, x, B, cot, grad, out_logabs, out_phase, ws, ws_bytes, st);
+}
+
+int64_t ds_ion_vjp_workspace_bytes(const ds_system* s, int64_t B) {
+    if (!s) return -1;
+    return ion_pass_bytes(s, B);
+}
+
+int ds_logpsi_ion_vjp(ds_system* s, const void* params, const void* x, int64_t B, const void* cot, double* out, void* out_logabs,
+                      void* out_phase, void* ws, int64_t ws_bytes, void* stream) {
+    if (s) ++s->call_seq;
+    if (!s || !params || !ws) return fail("ds_logpsi_ion_vjp: null argument");
+    if (!x) return fail("ds_logpsi_ion_vjp: x is null");
+    if (!cot) return fail("ds_logpsi_ion_vjp: cot is null");
+    if (!out) return fail("ds_logpsi_ion_vjp: out is null");
+    if (B < 1) return fail("ds_logpsi_ion_vjp: B must be >= 1 (got %lld)", (long long)B);
+    const int64_t cg = ion_pass_groups(s, ws_bytes);
+    if (cg < 1)
+        return fail("workspace too small for ds_logpsi_ion_vjp: %lld bytes < %lld for one group of %d walkers (see ds_ion_vjp_workspace_bytes)",
+                    (long long)ws_bytes, (long long)ion_pass_bytes(s, 1), ds::PV);
+    return DS_BY_DTYPE(s->dtype, logpsi_ion_vjp_impl, s, params, x, B, cot, out, out_logabs, out_phase, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int64_t ds_jacobian_workspace_bytes(const ds_system* s, int64_t B) {

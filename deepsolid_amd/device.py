@@ -128,6 +128,8 @@ class DeviceSystem:
         d.n_up, d.n_dn = self.nelec
         atoms = np.asarray(prim.atom_coords(), dtype=np.float64).reshape(-1, 3)
         d.n_atoms_prim = atoms.shape[0]
+        self.n_atoms_prim = int(atoms.shape[0])
+        self.prim_atoms = atoms.copy()
         d.prim_atoms = arr(atoms)
         d.prim_a[:] = np.asarray(prim.a, dtype=np.float64).reshape(-1).tolist()
         d.sim_a[:] = np.asarray(simulation_cell.a, dtype=np.float64).reshape(-1).tolist()
@@ -697,7 +699,8 @@ class DeviceSystem:
         force of the Ewald energy, hf = -d(E_ei + E_ii)/dR_a, and with `drift` (B, 3N) = Re grad log psi (`logpsi_grad(...)[1].real`)
         the zero-variance force zv = hf + dF of Assaraf and Caffarel with the cutoff `cutoff` (default and maximum: the Wigner-Seitz
         radius).  NOT the full force: the Pulay term is missing, so hf and zv are exact only for an exact psi (bias first order in
-        the error of psi); all-electron ions only.  `sums`: float64 device tensor (12 A + 1,) that is ADDED to = per (a, c)
+        the error of psi; `logpsi_ion_vjp` gives d log psi / dR_a for the atoms of the primitive cell and `estimator.PrimitiveForces`
+        the total force); all-electron ions only.  `sums`: float64 device tensor (12 A + 1,) that is ADDED to = per (a, c)
         [sum hf, sum hf^2, sum zv, sum zv^2] over the good walkers, then their number; it needs the drift.  A walker with a
         non-finite coordinate, drift or result is NaN, left out and counted.  `max_bytes` caps the workspace of `sums`: more
         passes, bit-identical results.  The ion-ion force is computed once on the host and cached on the system.
@@ -731,6 +734,40 @@ class DeviceSystem:
                                           _ptr(sums), _ptr(n_bad), _ptr(ws), ws.numel() if ws is not None else 0, _stream()),
                    'ds_ion_forces')
         return dict(hf=hf, zv=zv, n_bad=n_bad, sums=sums)
+
+    def logpsi_ion_vjp(self, params, x, cot, max_bytes=None):
+        """`ds_logpsi_ion_vjp` (csrc/ds_iongrad.h): per walker the gradient of
+        cot_b[0] log|psi_b| + cot_b[1] arg psi_b in the positions of the A atoms of the PRIMITIVE cell (`self.prim_atoms`), the
+        only ions psi sees; moving atom a moves all its images of the simulation cell together.  cot (B,) complex or (B, 2) real,
+        the convention of `logpsi_vjp`.  -> (out (B, A, 3) float64 for either dtype, NOT summed over the batch; log|psi| (B,);
+        phase (B,) complex).  `max_bytes` caps the workspace: more passes, the same bits."""
+        x = self._check_x(x)
+        B = x.shape[0]
+        if cot.is_complex():
+            cot = torch.view_as_real(cot)
+        cot = cot.to(device=self.device, dtype=self.dtype).contiguous()
+        if tuple(cot.shape) != (B, 2):
+            raise ValueError(f'cot must be ({B},) complex or ({B}, 2), got {tuple(cot.shape)}')
+        p = self.pack_params(params)
+        A = self.n_atoms_prim
+        out = torch.empty(B, A, 3, dtype=torch.float64, device=self.device)
+        la = torch.empty(B, dtype=self.dtype, device=self.device)
+        ph = torch.empty(B, 2, dtype=self.dtype, device=self.device)
+        if B > 0:
+            ws = self._workspace('ds_ion_vjp_workspace_bytes', int(B), max_bytes=max_bytes)
+            _lib.check(self.lib.ds_logpsi_ion_vjp(self.handle, _ptr(p), _ptr(x), B, _ptr(cot), _ptr(out), _ptr(la), _ptr(ph), _ptr(ws),
+                                                  ws.numel(), _stream()), 'ds_logpsi_ion_vjp')
+        return out, la, torch.view_as_complex(ph)
+
+    def logpsi_ion_grad(self, params, x, max_bytes=None):
+        """O = d log psi / d R_a per walker and atom of the primitive cell, complex (B, A, 3): Re = d log|psi|, Im = d arg psi, as
+        `logpsi_grad` gives them in the walker coordinates.  Two `logpsi_ion_vjp` calls, cot = (1, 0) and (0, 1)."""
+        B = x.shape[0]
+        one = torch.zeros(B, 2, dtype=self.dtype, device=self.device)
+        one[:, 0] = 1
+        re = self.logpsi_ion_vjp(params, x, one, max_bytes=max_bytes)[0]
+        im = self.logpsi_ion_vjp(params, x, one.flip(1), max_bytes=max_bytes)[0]
+        return torch.complex(re, im)
 
     def dmc_state(self, x, weight=None, ecp=False):
         """Fresh DMC walker state for `dmc_step(..., state_valid=False)`: dict of the six caller-owned device buffers (x is copied;

@@ -708,7 +708,8 @@ class IonForces:
     WHAT IS MISSING: the Pulay term 2 <(E_L - E) d log psi / dR_a> is not evaluated (the walker gradient comes from forward jets:
     there is no derivative with respect to an ion position).  hf and zv are therefore the force only for an exact psi, and their
     bias is FIRST ORDER in the error of the wave function.  All-electron ions only: a semi-local pseudopotential has force terms
-    of its own, which are not implemented (`pseudopotential` must be None).
+    of its own, which are not implemented (`pseudopotential` must be None).  `PrimitiveForces` (below) adds the Pulay term for the
+    atoms of the primitive cell.
 
     Every `update` is ONE `ds_logpsi_grad` call and ONE `ds_ion_forces` call that adds to 12 A + 1 float64 numbers; nothing is read
     back.  `cutoff`: r_c, by default (and at most) `wigner_seitz_radius` of the simulation cell.  `net`: the object
@@ -858,5 +859,244 @@ class IonForces:
     @classmethod
     def load(cls, path):
         """The accumulator saved at `path` as a fresh rank-local one without a network (see `from_state_dict`)."""
+        with np.load(path) as f:
+            return cls.from_state_dict({k: f[k] for k in f.files})
+
+
+# ------------------------------------------------------------------ total force on the primitive-cell atoms (csrc/ds_iongrad.h)
+def primitive_fold(sim_atoms, prim_atoms, prim_latvec):
+    """-> (owner (As,) int: the primitive atom each ion of the simulation cell is an image of, scale = As / A).  `get_supercell`
+    orders the ions atom-major, so image s belongs to atom s // scale; that is ASSERTED here: sim_atoms[s] - prim_atoms[s // scale]
+    must be a lattice vector of the primitive cell, otherwise ValueError (a cell built in another order would fold forces onto
+    the wrong atoms without any other symptom)."""
+    sim_atoms = np.asarray(sim_atoms, np.float64).reshape(-1, 3)
+    prim_atoms = np.asarray(prim_atoms, np.float64).reshape(-1, 3)
+    As, A = sim_atoms.shape[0], prim_atoms.shape[0]
+    if A < 1 or As % A:
+        raise ValueError(f'{As} ions in the simulation cell are not a multiple of the {A} atoms of the primitive cell')
+    scale = As // A
+    owner = np.arange(As) // scale
+    frac = (sim_atoms - prim_atoms[owner]) @ np.linalg.inv(np.asarray(prim_latvec, np.float64).reshape(3, 3))
+    off = np.abs(frac - np.round(frac)).max(axis=1)
+    if off.max() > 1e-8:
+        s = int(off.argmax())
+        raise ValueError(f'ion {s} of the simulation cell is not a lattice translate of primitive atom {s // scale}: the ions are not '
+                         'ordered atom-major (get_supercell), the fold onto the primitive atoms would be wrong')
+    return owner, scale
+
+
+class PrimitiveForces:
+    """The total force on each atom of the PRIMITIVE cell per simulation cell, zero-variance force plus Pulay term, accumulated on
+    the device over walker batches: an accumulator for `run_inference(accumulators=...)`.
+
+        F_a = sum_{s image of a} F^zv_s  -  2 Re < conj(E_L - E) (O_a - <O_a>) >,     O_a = d log psi / d R_a (complex)
+
+    F^zv is `IonForces`' zero-variance force on the ions of the simulation cell, E_L = ke + ewald the complex local energy and O_a
+    `DeviceSystem.logpsi_ion_grad`.  For a complex psi the piece 2 <Im E_L d arg psi> belongs to <Re d E_L / dR> and is kept: the
+    formula is the parameter gradient of `train.make_loss` with theta = R.
+    WHICH ATOMS: the network's atoms are the A atoms of the primitive cell and its features are periodic in the primitive lattice,
+    so moving atom a moves all `scale` images of it in the simulation cell together; the derivative of psi in a single ion of a
+    supercell does not exist in this ansatz.  The result is the q = 0 force that internal-coordinate relaxation needs.  The ions
+    of the simulation cell are atom-major (`primitive_fold` asserts it at construction).  All-electron ions only.
+
+    Every `update` is ONE BLOCK and runs four calls: `local_energy` (unless the caller passes its complex `energies`),
+    `logpsi_grad`, `ion_forces(want_walker=True)` and one `logpsi_ion_vjp` with cot_b = E_b - mean E of the block, whose batch sum
+    is the covariance numerator sum_b Re conj(E_b - E) O_b (the mean of O drops out: sum_b (E_b - E) = 0), so no second sweep is
+    needed.  Walkers that `ion_forces` marks bad (or whose energy is not finite) are left out of every sum of the block.  The
+    block appends one device row [n_good, sum Re E, sum Im E, per (a, c): sum zv, sum hf, sum t]; nothing is read back.
+    VMC ONLY: the Pulay term is a covariance under |psi|^2.  The accumulators of `run_dmc` deliver mixed estimates of plain
+    averages; a mixed estimate of a covariance term is not the DMC force, and this class does not pretend to give one."""
+
+    def __init__(self, net, params, cutoff=None):
+        self.apply = getattr(net, 'apply', net)
+        self.params = params
+        cell = self.apply.simulation_cell
+        prim = cell.original_cell
+        self._setup(np.asarray(cell.atom_coords(), np.float64), np.asarray(cell.atom_charges(), np.float64), np.asarray(cell.a, np.float64),
+                    np.asarray(prim.atom_coords(), np.float64), np.asarray(prim.a, np.float64), int(sum(cell.nelec)), cutoff)
+
+    def _setup(self, sim_atoms, charges, latvec, prim_atoms, prim_latvec, n_elec, cutoff):
+        self.sim_atoms = np.asarray(sim_atoms, np.float64).reshape(-1, 3)
+        self.charges = np.asarray(charges, np.float64).reshape(-1)
+        self.latvec = np.asarray(latvec, np.float64).reshape(3, 3)
+        self.atoms = np.asarray(prim_atoms, np.float64).reshape(-1, 3)
+        self.prim_latvec = np.asarray(prim_latvec, np.float64).reshape(3, 3)
+        self.owner, self.scale = primitive_fold(self.sim_atoms, self.atoms, self.prim_latvec)
+        self.n_elec = int(n_elec)
+        self.cutoff = force_cutoff(self.latvec, cutoff)
+        self.n_atoms = self.atoms.shape[0]
+        self.row_len = 3 + 9 * self.n_atoms
+        self.blocks = []                    # device rows, one per update
+        self.n_bad = torch.zeros(1, dtype=torch.int64)
+        self.n_walkers = 0
+        self.n_means = 1                    # block means subtracted per row: the ranks whose rows were added by reduce()
+        self.reduced = False
+
+    @property
+    def rows(self):
+        """(blocks, 3 + 9 A) float64 tensor of the block rows (on the device of the walkers)."""
+        if not self.blocks:
+            return torch.zeros(0, self.row_len, dtype=torch.float64)
+        return torch.stack(self.blocks)
+
+    # ---- accumulation
+    def update(self, data, energies=None):
+        """One block from the walkers `data` (B, 3N); `energies` (B,) complex: their local energies when the caller has them."""
+        if self.apply is None:
+            raise RuntimeError('PrimitiveForces.update: a loaded accumulator has no network; merge it into one that has')
+        if self.reduced:
+            raise RuntimeError('PrimitiveForces.update after reduce(): the rows are already summed over the ranks')
+        if data.shape[-1] != 3 * self.n_elec:
+            raise ValueError(f'walkers have {data.shape[-1]} coordinates, the cell has {self.n_elec} electrons')
+        x = data.reshape(-1, 3 * self.n_elec)
+        B = x.shape[0]
+        if B == 0:
+            return
+        system = self.apply.system
+        if energies is None:
+            ke, ew, _, _ = system.local_energy(self.params, x)
+            E = torch.complex(ke[:, 0].double() + ew.double(), ke[:, 1].double())
+        else:
+            E = torch.as_tensor(energies).to(device=x.device, dtype=torch.complex128).reshape(B)
+        drift = system.logpsi_grad(self.params, x)[1].real.contiguous()
+        f = system.ion_forces(x, drift, cutoff=self.cutoff, want_walker=True)
+        A, sc = self.n_atoms, self.scale
+        good = torch.isfinite(f['zv']).all(2).all(1) & torch.isfinite(f['hf']).all(2).all(1) & torch.isfinite(E.real) & torch.isfinite(E.imag)
+        zero = torch.zeros((), dtype=torch.float64, device=x.device)
+        w3 = good[:, None, None]
+        zv = torch.where(w3, f['zv'].reshape(B, A, sc, 3).sum(2), zero).sum(0)          # atom-major: image s of atom s // scale
+        hf = torch.where(w3, f['hf'].reshape(B, A, sc, 3).sum(2), zero).sum(0)
+        n = good.sum().to(torch.float64)
+        Er, Ei = torch.where(good, E.real, zero), torch.where(good, E.imag, zero)
+        sr, si = Er.sum(), Ei.sum()
+        cot = torch.stack([torch.where(good, Er - sr / n, zero), torch.where(good, Ei - si / n, zero)], 1)
+        O = system.logpsi_ion_vjp(self.params, x, cot)[0]
+        t = torch.where(w3, O, zero).sum(0)
+        row = torch.cat([torch.stack([n, sr, si]), torch.stack([zv, hf, t], 2).reshape(-1)])
+        self.blocks.append(row)
+        if self.n_bad.device != x.device:
+            self.n_bad = self.n_bad.to(x.device)
+        self.n_bad += (B - good.sum()).reshape(1)
+        self.n_walkers += int(B)
+
+    def _same_setup(self, other):
+        return (self.sim_atoms.shape == other.sim_atoms.shape and np.array_equal(self.sim_atoms, other.sim_atoms) and
+                self.atoms.shape == other.atoms.shape and np.array_equal(self.atoms, other.atoms) and
+                np.array_equal(self.charges, other.charges) and np.array_equal(self.latvec, other.latvec) and
+                np.array_equal(self.prim_latvec, other.prim_latvec) and self.n_elec == other.n_elec and self.cutoff == other.cutoff)
+
+    def merge(self, other):
+        """Append the blocks of another accumulator of the same cell and cutoff (its series continues this one's), add its counts."""
+        if not self._same_setup(other):
+            raise ValueError('PrimitiveForces.merge: the two accumulators differ in atoms, lattice, electron number or cutoff')
+        if self.reduced != other.reduced and constants.world_size() > 1 or self.n_means != other.n_means:
+            raise ValueError('PrimitiveForces.merge: one side is summed over the ranks and the other is rank-local')
+        dev = self.blocks[0].device if self.blocks else (other.blocks[0].device if other.blocks else None)
+        self.blocks = self.blocks + [b.to(dev) for b in other.blocks]
+        self.n_bad = self.n_bad + other.n_bad.to(self.n_bad.device)
+        self.n_walkers += other.n_walkers
+        return self
+
+    def reduce(self):
+        """Add the rows of all ranks block by block (every rank must hold the same number of blocks), the bad count and the walker
+        number, in one packed float64 all-reduce.  A summed row holds one subtracted mean per rank: `forces()` divides the Pulay
+        sums by n - ranks.  Once per accumulator: a second call raises; so does `update` afterwards."""
+        if self.reduced:
+            raise RuntimeError('PrimitiveForces.reduce was already called: reducing twice would count every rank again')
+        W = constants.world_size()
+        if W > 1:
+            rows = self.rows
+            dev = rows.device if rows.is_cuda else torch.device('cuda' if torch.cuda.is_available() else 'cpu')
+            nb = float(rows.shape[0])
+            head = constants.psum_if_pmap(torch.tensor([nb, nb * nb], dtype=torch.float64, device=dev))
+            if float(head[0]) != W * nb or float(head[1]) != W * nb * nb:
+                raise RuntimeError('PrimitiveForces.reduce: the ranks hold different numbers of blocks')
+            packed = torch.cat([rows.to(dev).reshape(-1), self.n_bad.to(dev, torch.float64),
+                                torch.tensor([self.n_walkers], dtype=torch.float64, device=dev)])
+            packed = constants.psum_if_pmap(packed)
+            k = rows.numel()
+            self.blocks = list(packed[:k].reshape(rows.shape).clone())
+            self.n_bad = packed[k:k + 1].round().to(torch.int64)
+            self.n_walkers = int(packed[k + 1].round())
+            self.n_means = self.n_means * W
+        self.reduced = True
+        return self
+
+    # ---- normalisation (host)
+    def forces(self):
+        """-> dict(total, zv, hf, pulay and their *_error (each (A, 3) float64, Ha/bohr, per primitive atom and simulation cell),
+        energy (complex block-weighted mean), n_blocks, n_walkers, n_bad, atoms (A, 3) of the primitive cell, cutoff).
+        Per block zv = sum zv / n, hf = sum hf / n, pulay = -2 sum t / (n - 1) (the block's own mean energy was subtracted: the
+        unbiased covariance), total = zv + pulay; each is averaged over the blocks weighted by n_good.  The error is `dmc.reblock`
+        over the block series: the blocks of a Markov chain are correlated and a covariance estimator has no per-walker variance
+        to fall back on (below eight blocks there is no level to halve to: the error is then the plain standard error of the block
+        series, NaN for a single block).  Blocks with too few good walkers for a covariance (n <= 1) are left out; NaN without a block."""
+        from .dmc import reblock
+        rows = self.rows.detach().cpu().numpy().reshape(-1, self.row_len)
+        A = self.n_atoms
+        rows = rows[rows[:, 0] > self.n_means]
+        out = dict(n_blocks=int(rows.shape[0]), n_walkers=self.n_walkers, n_bad=int(self.n_bad.sum()), atoms=self.atoms.copy(),
+                   cutoff=self.cutoff)
+        names = ('total', 'zv', 'hf', 'pulay')
+        if rows.shape[0] == 0:
+            for k in names:
+                out[k] = np.full((A, 3), np.nan)
+                out[k + '_error'] = np.full((A, 3), np.nan)
+            out['energy'] = complex(np.nan, np.nan)
+            return out
+        n = rows[:, 0]
+        body = rows[:, 3:].reshape(-1, A, 3, 3)
+        series = {'zv': body[..., 0] / n[:, None, None], 'hf': body[..., 1] / n[:, None, None],
+                  'pulay': -2.0 * body[..., 2] / (n - self.n_means)[:, None, None]}
+        series['total'] = series['zv'] + series['pulay']
+        for k in names:
+            v = series[k]
+            out[k] = (v * n[:, None, None]).sum(0) / n.sum()
+            out[k + '_error'] = np.array([[reblock(v[:, a, c], min_blocks=min(8, max(2, len(v))))[1] for c in range(3)] for a in range(A)])
+        out['energy'] = complex(rows[:, 1].sum() / n.sum(), rows[:, 2].sum() / n.sum())
+        return out
+
+    # ---- persistence
+    def state_dict(self):
+        """Plain numpy arrays: the block rows and counts and the setup they belong to."""
+        return {'rows': self.rows.detach().cpu().numpy().copy(), 'n_bad': self.n_bad.detach().cpu().numpy().copy(),
+                'n_walkers': np.int64(self.n_walkers), 'n_means': np.int64(self.n_means), 'atoms': self.atoms.copy(),
+                'sim_atoms': self.sim_atoms.copy(), 'charges': self.charges.copy(), 'latvec': self.latvec.copy(),
+                'prim_latvec': self.prim_latvec.copy(), 'n_elec': np.int64(self.n_elec), 'cutoff': np.float64(self.cutoff),
+                'reduced': np.bool_(self.reduced)}
+
+    @classmethod
+    def from_state_dict(cls, sd):
+        """An accumulator without a network: it can be merged, normalised and saved, not updated."""
+        acc = cls.__new__(cls)
+        acc.apply = acc.params = None
+        acc._setup(sd['sim_atoms'], sd['charges'], sd['latvec'], sd['atoms'], sd['prim_latvec'], int(sd['n_elec']), float(sd['cutoff']))
+        acc.blocks = list(torch.as_tensor(np.array(sd['rows'], dtype=np.float64).reshape(-1, acc.row_len)))
+        acc.n_bad = torch.as_tensor(np.array(sd['n_bad'], dtype=np.int64).reshape(1))
+        acc.n_walkers = int(sd['n_walkers'])
+        acc.n_means = int(sd['n_means'])
+        return acc
+
+    def load_state_dict(self, sd):
+        """Replace the rows and counts by those of `sd` (same cell and cutoff); the accumulator is open for `update` afterwards."""
+        other = PrimitiveForces.from_state_dict(sd)
+        if not self._same_setup(other):
+            raise ValueError('PrimitiveForces.load_state_dict: the state belongs to other atoms, another lattice or another cutoff')
+        self.blocks, self.n_bad = other.blocks, other.n_bad
+        self.n_walkers, self.n_means, self.reduced = other.n_walkers, other.n_means, False
+        return self
+
+    def save(self, path, results=True):
+        """One .npz of `state_dict()`; `results`: also the arrays of `forces()`."""
+        sd = self.state_dict()
+        if results:
+            r = self.forces()
+            sd.update({k: r[k] for k in r if k not in ('atoms', 'cutoff', 'n_walkers', 'n_bad')})
+        with open(path, 'wb') as f:
+            np.savez(f, **sd)
+
+    @classmethod
+    def load(cls, path):
+        """The accumulator saved at `path` as a fresh one without a network (see `from_state_dict`)."""
         with np.load(path) as f:
             return cls.from_state_dict({k: f[k] for k in f.files})

@@ -20,6 +20,9 @@ n_up n_dn pairs), through deepsolid_amd.estimator.SpinSquared, written to spin_s
 Hellmann-Feynman force of the Ewald energy and the zero-variance force of Assaraf and Caffarel with the Wigner-Seitz radius as its
 cutoff; --forces-cutoff X: the same with the cutoff X in bohr (at most the Wigner-Seitz radius).  The Pulay term is NOT evaluated,
 so both are the force only for an exact wave function (bias first order in its error); all-electron only: not with --ecp;
+--forces-total: the TOTAL force per atom of the primitive cell (zero-variance force + Pulay term), through
+deepsolid_amd.estimator.PrimitiveForces, written to forces_total.npz; one block per evaluation step, errors by reblocking the block
+series; honours --forces-cutoff; all-electron only: not with --ecp;
 --ecp FILE.npz: add the semi-local pseudopotential saved in FILE.npz (deepsolid_amd.pseudopotential.SemiLocalECP.save, built for
 THIS cell) to the local energy of training and evaluation: the rows then carry its batch mean E_loc + E_nl.  The
 cell of this example is all-electron, so with a real potential the numbers mean nothing: the point is the call sequence);
@@ -82,10 +85,13 @@ if '--spin-squared' in sys.argv:
         spin_pairs = int(sys.argv[i + 1])
         del sys.argv[i + 1]
     del sys.argv[i]
+forces_total = '--forces-total' in sys.argv
+if forces_total:
+    sys.argv.remove('--forces-total')
 forces, force_cutoff = False, None
 if '--forces-cutoff' in sys.argv:
     i = sys.argv.index('--forces-cutoff')
-    forces, force_cutoff = True, float(sys.argv[i + 1])
+    forces, force_cutoff = not forces_total, float(sys.argv[i + 1])
     del sys.argv[i:i + 2]
 if '--forces' in sys.argv:
     forces = True
@@ -112,8 +118,8 @@ if '--ecp' in sys.argv:
     i = sys.argv.index('--ecp')
     ecp_file = sys.argv[i + 1]
     del sys.argv[i:i + 2]
-if forces and ecp_file is not None:
-    sys.exit('--forces is all-electron only: the force terms of a pseudopotential are not implemented')
+if (forces or forces_total) and ecp_file is not None:
+    sys.exit('--forces / --forces-total is all-electron only: the force terms of a pseudopotential are not implemented')
 if dmc_pure is not None and dmc_blocks <= 0:
     sys.exit('--dmc-pure needs --dmc BLOCKS')
 if tmoves and (ecp_file is None or dmc_blocks <= 0):
@@ -157,6 +163,11 @@ if forces:
     from deepsolid_amd import estimator
     force_acc = estimator.IonForces(logdet, params, cutoff=force_cutoff)
     accumulators += (force_acc,)
+total_acc = None
+if forces_total:
+    from deepsolid_amd import estimator
+    total_acc = estimator.PrimitiveForces(logdet, params, cutoff=force_cutoff)
+    accumulators += (total_acc,)
 data, width, rows = inference.run_inference(slogdet, logdet, params, data, cell, iterations=10, burn_in=10, move_width=width,
                                             accumulators=accumulators, pseudopotential=ecp)
 if ecp is not None:
@@ -178,6 +189,16 @@ for acc in accumulators:
         for a in range(len(f['atoms'])):
             print('            %-2s HF (%9.4f %9.4f %9.4f) +- (%.4f %.4f %.4f)   ZV (%9.4f %9.4f %9.4f) +- (%.4f %.4f %.4f) Ha/Bohr'
                   % ((cell.atom_symbol(a),) + tuple(f['hf'][a]) + tuple(f['hf_error'][a]) + tuple(f['zv'][a]) + tuple(f['zv_error'][a])))
+        continue
+    if acc is total_acc:
+        acc.save('forces_total.npz', results=True)
+        f = acc.forces()
+        print('total force per primitive atom and simulation cell: cutoff %.4f Bohr, %d blocks, %d walkers (%d left out), reblocked errors'
+              % (f['cutoff'], f['n_blocks'], f['n_walkers'], f['n_bad']))
+        prim = cell.original_cell
+        for a in range(len(f['atoms'])):
+            print('            %-2s total (%9.4f %9.4f %9.4f) +- (%.4f %.4f %.4f)   ZV (%9.4f %9.4f %9.4f)   Pulay (%9.4f %9.4f %9.4f) Ha/Bohr'
+                  % ((prim.atom_symbol(a),) + tuple(f['total'][a]) + tuple(f['total_error'][a]) + tuple(f['zv'][a]) + tuple(f['pulay'][a])))
         continue
     if acc is momentum_acc:
         acc.save('momentum.npz', results=True)

@@ -490,6 +490,7 @@ int ds_spin_exchange_ratios(ds_system* sys, const void* params, const void* x, i
  *   dF has zero expectation over |psi|^2 and removes the 1/r^2 singularity (the infinite variance) of F^hf at an all-electron
  *   nucleus.  NOT included: the Pulay term 2 <(E_L - E) d log psi / dR_a>.  HF + ZV is the force only for an exact psi; its bias is
  *   first order in the error of the wave function.  All-electron ions only: no pseudopotential term.
+ *   (ds_logpsi_ion_vjp below gives d log psi / dR_a for the atoms of the primitive cell; estimator.PrimitiveForces adds the Pulay term.)
  *   - x (B, 3N) and drift (B, 3N) = Re grad log psi (the real parts of ds_logpsi_grad's out_grad): device arrays of the system's
  *     dtype.  drift is needed for out_zv and for sums, and may be NULL otherwise.  All arithmetic is float64 for either dtype.
  *   - r_c: 0 < r_c <= the Wigner-Seitz radius of the simulation cell (half its shortest lattice vector); with out_zv or sums also
@@ -512,6 +513,30 @@ int ds_spin_exchange_ratios(ds_system* sys, const void* params, const void* x, i
 int64_t ds_ion_forces_workspace_bytes(const ds_system* sys, int64_t B);
 int ds_ion_forces(ds_system* sys, const void* x, const void* drift, int64_t B, double r_c, const double* ion_ion, double* out_hf,
                   double* out_zv, double* sums, int64_t* n_bad, void* ws, int64_t ws_bytes, void* stream);
+
+/* Gradient of log psi in the ion positions, per walker (csrc/ds_iongrad.h): the primitive of the Pulay force
+ *   F_a = sum_{s image of a} F^zv_s - 2 Re < conj(E_L - E) (O_a - <O_a>) >,   O_a = d log psi / d R_a = d log|psi| + i d arg psi,
+ * which completes ds_ion_forces (estimator.PrimitiveForces).  E_L = ke + ewald is complex as ds_local_energy returns it: for a complex
+ * psi the term 2 <Im E_L d arg psi> belongs to the force.
+ *   out[b][a][c] = d/dR_{a,c} [ cot[b][0] log|psi_b| + cot[b][1] arg psi_b ]     PER WALKER (not summed over the batch)
+ * a runs over the A = n_atoms_prim atoms of the PRIMITIVE cell (`atoms`), the only ions psi sees: its features are
+ * f(wrap(r_i) - R_a), periodic in the primitive lattice, so moving atom a moves all its images in the simulation cell together.
+ * The derivative in a single ion of a supercell does not exist in this ansatz; what the call gives is the force on each primitive
+ * atom per simulation cell (q = 0).  The ions of the simulation cell are ordered atom-major (image s belongs to atom s / scale).
+ *   - cot (B, 2) of the system's dtype, the convention of ds_logpsi_vjp; out (B, A, 3) FLOAT64 for either dtype, overwritten;
+ *     out_logabs (B,) / out_phase (B, 2) optional, as in ds_logpsi_vjp.
+ *   - The forward and the seed are ds_logpsi_vjp's, and so is the one-electron cotangent chain down to layer 0; nothing that only
+ *     forms a parameter sum is launched and the pair-stream backward is left out (the pair stream does not depend on R).
+ *     k_ion_grad then contracts the cotangent of the input features and of the envelope with d f / d o in float64.
+ *   - Every network option of ds_system_desc runs.  All-electron ions only.  Large batches inherit the value chain's int8 split of
+ *     the residual hidden layers exactly as ds_logpsi_vjp does (float64 handles, DS_NO_I8_VAL unset).
+ *   - Every addition is made in a fixed order and chunks are cut at groups of 80 walkers: bit-identical from run to run and for any
+ *     workspace size.  No floating-point atomics.
+ * Refused with a ds_last_error message before any launch: a null handle, params, x, cot, out or ws, B < 1, a workspace below one
+ * group of 80 walkers (ds_ion_vjp_workspace_bytes(sys, 1)). */
+int64_t ds_ion_vjp_workspace_bytes(const ds_system* sys, int64_t B);
+int ds_logpsi_ion_vjp(ds_system* sys, const void* params, const void* x, int64_t B, const void* cot, double* out, void* out_logabs,
+                      void* out_phase, void* ws, int64_t ws_bytes, void* stream);
 
 /* Semi-local pseudopotential (ECP) energy of a batch of walkers (csrc/ds_ecp.h).  The reference has no
  * pseudopotentials: the conventions are this library's own.
@@ -920,7 +945,8 @@ int64_t ds_debug_stage(ds_system* sys, const void* params, const void* x, int64_
 #define DS_PROF_EWALD 9
 #define DS_PROF_SHARED_TERM 10    /* per-walker spin-mean term S = W_sh^T mean_i h_i (k_shared_term; layer 0: k_jet_gemm<.,0>) */
 #define DS_PROF_SINGLE_LR 11     /* k_layer1_lr: the first hidden layer on the low-rank form of the layer-0 output */
-#define DS_PROF_KINDS 12
+#define DS_PROF_ION_VJP 12      /* one chunk of ds_logpsi_ion_vjp: value chain, seed, one-electron sweep, k_ion_grad */
+#define DS_PROF_KINDS 13
 int ds_profile_enable(ds_system* sys, int on);
 int ds_profile_read(ds_system* sys, double* ms_total, int64_t* launches);
 /* In-kernel clock probe of the dominant kernel (hidden one-electron layers), active while profiling is enabled for it: one
