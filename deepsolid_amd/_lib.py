@@ -82,6 +82,7 @@ SIGNATURES = {
     'ds_last_error': (C.c_char_p, []),
     'ds_param_count': (C.c_int64, [_VP]),
     'ds_int8_layers': (C.c_int, [_VP]),
+    'ds_pair_recompute_layers': (C.c_int, [_VP, C.c_int]),
     'ds_param_layout': (C.c_int, [_VP, C.POINTER(ParamBlock), C.c_int]),
     'ds_workspace_bytes': (C.c_int64, [_VP, C.c_int64]),
     'ds_logpsi': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, C.c_int64, _VP]),

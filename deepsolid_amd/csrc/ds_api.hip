@@ -386,6 +386,7 @@ int ds_system_create(const ds_system_desc* ref_desc, ds_system** out) {
     s->use_lr = getenv("DS_NO_LOWRANK") == nullptr;
     s->use_pm_skip = getenv("DS_NO_PM_SKIP") == nullptr;
     s->use_pair_expand = getenv("DS_NO_PAIR_EXPAND") == nullptr;
+    s->use_pair_recompute = getenv("DS_NO_PAIR_RECOMPUTE") == nullptr;
     s->use_g4 = getenv("DS_NO_G4") == nullptr;
     s->use_i8 = getenv("DS_I8") != nullptr && getenv("DS_NO_I8") == nullptr;
     s->use_ldsb = getenv("DS_NO_LDSB") == nullptr;

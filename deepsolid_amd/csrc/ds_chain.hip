@@ -42,6 +42,7 @@ struct PairPlan {     // pair-stream layer l (l < n_double)
     bool expand;                              // k_two_layer_expand: the layer writes the pair-mean rows of one-electron layer l + 1 itself
     bool write_out;                           // the output itself has a reader (another pair layer, or the orbital head's pair means)
     unsigned xz; int EW, NW; size_t xlds;     // k_two_layer_expand: feature splits, electrons and waves per workgroup, LDS bytes
+    bool recompute_prev;                      // k_two_layer_expand<.., PREV>: the layer runs layer l - 1 in registers; that layer's output is not written
 };
 struct LayerPlan {    // one-electron layer l
     LayerKind kind;
@@ -90,6 +91,14 @@ int plan_chain(const ds_system* s, bool dump, ChainPlan<T>* p) {
     // jets, 24 electrons --, one group on ten tiles -- 48 electrons: two jets on the tenth tile)
     const int used = S.D - 16 * (ST - 1);
     p->g4 = !s->use_g4 ? 0 : (ST == 5 && used > 8 && used <= 12) ? 3 : (ST == 10 && used <= 4) ? 1 : 0;
+    // k_two_layer_expand's geometry for a pair layer of K2o output features, from whether it has a residual and whether its output is written
+    auto pair_geom = [&](PairPlan& pp, int K2o) {
+        pp.xz = (!pp.res && K2o == 32) ? 2 : 1;       // (a residual layer keeps its operands: all features in one workgroup)
+        // two electrons per workgroup where the output is written and a single electron's pairs would end in the middle of a 128-byte line
+        pp.EW = (pp.write_out && S.N % 16 == 8 && pp.xz == 2) ? 2 : 1;
+        pp.NW = (pp.EW * S.N + 15) / 16;
+        pp.xlds = ((size_t)(K2o / pp.xz) * 5 * pp.EW * S.N + (size_t)pp.EW * S.nch * (K2o / pp.xz) * 5) * sizeof(T);
+    };
     for (int l = 0; l < S.n_layers; ++l) {
         const int Kh = S.h1[l], K2 = S.h2[l], Nout = S.h1[l + 1], Kloc = Kh + S.nch * K2;
         LayerPlan& lp = p->layer[l];
@@ -103,15 +112,23 @@ int plan_chain(const ds_system* s, bool dump, ChainPlan<T>* p) {
             // (a first pair layer as wide as the pair features: its residual is added by k_pair_res_add behind the layer)
             pp.res_sep = s->res2[l] && l == 0;
             pp.res = s->res2[l] && !pp.res_sep;
-            pp.xz = (!pp.res && K2o == 32) ? 2 : 1;       // (a residual layer keeps its operands: all features in one workgroup)
             pp.write_out = l + 1 < S.n_double || s->use_last;
-            // two electrons per workgroup where the output is written and a single electron's pairs would end in the middle of a 128-byte line
-            pp.EW = (pp.write_out && S.N % 16 == 8 && pp.xz == 2) ? 2 : 1;
-            pp.NW = (pp.EW * S.N + 15) / 16;
-            pp.xlds = ((size_t)(K2o / pp.xz) * 5 * pp.EW * S.N + (size_t)pp.EW * S.nch * (K2o / pp.xz) * 5) * sizeof(T);
+            pair_geom(pp, K2o);
             // the layer and the spin means of its output in one kernel (a workgroup per electron) when the output jets of an electron's
             // pairs fit the LDS: the next level's rows land in the buffer the one-electron layer below writes its output to
             pp.expand = !dump && s->use_pair_expand && !pp.res_sep && l + 1 < S.n_layers && pp.NW <= 8 && pp.xlds <= 150 * 1024;
+            // A float64 residual layer behind a layer without residual on at most two k-steps of input features (layer 1 behind layer 0:
+            // 4 'nu' or 8 'tri' features) runs that layer itself and keeps its output as operands; the layer in front then writes the
+            // pair-mean rows only (one electron per workgroup, which its LDS test above already passed with more).
+            if (l >= 1) {
+                PairPlan& prev = p->layer[l - 1].pair;
+                pp.recompute_prev = sizeof(T) == 8 && !dump && s->use_pair_recompute && pp.res && pp.expand && S.h2[l - 1] <= 8 &&
+                                    !prev.res && !prev.res_sep && prev.expand;
+                if (pp.recompute_prev) {
+                    prev.write_out = false;
+                    pair_geom(prev, K2);
+                }
+            }
         }
         const bool res = s->res1[l];
         // a first layer as wide as its input features: the residual is added by k_layer_res_add behind the layer (see there)
@@ -211,9 +228,17 @@ int run_chain(ds_system* s, const T* params, const T* x, int64_t Bc, Arena<T> ws
                 // (the rows of level l + 1 land in the buffer the one-electron layer below writes its output to)
 #define DS_TWOX(NT2, RES) hipLaunchKernelGGL((ds::k_two_layer_expand<T, NT2, RES>), dim3(S.N / pp.EW, (unsigned)Bc, pp.xz), dim3(64 * pp.NW), pp.xlds, st, S, c.H2[hi], K2, W2, b2, \
                                              pp.write_out ? c.H2[hi ^ 1] : (T*)nullptr, c.G[gi ^ 1], S.h1[l + 1], S.ldk, plan.layer[l + 1].pm_unwritten ? 1 : 0, pp.EW)
-                if (K2o == 32 && pp.res) DS_TWOX(2, true);
+                // (recompute_prev: layer l - 1 left c.H2[hi] unwritten -- its input is still in the other buffer, and an output goes
+                //  to c.H2[hi] itself: the walkers of the input buffer are Kin, not K2o, features apart)
+#define DS_TWOXP(NT2) hipLaunchKernelGGL((ds::k_two_layer_expand<T, NT2, true, true>), dim3(S.N / pp.EW, (unsigned)Bc, pp.xz), dim3(64 * pp.NW), pp.xlds, st, S, c.H2[hi ^ 1], S.h2[l - 1], W2, b2, \
+                                         pp.write_out ? c.H2[hi] : (T*)nullptr, c.G[gi ^ 1], S.h1[l + 1], S.ldk, plan.layer[l + 1].pm_unwritten ? 1 : 0, pp.EW,               \
+                                         blk(s->i_w2[l - 1]), blk(s->i_b2[l - 1]))
+                if (pp.recompute_prev) {
+                    if constexpr (sizeof(T) == 8) { if (K2o == 32) DS_TWOXP(2); else DS_TWOXP(1); }      // (plan_chain: float64 only)
+                } else if (K2o == 32 && pp.res) DS_TWOX(2, true);
                 else if (pp.res) DS_TWOX(1, true);
                 else DS_TWOX(1, false);
+#undef DS_TWOXP
 #undef DS_TWOX
             } else {
                 const dim3 grid((S.NP / 16 + 3) / 4, (unsigned)Bc);
@@ -312,7 +337,7 @@ int run_chain(ds_system* s, const T* params, const T* x, int64_t Bc, Arena<T> ws
         }
         gi ^= 1;
         if (l < S.n_double) {
-            hi ^= 1;
+            if (!lp.pair.recompute_prev) hi ^= 1;      // (such a layer wrote, if at all, into the buffer the layer in front left unwritten)
             if (stop == STOP_H2_1 + l) return copy_out(dr, c.H2[hi], (size_t)S.h2[l + 1] * 5 * S.NP * Bc, st);
         }
     }
@@ -477,6 +502,15 @@ int int8_energy_layers(const ds_system* s, bool dump) {
     return plan_chain<double>(s, dump, &plan) == 0 ? plan.count(LayerKind::Int8, s->sd.n_layers) : 0;
 }
 
+// pair layers of the handle's energy chain that run the layer in front of them in registers (PairPlan::recompute_prev)
+template <typename T> int pair_recompute_count(const ds_system* s, bool dump) {
+    ChainPlan<T> plan;
+    if (plan_chain<T>(s, dump, &plan)) return 0;
+    int n = 0;
+    for (int l = 0; l < s->sd.n_double && l < s->sd.n_layers; ++l) n += plan.layer[l].pair.recompute_prev ? 1 : 0;
+    return n;
+}
+
 template <typename T> void launch_pair_res_add(dim3 grid, hipStream_t st, const T* Hin, int Kin, T* Hout, int Kout, int n_res, int NP) {
     hipLaunchKernelGGL((ds::k_pair_res_add<T>), grid, dim3(256), 0, st, Hin, Kin, Hout, Kout, n_res, NP);
 }
@@ -503,6 +537,11 @@ extern "C" {
 int ds_int8_layers(const ds_system* s) {
     if (!s) return -1;
     return int8_energy_layers(s, false);
+}
+
+int ds_pair_recompute_layers(const ds_system* s, int dump) {
+    if (!s) return -1;
+    return s->dtype == 0 ? pair_recompute_count<double>(s, dump != 0) : pair_recompute_count<float>(s, dump != 0);
 }
 
 int ds_local_energy(ds_system* s, const void* params, const void* x, int64_t B, void* out_ke, void* out_ewald, void* out_logabs,

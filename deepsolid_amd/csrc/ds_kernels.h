@@ -304,6 +304,15 @@ __global__ void __launch_bounds__(256) k_pair_res_add(const T* __restrict__ Hin,
 // partner means of the NEXT one-electron layer need no second pass over H2 and stay bit-reproducible.  Hout == nullptr:
 // the layer output itself is not needed (last pair layer of a log-psi forward).
 constexpr int PM_SLOTS = 3;
+// The tanh of a 5-jet (value, gradient along the pair's three coordinates, Laplacian): z0 is the pre-activation with its bias.
+template <typename T>
+__device__ __forceinline__ void pair_tanh_jet(T z0, T z1, T z2, T z3, T z4, T (&o)[5]) {
+    const T y = ds_tanh(z0), d1 = 1 - y * y, d2 = -2 * y * d1;
+    o[0] = y; o[1] = d1 * z1; o[2] = d1 * z2; o[3] = d1 * z3;
+    o[4] = d1 * z4 + d2 * 2 * (z1 * z1 + z2 * z2 + z3 * z3);
+}
+// A value as the compiler sees one it loaded: no product that made it is fused into the sums that use it.
+__device__ __forceinline__ double as_loaded(double x) { asm("" : "+v"(x)); return x; }
 template <typename T, int NT2, bool RES, bool VAL>
 __global__ void __launch_bounds__(256, ((RES && !VAL && sizeof(T) == 8 && NT2 == 2) ? 2 : 3)) k_two_layer(SysDev<T> S, const T* __restrict__ Hin, int Kin, const T* __restrict__ W,
                                                    const T* __restrict__ bias, T* __restrict__ Hout, T* __restrict__ PARTM = nullptr) {
@@ -370,10 +379,9 @@ __global__ void __launch_bounds__(256, ((RES && !VAL && sizeof(T) == 8 && NT2 ==
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int n = 16 * a + acc_row<T>(lane, r);
-            const T z0 = acc[a][0][r] + bias[n];
-            const T y = ds_tanh(z0), d1 = 1 - y * y, d2 = -2 * y * d1;
             const T z1 = acc[a][1][r], z2 = acc[a][2][r], z3 = acc[a][3][r], z4 = acc[a][4][r];
-            T o[5] = {y, d1 * z1, d1 * z2, d1 * z3, d1 * z4 + d2 * 2 * (z1 * z1 + z2 * z2 + z3 * z3)};
+            T o[5];
+            pair_tanh_jet(acc[a][0][r] + bias[n], z1, z2, z3, z4, o);
             if (VAL) {   // value chain: the five columns are five independent walkers
                 o[1] = ds_tanh(z1 + bias[n]); o[2] = ds_tanh(z2 + bias[n]); o[3] = ds_tanh(z3 + bias[n]); o[4] = ds_tanh(z4 + bias[n]);
             }
@@ -410,10 +418,17 @@ __global__ void __launch_bounds__(256, ((RES && !VAL && sizeof(T) == 8 && NT2 ==
 // for a kernel whose phases (load, products, tanh, sums, expand) follow each other behind barriers.  EW = 2 where the layer output is
 // written and N is an odd multiple of 8: a workgroup's stretch of every output row then begins and ends on a 128-byte line (with one
 // electron per workgroup neighbouring workgroups -- on different XCDs -- each wrote part of a line).
-template <typename T, int NT2, bool RES>
+// PREV (float64 residual layer behind a layer WITHOUT residual on a handful of input features -- pair layer 1 behind layer 0): the
+// layer's input is never in memory.  Hin / Kin are the input of the layer in front and W0 / b0 its weights; the wave runs that layer
+// for its pairs first -- all 16 NT2 features, per 16 of them the k-steps, bias and chain rule of k_two_layer_expand<T, 1, false>, whose
+// two 16-feature workgroups are the halves a = 0, 1 here -- and its accumulator element (a, c, r) is the kept operand bk[4 a + r][c]
+// (see k_two_layer).  The layer in front then writes the pair-mean rows only (its Hout == nullptr): 3.0 GB less written and 3.5 GB
+// less read per 4096 bcc-Li walkers, bit-identical rows.
+template <typename T, int NT2, bool RES, bool PREV = false>
 __global__ void __launch_bounds__(512) k_two_layer_expand(SysDev<T> S, const T* __restrict__ Hin, int Kin, const T* __restrict__ W,
                                                           const T* __restrict__ bias, T* __restrict__ Hout, T* __restrict__ G, int row0,
-                                                          int ldg, int skip, int EW) {
+                                                          int ldg, int skip, int EW, const T* __restrict__ W0 = nullptr,
+                                                          const T* __restrict__ b0 = nullptr) {
     typedef typename Acc4<T>::type acc_t;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int w = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63, tid = threadIdx.x, nt = blockDim.x;
@@ -431,12 +446,40 @@ __global__ void __launch_bounds__(512) k_two_layer_expand(SysDev<T> S, const T* 
 #pragma unroll
         for (int c = 0; c < 5; ++c) acc[a][c] = acc_t{0, 0, 0, 0};
     constexpr bool KEEP = RES && sizeof(T) == 8;       // (see k_two_layer: the residual is the operand the lane loaded)
+    static_assert(!PREV || KEEP, "the layer in front is recomputed into the kept operands of a float64 residual layer");
     T bk[KEEP ? 4 * NT2 : 1][5];
     if constexpr (KEEP) {
+        if constexpr (PREV) {
+            for (int ks = 0; ks < Kin / 4; ++ks) {
+                T av[NT2], bv[5];
 #pragma unroll
-        for (int ks = 0; ks < 4 * NT2; ++ks)
+                for (int a = 0; a < NT2; ++a) av[a] = W0[(size_t)(4 * ks + lq) * Kout + 16 * a + lr];
 #pragma unroll
-            for (int c = 0; c < 5; ++c) bk[ks][c] = Hw[(size_t)((4 * ks + lq) * 5 + c) * NP];
+                for (int c = 0; c < 5; ++c) bv[c] = Hw[(size_t)((4 * ks + lq) * 5 + c) * NP];
+#pragma unroll
+                for (int a = 0; a < NT2; ++a)
+#pragma unroll
+                    for (int c = 0; c < 5; ++c) acc[a][c] = mfma16(av[a], bv[c], acc[a][c]);
+            }
+#pragma unroll
+            for (int a = 0; a < NT2; ++a)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    T o[5];
+                    pair_tanh_jet(acc[a][0][r] + b0[16 * a + acc_row<T>(lane, r)], acc[a][1][r], acc[a][2][r], acc[a][3][r], acc[a][4][r], o);
+#pragma unroll
+                    for (int c = 0; c < 5; ++c) bk[4 * a + r][c] = as_loaded(o[c]);
+                }
+#pragma unroll
+            for (int a = 0; a < NT2; ++a)
+#pragma unroll
+                for (int c = 0; c < 5; ++c) acc[a][c] = acc_t{0, 0, 0, 0};
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < 4 * NT2; ++ks)
+#pragma unroll
+                for (int c = 0; c < 5; ++c) bk[ks][c] = Hw[(size_t)((4 * ks + lq) * 5 + c) * NP];
+        }
 #pragma unroll
         for (int ks = 0; ks < 4 * NT2; ++ks) {
             T av[NT2];
@@ -466,10 +509,8 @@ __global__ void __launch_bounds__(512) k_two_layer_expand(SysDev<T> S, const T* 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int n = 16 * a + acc_row<T>(lane, r);
-            const T z0 = acc[a][0][r] + bias[n0 + n];
-            const T y = ds_tanh(z0), d1 = 1 - y * y, d2 = -2 * y * d1;
-            const T z1 = acc[a][1][r], z2 = acc[a][2][r], z3 = acc[a][3][r], z4 = acc[a][4][r];
-            const T o[5] = {y, d1 * z1, d1 * z2, d1 * z3, d1 * z4 + d2 * 2 * (z1 * z1 + z2 * z2 + z3 * z3)};
+            T o[5];
+            pair_tanh_jet(acc[a][0][r] + bias[n0 + n], acc[a][1][r], acc[a][2][r], acc[a][3][r], acc[a][4][r], o);
 #pragma unroll
             for (int c = 0; c < 5; ++c) {
                 T v = o[c];
@@ -488,34 +529,47 @@ __global__ void __launch_bounds__(512) k_two_layer_expand(SysDev<T> S, const T* 
         sums[idx] = v / T(ns);
     }
     __syncthreads();
-    // (a thread per four consecutive slots of one row, rows walked in index order: a per-lane slot descriptor with two rows per
-    //  wave pass measured slower, EXPERIMENTS.md)
+    // The kernel is bound by the instructions it issues, not by its bytes (EXPERIMENTS.md), and this phase issued half of them: a
+    // thread keeps ONE group of four consecutive slots (a 32-byte store) and walks the rows, nt / QP of them per pass of the workgroup
+    // (bcc-Li: 120 of 128 lanes busy).  What a slot shows -- a spin mean, the own electron's gradient, a partner's -- is the same in
+    // every row; per row there are left the row's address, four LDS reads and the selects.  (A descriptor per lane with two rows per
+    // WAVE pass left 20 of 32 lanes busy and measured slower.)
     typedef T vec4 __attribute__((ext_vector_type(4)));
-    const int QP = P / 4;
-    for (int idx = tid; idx < EW * nch * Kout * QP; idx += nt) {
-        const int row = idx / QP, sq = idx - row * QP, k = row % Kout, es = row / Kout, s = es % nch, el = es / nch, e = e0 + el;
-        const int j0 = s == 0 ? 0 : S.n_up, ns = s == 0 ? S.n_up : S.n_dn;
-        if (skip) {
-            const int t = sq >> 2, lo = (2 + 3 * j0) >> 4, hi = (4 + 3 * (j0 + ns - 1)) >> 4;
-            if (!(t == 0 || t == ((2 + 3 * e) >> 4) || t == ((4 + 3 * e) >> 4) || (t >= lo && t <= hi))) continue;
-        }
-        const T inv = T(1) / T(ns);
-        const T* sm = sums + (es * Kout + k) * 5;
-        vec4 v;
+    const int QP = P / 4, CW = QP < nt ? QP : nt, RPP = nt / CW, rsub = tid / CW;
+    const T inv_s[2] = {T(1) / T(S.n_up), T(1) / T(nch > 1 ? S.n_dn : S.n_up)};
+    if (rsub < RPP)
+    for (int sq = tid - rsub * CW; sq < QP; sq += CW) {
+        // slot kinds: 0 = beyond the jets (zero), 1 = a spin mean (element smi of the row's sums), 2 = a gradient slot of electron sj
+        int kind[4], smi[4], sj[4], hoff[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            const int slot = 4 * sq + u;
-            T x = 0;
-            if (slot == 0) x = sm[0];
-            else if (slot == 1) x = sm[4];
-            else if (slot < S.D) {
-                const int j = (slot - 2) / 3, c = (slot - 2) - 3 * j;
-                if (j == e) x = -sm[1 + c];
-                else if (j >= j0 && j < j0 + ns) x = hs[(k * 5 + 1 + c) * PW + el * N + j] * inv;
-            }
-            v[u] = x;
+            const int slot = 4 * sq + u, j = (slot - 2) / 3, c = (slot - 2) - 3 * j;
+            kind[u] = slot < 2 ? 1 : slot < S.D ? 2 : 0;
+            smi[u] = slot == 0 ? 0 : slot == 1 ? 4 : kind[u] == 2 ? 1 + c : 0;
+            sj[u] = kind[u] == 2 ? j : 0;
+            hoff[u] = kind[u] == 2 ? (1 + c) * PW + j : 0;
         }
-        *reinterpret_cast<vec4*>(G + ((size_t)(w * N + e) * ldg + row0 + s * KT + n0 + k) * P + 4 * sq) = v;
+        const int t = sq >> 2;
+        for (int row = rsub; row < EW * nch * Kout; row += RPP) {
+            const int k = row % Kout, es = row / Kout, s = nch > 1 ? es & 1 : 0, el = nch > 1 ? es >> 1 : es, e = e0 + el;
+            const int j0 = s == 0 ? 0 : S.n_up, ns = s == 0 ? S.n_up : S.n_dn;
+            if (skip) {
+                const int lo = (2 + 3 * j0) >> 4, hi = (4 + 3 * (j0 + ns - 1)) >> 4;
+                if (!(t == 0 || t == ((2 + 3 * e) >> 4) || t == ((4 + 3 * e) >> 4) || (t >= lo && t <= hi))) continue;
+            }
+            const T inv = inv_s[s];
+            const T* sm = sums + (es * Kout + k) * 5;
+            const T* hk = hs + k * 5 * PW + el * N;
+            // (one read per slot through a selected address, the four in flight together, measured no faster: EXPERIMENTS.md)
+            vec4 v;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const T m = sm[smi[u]], h = hk[hoff[u]];
+                const bool own = sj[u] == e, partner = sj[u] >= j0 && sj[u] < j0 + ns;
+                v[u] = kind[u] == 2 ? (own ? -m : partner ? h * inv : T(0)) : kind[u] == 1 ? m : T(0);
+            }
+            *reinterpret_cast<vec4*>(G + ((size_t)(w * N + e) * ldg + row0 + s * KT + n0 + k) * P + 4 * sq) = v;
+        }
     }
 }
 

@@ -1009,6 +1009,11 @@ class DeviceSystem:
         (csrc/ds_i8.h; 0 unless the handle was created with DS_I8=1, or for shapes without an instance)."""
         return int(self.lib.ds_int8_layers(self.handle))
 
+    def pair_recompute_layers(self, dump=False):
+        """Number of pair layers per local-energy evaluation (dump: per stage dump) that run the pair layer in front of them in
+        registers (k_two_layer_expand<.., PREV>; 0 for a handle created with DS_NO_PAIR_RECOMPUTE=1, in float32, in a stage dump)."""
+        return int(self.lib.ds_pair_recompute_layers(self.handle, 1 if dump else 0))
+
     def profile_clock(self):
         """In-kernel clock probe of the hidden-layer kernel since profile(True): -> (shader cycles, 100 MHz reference ticks,
         GHz) summed over its workgroups; GHz is None when the probe did not run."""

@@ -129,6 +129,11 @@ const char* ds_last_error(void);
  * features).  Opt-in since round 6 (environment DS_I8=1 at ds_system_create): 0 otherwise, or when the architecture has no instance. */
 int ds_int8_layers(const ds_system* sys);
 
+/* Number of pair-stream layers per local-energy evaluation (dump != 0: per stage dump) that run the pair layer in front of them in
+ * registers instead of reading its output (float64 cells whose pair layers write the pair-mean rows themselves; 0 with
+ * DS_NO_PAIR_RECOMPUTE=1 at ds_system_create, for float32 handles and in a stage dump). */
+int ds_pair_recompute_layers(const ds_system* sys, int dump);
+
 int64_t ds_param_count(const ds_system* sys);
 /* fills up to `max_blocks` entries, returns the number of blocks */
 int ds_param_layout(const ds_system* sys, ds_param_block* blocks, int max_blocks);
