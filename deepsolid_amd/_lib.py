@@ -138,6 +138,8 @@ SIGNATURES = {
     'ds_spin_exchange_ratios': (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     'ds_ion_forces_workspace_bytes': (C.c_int64, [_VP, C.c_int64]),
     'ds_ion_forces': (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_double, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
+    'ds_stress_workspace_bytes': (C.c_int64, [_VP, C.c_int64]),
+    'ds_stress': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     'ds_ion_vjp_workspace_bytes': (C.c_int64, [_VP, C.c_int64]),
     'ds_logpsi_ion_vjp': (C.c_int, [_VP, _VP, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, C.c_int64, _VP]),
     'ds_ecp_create': (C.c_int, [C.POINTER(EcpDesc), C.POINTER(_VP)]),

@@ -11,6 +11,12 @@ import torch.distributed as dist
 
 PMAP_AXIS_NAME = 'qmc_pmap_axis'
 
+# 1 Ha / bohr^3 in GPa, from the CODATA 2018 recommended values (Tiesinga et al., Rev. Mod. Phys. 93, 025010 (2021)):
+# Hartree energy 4.3597447222071e-18 J, Bohr radius 5.29177210903e-11 m.  The one place the factor is stated (estimator.StressTensor).
+HARTREE_J = 4.3597447222071e-18
+BOHR_M = 5.29177210903e-11
+HARTREE_PER_BOHR3_IN_GPA = HARTREE_J / BOHR_M ** 3 * 1e-9          # 29421.0157...
+
 
 def world_size():
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1

@@ -78,33 +78,6 @@ template <typename T> inline int force_table_flags(const SysDev<T>& S) {
     return flags;
 }
 
-// min_image of ds_kernels.h in float64 on the handle's tables
-template <typename T>
-__device__ __forceinline__ void force_min_image(const SysDev<T>& S, const double d[3], double out[3]) {
-    if (S.dist_mode == 0) {
-        for (int c = 0; c < 3; ++c) {
-            const double Lc = (double)S.sim_a[4 * c];
-            out[c] = ds_pymod(d[c] + Lc / 2, Lc) - Lc / 2;
-        }
-    } else if (S.dist_mode == 1) {
-        double fr[3];
-        for (int c = 0; c < 3; ++c) {
-            const double f = d[0] * (double)S.sim_ainv[c] + d[1] * (double)S.sim_ainv[3 + c] + d[2] * (double)S.sim_ainv[6 + c];
-            fr[c] = ds_pymod(f + 0.5, 1.0) - 0.5;
-        }
-        for (int c = 0; c < 3; ++c)
-            out[c] = fr[0] * (double)S.sim_a[c] + fr[1] * (double)S.sim_a[3 + c] + fr[2] * (double)S.sim_a[6 + c];
-    } else {
-        double best = 0;
-        for (int s = 0; s < 27; ++s) {
-            const double v0 = d[0] + (double)S.shift27[3 * s], v1 = d[1] + (double)S.shift27[3 * s + 1],
-                         v2 = d[2] + (double)S.shift27[3 * s + 2];
-            const double nn = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
-            if (s == 0 || nn < best) { best = nn; out[0] = v0; out[1] = v1; out[2] = v2; }
-        }
-    }
-}
-
 // the fixed tree over the 256 threads on NV arrays red[v][256]; the result is in red[v][0] after the last barrier
 template <int NV> __device__ __forceinline__ void force_tree(double* red, int tid) {
     __syncthreads();
@@ -247,7 +220,7 @@ __global__ void __launch_bounds__(256) k_ion_forces(SysDev<T> S, const T* __rest
         for (int i = tid; i < N; i += 256) {
             double d[3], mi[3];
             for (int c = 0; c < 3; ++c) d[c] = xs[3 * i + c] - (double)S.sim_atoms[3 * a + c];
-            force_min_image(S, d, mi);
+            min_image(S, d, mi);         // (ds_kernels.h, in float64 on the handle's tables)
             for (int c = 0; c < 3; ++c) vmi[3 * i + c] = mi[c];
             if (!want_zv) continue;
             // The image of the ZV term is the true nearest one, u: the fractional wrap of d, then the nearest of the 27 around it

@@ -1484,25 +1484,26 @@ __global__ void __launch_bounds__(256) k_combine_val(SysDev<T> S, const T* __res
 // =====================================================================================
 // 6. Ewald energy per walker (ewaldsum.py:138-191) with the minimal-image dispatch of distance.py:32-141
 // =====================================================================================
-template <typename T>
-__device__ __forceinline__ void min_image(const SysDev<T>& S, const T d[3], T out[3]) {
+// R: the type of the arithmetic (k_ewald: the handle's own T; k_stress of ds_stress.h: double on either handle's tables)
+template <typename T, typename R>
+__device__ __forceinline__ void min_image(const SysDev<T>& S, const R d[3], R out[3]) {
     if (S.dist_mode == 0) {           // diagonal_dist_i  distance.py:110-128
         for (int c = 0; c < 3; ++c) {
-            const T Lc = S.sim_a[4 * c];
+            const R Lc = (R)S.sim_a[4 * c];
             out[c] = ds_pymod(d[c] + Lc / 2, Lc) - Lc / 2;
         }
     } else if (S.dist_mode == 1) {    // orthogonal_dist_i  distance.py:91-108
-        T fr[3];
+        R fr[3];
         for (int c = 0; c < 3; ++c) {
-            const T f = d[0] * S.sim_ainv[c] + d[1] * S.sim_ainv[3 + c] + d[2] * S.sim_ainv[6 + c];
-            fr[c] = ds_pymod(f + T(0.5), T(1)) - T(0.5);
+            const R f = d[0] * (R)S.sim_ainv[c] + d[1] * (R)S.sim_ainv[3 + c] + d[2] * (R)S.sim_ainv[6 + c];
+            fr[c] = ds_pymod(f + R(0.5), R(1)) - R(0.5);
         }
-        for (int c = 0; c < 3; ++c) out[c] = fr[0] * S.sim_a[c] + fr[1] * S.sim_a[3 + c] + fr[2] * S.sim_a[6 + c];
+        for (int c = 0; c < 3; ++c) out[c] = fr[0] * (R)S.sim_a[c] + fr[1] * (R)S.sim_a[3 + c] + fr[2] * (R)S.sim_a[6 + c];
     } else {                          // general_dist_i  distance.py:70-89 (first minimum on ties)
-        T best = 0;
+        R best = 0;
         for (int s = 0; s < 27; ++s) {
-            const T v0 = d[0] + S.shift27[3 * s], v1 = d[1] + S.shift27[3 * s + 1], v2 = d[2] + S.shift27[3 * s + 2];
-            const T nn = ds_sqrt(v0 * v0 + v1 * v1 + v2 * v2);
+            const R v0 = d[0] + (R)S.shift27[3 * s], v1 = d[1] + (R)S.shift27[3 * s + 1], v2 = d[2] + (R)S.shift27[3 * s + 2];
+            const R nn = ds_sqrt(v0 * v0 + v1 * v1 + v2 * v2);
             if (s == 0 || nn < best) { best = nn; out[0] = v0; out[1] = v1; out[2] = v2; }
         }
     }

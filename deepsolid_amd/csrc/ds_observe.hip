@@ -1,12 +1,14 @@
 // ds_observe.hip -- observables of a batch of walkers that need no wave function (ds_obs.h, ds_realspace.h): structure factor and
 // polarization sums, electron density and pair-correlation counts; and forward walking for the DMC (ds_fw.h): ancestor tables, the
 // counts with a weight and a source row per walker, weighted sums of per-walker values; and the ionic forces (ds_force.h), which need
-// the handle's Ewald tables and the caller's drift but no forward of their own.
+// the handle's Ewald tables and the caller's drift but no forward of their own; and the strain derivative of the energy (ds_stress.h),
+// which needs the same tables and the caller's walker gradient.
 #include "ds_host.h"
 #include "ds_obs.h"
 #include "ds_realspace.h"
 #include "ds_fw.h"
 #include "ds_force.h"
+#include "ds_stress.h"
 
 namespace ds {
 namespace host {
@@ -126,6 +128,23 @@ template <typename T> int force_tables(ds_system* s) { return ds::force_table_fl
 
 // doubles of workspace per group of FORCE_GROUP walkers: their rows and the group's partial sums
 static int64_t force_group_doubles(const ds_system* s) { return (int64_t)ds::FORCE_GROUP * 6 * s->sd.As + 12 * s->sd.As + 1; }
+
+// strain derivatives (ds_stress.h): the walkers [b0, b0 + nb) of the batch; rows: of this launch
+template <typename T>
+void stress(ds_system* s, const void* x, const void* grad, int64_t b0, int64_t nb, const double* ion_ion, double* out, double* rows,
+            int64_t* n_bad, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const int tables = ds::stress_table_flags(S);     // (>= 0: checked by ds_stress)
+    const size_t n3 = 3 * (size_t)S.N;
+    hipLaunchKernelGGL((ds::k_stress<T>), dim3((unsigned)nb), dim3(256), ds::stress_lds_doubles(S, tables != 0) * sizeof(double), st, S,
+                       (const T*)x + b0 * n3, grad ? (const T*)grad + b0 * 2 * n3 : nullptr, ion_ion, tables,
+                       out ? out + b0 * 6 * ds::STRESS_ROWS : nullptr, rows, (unsigned long long*)n_bad);
+}
+
+template <typename T> int stress_tables(ds_system* s) { return ds::stress_table_flags(dev<T>(s)); }
+
+// doubles of workspace per group of FORCE_GROUP walkers: their rows and the group's partial sums
+static int64_t stress_group_doubles() { return (int64_t)ds::FORCE_GROUP * 6 * ds::STRESS_ROWS + ds::STRESS_K; }
 
 }  // namespace host
 }  // namespace ds
@@ -328,6 +347,54 @@ int ds_ion_forces(ds_system* s, const void* x, const void* drift, int64_t B, dou
         hipLaunchKernelGGL(ds::k_force_part, dim3((unsigned)groups), dim3(ds::FORCE_GROUP), 0, st, (const double*)rows, (long long)nb, A, part);
         HIP_OK(hipGetLastError());
         hipLaunchKernelGGL(ds::k_force_final, dim3((K + 255) / 256), dim3(256), 0, st, (const double*)part, (long long)groups, K, sums);
+        HIP_OK(hipGetLastError());
+    }
+    return 0;
+}
+
+int64_t ds_stress_workspace_bytes(const ds_system* s, int64_t B) {
+    if (!s || B < 1) return -1;
+    const int64_t per = stress_group_doubles() * (int64_t)sizeof(double);
+    const int64_t groups = (B + ds::FORCE_GROUP - 1) / ds::FORCE_GROUP;
+    return per * std::max<int64_t>(1, std::min<int64_t>(groups, workspace_budget() / per));
+}
+
+int ds_stress(ds_system* s, const void* x, const void* grad, int64_t B, const double* ion_ion, double* out, double* sums, int64_t* n_bad,
+              void* ws, int64_t ws_bytes, void* stream) {
+    if (!s || !x) return fail("ds_stress: null argument");
+    if (B < 1) return fail("ds_stress: B must be >= 1 (got %lld)", (long long)B);
+    if (!out && !sums) return fail("ds_stress: out and sums are both null, nothing to write");
+    if (sums && !grad) return fail("ds_stress: sums hold the kinetic rows too: they need the gradient (got a null grad)");
+    if (DS_BY_DTYPE(s->dtype, stress_tables, s) < 0)
+        return fail("ds_stress: %d electrons need more than %d KB of LDS per walker: not supported", s->sd.N, (int)(ds::FORCE_LDS_MAX / 1024));
+    const int64_t per = stress_group_doubles() * (int64_t)sizeof(double);
+    int64_t fit = 0;
+    if (sums) {
+        fit = ws ? ws_bytes / per : 0;
+        if (fit < 1)
+            return fail("workspace too small for ds_stress: %lld bytes < %lld for one group of %d walkers (see ds_stress_workspace_bytes)",
+                        (long long)(ws ? ws_bytes : 0), (long long)per, ds::FORCE_GROUP);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (!sums) {
+        DS_BY_DTYPE(s->dtype, stress, s, x, grad, (int64_t)0, B, ion_ion, out, (double*)nullptr, n_bad, st);
+        HIP_OK(hipGetLastError());
+        return 0;
+    }
+    // passes of `fit` groups, cut at multiples of FORCE_GROUP walkers of the batch as in ds_ion_forces: the same additions in the
+    // same order for any workspace
+    fit = std::min<int64_t>(fit, (B + ds::FORCE_GROUP - 1) / ds::FORCE_GROUP);
+    double* rows = (double*)ws;
+    double* part = rows + (size_t)fit * ds::FORCE_GROUP * 6 * ds::STRESS_ROWS;
+    for (int64_t b0 = 0; b0 < B; b0 += fit * ds::FORCE_GROUP) {
+        const int64_t nb = std::min<int64_t>(B - b0, fit * ds::FORCE_GROUP);
+        const int64_t groups = (nb + ds::FORCE_GROUP - 1) / ds::FORCE_GROUP;
+        DS_BY_DTYPE(s->dtype, stress, s, x, grad, b0, nb, ion_ion, out, rows, n_bad, st);
+        HIP_OK(hipGetLastError());
+        hipLaunchKernelGGL(ds::k_stress_part, dim3((unsigned)groups), dim3(ds::FORCE_GROUP), 0, st, (const double*)rows, (long long)nb, part);
+        HIP_OK(hipGetLastError());
+        hipLaunchKernelGGL(ds::k_force_final, dim3((ds::STRESS_K + 255) / 256), dim3(256), 0, st, (const double*)part, (long long)groups,
+                           ds::STRESS_K, sums);
         HIP_OK(hipGetLastError());
     }
     return 0;

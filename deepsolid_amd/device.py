@@ -735,6 +735,45 @@ class DeviceSystem:
                    'ds_ion_forces')
         return dict(hf=hf, zv=zv, n_bad=n_bad, sums=sums)
 
+    def stress(self, x, grad=None, sums=None, want_walker=True, max_bytes=None):
+        """`ds_stress` (csrc/ds_stress.h): per walker the strain derivative dE / d eps of the energy, as
+        symmetric tensors in the component order xx, yy, zz, yz, xz, xy, in Hartree: parts (B, 4, 6) float64 with the rows
+        kin (-sum_i Re(d_i conj d_i^T), d = `grad` (B, 3N) complex = `logpsi_grad(...)[1]`; zero without `grad`), ee, ei (the Ewald sums
+        of `ewald` under a homogeneous strain: alpha, the G list and the minimal images held fixed) and total = kin + ee + ei + the
+        ion-ion constant.  The stress is total / volume, the pressure -tr / 3 of that (`estimator.StressTensor`).  NOT the full
+        stress of a variational psi: the change of psi with the cell at fixed parameters is missing; all-electron ions only.
+        `sums`: float64 device tensor (49,) that is ADDED to = per row and component [sum, sum of squares] over the good walkers, then
+        their number; it needs `grad`.  A walker with a non-finite coordinate, gradient or result is NaN, left out and counted.
+        `max_bytes` caps the workspace of `sums`: more passes, bit-identical results.  The ion-ion constant
+        (`ewaldsum.ion_ion_stress`) is computed once on the host and cached on the system.
+        -> dict(parts (B, 4, 6) or None without `want_walker`, n_bad (1,) int64 device tensor, sums).  No host synchronisation."""
+        x = self._check_x(x)
+        B = x.shape[0]
+        if grad is not None:
+            if not (grad.is_cuda and grad.is_complex() and torch.view_as_real(grad).dtype == self.dtype and
+                    tuple(grad.shape) == tuple(x.shape)):
+                raise ValueError(f'grad must be a complex device tensor of shape {tuple(x.shape)} with {self.dtype} parts')
+            grad = torch.view_as_real(grad.contiguous())
+        if sums is not None:
+            if not (sums.is_cuda and sums.dtype == torch.float64 and sums.is_contiguous() and tuple(sums.shape) == (49,)):
+                raise ValueError('sums must be a contiguous float64 device tensor of shape (49,)')
+            if grad is None:
+                raise ValueError('sums hold the kinetic rows too: they need grad')
+        if not want_walker and sums is None:
+            raise ValueError('nothing to compute: neither the walker tensors nor sums are asked for')
+        parts = torch.empty(B, 4, 6, dtype=torch.float64, device=self.device) if want_walker else None
+        n_bad = torch.zeros(1, dtype=torch.int64, device=self.device)
+        if B == 0:
+            return dict(parts=parts, n_bad=n_bad, sums=sums)
+        if getattr(self, '_ion_ion_stress', None) is None:
+            from .ewaldsum import VOIGT, ion_ion_stress
+            ii = ion_ion_stress(self.cell, tables=self.tables)
+            self._ion_ion_stress = torch.as_tensor(np.array([ii[a, b] for a, b in VOIGT]), dtype=torch.float64, device=self.device)
+        ws = self._workspace('ds_stress_workspace_bytes', int(B), max_bytes=max_bytes) if sums is not None else None
+        _lib.check(self.lib.ds_stress(self.handle, _ptr(x), _ptr(grad), B, _ptr(self._ion_ion_stress), _ptr(parts), _ptr(sums),
+                                      _ptr(n_bad), _ptr(ws), ws.numel() if ws is not None else 0, _stream()), 'ds_stress')
+        return dict(parts=parts, n_bad=n_bad, sums=sums)
+
     def logpsi_ion_vjp(self, params, x, cot, max_bytes=None):
         """`ds_logpsi_ion_vjp` (csrc/ds_iongrad.h): per walker the gradient of
         cot_b[0] log|psi_b| + cot_b[1] arg psi_b in the positions of the A atoms of the PRIMITIVE cell (`self.prim_atoms`), the

@@ -863,6 +863,349 @@ class IonForces:
             return cls.from_state_dict({k: f[k] for k in f.files})
 
 
+# ------------------------------------------------------------------ stress tensor and pressure (csrc/ds_stress.h)
+# The reference has no stress estimator; the conventions of this section are this project's own.
+STRESS_ROWS = ('kin', 'ee', 'ei', 'total')
+
+
+def voigt_to_matrix(v):
+    """(..., 6) in the component order xx, yy, zz, yz, xz, xy of `ds_stress` -> (..., 3, 3) symmetric."""
+    from .ewaldsum import VOIGT
+    v = np.asarray(v, np.float64)
+    out = np.empty(v.shape[:-1] + (3, 3))
+    for k, (a, b) in enumerate(VOIGT):
+        out[..., a, b] = out[..., b, a] = v[..., k]
+    return out
+
+
+def strain_generators():
+    """(6, 3, 3): the symmetric matrices E_k with eps = h E_k the strain whose derivative in h is the component k (xx, yy, zz, yz, xz, xy)
+    of a strain derivative as `ds_stress` defines it (the two off-diagonal entries count as independent: each is h / 2)."""
+    from .ewaldsum import VOIGT
+    E = np.zeros((6, 3, 3))
+    for k, (a, b) in enumerate(VOIGT):
+        E[k, a, b] += 0.5
+        E[k, b, a] += 0.5
+    return E
+
+
+class StressTensor:
+    """Stress tensor and pressure of the simulation cell, accumulated on the device over any number of walker batches: an accumulator
+    for `run_inference(accumulators=...)` (VMC) and, without the wave-function term, `run_dmc(accumulators=...)` (the mixed estimate,
+    on comb blocks).
+
+        sigma_ab = < kin_ab + dE_ewald / d eps_ab > / V     (Ha / bohr^3),      P = -tr sigma / 3
+
+    kin_ab = -sum_i Re(d_ia conj d_ib), d = grad log psi, is the integrated-by-parts kinetic tensor (<tr kin> = -2 <T>; valid under
+    periodic and twisted boundary conditions) and dE_ewald / d eps the derivative of the Ewald sums of `ds_ewald` under a homogeneous
+    strain eps of the cell, electrons and ions scaled along, with alpha, the G list and the minimal images held fixed
+    (`DeviceSystem.stress`).  For a pure Coulomb Hamiltonian tr(dE_ewald / d eps) = -E_ewald, so P = (2 <T> + <V>) / (3 V): the virial
+    theorem, which the truncated sums obey to their convergence error.
+    sigma is the stress only for an exact psi: for a variational psi the energy also changes because psi at fixed parameters changes
+    with the cell (its features, envelopes and k points), a bias first order in the error of the wave function.  The variance of
+    the kinetic tensor is NOT the zero variance of E_L: kin fluctuates even for an exact psi.  All-electron ions only
+    (`pseudopotential` must be None).
+
+    Every `update` is ONE `ds_logpsi_grad` call and ONE `ds_stress` call; nothing is read back.  `net`: the object
+    `make_solid_fermi_net` returns (or its `.apply`).
+
+    `wavefunction_term=True` adds the missing term,
+
+        sigma^tot_ab V = < kin + dE_ewald / d eps >_ab + 2 Re < conj(E_L - E)(O_ab - <O_ab>) >,   O_ab = d log psi_eps((1 + eps) x) / d eps_ab
+
+    (the Jacobian of the normalisation is a constant and drops out of the covariance), with O by central differences over
+    strained handles: `supercell.strained` and `DeviceSystem.for_network` for +-`strain_step` along each of the six components,
+    TWELVE handles built once at the first update, O_k = [log psi_{+h}(x (1 + h E_k)) - log psi_{-h}(x (1 - h E_k))] / 2h with the
+    phase difference taken modulo 2 pi.  Every `update` is then ONE BLOCK, as for `PrimitiveForces`: `local_energy` (unless the
+    caller passes `energies`), `logpsi_grad`, `ds_stress` and TWELVE `logpsi` forwards, and appends one device row
+    [n_good, sum Re E, sum Im E, sum total (6), sum t (6)], t = Re conj(E_b - mean E of the block) O_b.  `stress()` then also gives
+    sigma_total and pressure_total with errors from reblocking the block series.  float64 handles only (a float32 forward loses the
+    difference); VMC only: `run_dmc` refuses it (`vmc_only`)."""
+
+    ROW_LEN = 15
+
+    def __init__(self, net, params, pseudopotential=None, wavefunction_term=False, strain_step=1e-4):
+        if pseudopotential is not None:
+            raise NotImplementedError('StressTensor: the strain derivative of a semi-local pseudopotential is not implemented '
+                                      '(all-electron ions only)')
+        self.apply = getattr(net, 'apply', net)
+        self.params = params
+        if wavefunction_term:
+            if getattr(self.apply, 'dtype', torch.float64) != torch.float64:
+                raise ValueError('StressTensor(wavefunction_term=True) needs a float64 network: the central difference of log psi over '
+                                 'a strain step of 1e-4 is below the resolution of a float32 forward')
+            if not (np.isfinite(strain_step) and 0.0 < float(strain_step) < 0.1):
+                raise ValueError(f'strain_step = {strain_step} must be positive and small')
+        cell = self.apply.simulation_cell
+        self._setup(np.asarray(cell.atom_coords(), np.float64), np.asarray(cell.atom_charges(), np.float64),
+                    np.asarray(cell.a, np.float64), int(sum(cell.nelec)), wavefunction_term, strain_step)
+
+    def _setup(self, atoms, charges, latvec, n_elec, wavefunction_term=False, strain_step=1e-4):
+        self.atoms = np.asarray(atoms, np.float64).reshape(-1, 3)
+        self.charges = np.asarray(charges, np.float64).reshape(-1)
+        self.latvec = np.asarray(latvec, np.float64).reshape(3, 3)
+        self.n_elec = int(n_elec)
+        self.volume = float(abs(np.linalg.det(self.latvec)))
+        self.wavefunction_term = bool(wavefunction_term)
+        self.vmc_only = self.wavefunction_term                  # (read by `run_dmc`)
+        self.strain_step = float(strain_step)
+        self._strained = None                                   # [(system +h, F +h, system -h, F -h)] per component, on first use
+        self.sums = torch.zeros(49, dtype=torch.float64)        # of `ds_stress`; moved to the walkers' device by the first update
+        self.trace_sums = torch.zeros(2, dtype=torch.float64)   # sum and sum of squares of tr(total) over the good walkers (for P)
+        self.blocks = []                                        # device rows, one per update (wavefunction_term)
+        self.n_bad = torch.zeros(1, dtype=torch.int64)
+        self.n_walkers = 0
+        self.n_means = 1                    # block means subtracted per row: the ranks whose rows were added by reduce()
+        self.reduced = False
+
+    @property
+    def rows(self):
+        """(blocks, 15) float64 tensor of the block rows of the wave-function term (on the device of the walkers)."""
+        if not self.blocks:
+            return torch.zeros(0, self.ROW_LEN, dtype=torch.float64)
+        return torch.stack(self.blocks)
+
+    # ---- the strain derivative of log psi
+    def strained_systems(self):
+        """The twelve handles of the wave-function term, built once: per component k the `DeviceSystem` of the cell strained by
+        +h E_k and by -h E_k (`strain_generators`), each with its deformation matrix 1 +- h E_k as a device tensor."""
+        if self._strained is None:
+            from .device import DeviceSystem
+            from .supercell import strained
+            base = self.apply.system
+            out = []
+            for E in strain_generators():
+                pair = []
+                for sgn in (+1.0, -1.0):
+                    cell, klist = strained(self.apply.simulation_cell, self.apply.klist, sgn * self.strain_step * E)
+                    sysd = DeviceSystem.for_network(cell, klist, self.apply.net_kw, torch.float64)
+                    pair += [sysd, torch.as_tensor(np.eye(3) + sgn * self.strain_step * E, dtype=torch.float64, device=base.device)]
+                out.append(tuple(pair))
+            self._strained = out
+        return self._strained
+
+    def strain_log_derivative(self, x):
+        """O (B, 6) complex128: d log psi_eps((1 + eps) x) / d eps_k at eps = 0 by central differences over the strained handles,
+        twelve `logpsi` forwards; Re = d log|psi|, Im = d arg psi (the phase difference modulo 2 pi)."""
+        B = x.shape[0]
+        O = torch.empty(B, 6, dtype=torch.complex128, device=x.device)
+        for k, (sp, Fp, sm, Fm) in enumerate(self.strained_systems()):
+            lap, php = sp.logpsi(self.params, (x.reshape(B, -1, 3) @ Fp).reshape(B, -1))
+            lam, phm = sm.logpsi(self.params, (x.reshape(B, -1, 3) @ Fm).reshape(B, -1))
+            dph = torch.angle(torch.view_as_complex(php.contiguous()) * torch.view_as_complex(phm.contiguous()).conj())
+            O[:, k] = torch.complex(lap - lam, dph) / (2.0 * self.strain_step)
+        return O
+
+    # ---- accumulation
+    def update(self, data, energies=None):
+        """Add the tensors of every walker of `data` (B, 3N) to the sums: one `ds_logpsi_grad` and one `ds_stress` call, no device ->
+        host copy.  With the wave-function term the call is one block (see the class); `energies` (B,) complex: the walkers'
+        local energies when the caller has them (used by the wave-function term only)."""
+        if self.apply is None:
+            raise RuntimeError('StressTensor.update: a loaded accumulator has no network; merge it into one that has')
+        if self.reduced:
+            raise RuntimeError('StressTensor.update after reduce(): the sums are already summed over the ranks')
+        if data.shape[-1] != 3 * self.n_elec:
+            raise ValueError(f'walkers have {data.shape[-1]} coordinates, the cell has {self.n_elec} electrons')
+        x = data.reshape(-1, 3 * self.n_elec)
+        B = x.shape[0]
+        if B == 0:
+            return
+        if self.sums.device != x.device:
+            self.sums, self.trace_sums, self.n_bad = self.sums.to(x.device), self.trace_sums.to(x.device), self.n_bad.to(x.device)
+        system = self.apply.system
+        if self.wavefunction_term:
+            self.strained_systems()             # (before anything is added: a failure leaves the accumulator as it was)
+            if energies is None:
+                ke, ew, _, _ = system.local_energy(self.params, x)
+                E = torch.complex(ke[:, 0].double() + ew.double(), ke[:, 1].double())
+            else:
+                E = torch.as_tensor(energies).to(device=x.device, dtype=torch.complex128).reshape(B)
+        grad = system.logpsi_grad(self.params, x)[1]
+        out = system.stress(x, grad, sums=self.sums, want_walker=True)
+        total = out['parts'][:, 3]
+        finite = torch.isfinite(total).all(1)
+        zero = torch.zeros((), dtype=torch.float64, device=x.device)
+        tr = torch.where(finite, total[:, :3].sum(dim=1), zero)             # (a bad walker's rows are NaN: left out)
+        self.trace_sums += torch.stack([tr.sum(), (tr * tr).sum()])
+        self.n_bad += out['n_bad']
+        if self.wavefunction_term:
+            O = self.strain_log_derivative(x)
+            good = finite & torch.isfinite(E.real) & torch.isfinite(E.imag) & torch.isfinite(O.real).all(1) & torch.isfinite(O.imag).all(1)
+            n = good.sum().to(torch.float64)
+            Er, Ei = torch.where(good, E.real, zero), torch.where(good, E.imag, zero)
+            sr, si = Er.sum(), Ei.sum()
+            dr, di = torch.where(good, Er - sr / n, zero), torch.where(good, Ei - si / n, zero)
+            g2 = good[:, None]
+            t = (dr[:, None] * torch.where(g2, O.real, zero) + di[:, None] * torch.where(g2, O.imag, zero)).sum(0)    # Re conj(dE) O
+            self.blocks.append(torch.cat([torch.stack([n, sr, si]), torch.where(g2, total, zero).sum(0), t]))
+        self.n_walkers += int(B)                    # only now: a call that raised leaves the count with the sums
+
+    def _same_setup(self, other):
+        return (self.atoms.shape == other.atoms.shape and np.array_equal(self.atoms, other.atoms) and
+                np.array_equal(self.charges, other.charges) and np.array_equal(self.latvec, other.latvec) and
+                self.n_elec == other.n_elec and self.wavefunction_term == other.wavefunction_term and
+                (not self.wavefunction_term or self.strain_step == other.strain_step))
+
+    def merge(self, other):
+        """Add the sums, the bad count and the walker number of another accumulator of the same ions and lattice (and the same
+        wave-function term and strain step; its blocks continue this one's series).  Both sides must be in the same state (rank-local
+        or summed over the ranks), as for `IonForces.merge`."""
+        if not self._same_setup(other):
+            raise ValueError('StressTensor.merge: the two accumulators differ in ions, lattice, electron number or wave-function term')
+        if self.reduced != other.reduced and constants.world_size() > 1 or self.n_means != other.n_means:
+            raise ValueError('StressTensor.merge: one side is summed over the ranks and the other is rank-local')
+        self.sums = self.sums + other.sums.to(self.sums.device)
+        self.trace_sums = self.trace_sums + other.trace_sums.to(self.trace_sums.device)
+        self.n_bad = self.n_bad + other.n_bad.to(self.n_bad.device)
+        dev = self.blocks[0].device if self.blocks else (other.blocks[0].device if other.blocks else None)
+        self.blocks = self.blocks + [b.to(dev) for b in other.blocks]
+        self.n_walkers += other.n_walkers
+        return self
+
+    def reduce(self):
+        """Sum the sums, the block rows (block by block: every rank must hold the same number), the bad count and the walker number
+        over the ranks in ONE packed float64 all-reduce (counts below 2^53 are exact; the identity at world size 1).  Once per
+        accumulator: a second call raises."""
+        if self.reduced:
+            raise RuntimeError('StressTensor.reduce was already called: reducing twice would count every rank again')
+        W = constants.world_size()
+        if W > 1:
+            dev = self.sums.device if self.sums.is_cuda else torch.device('cuda' if torch.cuda.is_available() else 'cpu')
+            rows = self.rows.to(dev)
+            nb = float(rows.shape[0])
+            packed = torch.cat([self.sums.to(dev), self.trace_sums.to(dev), self.n_bad.to(dev, torch.float64),
+                                torch.tensor([self.n_walkers, nb, nb * nb], dtype=torch.float64, device=dev)])
+            packed = constants.psum_if_pmap(packed)
+            if float(packed[53]) != W * nb or float(packed[54]) != W * nb * nb:
+                raise RuntimeError('StressTensor.reduce: the ranks hold different numbers of blocks')
+            if rows.numel():
+                self.blocks = list(constants.psum_if_pmap(rows.reshape(-1)).reshape(rows.shape).clone())
+                self.n_means = self.n_means * W
+            self.sums = packed[:49].clone()
+            self.trace_sums = packed[49:51].clone()
+            self.n_bad = packed[51:52].round().to(torch.int64)
+            self.n_walkers = int(packed[52].round())
+        self.reduced = True                 # only now: a collective that raised leaves the accumulator as it was
+        return self
+
+    # ---- normalisation (host)
+    def stress(self):
+        """-> dict(sigma (3, 3) float64 in Ha / bohr^3 = the mean of the total row over the volume, sigma_error, parts = dict(kin, ee, ei
+        (3, 3) means over the volume, ii the ion-ion constant likewise, and kin_error, ee_error, ei_error), pressure = -tr sigma / 3 and
+        pressure_error (Ha / bohr^3), pressure_gpa and pressure_gpa_error (`constants.HARTREE_PER_BOHR3_IN_GPA`), volume (bohr^3),
+        n_walkers, n_bad).  Means are over the n_good walkers whose tensors were finite; every error is
+        sqrt((sum t^2 / n_good - mean^2) / (n_good - 1)), a NAIVE standard error over walkers -- it takes them as independent and
+        ignores the autocorrelation of the Markov chain, so it is a lower bound on a real run (NaN below two good walkers).  The
+        pressure's error comes from the walkers' own traces, not from the component errors (which are correlated).  NaN everywhere
+        without a good walker.  sigma does not hold the wave-function term.
+        With `wavefunction_term` also: sigma_total = sigma + wavefunction (3, 3), per block sum total / n / V and
+        2 sum t / (n - 1) / V (the block's own mean energy was subtracted: the unbiased covariance), averaged over the blocks weighted
+        by n_good; sigma_total_error, wavefunction_error, pressure_total, pressure_total_error and pressure_total_gpa, the errors by
+        `dmc.reblock` over the block series (below eight blocks the plain standard error of the series, NaN for a single block);
+        n_blocks.  Blocks with n <= 1 good walkers are left out; NaN without a block."""
+        s = self.sums.detach().cpu().numpy()
+        t = self.trace_sums.detach().cpu().numpy()
+        n = float(s[48])
+        V = self.volume
+        q = s[:48].reshape(4, 6, 2)
+        nan33 = np.full((3, 3), np.nan)
+        gpa = constants.HARTREE_PER_BOHR3_IN_GPA
+        out = dict(volume=V, n_walkers=self.n_walkers, n_bad=int(self.n_bad.sum()))
+        if n < 1:
+            out.update(sigma=nan33, sigma_error=nan33.copy(), pressure=np.nan, pressure_error=np.nan, pressure_gpa=np.nan,
+                       pressure_gpa_error=np.nan,
+                       parts={k: nan33.copy() for k in ('kin', 'ee', 'ei', 'ii', 'kin_error', 'ee_error', 'ei_error')})
+        else:
+            mean = q[:, :, 0] / n
+            var = np.maximum(q[:, :, 1] / n - mean * mean, 0.0)
+            err = np.sqrt(var / (n - 1)) if n > 1 else np.full((4, 6), np.nan)
+            m33, e33 = voigt_to_matrix(mean) / V, voigt_to_matrix(err) / V
+            parts = {name: m33[k] for k, name in enumerate(STRESS_ROWS[:3])}
+            parts.update({name + '_error': e33[k] for k, name in enumerate(STRESS_ROWS[:3])})
+            parts['ii'] = m33[3] - ((m33[0] + m33[1]) + m33[2])
+            tr_mean = t[0] / n
+            tr_err = np.sqrt(max(t[1] / n - tr_mean * tr_mean, 0.0) / (n - 1)) if n > 1 else np.nan
+            pressure = -np.trace(m33[3]) / 3.0
+            out.update(sigma=m33[3], sigma_error=e33[3], parts=parts, pressure=pressure, pressure_error=tr_err / (3.0 * V),
+                       pressure_gpa=pressure * gpa, pressure_gpa_error=tr_err / (3.0 * V) * gpa)
+        if self.wavefunction_term:
+            from .dmc import reblock
+            rows = self.rows.detach().cpu().numpy().reshape(-1, self.ROW_LEN)
+            rows = rows[rows[:, 0] > self.n_means]
+            out['n_blocks'] = int(rows.shape[0])
+            if rows.shape[0] == 0:
+                out.update(sigma_total=nan33.copy(), sigma_total_error=nan33.copy(), wavefunction=nan33.copy(),
+                           wavefunction_error=nan33.copy(), pressure_total=np.nan, pressure_total_error=np.nan, pressure_total_gpa=np.nan)
+                return out
+            nb = rows[:, 0]
+            series = {'wavefunction': 2.0 * rows[:, 9:15] / (nb - self.n_means)[:, None] / V}
+            series['sigma_total'] = rows[:, 3:9] / nb[:, None] / V + series['wavefunction']
+            lvl = min(8, max(2, len(nb)))
+            for k, v in series.items():
+                out[k] = voigt_to_matrix((v * nb[:, None]).sum(0) / nb.sum())
+                out[k + '_error'] = voigt_to_matrix(np.array([reblock(v[:, c], min_blocks=lvl)[1] for c in range(6)]))
+            p = -series['sigma_total'][:, :3].sum(1) / 3.0
+            out['pressure_total'] = float((p * nb).sum() / nb.sum())
+            out['pressure_total_error'] = float(reblock(p, min_blocks=lvl)[1])
+            out['pressure_total_gpa'] = out['pressure_total'] * gpa
+        return out
+
+    # ---- persistence
+    def state_dict(self):
+        """Plain numpy arrays: the sums, block rows and counts and the setup they belong to."""
+        return {'sums': self.sums.detach().cpu().numpy().copy(), 'trace_sums': self.trace_sums.detach().cpu().numpy().copy(),
+                'rows': self.rows.detach().cpu().numpy().copy(), 'n_means': np.int64(self.n_means),
+                'n_bad': self.n_bad.detach().cpu().numpy().copy(), 'n_walkers': np.int64(self.n_walkers), 'atoms': self.atoms.copy(),
+                'charges': self.charges.copy(), 'latvec': self.latvec.copy(), 'n_elec': np.int64(self.n_elec),
+                'wavefunction_term': np.bool_(self.wavefunction_term), 'strain_step': np.float64(self.strain_step),
+                'reduced': np.bool_(self.reduced)}
+
+    def load_state_dict(self, sd):
+        """Replace the sums, rows and counts by those of `sd` (same ions, lattice and wave-function term); the accumulator is
+        rank-local and open for `update` afterwards."""
+        other = StressTensor.from_state_dict(sd)
+        if not self._same_setup(other):
+            raise ValueError('StressTensor.load_state_dict: the state belongs to other ions, another lattice or another wave-function term')
+        self.sums, self.trace_sums = other.sums.to(self.sums.device), other.trace_sums.to(self.trace_sums.device)
+        self.n_bad = other.n_bad.to(self.n_bad.device)
+        self.blocks, self.n_means = other.blocks, other.n_means
+        self.n_walkers, self.reduced = other.n_walkers, False
+        return self
+
+    @classmethod
+    def from_state_dict(cls, sd):
+        """An accumulator without a network: it can be merged, normalised and saved, not updated."""
+        acc = cls.__new__(cls)
+        acc.apply = acc.params = None
+        acc._setup(sd['atoms'], sd['charges'], sd['latvec'], int(sd['n_elec']),
+                   bool(sd['wavefunction_term']) if 'wavefunction_term' in sd else False,
+                   float(sd['strain_step']) if 'strain_step' in sd else 1e-4)
+        acc.sums = torch.as_tensor(np.array(sd['sums'], dtype=np.float64).reshape(49))
+        acc.trace_sums = torch.as_tensor(np.array(sd['trace_sums'], dtype=np.float64).reshape(2))
+        if 'rows' in sd:
+            acc.blocks = list(torch.as_tensor(np.array(sd['rows'], dtype=np.float64).reshape(-1, cls.ROW_LEN)))
+        acc.n_means = int(sd['n_means']) if 'n_means' in sd else 1
+        acc.n_bad = torch.as_tensor(np.array(sd['n_bad'], dtype=np.int64).reshape(1))
+        acc.n_walkers = int(sd['n_walkers'])
+        return acc                          # reduced stays False: the loaded sums are this rank's contribution from here on
+
+    def save(self, path, results=True):
+        """One .npz of `state_dict()`; `results`: also the arrays and numbers of `stress()` (but its `parts`)."""
+        sd = self.state_dict()
+        if results:
+            r = self.stress()
+            sd.update({k: np.asarray(v, np.float64) for k, v in r.items() if k not in ('parts', 'n_walkers', 'n_bad')})
+        with open(path, 'wb') as f:
+            np.savez(f, **sd)
+
+    @classmethod
+    def load(cls, path):
+        """The accumulator saved at `path` as a fresh rank-local one without a network (see `from_state_dict`)."""
+        with np.load(path) as f:
+            return cls.from_state_dict({k: f[k] for k in f.files})
+
+
 # ------------------------------------------------------------------ total force on the primitive-cell atoms (csrc/ds_iongrad.h)
 def primitive_fold(sim_atoms, prim_atoms, prim_latvec):
     """-> (owner (As,) int: the primitive atom each ion of the simulation cell is an image of, scale = As / A).  `get_supercell`

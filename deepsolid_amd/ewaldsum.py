@@ -129,6 +129,43 @@ def ion_ion_forces(cell, ewald_gmax=EWALD_GMAX, tables=None):
     return F
 
 
+VOIGT = ((0, 0), (1, 1), (2, 2), (1, 2), (0, 2), (0, 1))      # the component order xx, yy, zz, yz, xz, xy of `ds_stress`
+
+
+def reciprocal_strain_weights(gpoints, gweight, alpha):
+    """(NG, 3, 3): d w_G / d eps_ab = w_G [-delta_ab + 2 G_a G_b (1 / G^2 + 1 / (4 alpha^2))] under G -> G (1 + eps)^-1,
+    V -> V (1 + tr eps) at fixed alpha."""
+    g2 = np.einsum('gk,gk->g', gpoints, gpoints)
+    f = 2.0 * (1.0 / g2 + 0.25 / alpha ** 2)
+    return gweight[:, None, None] * (f[:, None, None] * gpoints[:, :, None] * gpoints[:, None, :] - np.eye(3)[None])
+
+
+def ion_ion_stress(cell, ewald_gmax=EWALD_GMAX, tables=None):
+    """(3, 3) float64, symmetric, in Hartree: d E_ii / d eps_ab of the ion-ion Ewald energy `EwaldTables.ion_ion + ii_const` under a
+    homogeneous strain of the cell, with alpha, the integer G list and the minimal-image choice of every pair held fixed (DESIGN.md
+    section 23).  A constant of the geometry: the ion-ion part of the stress (`DeviceSystem.stress`), which is this over the volume.
+      real space:  pair a < b, v = mi(R_a - R_b) + D_s over the 27 cells:  Z_a Z_b f'(r) v_a v_b / r,
+                   f'(r) = -[erfc(alpha r)/r^2 + (2 alpha/sqrt pi) exp(-alpha^2 r^2)/r]
+      reciprocal:  sum_G dw_G |S_ion(G)|^2  (`reciprocal_strain_weights`; the phases G.R do not change)
+      constants:   d(ii_const) = -[(sum Z)^2 / 2] ijconst delta_ab  (the -alpha / sqrt pi of squareconst has no derivative)"""
+    from scipy.special import erfc
+    t = tables if tables is not None else EwaldTables(cell, ewald_gmax)
+    q, R, al = t.atom_charges, t.atom_coords, t.alpha
+    n = len(q)
+    out = np.zeros((3, 3))
+    shifts = np.stack(np.meshgrid(*[np.arange(-1, 2)] * 3, indexing='ij'), -1).reshape(-1, 3) @ t.latvec
+    for a in range(n):
+        for b in range(a + 1, n):
+            d = distance.minimal_image_host(t.latvec, t.dist_mode, R[a] - R[b])
+            v = d[None, :] + shifts
+            r = np.linalg.norm(v, axis=1)
+            h = -(erfc(al * r) / r ** 2 + 2 * al / np.sqrt(np.pi) * np.exp(-(al * r) ** 2) / r) / r
+            out += q[a] * q[b] * np.einsum('s,sa,sb->ab', h, v, v)
+    out += np.einsum('g,gab->ab', np.abs(t.ion_exp) ** 2, reciprocal_strain_weights(t.gpoints, t.gweight, al))
+    out -= 0.5 * t.i_sum ** 2 * t.ijconst * np.eye(3)
+    return 0.5 * (out + out.T)                     # (symmetric to the last bit, whatever order the contractions summed in)
+
+
 class EwaldSum(EwaldTables):
     """Reference-shaped class: ``energy(configs)`` -> (ee, ei, ii) on the GPU.
 

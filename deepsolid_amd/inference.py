@@ -221,6 +221,10 @@ def run_dmc(slog_net, logdet_net, params, data, simulation_cell, blocks, steps_p
         dmc.make_dmc_step(logdet_net, simulation_cell, tau, steps_per_block, pseudopotential=pseudopotential)      # (refuses it)
     if accumulators and (branch_every <= 0 or steps_per_block % branch_every != 0):
         raise ValueError('accumulators need blocks that end on a comb: steps_per_block must be a multiple of branch_every')
+    for acc in accumulators:
+        if getattr(acc, 'vmc_only', False):
+            raise ValueError(f'{type(acc).__name__} holds a covariance under |psi|^2 (the wave-function term of the stress): it is a VMC '
+                             'estimator, a mixed estimate of it is not the DMC value; use it with run_inference')
     system = logdet_net.apply.system
     scale = float(getattr(simulation_cell, 'scale', 1))
     batch = data.shape[0]

@@ -83,6 +83,33 @@ def get_supercell(cell, S, sym_type='minimal', nelec=None):
     return set_symmetry_lat(sc, sym_type)
 
 
+def strained(simulation_cell, klist, eps):
+    """The simulation cell and its k list under the homogeneous strain `eps` (symmetric 3 x 3), for the strain derivative of log psi
+    (`estimator.StressTensor(wavefunction_term=True)`): every lattice vector and atom position v -> v (1 + eps),
+    every reciprocal vector and k point k -> k (1 + eps)^-1, for the simulation cell and its primitive cell alike.  The supercell
+    matrix, the fractional coordinates of the atoms, the electron numbers and the twist (k . a for every lattice vector a) are
+    unchanged; the feature lattices AV / BV follow the reciprocal vectors.  -> (cell', klist')."""
+    F = np.eye(3) + np.asarray(eps, dtype=np.float64).reshape(3, 3)
+    if not np.allclose(F, F.T, rtol=0, atol=1e-15):
+        raise ValueError('strained: eps must be symmetric')
+    Finv = np.linalg.inv(F)
+
+    def one(cell):
+        atom = [(cell.atom_symbol(i), xyz @ F) for i, xyz in enumerate(np.asarray(cell.atom_coords(), dtype=np.float64))]
+        out = Cell(np.asarray(cell.lattice_vectors(), dtype=np.float64) @ F, atom, spin=cell.spin, nelec=cell.nelec,
+                   charge=getattr(cell, 'charge', 0))
+        if getattr(cell, 'BV', None) is not None:
+            out.BV = np.asarray(cell.BV, dtype=np.float64) @ Finv
+            out.AV = np.linalg.pinv(out.BV).T
+        return out
+    sim = one(simulation_cell)
+    prim = simulation_cell.original_cell
+    sim.original_cell = sim if prim is simulation_cell else one(prim)
+    sim.S = np.array(simulation_cell.S, dtype=np.float64)
+    sim.scale = simulation_cell.scale
+    return sim, [np.asarray(k, dtype=np.float64).reshape(-1, 3) @ Finv for k in klist]
+
+
 def make_klist(simulation_cell, twist=(0.0, 0.0, 0.0)):
     """Occupied k-point list per spin, shaped like ``hf.SCF.klist``
     (reference hf.py:61-62 for the twist shift, :99-104 for the grouping):

@@ -23,6 +23,12 @@ so both are the force only for an exact wave function (bias first order in its e
 --forces-total: the TOTAL force per atom of the primitive cell (zero-variance force + Pulay term), through
 deepsolid_amd.estimator.PrimitiveForces, written to forces_total.npz; one block per evaluation step, errors by reblocking the block
 series; honours --forces-cutoff; all-electron only: not with --ecp;
+--stress: the stress tensor and the pressure of the cell over the evaluation, through deepsolid_amd.estimator.StressTensor, written to
+stress.npz: the integrated-by-parts kinetic tensor plus the strain derivative of the Ewald sums over the volume, naive errors.  The
+change of psi with the cell at fixed parameters is NOT evaluated, so it is the stress only for an exact wave function; all-electron
+only: not with --ecp;
+--stress-total: the same with the wave-function term (StressTensor(wavefunction_term=True): twelve strained handles, twelve more
+forwards per evaluation step, one block per step, errors by reblocking), written to stress_total.npz;
 --ecp FILE.npz: add the semi-local pseudopotential saved in FILE.npz (deepsolid_amd.pseudopotential.SemiLocalECP.save, built for
 THIS cell) to the local energy of training and evaluation: the rows then carry its batch mean E_loc + E_nl.  The
 cell of this example is all-electron, so with a real potential the numbers mean nothing: the point is the call sequence);
@@ -96,6 +102,12 @@ if '--forces-cutoff' in sys.argv:
 if '--forces' in sys.argv:
     forces = True
     sys.argv.remove('--forces')
+stress_total = '--stress-total' in sys.argv
+if stress_total:
+    sys.argv.remove('--stress-total')
+stress = '--stress' in sys.argv
+if stress:
+    sys.argv.remove('--stress')
 dmc_blocks, dmc_tau = 0, 0.01
 if '--dmc-tau' in sys.argv:
     i = sys.argv.index('--dmc-tau')
@@ -120,6 +132,8 @@ if '--ecp' in sys.argv:
     del sys.argv[i:i + 2]
 if (forces or forces_total) and ecp_file is not None:
     sys.exit('--forces / --forces-total is all-electron only: the force terms of a pseudopotential are not implemented')
+if (stress or stress_total) and ecp_file is not None:
+    sys.exit('--stress / --stress-total is all-electron only: the strain derivative of a pseudopotential is not implemented')
 if dmc_pure is not None and dmc_blocks <= 0:
     sys.exit('--dmc-pure needs --dmc BLOCKS')
 if tmoves and (ecp_file is None or dmc_blocks <= 0):
@@ -168,6 +182,16 @@ if forces_total:
     from deepsolid_amd import estimator
     total_acc = estimator.PrimitiveForces(logdet, params, cutoff=force_cutoff)
     accumulators += (total_acc,)
+stress_acc = None
+if stress:
+    from deepsolid_amd import estimator
+    stress_acc = estimator.StressTensor(logdet, params)
+    accumulators += (stress_acc,)
+stress_total_acc = None
+if stress_total:
+    from deepsolid_amd import estimator
+    stress_total_acc = estimator.StressTensor(logdet, params, wavefunction_term=True)
+    accumulators += (stress_total_acc,)
 data, width, rows = inference.run_inference(slogdet, logdet, params, data, cell, iterations=10, burn_in=10, move_width=width,
                                             accumulators=accumulators, pseudopotential=ecp)
 if ecp is not None:
@@ -199,6 +223,24 @@ for acc in accumulators:
         for a in range(len(f['atoms'])):
             print('            %-2s total (%9.4f %9.4f %9.4f) +- (%.4f %.4f %.4f)   ZV (%9.4f %9.4f %9.4f)   Pulay (%9.4f %9.4f %9.4f) Ha/Bohr'
                   % ((prim.atom_symbol(a),) + tuple(f['total'][a]) + tuple(f['total_error'][a]) + tuple(f['zv'][a]) + tuple(f['pulay'][a])))
+        continue
+    if acc is stress_acc:
+        acc.save('stress.npz', results=True)
+        t = acc.stress()
+        print('stress:     V = %.3f Bohr^3, naive errors over %d walkers (%d left out); no wave-function term: exact only for an exact psi'
+              % (t['volume'], t['n_walkers'], t['n_bad']))
+        for a in range(3):
+            print('            (%10.6f %10.6f %10.6f) +- (%.6f %.6f %.6f) Ha/Bohr^3' % (tuple(t['sigma'][a]) + tuple(t['sigma_error'][a])))
+        print('            P = %.6f +- %.6f Ha/Bohr^3 = %.2f +- %.2f GPa' % (t['pressure'], t['pressure_error'], t['pressure_gpa'],
+                                                                           t['pressure_gpa_error']))
+        continue
+    if acc is stress_total_acc:
+        acc.save('stress_total.npz', results=True)
+        t = acc.stress()
+        print('total stress: %d blocks, %d walkers (%d left out), reblocked errors; with the wave-function term' % (t['n_blocks'], t['n_walkers'], t['n_bad']))
+        for a in range(3):
+            print('            (%10.6f %10.6f %10.6f) +- (%.6f %.6f %.6f) Ha/Bohr^3' % (tuple(t['sigma_total'][a]) + tuple(t['sigma_total_error'][a])))
+        print('            P = %.6f +- %.6f Ha/Bohr^3 = %.2f GPa' % (t['pressure_total'], t['pressure_total_error'], t['pressure_total_gpa']))
         continue
     if acc is momentum_acc:
         acc.save('momentum.npz', results=True)

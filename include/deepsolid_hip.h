@@ -519,6 +519,42 @@ int64_t ds_ion_forces_workspace_bytes(const ds_system* sys, int64_t B);
 int ds_ion_forces(ds_system* sys, const void* x, const void* drift, int64_t B, double r_c, const double* ion_ion, double* out_hf,
                   double* out_zv, double* sums, int64_t* n_bad, void* ws, int64_t ws_bytes, void* stream);
 
+/* Strain derivative of the energy of a batch of walkers (csrc/ds_stress.h): what the stress tensor and the
+ * pressure are made of.  The reference has no stress estimator: the conventions are this library's own.
+ *   Homogeneous strain eps (symmetric 3 x 3): every electron and ion position and every lattice vector v -> v (1 + eps), reciprocal
+ *   vectors G -> G (1 + eps)^-1, V -> V (1 + tr eps).  Held fixed: alpha, the integer list of G points above the weight cut-off, and
+ *   the minimal-image choice of every pair -- exactly what ds_ewald sums.  Per walker, as symmetric tensors in the component order
+ *   xx, yy, zz, yz, xz, xy, in Hartree (dE / d eps; the stress is the total over the cell volume, the pressure -tr / 3 of that):
+ *       kin_ab = -sum_i (Re d_ia Re d_ib + Im d_ia Im d_ib),  d = grad log psi: the integrated-by-parts kinetic tensor, -2 K_ab with
+ *                <tr K> = <T>; valid under periodic and twisted boundary conditions; its variance is NOT the zero variance of E_L
+ *       ee, ei = d E_ee / d eps_ab, d E_ei / d eps_ab of the Ewald expressions of ds_ewald: the real-space sums over the same pairs
+ *                and 27 images with q f'(r) v_a v_b / r, f'(r) = -[erfc(alpha r) / r^2 + (2 alpha / sqrt pi) exp(-alpha^2 r^2) / r]; the
+ *                reciprocal sums with dw_G = w_G [-delta_ab + 2 G_a G_b (1 / G^2 + 1 / (4 alpha^2))] at unchanged phases; and the
+ *                constants, d ijconst = -ijconst delta_ab.  They go as 1 / r at a nucleus, like the potential energy: finite variance
+ *       total  = kin + ee + ei + ion_ion
+ *   kin + Ewald is the strain derivative of the energy only for an exact psi: for a variational psi the energy also changes because
+ *   psi at fixed parameters changes with the cell; that term is not evaluated.  All-electron ions only: no pseudopotential term.
+ *   - x (B, 3N): device array of the system's dtype.  grad (B, 3N, 2) = (Re, Im) of grad log psi as ds_logpsi_grad writes out_grad,
+ *     the system's dtype; NULL leaves the kinetic row zero (total is then the Ewald part alone) and is refused with sums.  All
+ *     arithmetic is float64 for either dtype.
+ *   - ion_ion: 6 float64 on the device, optional: d E_ii / d eps, a constant of the geometry, added to the total row.
+ *   - out (B, 4, 6) float64, optional: the rows kin, ee, ei, total.
+ *   - sums: device float64 [2 x 4 x 6 + 1], ADDED to and never zeroed, optional: per row and component, at 2 (6 row + component),
+ *       [ sum, sum of squares ]  over the good walkers of the call, then their number.
+ *   - A walker with a non-finite coordinate, gradient or result is bad: NaN in all its outputs, left out of sums, counted in n_bad
+ *     (device (1,) int64, ADDED to; optional).
+ *   - ws: needed for sums only: at least one group of 256 walkers (256 x 24 + 49 doubles).
+ * Every addition is made in a fixed order (ds_stress.h): per thread its G points, pairs and electrons in order, the LDS tree over the
+ * 256 threads of a walker's workgroup, the same tree over the 256 walkers of a group, the groups in order onto sums.  Groups are cut
+ * at multiples of 256 walkers of the batch whatever the workspace, so the results are bit-identical from run to run and for ANY
+ * workspace size.  No floating-point atomics, no host synchronisation, no allocation.
+ * Refused with a ds_last_error message before any launch: a null handle or x, B < 1, nothing to write (out and sums both NULL), sums
+ * without grad, with sums a workspace below one group, and a kernel LDS layout above 64 KB (no handle the library creates reaches
+ * it: the layout without phase tables is 49.6 KB at the largest N = 128). */
+int64_t ds_stress_workspace_bytes(const ds_system* sys, int64_t B);
+int ds_stress(ds_system* sys, const void* x, const void* grad, int64_t B, const double* ion_ion, double* out, double* sums,
+              int64_t* n_bad, void* ws, int64_t ws_bytes, void* stream);
+
 /* Gradient of log psi in the ion positions, per walker (csrc/ds_iongrad.h): the primitive of the Pulay force
  *   F_a = sum_{s image of a} F^zv_s - 2 Re < conj(E_L - E) (O_a - <O_a>) >,   O_a = d log psi / d R_a = d log|psi| + i d arg psi,
  * which completes ds_ion_forces (estimator.PrimitiveForces).  E_L = ke + ewald is complex as ds_local_energy returns it: for a complex
