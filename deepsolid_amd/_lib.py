@@ -174,6 +174,10 @@ SIGNATURES = {
     'ds_hf_create': (C.c_int, [C.POINTER(HfDesc), C.POINTER(_VP)]),
     'ds_hf_destroy': (None, [_VP]),
     'ds_hf_orbitals': (C.c_int, [_VP, C.c_int, _VP, C.c_int64, _VP, _VP, _VP]),
+    'ds_hf_orbitals_at': (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_int64, _VP, _VP]),
+    'ds_obdm_workspace_bytes': (C.c_int64, [_VP, C.c_int64, C.c_int]),
+    'ds_obdm_accumulate': (C.c_int, [_VP, C.c_int, _VP, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                     C.c_int64, _VP]),
 }
 
 PROF_KINDS = ('features', 'm2_expand', 'two_layer', 'single_first', 'single_hidden', 'orbital', 'det_inverse',

@@ -1,4 +1,4 @@
-// ds_hf.h -- occupied Hartree-Fock crystalline orbitals of a Gaussian basis at a batch of walkers.
+// ds_hf.h -- Hartree-Fock crystalline orbitals of a Gaussian basis at a batch of walkers or at arbitrary points.
 //
 // Reference: DeepSolid/hf.py:106-153 (`eval_orbitals_pbc`, `eval_mos_pbc`, `eval_orb_mat`), which calls PySCF's
 // `PBCGTOval_sph` on the host.  Conventions:
@@ -16,6 +16,9 @@
 //   4. the 16 x nao AO tile goes back to LDS; lane o contracts it with the MO coefficients of orbital o over mu in index order,
 //      applies the wrap phase and stores one complex128.
 // No atomics, no cross-wave reduction: the bits of one electron's row depend on its position alone.
+// Steps 1-4 are the device function hf_orbital_row; k_hf_orbitals (the electrons of a batch of walkers: the spin follows from the
+// electron index), k_hf_orbitals_at (arbitrary points, the spin is an argument) and k_obdm_basis (ds_obdm.h) only say where the
+// point comes from and where the row goes.
 // Beyond 8 k points every k group is a workgroup of its own that evaluates the chi tiles again: the exponentials, which bound the
 // kernel at n_k = 8 (EXPERIMENTS.md), are paid ceil(n_k / 8) times per electron.
 #pragma once
@@ -57,22 +60,17 @@ constexpr double HF_D_XY = 1.0925484305920792;     // sqrt(15 / 4 pi)
 constexpr double HF_D_Z2 = 0.31539156525252005;    // sqrt(5 / 16 pi)
 constexpr double HF_D_X2Y2 = 0.54627421529603959;  // sqrt(15 / 16 pi)
 
-template <typename T, int NT, int CH>
-__global__ __launch_bounds__(64) void k_hf_orbitals(HfArgs A, const T* __restrict__ x, long long n_points,
-                                                    double* __restrict__ out_up, double* __restrict__ out_dn) {
+// The orbitals of spin `sp` at ONE point r (float64), by one wave: steps 1-4 of the head of the file for the k group `kg`.  Lane o
+// (o < orbitals of the spin, k point of o in the group) stores orbital o at row[2 o], row[2 o + 1].  Every kernel that evaluates
+// orbitals goes through this function, so a point's bits depend on (r, sp) alone, whichever kernel asks.
+template <int NT, int CH>
+__device__ __forceinline__ void hf_orbital_row(const HfArgs& A, const double r[3], int sp, int kg, double* __restrict__ row_out) {
     constexpr int LD = 16 * NT + 1;
     __shared__ double chi[CH * LD];
     const int lane = threadIdx.x;
-    const long long p = blockIdx.x;
-    if (p >= n_points) return;
-    const int N = A.n_up + A.n_dn;
-    const long long b = p / N;
-    const int e = (int)(p - b * N);
-    const int kg = blockIdx.y;
 
     // 1. wrap into the primitive cell
-    double r[3], rp[3], wr[3];
-    for (int c = 0; c < 3; ++c) r[c] = (double)x[p * 3 + c];
+    double rp[3], wr[3];
     wrap_point<double>(r, A.a, A.ainv, rp, wr);
 
     typedef Acc4<double>::type acc_t;
@@ -138,9 +136,7 @@ __global__ __launch_bounds__(64) void k_hf_orbitals(HfArgs A, const T* __restric
         for (int g = 0; g < 4; ++g) chi[acc_row<double>(lane, g) * LD + 16 * t + (lane & 15)] = acc[t][g];
     __syncthreads();
 
-    const int sp = e < A.n_up ? 0 : 1;
     const int ns = sp ? A.n_dn : A.n_up;
-    const int el = sp ? e - A.n_up : e;
     if (lane >= ns) return;
     const int k = A.orb_k[sp][lane];
     if ((k >> 3) != kg) return;
@@ -159,10 +155,36 @@ __global__ __launch_bounds__(64) void k_hf_orbitals(HfArgs A, const T* __restric
     const double ang = A.kpts[3 * k] * t3[0] + A.kpts[3 * k + 1] * t3[1] + A.kpts[3 * k + 2] * t3[2];
     double sn, cs;
     sincos(ang, &sn, &cs);
-    double* out = sp ? out_dn : out_up;
-    const long long o = 2 * ((b * ns + el) * (long long)ns + lane);
-    out[o] = ore * cs - oim * sn;
-    out[o + 1] = ore * sn + oim * cs;
+    row_out[2 * lane] = ore * cs - oim * sn;
+    row_out[2 * lane + 1] = ore * sn + oim * cs;
+}
+
+// out_s[b][electron of spin s][orbital of spin s] at the electrons of B walkers: the spin follows from the electron index
+template <typename T, int NT, int CH>
+__global__ __launch_bounds__(64) void k_hf_orbitals(HfArgs A, const T* __restrict__ x, long long n_points,
+                                                    double* __restrict__ out_up, double* __restrict__ out_dn) {
+    const long long p = blockIdx.x;
+    if (p >= n_points) return;
+    const int N = A.n_up + A.n_dn;
+    const long long b = p / N;
+    const int e = (int)(p - b * N);
+    const int sp = e < A.n_up ? 0 : 1;
+    const int ns = sp ? A.n_dn : A.n_up;
+    const int el = sp ? e - A.n_up : e;
+    double r[3];
+    for (int c = 0; c < 3; ++c) r[c] = (double)x[p * 3 + c];
+    hf_orbital_row<NT, CH>(A, r, sp, blockIdx.y, (sp ? out_dn : out_up) + 2 * ((b * ns + el) * (long long)ns));
+}
+
+// out[p][orbital of spin sp] at P arbitrary points (P, 3): the spin is the caller's
+template <typename T, int NT, int CH>
+__global__ __launch_bounds__(64) void k_hf_orbitals_at(HfArgs A, const T* __restrict__ pts, long long n_points, int sp,
+                                                       double* __restrict__ out) {
+    const long long p = blockIdx.x;
+    if (p >= n_points) return;
+    double r[3];
+    for (int c = 0; c < 3; ++c) r[c] = (double)pts[p * 3 + c];
+    hf_orbital_row<NT, CH>(A, r, sp, blockIdx.y, out + 2 * p * (long long)(sp ? A.n_dn : A.n_up));
 }
 
 }  // namespace ds

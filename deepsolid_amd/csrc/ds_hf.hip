@@ -1,6 +1,8 @@
-// ds_hf.hip -- host side of the Hartree-Fock orbital provider (ds_hf_create / ds_hf_destroy / ds_hf_orbitals); kernel: ds_hf.h
+// ds_hf.hip -- host side of the Hartree-Fock orbital provider (ds_hf_create / ds_hf_destroy / ds_hf_orbitals / ds_hf_orbitals_at;
+// kernels: ds_hf.h) and of the one-body density matrix in such a basis (ds_obdm_workspace_bytes / ds_obdm_accumulate; ds_obdm.h)
 #include "ds_base.h"
 #include "ds_hf.h"
+#include "ds_obdm.h"
 
 struct ds_hf {
     ds::HfArgs A;
@@ -37,6 +39,82 @@ void hf_dispatch(const ds_hf* h, const void* x, long long np, void* up, void* dn
         case 4: hf_launch<T, 4, 64>(h, x, np, up, dn, st); break;
         default: hf_launch<T, 8, 32>(h, x, np, up, dn, st); break;      // 32-image chunks keep the LDS tile at 33 KB
     }
+}
+
+template <typename T, int NT, int CH>
+void hf_at_launch(const ds_hf* h, const void* pts, long long np, int sp, void* out, hipStream_t st) {
+    hipLaunchKernelGGL((ds::k_hf_orbitals_at<T, NT, CH>), dim3((unsigned)np, (unsigned)h->n_kgroups), dim3(64), 0, st, h->A, (const T*)pts,
+                       np, sp, (double*)out);
+}
+
+template <typename T>
+void hf_at_dispatch(const ds_hf* h, const void* pts, long long np, int sp, void* out, hipStream_t st) {
+    switch (h->nt) {
+        case 1: hf_at_launch<T, 1, 64>(h, pts, np, sp, out, st); break;
+        case 2: hf_at_launch<T, 2, 64>(h, pts, np, sp, out, st); break;
+        case 4: hf_at_launch<T, 4, 64>(h, pts, np, sp, out, st); break;
+        default: hf_at_launch<T, 8, 32>(h, pts, np, sp, out, st); break;
+    }
+}
+
+// ------------------------------------------------------------------ one-body density matrix, ds_obdm.h
+// Workspace of ds_obdm_accumulate for chunks of ng groups of OBDM_GROUP samples, in float64.  Shared by all chunks: the call's
+// running sums (one partial row).  Per chunk: one partial row per group and the basis values at r_e and r' of every sample.
+struct ObdmWs { double *ACC, *PART, *PHI; };
+inline ObdmWs carve_obdm(Arena<double>& a, int Mb, int64_t ng) {
+    const size_t row = (size_t)ds::obdm_row(Mb);
+    ObdmWs w{};
+    w.ACC = a.take(row);
+    w.PART = a.take((size_t)ng * row);
+    w.PHI = a.take((size_t)ng * ds::OBDM_GROUP * 2 * 2 * (size_t)Mb);
+    return w;
+}
+inline int64_t obdm_bytes(int Mb, int64_t ng) {
+    return (int64_t)measure([&](Arena<double>& a) { carve_obdm(a, Mb, ng); }) * 8;
+}
+constexpr int64_t OBDM_MAX_GROUPS = 1 << 22;             // 2 n blocks of k_obdm_basis stay below 2^31
+constexpr int64_t OBDM_WS_BUDGET = 256LL << 20;          // what ds_obdm_workspace_bytes asks for at most (one group at least)
+
+template <typename T, int NT, int CH>
+void obdm_basis_launch(const ds_hf* h, const ds::ObdmArgs& O, const void* x, const void* shift, double* phi, hipStream_t st) {
+    hipLaunchKernelGGL((ds::k_obdm_basis<T, NT, CH>), dim3((unsigned)(2 * O.n), (unsigned)h->n_kgroups), dim3(64), 0, st, h->A, O,
+                       (const T*)x, (const T*)shift, phi);
+}
+
+template <typename T>
+int obdm_impl(ds_hf* h, const void* x, int64_t B, int N, int n_up, int M, int first, const void* ratio, const void* shift,
+              const double* weight, double* dm, double* ov, int64_t* n_bad, void* ws, int64_t ws_bytes, hipStream_t st) {
+    const int M_up = h->A.n_up, M_dn = h->A.n_dn, Mb = std::max(M_up, M_dn);
+    const int64_t total = B * (int64_t)M, groups_all = (total + ds::OBDM_GROUP - 1) / ds::OBDM_GROUP;
+    // the chunk length follows from the workspace: the largest number of groups whose layout fits
+    const int64_t fixed = obdm_bytes(Mb, 0), per = obdm_bytes(Mb, 1) - fixed;
+    const int64_t ng = std::min<int64_t>({(ws_bytes - fixed) / per, OBDM_MAX_GROUPS, groups_all});
+    if (!ws || ng < 1) return fail("workspace too small for ds_obdm_accumulate: %lld bytes < %lld for one group of %d samples",
+                                   (long long)(ws ? ws_bytes : 0), (long long)obdm_bytes(Mb, 1), ds::OBDM_GROUP);
+    Arena<double> a = arena_of<double>(ws, ws_bytes);
+    const ObdmWs w = carve_obdm(a, Mb, ng);
+    if (!a.ok) return carve_fail("one-body density matrix");
+    ds::ObdmArgs O;
+    O.M = M; O.N = N; O.n_up = n_up; O.first = first; O.Mb = Mb;
+    const long long row = ds::obdm_row(Mb);
+    const int64_t chunk = ng * ds::OBDM_GROUP;
+    for (int64_t g0 = 0; g0 < total; g0 += chunk) {
+        O.g0 = g0; O.n = std::min(chunk, total - g0);
+        const int64_t groups = (O.n + ds::OBDM_GROUP - 1) / ds::OBDM_GROUP;
+        switch (h->nt) {
+            case 1: obdm_basis_launch<T, 1, 64>(h, O, x, shift, w.PHI, st); break;
+            case 2: obdm_basis_launch<T, 2, 64>(h, O, x, shift, w.PHI, st); break;
+            case 4: obdm_basis_launch<T, 4, 64>(h, O, x, shift, w.PHI, st); break;
+            default: obdm_basis_launch<T, 8, 32>(h, O, x, shift, w.PHI, st); break;
+        }
+        hipLaunchKernelGGL((ds::k_obdm_accumulate<T>), dim3((unsigned)groups), dim3(64 * ds::OBDM_WAVES), 0, st, O, M_up, M_dn,
+                           (const T*)ratio, weight, (const double*)w.PHI, w.PART);
+        hipLaunchKernelGGL(ds::k_obdm_final, dim3((unsigned)((row + 255) / 256)), dim3(256), 0, st, (const double*)w.PART,
+                           (long long)groups, Mb, M_up, M_dn, g0 == 0 ? 1 : 0, g0 + chunk >= total ? 1 : 0, w.ACC, dm, ov,
+                           (long long*)n_bad);
+    }
+    HIP_OK(hipGetLastError());
+    return 0;
 }
 
 }  // namespace host
@@ -164,6 +242,46 @@ int ds_hf_orbitals(ds_hf* h, int dtype, const void* x, int64_t B, void* out_up, 
     DS_BY_DTYPE(dtype, hf_dispatch, h, x, np, out_up, out_dn, st);
     HIP_OK(hipGetLastError());
     return 0;
+}
+
+int ds_hf_orbitals_at(ds_hf* h, int spin, int dtype, const void* points, int64_t P, void* out, void* stream) {
+    if (!h) return fail("ds_hf_orbitals_at: null handle");
+    if (spin != 0 && spin != 1) return fail("ds_hf_orbitals_at: spin must be 0 or 1 (got %d)", spin);
+    if (dtype != 0 && dtype != 1) return fail("dtype must be 0 or 1");
+    if (P < 0) return fail("ds_hf_orbitals_at: P must be >= 0 (got %lld)", (long long)P);
+    if ((spin ? h->A.n_dn : h->A.n_up) == 0 || P == 0) return 0;
+    if (!points || !out) return fail("ds_hf_orbitals_at: null points or output");
+    if (P > 2147483647LL) return fail("ds_hf_orbitals_at: %lld points in one call; at most 2^31 - 1", (long long)P);
+    hipStream_t st = (hipStream_t)stream;
+    DS_BY_DTYPE(dtype, hf_at_dispatch, h, points, (long long)P, spin, out, st);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+int64_t ds_obdm_workspace_bytes(const ds_hf* h, int64_t B, int n_samples) {
+    if (!h || B < 1 || n_samples < 1) return -1;
+    const int Mb = std::max(h->A.n_up, h->A.n_dn);
+    const int64_t groups = (B * (int64_t)n_samples + ds::OBDM_GROUP - 1) / ds::OBDM_GROUP;
+    const int64_t fixed = obdm_bytes(Mb, 0), per = obdm_bytes(Mb, 1) - fixed;
+    return obdm_bytes(Mb, std::min<int64_t>({groups, OBDM_MAX_GROUPS, std::max<int64_t>(1, (OBDM_WS_BUDGET - fixed) / per)}));
+}
+
+int ds_obdm_accumulate(ds_hf* h, int dtype, const void* x, int64_t B, int n_elec, int n_up, int n_samples, int first_electron,
+                       const void* ratio, const void* shift, const double* weight, double* dm_sums, double* ov_sums, int64_t* n_bad,
+                       void* ws, int64_t ws_bytes, void* stream) {
+    if (!h || !x || !ratio || !shift) return fail("ds_obdm_accumulate: null basis, x, ratio or shift");
+    if (!dm_sums && !ov_sums) return fail("ds_obdm_accumulate: dm_sums and ov_sums are both null, nothing to write");
+    if (dtype != 0 && dtype != 1) return fail("ds_obdm_accumulate: dtype must be 0 or 1 (got %d)", dtype);
+    if (B < 1) return fail("ds_obdm_accumulate: B must be >= 1 (got %lld)", (long long)B);
+    if (n_samples < 1) return fail("ds_obdm_accumulate: n_samples must be >= 1 (got %d)", n_samples);
+    if (n_elec < 1) return fail("ds_obdm_accumulate: n_elec must be >= 1 (got %d)", n_elec);
+    if (n_up < 0 || n_up > n_elec) return fail("ds_obdm_accumulate: n_up must be in 0..%d (got %d)", n_elec, n_up);
+    if (first_electron < 0 || first_electron >= n_elec)
+        return fail("ds_obdm_accumulate: first_electron must be in 0..%d (got %d)", n_elec - 1, first_electron);
+    if (B > 2147483647LL / n_samples)
+        return fail("ds_obdm_accumulate: %lld x %d samples in one call; at most 2^31 - 1", (long long)B, n_samples);
+    return DS_BY_DTYPE(dtype, obdm_impl, h, x, B, n_elec, n_up, n_samples, first_electron, ratio, shift, weight, dm_sums, ov_sums, n_bad,
+                       ws, ws_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // ds_host.h -- what the host units of libdeepsolid_hip.so share (ds_api.hip, ds_chain.hip, ds_det.hip, ds_value.hip,
-// ds_gradpass.hip, ds_minsr.hip, ds_sample.hip, ds_dmc.hip, ds_observe.hip) on top of ds_base.h: the workspace arena, the handle, the workspace layouts of the
+// ds_gradpass.hip, ds_minsr.hip, ds_sample.hip, ds_dmc.hip, ds_observe.hip) on top of ds_base.h (error slot, workspace arena): the handle, the workspace layouts of the
 // two chains and the few functions that one unit calls in another.  Internal to the library.
 #pragma once
 #include "ds_base.h"
@@ -7,24 +7,6 @@
 
 namespace ds {
 namespace host {
-
-template <typename I> inline I rup(I x, int m) { return (x + m - 1) / m * m; }
-
-// A workspace as a stack of elements of T.  Every layout below is ONE function over an arena and serves both as the size of the
-// layout and as its pointers: with a base, take(n) hands out the next n elements (carve mode); with a null base it only counts
-// (measure mode: `used` is the extent).  An entry point checks `ok` after carving and before its first launch.
-template <typename T> struct Arena {
-    T* base = nullptr;
-    size_t cap = SIZE_MAX, used = 0;
-    bool ok = true;                                  // false once more was taken than `cap` -- here or in a part() of this arena
-    T* take(size_t n) { T* p = base ? base + used : nullptr; used += n; ok = ok && used <= cap; return p; }
-    void align(size_t k) { take((k - used % k) % k); }
-    // a buffer of n elements already handed out, carved up again (buffers that live inside an idle one); its overrun counts here
-    template <typename F> void part(T* buf, size_t n, F&& carve) { Arena a{buf, n}; carve(a); ok = ok && a.ok; }
-};
-template <typename T> Arena<T> arena_of(void* ws, int64_t ws_bytes) { return Arena<T>{(T*)ws, (size_t)std::max<int64_t>(ws_bytes, 0) / sizeof(T)}; }
-// extent, in elements, of a layout function
-template <typename F> size_t measure(F&& layout) { Arena<double> a; layout(a); return a.used; }
 
 // A pass over groups of PV walkers: elements shared by all groups and elements per group (measured from the pass's layout function)
 struct PassSize { size_t fixed, per_group; };
@@ -37,8 +19,6 @@ inline int64_t groups_per_pass(int64_t B, int64_t esz, const PassSize& z, int64_
 inline int64_t groups_that_fit(int64_t ws_bytes, int64_t esz, const PassSize& z) {
     return (ws_bytes / esz - (int64_t)z.fixed) / (int64_t)z.per_group;
 }
-
-inline int carve_fail(const char* what) { return fail("internal: %s: workspace carve exceeds its size", what); }
 
 // per-walker workspace carve, in elements
 struct WsLayout {

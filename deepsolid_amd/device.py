@@ -17,6 +17,7 @@ from . import _lib
 from .params import ParamMap
 
 _DTYPES = {torch.float64: 0, torch.float32: 1}
+OBDM_GROUP = 128        # ds::OBDM_GROUP of csrc/ds_obdm.h: samples per partial row of ds_obdm_accumulate (chunks are whole groups)
 
 
 def _pd(a):
@@ -1301,6 +1302,73 @@ class HfOrbitalTables:
                 _lib.check(self.lib.ds_hf_orbitals(self.handle, _DTYPES[x.dtype], _ptr(x), B, _ptr(outs[0] if self.nelec[0] else None),
                                                    _ptr(outs[1] if self.nelec[1] else None), _stream()), 'ds_hf_orbitals')
         return [torch.view_as_complex(o) for o in outs]
+
+    def _points_like(self, what, t, shape_tail):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == self.device):
+            raise RuntimeError(f'HfOrbitalTables.{what} must live on {self.device} (no CPU path)')
+        if t.dtype not in _DTYPES:
+            raise TypeError(f'HfOrbitalTables.{what} must be float64 or float32, got {t.dtype}')
+        if tuple(t.shape[t.dim() - len(shape_tail):]) != tuple(shape_tail) or t.dim() != len(shape_tail) + 1:
+            raise ValueError(f'HfOrbitalTables.{what} must have shape (*, {", ".join(str(v) for v in shape_tail)}), got {tuple(t.shape)}')
+        return t.contiguous()
+
+    def orbitals_at(self, points, spin):
+        """points (P, 3) float64 / float32 device tensor -> (P, M_spin) complex128: the orbitals of ONE spin at arbitrary points
+        (`ds_hf_orbitals_at`); at an electron's position the bits are those of `orbitals`.  A spin without orbitals gives (P, 0)."""
+        spin = int(spin)
+        if spin not in (0, 1):
+            raise ValueError(f'HfOrbitalTables.orbitals_at: spin must be 0 or 1, got {spin}')
+        points = self._points_like('orbitals_at: points', points, (3,))
+        P, ns = int(points.shape[0]), self.nelec[spin]
+        out = torch.empty(P, ns, 2, dtype=torch.float64, device=self.device)
+        if P and ns:
+            with torch.cuda.device(self.device):
+                _lib.check(self.lib.ds_hf_orbitals_at(self.handle, spin, _DTYPES[points.dtype], _ptr(points), P, _ptr(out), _stream()),
+                           'ds_hf_orbitals_at')
+        return torch.view_as_complex(out) if ns else torch.empty(P, 0, dtype=torch.complex128, device=self.device)
+
+    def obdm_accumulate(self, x, nelec, n_samples, first_electron, ratios, shifts, weights=None, dm_sums=None, ov_sums=None,
+                        max_bytes=None):
+        """`ds_obdm_accumulate`: fold the ratios q (B, M) complex (or (B, M, 2) real) and shifts (B, M, 3) that
+        `DeviceSystem.one_body_ratios(..., want_ratios=True, want_shifts=True)` exports for the walkers x (B, 3N), N = sum(nelec),
+        into the sums of the one-body density matrix in this basis (include/deepsolid_hip.h):
+            dm_sums[s][i][j] += w q conj(phi_i(r')) phi_j(r_e),      ov_sums[s][i][j] += w conj(phi_i(r')) phi_j(r').
+        x, ratios and shifts share one dtype (float64 or float32); `weights` (B, M) float64 or None (1).  `dm_sums` / `ov_sums`:
+        float64 device tensors (2, Mb, Mb, 2), Mb = max(M_up, M_dn), ADDED to (None: fresh zero ones).  `max_bytes` caps the
+        workspace: more chunks, bit-identical sums.  -> dict(dm_sums, ov_sums, n_bad (2,) int64 device tensor: samples left out
+        because q or the weight was not finite).  No host synchronisation."""
+        x = self._points_like('obdm_accumulate: walkers', x, (3 * (int(nelec[0]) + int(nelec[1])),))
+        B, M, N = int(x.shape[0]), int(n_samples), int(nelec[0]) + int(nelec[1])
+        if ratios.is_complex():
+            ratios = torch.view_as_real(ratios)
+        ratios = self._points_like('obdm_accumulate: ratios', ratios, (M, 2))
+        shifts = self._points_like('obdm_accumulate: shifts', shifts, (M, 3))
+        if ratios.dtype != x.dtype or shifts.dtype != x.dtype or ratios.shape[0] != B or shifts.shape[0] != B:
+            raise ValueError(f'obdm_accumulate: ratios ({B}, {M}, 2) and shifts ({B}, {M}, 3) must have the walkers\' dtype {x.dtype}')
+        if weights is not None:
+            if not (weights.is_cuda and weights.dtype == torch.float64 and tuple(weights.shape) == (B, M)):
+                raise ValueError(f'obdm_accumulate: weights must be a float64 device tensor of shape ({B}, {M})')
+            weights = weights.contiguous()
+        Mb = max(self.nelec)
+        sums = []
+        for name, t in (('dm_sums', dm_sums), ('ov_sums', ov_sums)):
+            if t is None:
+                t = torch.zeros(2, Mb, Mb, 2, dtype=torch.float64, device=self.device)
+            elif not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == (2, Mb, Mb, 2)):
+                raise ValueError(f'obdm_accumulate: {name} must be a contiguous float64 device tensor of shape (2, {Mb}, {Mb}, 2)')
+            sums.append(t)
+        n_bad = torch.zeros(2, dtype=torch.int64, device=self.device)
+        need = int(self.lib.ds_obdm_workspace_bytes(self.handle, B, M))
+        if need < 0:
+            raise ValueError(f'obdm_accumulate: B = {B} and n_samples = {M} must be >= 1')
+        if max_bytes is not None:
+            need = min(need, int(max_bytes))
+        ws = torch.empty(max(need, 8) // 8, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.ds_obdm_accumulate(self.handle, _DTYPES[x.dtype], _ptr(x), B, N, int(nelec[0]), M, int(first_electron),
+                                                   _ptr(ratios), _ptr(shifts), _ptr(weights), _ptr(sums[0]), _ptr(sums[1]),
+                                                   _ptr(n_bad), _ptr(ws), ws.numel() * 8, _stream()), 'ds_obdm_accumulate')
+        return dict(dm_sums=sums[0], ov_sums=sums[1], n_bad=n_bad)
 
 
 class EcpTables:

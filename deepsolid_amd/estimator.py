@@ -1443,3 +1443,238 @@ class PrimitiveForces:
         """The accumulator saved at `path` as a fresh one without a network (see `from_state_dict`)."""
         with np.load(path) as f:
             return cls.from_state_dict({k: f[k] for k in f.files})
+
+
+# ------------------------------------------------------------------ one-body density matrix (csrc/ds_obdm.h)
+# The reference has no such estimator; the conventions of this section are this project's own (DESIGN.md section 24).
+def _integer_matrix(m, what, tol=1e-8):
+    r = np.rint(m)
+    if not np.all(np.abs(m - r) <= tol):
+        raise ValueError(f'OneBodyDensityMatrix: {what} (largest distance from an integer {float(np.abs(m - r).max()):.3e})')
+    return r
+
+
+class OneBodyDensityMatrix:
+    """Spin-resolved one-body reduced density matrix of a network's wavefunction in a basis of crystalline orbitals, accumulated on
+    the device over any number of walker batches: an accumulator for `run_inference(accumulators=...)`.
+
+    `basis`: a `hf.GaussianOrbitals`; its columns per spin are the basis functions phi^s_i (M_s <= 64 of them, `basis.nelec` =
+    (M_up, M_dn)), not necessarily occupied or orthonormal and independent of the network's electron numbers.  With
+    chi = phi / sqrt(Omega_S / Omega_p), Omega_p = |det basis.a| (PySCF normalises an orbital over that cell),
+
+        n^s_ij = < sum_{e in s} int_{Omega_S} dr' chi_i*(r') chi_j(r_e) psi(.., r_e -> r', ..) / psi(R) >,
+        S^s_ij = int_{Omega_S} dr' chi_i*(r') chi_j(r').
+
+    Every `update` is ONE `ds_one_body_ratios` call that moves, per walker, `samples_per_walker` = M electrons in turn (default N)
+    by shifts uniform in the simulation cell and exports (q, s), and ONE `ds_obdm_accumulate` call that folds them with the basis
+    at r_e and r' into float64 sums; nothing is read back.  The Philox offset advances by 1 per update, `first_electron` by M mod
+    N, the seed is decorrelated over the ranks as in `MomentumDistribution`.  `net`: the object `make_solid_fermi_net` returns
+    (or its `.apply`).
+
+    Refused at construction (ValueError), since the integrand is periodic over the simulation cell only then: a simulation cell
+    that is not a superlattice of the basis's cell (`sim.a @ inv(basis.a)` integer to 1e-8), a basis k point that is not
+    Bloch-allowed ((k - k_t) . a_S / 2 pi integer to 1e-8, k_t the first `klist` entry), more than 64 basis functions per spin.
+
+    Limits: uniform r' has a large variance for core orbitals of all-electron ions (of order Omega_S over the orbital's volume) --
+    valence bands and pseudopotential cells are the use case; importance-sampled r' enters through `update(data, shifts=...,
+    weights=...)`.  No error bars (merge several accumulators).  Under `run_dmc` the result is the mixed estimate."""
+
+    MAX_ORB = 64
+
+    def __init__(self, net, params, basis, samples_per_walker=None, seed=0):
+        self.apply = getattr(net, 'apply', net)
+        self.params = params
+        self.basis = basis
+        cell = self.apply.simulation_cell
+        self._setup((int(cell.nelec[0]), int(cell.nelec[1])), cell.a, basis.a, basis.kpts, basis.nelec, samples_per_walker)
+        ratio = self.sim_a @ np.linalg.inv(self.basis_a)
+        _integer_matrix(ratio, 'the simulation cell is not a superlattice of the basis cell: sim.a @ inv(basis.a) is not an integer matrix')
+        kl = [np.asarray(k, dtype=np.float64).reshape(-1, 3) for k in self.apply.klist]
+        kt = np.concatenate(kl, axis=0)[0]
+        _integer_matrix((self.basis_kpts - kt[None, :]) @ self.sim_a.T / (2.0 * np.pi),
+                        'a basis k point is not Bloch-allowed: (k - k_t) . a_S / 2 pi is not an integer vector')
+        self.seed = (int(seed) * max(1, constants.world_size()) + constants.rank()) % (1 << 63)
+
+    def _setup(self, nelec, sim_a, basis_a, basis_kpts, norb, samples_per_walker):
+        self.nelec = (int(nelec[0]), int(nelec[1]))
+        self.sim_a = np.array(sim_a, dtype=np.float64).reshape(3, 3)
+        self.basis_a = np.array(basis_a, dtype=np.float64).reshape(3, 3)
+        self.basis_kpts = np.ascontiguousarray(np.asarray(basis_kpts, dtype=np.float64).reshape(-1, 3))
+        self.norb = (int(norb[0]), int(norb[1]))
+        if min(self.norb) < 0 or max(self.norb) < 1 or max(self.norb) > self.MAX_ORB:
+            raise ValueError(f'OneBodyDensityMatrix: {self.norb} basis functions per spin; 0..{self.MAX_ORB} (one at least) are supported')
+        n_el = sum(self.nelec)
+        self.samples_per_walker = n_el if samples_per_walker is None else int(samples_per_walker)
+        if self.samples_per_walker < 1:
+            raise ValueError(f'samples_per_walker = {samples_per_walker} must be >= 1')
+        mb = max(self.norb)
+        self.dm_sums = torch.zeros(2, mb, mb, 2, dtype=torch.float64)      # moved to the walkers' device by the first update
+        self.ov_sums = torch.zeros(2, mb, mb, 2, dtype=torch.float64)
+        self.n_bad = torch.zeros(2, dtype=torch.int64)
+        self.samples = np.zeros(2, dtype=np.int64)
+        self.offset = 0
+        self.first_electron = 0
+        self.seed = 0
+        self.reduced = False
+
+    # ---- accumulation
+    def update(self, data, shifts=None, weights=None):
+        """Add `samples_per_walker` samples of every walker of `data` (B, 3N) to the sums: two library calls, no device -> host
+        copy.  `shifts` (B, M, 3) replaces the uniform shifts by the caller's, drawn from a density p(s); `weights` (B, M) float64
+        then holds 1 / (Omega_S p(s)).  The samples per spin are counted on the host: they follow from first_electron alone."""
+        if self.apply is None:
+            raise RuntimeError('OneBodyDensityMatrix.update: a loaded accumulator has no network; merge it into one that has')
+        if self.reduced:
+            raise RuntimeError('OneBodyDensityMatrix.update after reduce(): the sums are already summed over the ranks')
+        n_el, m = sum(self.nelec), self.samples_per_walker
+        if data.shape[-1] != 3 * n_el:
+            raise ValueError(f'walkers have {data.shape[-1]} coordinates, the cell has {n_el} electrons')
+        x = data.reshape(-1, 3 * n_el)
+        sysd = self.apply.system
+        if self.dm_sums.device != x.device:
+            self.dm_sums, self.ov_sums, self.n_bad = self.dm_sums.to(x.device), self.ov_sums.to(x.device), self.n_bad.to(x.device)
+        out = sysd.one_body_ratios(self.params, x, m, first_electron=self.first_electron, seed=self.seed, offset=self.offset,
+                                   shifts=shifts, want_ratios=True, want_shifts=True)
+        if weights is not None:
+            weights = weights.to(device=x.device, dtype=torch.float64)
+        res = self.basis._device_tables(x.device).obdm_accumulate(x, self.nelec, m, self.first_electron, out['ratios'], out['shifts'],
+                                                                  weights=weights, dm_sums=self.dm_sums, ov_sums=self.ov_sums)
+        self.n_bad += res['n_bad']
+        up = int(np.count_nonzero((self.first_electron + np.arange(m)) % n_el < self.nelec[0]))
+        self.samples += np.asarray([up, m - up], dtype=np.int64) * int(x.shape[0])
+        self.offset += 1
+        self.first_electron = (self.first_electron + m) % n_el
+
+    def _same_setup(self, other):
+        """Electron numbers, both lattices, the basis's k points and its functions per spin.  (The orbital coefficients are not
+        part of the state: merging sums of two different bases on the same k points is the caller's error.)"""
+        return self.nelec == other.nelec and self.norb == other.norb and np.array_equal(self.sim_a, other.sim_a) and \
+            np.array_equal(self.basis_a, other.basis_a) and np.array_equal(self.basis_kpts, other.basis_kpts)
+
+    def merge(self, other):
+        """Add the sums, sample counts and bad counts of another accumulator of the same setup.  Both sides must be in the same
+        state (rank-local or summed over the ranks), as for `RealSpaceAccumulator.merge`."""
+        if not self._same_setup(other):
+            raise ValueError('OneBodyDensityMatrix.merge: the two accumulators differ in electron numbers, cells or basis')
+        if self.reduced != other.reduced and constants.world_size() > 1:
+            raise ValueError('OneBodyDensityMatrix.merge: one side is summed over the ranks and the other is rank-local')
+        self.dm_sums = self.dm_sums + other.dm_sums.to(self.dm_sums.device)
+        self.ov_sums = self.ov_sums + other.ov_sums.to(self.ov_sums.device)
+        self.n_bad = self.n_bad + other.n_bad.to(self.n_bad.device)
+        self.samples = self.samples + other.samples
+        return self
+
+    def reduce(self):
+        """Sum both sums, the bad counts and the sample counts over the ranks in ONE packed float64 all-reduce (counts below 2^53
+        are exact; the identity at world size 1).  Once per accumulator: a second call raises."""
+        if self.reduced:
+            raise RuntimeError('OneBodyDensityMatrix.reduce was already called: reducing twice would count every rank again')
+        if constants.world_size() > 1:
+            dev = self.dm_sums.device if self.dm_sums.is_cuda else torch.device('cuda' if torch.cuda.is_available() else 'cpu')
+            n = self.dm_sums.numel()
+            packed = torch.cat([self.dm_sums.reshape(-1).to(dev), self.ov_sums.reshape(-1).to(dev), self.n_bad.to(dev, torch.float64),
+                                torch.as_tensor(self.samples, dtype=torch.float64, device=dev)])
+            packed = constants.psum_if_pmap(packed)
+            self.dm_sums = packed[:n].reshape(self.dm_sums.shape).clone()
+            self.ov_sums = packed[n:2 * n].reshape(self.ov_sums.shape).clone()
+            self.n_bad = packed[2 * n:2 * n + 2].round().to(torch.int64)
+            self.samples = packed[2 * n + 2:2 * n + 4].round().cpu().numpy().astype(np.int64)
+        self.reduced = True                 # only now: a collective that raised leaves the accumulator as it was
+        return self
+
+    # ---- normalisation (host)
+    def _normalised(self, sums, electrons):
+        s = sums.detach().cpu().numpy()
+        good = self.samples - self.n_bad.detach().cpu().numpy()
+        omega_p = abs(np.linalg.det(self.basis_a))
+        out = []
+        for sp in range(2):
+            m = self.norb[sp]
+            z = s[sp, :m, :m, 0] + 1j * s[sp, :m, :m, 1]
+            scale = (self.nelec[sp] if electrons else 1.0) * omega_p
+            out.append(scale * z / good[sp] if good[sp] > 0 else (np.zeros((m, m), np.complex128) if electrons and self.nelec[sp] == 0
+                                                                   else np.full((m, m), np.nan, np.complex128)))
+        return tuple(out)
+
+    def density_matrix(self):
+        """(n^up (M_up, M_up), n^dn (M_dn, M_dn)) complex128: n^s = N_s Omega_p dm_sums[s] / (samples on s - bad samples on s).
+        A spin without electrons is 0, one without good samples NaN."""
+        return self._normalised(self.dm_sums, True)
+
+    def overlap(self):
+        """(S^up, S^dn) complex128: S^s = Omega_p ov_sums[s] / (samples on s - bad samples on s), the sampled overlap of the basis
+        over the simulation cell in the normalisation of `density_matrix`; NaN for a spin without good samples."""
+        return self._normalised(self.ov_sums, False)
+
+    def natural_orbitals(self, spin, overlap='sampled'):
+        """-> (occupations (M,) descending, c (M, M)): the generalised Hermitian eigenproblem D c = S c diag(occ) with
+        D = (n + n^dagger) / 2 and S = (S + S^dagger) / 2 of `overlap()` ('sampled') or the unit matrix ('identity': for a basis
+        known to be orthonormal over its cell).  Column a of c holds the coefficients of natural orbital a in the basis functions;
+        c^dagger S c = 1."""
+        if overlap not in ('sampled', 'identity'):
+            raise ValueError(f"overlap must be 'sampled' or 'identity', got {overlap!r}")
+        n = self.density_matrix()[int(spin)]
+        d = 0.5 * (n + n.conj().T)
+        if overlap == 'identity':
+            s = np.eye(d.shape[0], dtype=np.complex128)
+        else:
+            s = self.overlap()[int(spin)]
+            s = 0.5 * (s + s.conj().T)
+        low = np.linalg.cholesky(s)                                       # S = L L^dagger (raises if S is not positive definite)
+        linv = np.linalg.inv(low)
+        occ, v = np.linalg.eigh(linv @ d @ linv.conj().T)
+        order = np.argsort(occ)[::-1]
+        return occ[order], (linv.conj().T @ v)[:, order]
+
+    # ---- persistence
+    def state_dict(self):
+        """Plain numpy arrays: the sums and counts, the setup they belong to and where the noise stream stands."""
+        return {'dm_sums': self.dm_sums.detach().cpu().numpy().copy(), 'ov_sums': self.ov_sums.detach().cpu().numpy().copy(),
+                'samples': self.samples.copy(), 'n_bad': self.n_bad.detach().cpu().numpy().copy(),
+                'nelec': np.asarray(self.nelec, np.int64), 'simulation_lattice': self.sim_a.copy(), 'basis_lattice': self.basis_a.copy(),
+                'basis_kpts': self.basis_kpts.copy(), 'basis_norb': np.asarray(self.norb, np.int64),
+                'samples_per_walker': np.int64(self.samples_per_walker), 'offset': np.int64(self.offset),
+                'first_electron': np.int64(self.first_electron), 'reduced': np.bool_(self.reduced)}
+
+    def load_state_dict(self, sd):
+        """Replace the sums, counts and stream position by those of `sd` (same setup); the accumulator is rank-local and open for
+        `update` afterwards."""
+        other = OneBodyDensityMatrix.from_state_dict(sd)
+        if not self._same_setup(other):
+            raise ValueError('OneBodyDensityMatrix.load_state_dict: the state belongs to other electron numbers, cells or basis')
+        dev = self.dm_sums.device
+        self.dm_sums, self.ov_sums, self.n_bad = other.dm_sums.to(dev), other.ov_sums.to(dev), other.n_bad.to(dev)
+        self.samples = other.samples
+        self.offset, self.first_electron, self.reduced = other.offset, other.first_electron, False
+        return self
+
+    @classmethod
+    def from_state_dict(cls, sd):
+        """An accumulator without a network or basis: it can be merged, normalised and saved, not updated."""
+        acc = cls.__new__(cls)
+        acc.apply = acc.params = acc.basis = None
+        acc._setup(sd['nelec'], sd['simulation_lattice'], sd['basis_lattice'], sd['basis_kpts'], sd['basis_norb'],
+                   int(sd['samples_per_walker']) if 'samples_per_walker' in sd else None)
+        mb = max(acc.norb)
+        acc.dm_sums = torch.as_tensor(np.array(sd['dm_sums'], dtype=np.float64).reshape(2, mb, mb, 2))
+        acc.ov_sums = torch.as_tensor(np.array(sd['ov_sums'], dtype=np.float64).reshape(2, mb, mb, 2))
+        acc.n_bad = torch.as_tensor(np.array(sd['n_bad'], dtype=np.int64).reshape(2))
+        acc.samples = np.array(sd['samples'], dtype=np.int64).reshape(2)
+        acc.offset = int(sd['offset']) if 'offset' in sd else 0
+        acc.first_electron = int(sd['first_electron']) if 'first_electron' in sd else 0
+        return acc                          # reduced stays False: the loaded sums are this rank's contribution from here on
+
+    def save(self, path, results=True):
+        """One .npz of `state_dict()`; `results`: also `dm_up`, `dm_dn`, `overlap_up`, `overlap_dn`, the normalised matrices."""
+        sd = self.state_dict()
+        if results:
+            sd['dm_up'], sd['dm_dn'] = self.density_matrix()
+            sd['overlap_up'], sd['overlap_dn'] = self.overlap()
+        with open(path, 'wb') as f:
+            np.savez(f, **sd)
+
+    @classmethod
+    def load(cls, path):
+        """The accumulator saved at `path` as a fresh rank-local one without a network (see `from_state_dict`)."""
+        with np.load(path) as f:
+            return cls.from_state_dict({k: f[k] for k in f.files})

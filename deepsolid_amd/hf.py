@@ -255,6 +255,26 @@ class GaussianOrbitals:
             return [torch.from_numpy(m) for m in self._orb_mat_host(x.detach().to(torch.float64).numpy())]
         return self._orb_mat_host(np.asarray(x, dtype=np.float64))
 
+    def eval_orbitals_at(self, points, spin):
+        """The orbitals of ONE spin at arbitrary points: points (P, 3) -> (P, M_spin) complex128, [point, orbital], columns in
+        the order of `eval_orb_mat`.  A device tensor (float64 or float32) is evaluated by the HIP kernel (`ds_hf_orbitals_at`)
+        and stays on the device; a numpy array (or a host tensor) gives `eval_aos_host @ mo_coeff`, as a numpy array (host
+        tensor)."""
+        spin = int(spin)
+        if spin not in (0, 1):
+            raise ValueError(f'spin must be 0 or 1, got {spin}')
+        if len(points.shape) != 2 or points.shape[1] != 3:
+            raise ValueError(f'points must be (P, 3), got {tuple(points.shape)}')
+        if isinstance(points, torch.Tensor) and points.is_cuda:
+            if points.dtype not in (torch.float64, torch.float32):
+                points = points.to(torch.float64)
+            return self._device_tables(points.device).orbitals_at(points, spin)
+        host = isinstance(points, torch.Tensor)
+        r = points.detach().to(torch.float64).numpy() if host else np.asarray(points, dtype=np.float64)
+        ao = self.eval_aos_host(r)                                                         # (n_k, P, nao)
+        out = np.concatenate([ao[k] @ c for k, c in enumerate(self.mo_coeff[spin])], axis=-1).reshape(r.shape[0], self.nelec[spin])
+        return torch.from_numpy(out) if host else out
+
     def eval_slogdet(self, x):
         """hf.py:155-165: (phase, log|det|) of the product of the spin determinants, where `x` lives."""
         mats = [m for m in self.eval_orb_mat(x) if m.shape[-1] > 0]

@@ -14,6 +14,8 @@ move the pretraining walkers on the network's density or on the Hartree-Fock den
 deepsolid_amd.estimator.RealSpaceAccumulator, written to realspace.npz in the working directory;
 --momentum SHELLS: the spin-resolved momentum distribution n(k) on the (2 SHELLS + 1)^3 Bloch-allowed k points around the twist,
 through deepsolid_amd.estimator.MomentumDistribution, written to momentum.npz;
+--obdm: with --hf, the spin-resolved one-body density matrix in the basis of the file's orbitals and its natural occupation numbers,
+through deepsolid_amd.estimator.OneBodyDensityMatrix, written to obdm.npz;
 --spin-squared [PAIRS]: the total spin <S^2> from PAIRS spin-exchange ratios per walker and evaluation step (default: all
 n_up n_dn pairs), through deepsolid_amd.estimator.SpinSquared, written to spin_squared.npz;
 --forces: the forces on the two ions over the evaluation, through deepsolid_amd.estimator.IonForces, written to forces.npz: the
@@ -83,6 +85,11 @@ if '--momentum' in sys.argv:
     i = sys.argv.index('--momentum')
     momentum_shells = int(sys.argv[i + 1])
     del sys.argv[i:i + 2]
+obdm = '--obdm' in sys.argv
+if obdm:
+    sys.argv.remove('--obdm')
+    if scf_approx is None:
+        sys.exit('--obdm needs --hf FILE.npz: the orbitals of the file are the basis of the density matrix')
 spin_squared, spin_pairs = False, None
 if '--spin-squared' in sys.argv:
     i = sys.argv.index('--spin-squared')
@@ -167,6 +174,11 @@ if momentum_shells is not None:
     from deepsolid_amd import estimator
     accumulators += (estimator.MomentumDistribution(logdet, params, shells=momentum_shells),)
 momentum_acc = accumulators[-1] if momentum_shells is not None else None
+obdm_acc = None
+if obdm:
+    from deepsolid_amd import estimator
+    obdm_acc = estimator.OneBodyDensityMatrix(logdet, params, scf_approx)
+    accumulators += (obdm_acc,)
 spin_acc = None
 if spin_squared:
     from deepsolid_amd import estimator
@@ -241,6 +253,16 @@ for acc in accumulators:
         for a in range(3):
             print('            (%10.6f %10.6f %10.6f) +- (%.6f %.6f %.6f) Ha/Bohr^3' % (tuple(t['sigma_total'][a]) + tuple(t['sigma_total_error'][a])))
         print('            P = %.6f +- %.6f Ha/Bohr^3 = %.2f GPa' % (t['pressure_total'], t['pressure_total_error'], t['pressure_total_gpa']))
+        continue
+    if acc is obdm_acc:
+        acc.save('obdm.npz', results=True)
+        print('1-RDM:      %d / %d basis functions, %d / %d samples (%d / %d left out); no error bars'
+              % (acc.norb + tuple(acc.samples) + (int(acc.n_bad[0]), int(acc.n_bad[1]))))
+        for sp, name in enumerate(('up', 'down')):
+            if acc.norb[sp] and acc.nelec[sp]:
+                occ = acc.natural_orbitals(sp)[0]
+                print('            natural occupations %-4s (sampled overlap): %s   sum = %.4f of %d electrons'
+                      % (name, ' '.join('%.4f' % v for v in occ), occ.sum(), acc.nelec[sp]))
         continue
     if acc is momentum_acc:
         acc.save('momentum.npz', results=True)

@@ -1047,6 +1047,75 @@ void ds_hf_destroy(ds_hf* hf);
  * Needs no workspace; no atomics and a fixed summation order: a walker's rows have the same bits wherever it sits in the batch.
  * A chunk of 64 images (32 beyond 64 AOs) is skipped when alpha_min |d|^2 > 90 for each of its images and every atom. */
 int ds_hf_orbitals(ds_hf* hf, int dtype, const void* x, int64_t B, void* out_up, void* out_dn, void* stream);
+/* The orbitals of ONE spin at arbitrary points: points (P, 3) device array of `dtype`, out (P, M_spin) complex128 [point, orbital].
+ * The same computation as ds_hf_orbitals, by the same device function (wrap into the primitive cell, wrap phase, image sum on
+ * v_mfma_f64_16x16x4_f64, contraction with the MO columns in index order); only the spin is the argument's instead of derived from
+ * an electron index: for an electron's position the bits are those ds_hf_orbitals returns for it.  M_spin == 0 or P == 0 returns 0
+ * and launches nothing.  At most 2^31 - 1 points per call. */
+int ds_hf_orbitals_at(ds_hf* hf, int spin, int dtype, const void* points, int64_t P, void* out, void* stream);
+
+/* One-body reduced density matrix (1-RDM) in a basis of crystalline orbitals, folded from the ratios and shifts that
+ * ds_one_body_ratios exports (csrc/ds_obdm.h); needs no ds_system.  The reference has no such estimator: the
+ * conventions are this library's own.
+ *
+ * A basis is a ds_hf (a `hf.GaussianOrbitals` object).
+ *   - Its columns per spin are the basis functions phi^s_i, i < M_s <= 64.
+ *   - They need not be occupied or orthonormal.  Its `nelec` is simply (M_up, M_dn).
+ *   - It is independent of the electron numbers of the network.
+ *   - PySCF normalises an orbital to 1 over the basis's primitive cell, volume Omega_p = |det a|.
+ *
+ * For spin s:
+ *     n^s_ij = < sum_{e in s} int_{Omega_S} dr' chi_i*(r') chi_j(r_e) psi(..., r_e -> r', ...)/psi(R) >_{|psi|^2},
+ *                                                                                       chi = phi / sqrt(Omega_S/Omega_p)
+ *     S^s_ij = int_{Omega_S} dr' chi_i*(r') chi_j(r')
+ * Here r' = r_e + s, and s is uniform in the simulation cell Omega_S, as drawn by ds_one_body_ratios.
+ *
+ * One sample (w, m) moves electron e = (first_electron + m) % N of walker w.  Its spin is s(e) = 0 if e < n_up, else 1.  With an
+ * optional weight w_s (default 1) it adds:
+ *     dm_sums[s][i][j] += w_s q conj(phi^s_i(r')) phi^s_j(r_e)
+ *     ov_sums[s][i][j] += w_s   conj(phi^s_i(r')) phi^s_j(r')
+ * The weight is 1/(Omega_S p(s)) for a caller who supplies shifts from another proposal density p.
+ *
+ * Host normalisation, with the same sample counting as the momentum distribution:
+ *   - n^s = N_s Omega_p dm_sums[s] / good_s
+ *   - S^s = Omega_p ov_sums[s] / good_s
+ *   - good_s = samples on s - bad_s
+ * With phi_k = e^{ik.r}/sqrt(Omega_p) this reduces to n_s(k) of section 16.
+ *
+ * A sample whose q or weight is not finite is left out of both sums and counted per spin.
+ *
+ * The integrand is periodic over Omega_S only under two conditions (checked by `estimator.OneBodyDensityMatrix`, not here):
+ *   - the simulation cell is a superlattice of the basis's cell, so sim.a @ inv(basis.a) is an integer matrix;
+ *   - every basis k point is Bloch-allowed, so (k - k_t).a_S/2pi is an integer vector for the network's k_t.
+ *
+ * Arguments: x (B, 3N); ratio (B, M, 2) and shift (B, M, 3) exactly as ds_one_body_ratios writes them; x, ratio and shift of `dtype`
+ * (0 = f64, 1 = f32); weight (B, M) float64 or NULL; dm_sums and ov_sums (2, Mb, Mb, 2) float64 with Mb = max(M_up, M_dn), ADDED to
+ * and never zeroed, either one may be NULL, not both; rows and columns >= M_s are not touched; n_bad (2,) int64, added to, optional.
+ * r_e is the walker's coordinate widened to float64; r' is formed as (T)((double)r_e + (double)shift) in the type T of `dtype` --
+ * the expression and type in which ds_one_body_ratios forms the displaced coordinate -- and then widened: the basis is evaluated
+ * where the network was.  (In float32 the exported shift is the drawn float64 shift rounded once, so r' can differ from the
+ * network's by one float32 rounding; a float32 caller who needs the identical point replays the exported shifts in both calls.)
+ *
+ * Per chunk of samples: (1) the basis of spin s(e) at r_e and at r' into the workspace, through the device function of
+ * ds_hf_orbitals_at; (2) k_obdm_accumulate: one workgroup per fixed group of 128 consecutive global sample indices contracts, on
+ * the f64 MFMA and per spin, the rows [Re; Im] of conj phi(r') against the columns of w_s q phi(r_e) (and of w_s phi(r')) staged
+ * through LDS -- a sample of the other spin or a bad one is an exact zero -- and writes one partial row; (3) a second kernel adds the
+ * rows in row order to a running sum and after the last chunk adds that to the caller's buffers.  No floating-point atomics, no
+ * host synchronisation, no allocation.  The sums are bit-identical from run to run and for ANY ws_bytes: chunks are whole groups,
+ * a smaller workspace means more chunks; below one group the call is an error.  A second call on the same buffers doubles them
+ * exactly.  ds_obdm_workspace_bytes: room for every group of the call, at most 256 MiB (one group at least); -1 for a null basis,
+ * B < 1 or n_samples < 1.
+ *
+ * Refused before any launch: a null basis, x, ratio or shift; both sums NULL; B < 1; n_samples < 1; n_elec < 1; n_up outside
+ * 0..n_elec; first_electron outside 0..n_elec-1; dtype not 0 or 1; more than 2^31 - 1 samples.  A spin that has electrons but no
+ * basis functions contributes nothing and is not counted as bad.
+ *
+ * Limits: uniform r' has a large variance for core orbitals of all-electron ions (of order Omega_S over the orbital's volume);
+ * valence bands and pseudopotential cells are the use case.  No error bars.  <= 64 basis functions per spin, <= 128 AOs, l <= 2. */
+int64_t ds_obdm_workspace_bytes(const ds_hf* basis, int64_t B, int n_samples);
+int ds_obdm_accumulate(ds_hf* basis, int dtype, const void* x, int64_t B, int n_elec, int n_up, int n_samples, int first_electron,
+                       const void* ratio, const void* shift, const double* weight, double* dm_sums, double* ov_sums, int64_t* n_bad,
+                       void* ws, int64_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
