@@ -63,6 +63,7 @@ struct ds_system {
     void* lr_w0t = nullptr;           // transposed / padded layer-0 weights of that kernel, refilled from the parameters at every call
     int64_t val_i8_min_tiles = 512;   // (group, electron) tiles from which they do: two per CU (DS_I8_VAL_MIN_TILES overrides: measurements)
     bool use_i8_val = true;           // DS_NO_I8_VAL unset: the value chain's residual hidden layers run as the int8 split too (large batches)
+    int val_i8_call = 0;              // 0: a launch of the value chain decides by its own tiles; +1 / -1: the call has decided for all of its launches (ValI8Call)
     bool use_pair_fuse = true;        // DS_NO_PAIR_FUSE unset: a log-psi forward runs all pair layers in one launch (k_pair_stream_val, ds_value.h)
     bool use_ldsb = true;             // DS_NO_LDSB unset: float32 cells with more than 10 slot tiles run the orbital head with LDS-staged jet rows (ds_ldsb.h)
     bool use_i8 = false;              // DS_I8=1: dense hidden layers of the 5-slot-tile float64 cells run their per-electron contraction as a 47-bit int8 split (ds_i8.h); default since round 6: float64 MFMA (the split measured 17.0-17.7 ms against 19.6 at 13 x the energy error)
@@ -180,6 +181,20 @@ ValBufs<T> carve_value(const ds_system* s, Arena<T>& a, int64_t ng) {
     b.MINV = nullptr;
     return b;
 }
+
+// A pass whose result is promised to be the same bits for any workspace size runs its value chain in launches whose size the workspace
+// decides, and a launch of 512 or more (group, electron) tiles takes the int8 split of the residual hidden layers (ds_value.hip), which
+// agrees with the float64 kernels to 1e-12, not to the bit.  Such a pass decides once, from the configurations of the whole call:
+// every launch inside the scope, the forward of the undisplaced walkers included, takes the same kernels.
+struct ValI8Call {
+    ds_system* s;
+    ValI8Call(ds_system* s_, int64_t n_elec, int64_t configurations) : s(s_) {
+        s->val_i8_call = n_elec * ((configurations + ds::PV - 1) / ds::PV) >= s->val_i8_min_tiles ? 1 : -1;
+    }
+    ~ValI8Call() { s->val_i8_call = 0; }
+    ValI8Call(const ValI8Call&) = delete;
+    ValI8Call& operator=(const ValI8Call&) = delete;
+};
 
 // ---------------------------------------------------------------- the workspace of the pseudopotential energy (ds_sample.hip, ds_dmc.hip)
 // groups of PV configurations per chunk of the passes that walk configurations: a chunk has at most 65535 of them

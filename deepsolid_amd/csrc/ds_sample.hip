@@ -122,6 +122,7 @@ int one_body_impl(ds_system* s, const void* params, const void* x_, int64_t B, i
     Arena<T> a = arena_of<T>(ws, ws_bytes);
     const OneBodyWs<T> w = carve_onebody<T>(s, a, B, ng);
     if (!a.ok) return carve_fail("one-body ratios");
+    const ValI8Call one_path(s, S.N, total);         // (the same value-chain kernels whatever the chunks are)
     if (int rc = logpsi_forward(s, params, x, B, w.LA0, w.PH0, w.wsv, w.wsv_bytes, st)) return rc;
     ds::OneBodyArgs A;
     for (int i = 0; i < 9; ++i) A.a[i] = s->d.sim_a[i];
@@ -186,6 +187,7 @@ int spin_exchange_impl(ds_system* s, const void* params, const void* x_, int64_t
     Arena<T> a = arena_of<T>(ws, ws_bytes);
     const SpinWs<T> w = carve_spin<T>(s, a, B, M, ng);
     if (!a.ok) return carve_fail("spin-exchange ratios");
+    const ValI8Call one_path(s, S.N, total);         // (the same value-chain kernels whatever the chunks are)
     if (int rc = logpsi_forward(s, params, x, B, w.LA0, w.PH0, w.wsv, w.wsv_bytes, st)) return rc;
     ds::SpinArgs A;
     A.M = M; A.N = S.N; A.n_up = S.n_up; A.n_dn = S.n_dn; A.first = first;
@@ -242,6 +244,7 @@ int ecp_energy_impl(ds_system* s, const ds_ecp* e, const void* params, const voi
         return fail("ds_ecp_energy: pair capacity exceeded: the walkers have %lld pairs inside the non-local cutoffs, pair_capacity is %lld",
                     pairs, (long long)cap);
     const int64_t total = pairs * nq;
+    const ValI8Call one_path(s, S.N, total);         // (the same value-chain kernels whatever the chunks are)
     if (total > 0)
         if (int rc = logpsi_forward(s, params, x, B, w.LA0, w.PH0, w.wsv, w.wsv_bytes, st)) return rc;
     ds::EcpChunk A;

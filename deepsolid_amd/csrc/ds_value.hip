@@ -167,7 +167,8 @@ int run_value_chain(ds_system* s, const T* params, const T* x, int64_t Bc, const
         // residual hidden layers of the 256-feature networks with enough (group, electron) tiles to give every CU's persistent workgroup
         // two or more: the int8 split of the forward-Laplacian chain (ds_i8.h) with the value epilogue -- 43 us per tile against the
         // float64 MFMA kernel's 73 (the float64 MFMA shares the FP64 datapath with the tanh polynomials, the int8 MFMA does not)
-        if (sizeof(T) == 8 && int8_value_layer(s, l) && (int64_t)S.N * ng >= (int64_t)s->val_i8_min_tiles) {
+        const bool i8_tiles = s->val_i8_call ? s->val_i8_call > 0 : (int64_t)S.N * ng >= (int64_t)s->val_i8_min_tiles;
+        if (sizeof(T) == 8 && int8_value_layer(s, l) && i8_tiles) {
             launch_layer_i8(s, l, true, (const double*)blk(s->i_wloc[l]), Kloc, Nout, (const double*)Gin, gts, (const double*)ZB, (double*)Gout,
                                   (int)(S.N * ng), st);
         } else if (s->res1[l] && !res_sep) {

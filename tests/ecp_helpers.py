@@ -181,10 +181,7 @@ def oracle_ratios(o, x, xd, w):
     exp(log psi(R') - log psi(R)) with the complex eval_logdet; configuration c belongs to walker w[c]."""
     if len(xd) == 0:
         return np.zeros(0, dtype=np.complex128)
-    with o._ctx(), torch.no_grad():
-        f = torch.func.vmap(lambda y: o.ld.apply(o.p, y))
-        l0 = f(o._x(np.asarray(x, dtype=np.float64)))
-        l1 = f(o._x(xd))
+    l0, l1 = o.logdet(x), o.logdet(xd)
     return np.exp((l1 - l0[torch.as_tensor(w)]).to(torch.complex128).numpy())
 
 
@@ -217,6 +214,14 @@ CASES = {
     'li_polarized': (2.2895, [0, 1, 2]),
     'lih_fulldet': (2.18, [2, 2, 2]),
 }
+# The large cells, on their first two fixture walkers (the oracle costs 4-23 ms per configuration there); kept apart from CASES,
+# which the tests of the small cells walk with every fixture walker.  Half the smallest height is 3.89 Bohr (diamond) and 6.87
+# (bcc_li_333); the nearest distance to a cutoff is 2.2e-3 and 4.7e-3 Bohr.
+LARGE_CASES = {
+    'diamond': (1.2, [17, 18]),
+    'bcc_li_333': (1.2, [5, 9]),
+}
+LARGE_WALKERS = 2
 LOCAL_FRACTION = 0.8
 CUTOFF_MARGIN = 1e-6
 
@@ -233,12 +238,13 @@ def make_ecp(cell, r_cut, n_quad=12):
 
 
 @functools.lru_cache(maxsize=None)
-def fixture(name, n_quad=12, f32=False):
-    """Case `name` on its fixture walkers (rounded to float32 with `f32`): dict x, ecp, cell, pairs (the pair list).  Asserts the
-    pair counts of CASES and that no pair lies within 1e-6 Bohr of a cutoff, so that none can flip between model and kernel."""
+def fixture(name, n_quad=12, f32=False, n_walkers=None):
+    """Case `name` on its fixture walkers (the first `n_walkers` of them; rounded to float32 with `f32`): dict x, ecp, cell, pairs
+    (the pair list).  Asserts the pair counts of CASES / LARGE_CASES and that no pair lies within 1e-6 Bohr of a cutoff, so that
+    none can flip between model and kernel."""
     fx, cell, _, _, _ = sh.case(name)
-    r_cut, counts = CASES[name]
-    x = np.asarray(fx['x'], dtype=np.float64)
+    r_cut, counts = CASES[name] if name in CASES else LARGE_CASES[name]
+    x = np.asarray(fx['x'], dtype=np.float64)[:n_walkers]
     if f32:
         x = x.astype(np.float32).astype(np.float64)
     ecp = make_ecp(cell, r_cut, n_quad)
@@ -253,10 +259,10 @@ def fixture(name, n_quad=12, f32=False):
 
 
 @functools.lru_cache(maxsize=None)
-def reference(name, n_quad=12, f32=False):
+def reference(name, n_quad=12, f32=False, n_walkers=None):
     """Oracle side of case `name` with the rotations of (SEED, OFFSET), computed once: the fixture's entries plus rot (B, 3, 3),
     xd, q (oracle ratios), Wn (weights / N_q), e_loc, e_loc_mag, e_loc_terms, e_nl, e_nl_scale."""
-    fx = dict(fixture(name, n_quad, f32))
+    fx = dict(fixture(name, n_quad, f32, n_walkers))
     x, ecp, pl = fx['x'], fx['ecp'], fx['pairs']
     B = len(x)
     rot = replay_rotations(SEED, OFFSET, B)

@@ -48,10 +48,8 @@ def oracle_ratios(o, x, s, first):
     eval_logdet = log|psi| + i arg psi.  With a float32 oracle the configurations are rounded to float32 first."""
     xd = displaced(x, s, first)
     B, M, n3 = xd.shape
-    with o._ctx(), torch.no_grad():
-        f = torch.func.vmap(lambda y: o.ld.apply(o.p, y))
-        l0 = f(o._x(np.asarray(x, dtype=np.float64)))
-        l1 = f(o._x(xd.reshape(B * M, n3))).reshape(B, M)
+    l0 = o.logdet(x)
+    l1 = o.logdet(xd.reshape(B * M, n3)).reshape(B, M)
     d = (l1 - l0[:, None]).to(torch.complex128).numpy()
     return np.exp(d)
 
@@ -128,10 +126,11 @@ def grid_shifts(a, B, N):
 
 
 @functools.lru_cache(maxsize=None)
-def reference(name, seed, offset, M, first, f32=False):
-    """Oracle side of the Philox-mode tests of case `name` on its fixture walkers, computed once: dict x, s, q, cell, nelec."""
+def reference(name, seed, offset, M, first, f32=False, n_walkers=None):
+    """Oracle side of the Philox-mode tests of case `name` on its fixture walkers (the first `n_walkers` of them), computed once:
+    dict x, s, q, cell, nelec."""
     fx, cell, _, _, _ = sh.case(name)
-    x = np.asarray(fx['x'], dtype=np.float64)
+    x = np.asarray(fx['x'], dtype=np.float64)[:n_walkers]
     if f32:
         x = x.astype(np.float32).astype(np.float64)
     s, _ = replay_shifts(seed, offset, len(x), M, cell.a)

@@ -100,6 +100,18 @@ def tiled_walkers(cell, x, B):
     return ((frac - np.floor(frac)) @ a).reshape(B, -1)
 
 
+def distinct_walkers(cell, x, B):
+    """`tiled_walkers` plus a displacement of every coordinate, uniform in +-0.05 Bohr from a fixed seed, wrapped into the cell again:
+    B rows of which no two are equal, so a result read from the wrong walker differs.  Row w is the same for every B > w."""
+    t = tiled_walkers(cell, x, B)
+    a = np.asarray(cell.a, dtype=np.float64).reshape(3, 3)
+    t = t + np.random.default_rng(20251021).uniform(-0.05, 0.05, t.shape)
+    frac = t.reshape(B, -1, 3) @ np.linalg.inv(a)
+    out = ((frac - np.floor(frac)) @ a).reshape(B, -1)
+    assert len(np.unique(out, axis=0)) == B
+    return out
+
+
 class Oracle:
     """The CPU oracle of one case: log|psi| and its complex walker gradient per walker (torch autograd over oracle/network.py),
     and single moves of the four samplers of oracle/qmc.py with the margin every decision was taken on.
@@ -130,6 +142,20 @@ class Oracle:
                 store.clear()
             store[k] = fn(xs)
         return store[k]
+
+    def logdet(self, xs, step=None):
+        """The complex eval_logdet = log|psi| + i arg psi of every row of xs (n, 3N), `step` rows per vmap -> torch tensor (n,) in
+        the oracle's complex dtype.  Default: 8 rows from 48 electrons on (one vmap over a thousand configurations of such a cell
+        needs more memory than a test may take; 8 rows stay under 0.9 GB up to 108 electrons), all rows in one vmap below, where
+        the results are what they were before there were slices.  With a float32 oracle the rows are rounded to float32."""
+        xs = self._x(np.array(xs, dtype=np.float64))
+        if step is None:
+            step = 8 if self.n >= 48 else max(len(xs), 1)
+        with self._ctx(), torch.no_grad():
+            f = torch.func.vmap(lambda y: self.ld.apply(self.p, y))
+            if len(xs) == 0:
+                return torch.zeros(0, dtype=torch.complex64 if self.rd == torch.float32 else torch.complex128)
+            return torch.cat([f(xs[i:i + step]) for i in range(0, len(xs), step)])
 
     def logabs(self, p, xs):
         """f(params, x) of oracle/qmc.py: log|psi| of a batch (the per-walker oracle under torch.func.vmap)."""

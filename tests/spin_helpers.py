@@ -23,11 +23,12 @@ def pair_indices(M, nelec, first):
     return (first + np.arange(M)) % (nelec[0] * nelec[1])
 
 
-def swapped(x, nelec):
-    """x (B, 3N) -> P_p R for every pair (B, P, 3N): the positions of electrons i and j exchanged, nothing wrapped."""
+def swapped(x, nelec, which=None):
+    """x (B, 3N) -> P_p R for every pair, or for the pairs `which` (P,), (B, P, 3N): the positions of electrons i and j exchanged,
+    nothing wrapped."""
     x = np.asarray(x, dtype=np.float64)
     B, N = x.shape[0], x.shape[1] // 3
-    pr = pairs(nelec)
+    pr = pairs(nelec) if which is None else pairs(nelec)[np.asarray(which)]
     P = len(pr)
     xs = np.repeat(x.reshape(B, 1, N, 3), P, axis=1).copy()
     r = x.reshape(B, N, 3)
@@ -38,16 +39,15 @@ def swapped(x, nelec):
 
 def oracle_ratios(o, x, nelec, M, first):
     """q (B, M) complex128 from the oracle `o` (sampler_helpers.Oracle): exp(log psi(P_p R) - log psi(R)) with the complex
-    eval_logdet = log|psi| + i arg psi, sample m taking pair (first + m) % P.  Every pair is evaluated once.  With a float32
-    oracle the configurations are rounded to float32 first."""
-    xs = swapped(x, nelec)
+    eval_logdet = log|psi| + i arg psi, sample m taking pair (first + m) % P.  Every pair that a sample takes is evaluated once, no
+    other.  With a float32 oracle the configurations are rounded to float32 first."""
+    taken, where = np.unique(pair_indices(M, nelec, first), return_inverse=True)
+    xs = swapped(x, nelec, taken)
     B, P, n3 = xs.shape
-    with o._ctx(), torch.no_grad():
-        f = torch.func.vmap(lambda y: o.ld.apply(o.p, y))
-        l0 = f(o._x(np.asarray(x, dtype=np.float64)))
-        l1 = f(o._x(xs.reshape(B * P, n3))).reshape(B, P)
+    l0 = o.logdet(x)
+    l1 = o.logdet(xs.reshape(B * P, n3)).reshape(B, P)
     q = np.exp((l1 - l0[:, None]).to(torch.complex128).numpy())
-    return q[:, pair_indices(M, nelec, first)]
+    return q[:, where]
 
 
 def plane_wave_pair_ratios(x, pw_klist, nelec):
@@ -103,6 +103,20 @@ def reference(name, f32=False):
     q = oracle_ratios(sh.oracle(name, f32), x, nelec, P, 0)
     q.setflags(write=False)
     return dict(x=x, q_all=q, cell=cell, nelec=nelec)
+
+
+@functools.lru_cache(maxsize=None)
+def large_reference(name, M, first_pair, f32=False, n_walkers=2):
+    """Oracle side of a large cell on its first `n_walkers` fixture walkers, computed once: only the pairs the M samples from
+    `first_pair` take are evaluated.  -> dict x, q (B, M), cell, nelec."""
+    fx, cell, _, _, _ = sh.case(name)
+    x = np.asarray(fx['x'], dtype=np.float64)[:n_walkers]
+    if f32:
+        x = x.astype(np.float32).astype(np.float64)
+    nelec = tuple(int(v) for v in cell.nelec)
+    q = oracle_ratios(sh.oracle(name, f32), x, nelec, M, first_pair)
+    q.setflags(write=False)
+    return dict(x=x, q=q, cell=cell, nelec=nelec)
 
 
 @functools.lru_cache(maxsize=None)
