@@ -147,6 +147,9 @@ SIGNATURES = {
     'ds_ecp_workspace_bytes': (C.c_int64, [_VP, _VP, C.c_int64, C.c_int64]),
     'ds_ecp_energy': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_uint64, C.c_uint64, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP,
                                C.c_int64, _VP]),
+    'ds_ecp_forces_workspace_bytes': (C.c_int64, [_VP, _VP, C.c_int64, C.c_int64]),
+    'ds_ecp_forces': (C.c_int, [_VP, _VP, _VP, _VP, C.c_int64, C.c_uint64, C.c_uint64, _VP, C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP,
+                               _VP, C.c_int64, _VP]),
     'ds_dmc_workspace_bytes': (C.c_int64, [_VP, C.c_int64]),
     'ds_dmc_step': _dmc_step_sig(8, 3, 2, ecp=False),
     'ds_dmc_ecp_workspace_bytes': (C.c_int64, [_VP, _VP, C.c_int64, C.c_int64]),

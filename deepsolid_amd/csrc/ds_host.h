@@ -302,6 +302,11 @@ int ecp_check(const ds_system* s, const ds_ecp* e, int64_t B, int64_t pair_capac
 int ecp_n_quad(const ds_ecp* e);
 int64_t ecp_default_groups(const ds_system* s, int64_t B, int64_t pair_capacity, int nq);
 
+// ds_observe.hip: the sums of ds_ion_forces on rows [nw][2][A][3] that another call has filled (ds_ecp_forces): k_force_part over the
+// groups of FORCE_SUM_GROUP (= ds::FORCE_GROUP) walkers into part [groups][12 A + 1], then k_force_final onto sums, the groups in order
+constexpr int64_t FORCE_SUM_GROUP = 256;
+int force_sums(const double* rows, int64_t nw, int A, double* part, double* sums, hipStream_t st);
+
 // ds_det.hip: the determinant stage of both chains.  Energy chain: inverse + determinant of channel ch, then tr(Y_d), sum Y_d Y_d^T;
 // value chain: log det of every channel (and the inverses when vb.MINV is set)
 template <typename T>

@@ -129,6 +129,17 @@ template <typename T> int force_tables(ds_system* s) { return ds::force_table_fl
 // doubles of workspace per group of FORCE_GROUP walkers: their rows and the group's partial sums
 static int64_t force_group_doubles(const ds_system* s) { return (int64_t)ds::FORCE_GROUP * 6 * s->sd.As + 12 * s->sd.As + 1; }
 
+static_assert(FORCE_SUM_GROUP == ds::FORCE_GROUP, "ds_host.h restates the group of k_force_part");
+int force_sums(const double* rows, int64_t nw, int A, double* part, double* sums, hipStream_t st) {
+    const int64_t groups = (nw + ds::FORCE_GROUP - 1) / ds::FORCE_GROUP;
+    const int K = 12 * A + 1;
+    hipLaunchKernelGGL(ds::k_force_part, dim3((unsigned)groups), dim3(ds::FORCE_GROUP), 0, st, rows, (long long)nw, A, part);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(ds::k_force_final, dim3((K + 255) / 256), dim3(256), 0, st, (const double*)part, (long long)groups, K, sums);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
 // strain derivatives (ds_stress.h): the walkers [b0, b0 + nb) of the batch; rows: of this launch
 template <typename T>
 void stress(ds_system* s, const void* x, const void* grad, int64_t b0, int64_t nb, const double* ion_ion, double* out, double* rows,

@@ -1,11 +1,12 @@
-// ds_sample.hip -- the samplers and what shares their kernels (ds_mcmc.h, ds_onebody.h, ds_spin.h, ds_ecp.h): the three fused Metropolis
-// loops, the one-body ratios and n(k), the spin-exchange ratios and the sums of <S^2>, the pseudopotential energy and its handle, the
-// single proposal / selection steps (ds_mh_*), the batch statistics and the host side of Philox.
+// ds_sample.hip -- the samplers and what shares their kernels (ds_mcmc.h, ds_onebody.h, ds_spin.h, ds_ecp.h, ds_ecp_force.h): the three
+// fused Metropolis loops, the one-body ratios and n(k), the spin-exchange ratios and the sums of <S^2>, the pseudopotential energy, its
+// forces and its handle, the single proposal / selection steps (ds_mh_*), the batch statistics and the host side of Philox.
 #include "ds_host.h"
 #include "ds_mcmc.h"
 #include "ds_onebody.h"
 #include "ds_spin.h"
 #include "ds_ecp.h"
+#include "ds_ecp_force.h"
 
 struct ds_ecp {
     ds::EcpDev D;
@@ -290,6 +291,103 @@ int ecp_tmove(ds_system* s, const ds_ecp* e, const void* view, void* x, int64_t 
 }
 
 int ecp_n_quad(const ds_ecp* e) { return e->D.n_quad; }
+
+// ------------------------------------------------------------------ pseudopotential forces, ds_ecp_force.h
+// Workspace of ds_ecp_forces for B walkers, A ions, at most `cap` pairs, nq points per pair and chunks of ng groups of PV
+// configurations.  Shared by all chunks: what carve_ecp shares (log|psi(R)|, phase(R), and in 8-byte elements the rotation, E_loc, the
+// pair count, the offsets and the flag per walker, the pair records), then the second flag (a pair at r = 0), the second record array
+// v'_l(r), 6 nq terms per pair, F^loc (B, A, 3), the rows (B, 2, A, 3) = (F^pp, F^tot) and one row of partial sums per 256 walkers.
+// Per chunk: the displaced rows, their log|psi| / phase / gradient, and the forward-Laplacian chain's buffers for ng PV walkers (on
+// a 64-element border), which also serve the pass over the walkers themselves.
+template <typename T> struct EcpForceWs {
+    T *LA0, *PH0, *XD, *LA, *PH, *GR;
+    double *ROT, *ELOC, *PR, *PVL, *PDV, *TERM, *FLOC, *ROWS, *PART;
+    long long *CNT, *OFF, *PW;
+    int *BAD, *BADF, *PI;
+    void* wsc; int64_t wsc_bytes;
+};
+template <typename T> EcpForceWs<T> carve_ecp_force(const ds_system* s, Arena<T>& a, int64_t B, int A, int64_t cap, int nq, int64_t ng) {
+    const size_t nc = (size_t)ng * ds::PV, b = (size_t)B, p = (size_t)cap, groups = (b + FORCE_SUM_GROUP - 1) / FORCE_SUM_GROUP;
+    EcpForceWs<T> w{};
+    w.LA0 = a.take(b); w.PH0 = a.take(2 * b);
+    a.align(2);
+    w.ROT = (double*)a.take(2 * 9 * b); w.ELOC = (double*)a.take(2 * b);
+    w.CNT = (long long*)a.take(2 * b); w.OFF = (long long*)a.take(2 * (b + 1));
+    w.BAD = (int*)a.take(2 * ((b + 1) / 2)); w.BADF = (int*)a.take(2 * ((b + 1) / 2));
+    w.PW = (long long*)a.take(2 * p); w.PI = (int*)a.take(2 * p);
+    w.PR = (double*)a.take(2 * 4 * p); w.PVL = (double*)a.take(2 * 3 * p); w.PDV = (double*)a.take(2 * 3 * p);
+    w.TERM = (double*)a.take(2 * 6 * p * (size_t)nq);
+    w.FLOC = (double*)a.take(2 * 3 * (size_t)A * b); w.ROWS = (double*)a.take(2 * 6 * (size_t)A * b);
+    w.PART = (double*)a.take(2 * groups * (12 * (size_t)A + 1));
+    w.XD = a.take(nc * 3 * s->sd.N); w.LA = a.take(nc); w.PH = a.take(2 * nc); w.GR = a.take(nc * 3 * s->sd.N * 2);
+    a.align(64);
+    w.wsc = a.take(s->ws.per_walker * nc);
+    w.wsc_bytes = (int64_t)(s->ws.per_walker * nc * sizeof(T));
+    return w;
+}
+inline int64_t ecp_force_bytes(const ds_system* s, int64_t B, int A, int64_t cap, int nq, int64_t ng) {
+    return (int64_t)measure([&](Arena<double>& a) { carve_ecp_force<double>(s, a, B, A, cap, nq, ng); }) * (s->dtype == 0 ? 8 : 4);
+}
+
+template <typename T>
+int ecp_forces_impl(ds_system* s, const ds_ecp* e, const void* params, const void* x_, int64_t B, uint64_t seed, uint64_t offset,
+                    const double* rotations, int64_t cap, const double* base, double* out_force, double* sums, int64_t* n_bad,
+                    int64_t* out_pairs, double* out_rotation, void* ws, int64_t ws_bytes, hipStream_t st) {
+    const ds::SysDev<T>& S = dev<T>(s);
+    const ds::EcpDev& E = e->D;
+    const T* x = (const T*)x_;
+    const int nq = E.n_quad, A = E.n_atoms;
+    // the chunk length follows from the workspace, as in ecp_energy_impl, with the forward-Laplacian chain's per-walker layout
+    const int64_t fixed = ecp_force_bytes(s, B, A, cap, nq, 0), per = ecp_force_bytes(s, B, A, cap, nq, 1) - fixed;
+    int64_t ng = std::min<int64_t>({(ws_bytes - fixed) / per + 1, OB_MAX_GROUPS, (std::max(cap * nq, B) + ds::PV - 1) / ds::PV});
+    while (ng >= 1 && ecp_force_bytes(s, B, A, cap, nq, ng) > ws_bytes) --ng;
+    if (ng < 1) return fail("workspace too small for ds_ecp_forces: %lld bytes < %lld for one group of %d configurations",
+                            (long long)ws_bytes, (long long)ecp_force_bytes(s, B, A, cap, nq, 1), ds::PV);
+    Arena<T> a = arena_of<T>(ws, ws_bytes);
+    const EcpForceWs<T> w = carve_ecp_force<T>(s, a, B, A, cap, nq, ng);
+    if (!a.ok) return carve_fail("pseudopotential forces");
+    const dim3 gw((unsigned)((B + 63) / 64)), bw(64);
+    hipLaunchKernelGGL((ds::k_ecp_scan<T>), gw, bw, 0, st, E, x, (long long)B, S.N, ds::PhiloxKey{seed, offset}, rotations, w.ROT, w.ELOC,
+                       w.CNT, w.BAD, out_rotation);
+    hipLaunchKernelGGL(ds::k_ecp_offsets, dim3(1), dim3(1024), 0, st, (const long long*)w.CNT, (long long)B, w.OFF, (long long*)out_pairs);
+    hipLaunchKernelGGL((ds::k_ecp_fill<T>), gw, bw, 0, st, E, x, (long long)B, S.N, (const int*)w.BAD, (const long long*)w.OFF,
+                       (long long)cap, w.PW, w.PI, w.PR, w.PVL);
+    // the one synchronisation of the call: the host needs the pair total to size the chunks
+    long long pairs = 0;
+    HIP_OK(hipMemcpyAsync(&pairs, w.OFF + B, sizeof(long long), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    if (pairs > cap)
+        return fail("ds_ecp_forces: pair capacity exceeded: the walkers have %lld pairs inside the non-local cutoffs, pair_capacity is %lld",
+                    pairs, (long long)cap);
+    hipLaunchKernelGGL((ds::k_ecp_force_local<T>), gw, bw, 0, st, E, x, (long long)B, S.N, (const int*)w.BAD, w.FLOC, w.BADF);
+    const int64_t total = pairs * nq, chunk = ng * ds::PV, stride = cap * nq;
+    if (total > 0) {
+        hipLaunchKernelGGL(ds::k_ecp_fill_deriv, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, st, E, pairs, (const int*)w.PI,
+                           (const double*)w.PR, w.PDV);
+        // log psi(R) of the ratios: the same chain, one pass over the B walkers (its gradient is not used)
+        for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+            const int64_t nb = std::min(chunk, B - b0);
+            if (int rc = logpsi_grad_forward(s, params, x + b0 * 3 * S.N, nb, w.LA0 + b0, w.PH0 + 2 * b0, w.GR, w.wsc, w.wsc_bytes, st)) return rc;
+        }
+    }
+    ds::EcpChunk C;
+    C.N = S.N; C.n_quad = nq;
+    for (int64_t c0 = 0; c0 < total; c0 += chunk) {
+        C.c0 = c0; C.n = std::min(chunk, total - c0);
+        hipLaunchKernelGGL((ds::k_ecp_propose<T>), dim3((unsigned)((C.n * S.N + 255) / 256)), dim3(256), 0, st, E, C, x, (const double*)w.ROT,
+                           (const long long*)w.PW, (const int*)w.PI, (const double*)w.PR, w.XD);
+        if (int rc = logpsi_grad_forward(s, params, w.XD, C.n, w.LA, w.PH, w.GR, w.wsc, w.wsc_bytes, st)) return rc;
+        hipLaunchKernelGGL((ds::k_ecp_force_term<T>), dim3((unsigned)((C.n + 255) / 256)), dim3(256), 0, st, E, C, (const double*)w.ROT,
+                           (const long long*)w.PW, (const int*)w.PI, (const double*)w.PR, (const double*)w.PVL, (const double*)w.PDV,
+                           (const T*)w.LA0, (const T*)w.PH0, (const T*)w.LA, (const T*)w.PH, (const T*)w.GR, (long long)stride, w.TERM);
+    }
+    hipLaunchKernelGGL(ds::k_ecp_force_walker, dim3((unsigned)B), dim3(64 * ds::ECPF_WAVES), 0, st, (const double*)w.TERM, (long long)stride,
+                       (const long long*)w.OFF, (const int*)w.PI, (const double*)w.FLOC, (const int*)w.BADF, base, A, nq, out_force,
+                       sums ? w.ROWS : (double*)nullptr, (unsigned long long*)n_bad);
+    HIP_OK(hipGetLastError());
+    if (sums) return force_sums(w.ROWS, B, A, w.PART, sums, st);
+    return 0;
+}
 
 int64_t ecp_default_groups(const ds_system* s, int64_t B, int64_t pair_capacity, int nq) {
     // as many groups per chunk as ds_workspace_bytes gives the value chain of pair_capacity * n_quad walkers
@@ -701,6 +799,29 @@ int ds_ecp_energy(ds_system* s, const ds_ecp* e, const void* params, const void*
     hipStream_t st = (hipStream_t)stream;
     return ecp_energy_forward(s, e, params, x, B, philox_seed, philox_offset, rotations, pair_capacity, out_energy, out_pairs, out_ratio,
                               out_rotation, ws, ws_bytes, st, nullptr, nullptr);
+}
+
+int64_t ds_ecp_forces_workspace_bytes(const ds_system* s, const ds_ecp* e, int64_t B, int64_t pair_capacity) {
+    if (!s || !e) { fail("null argument"); return -1; }
+    if (ecp_check(s, e, B, pair_capacity)) return -1;
+    // as many groups per chunk as ds_workspace_bytes gives the forward-Laplacian chain of pair_capacity * n_quad walkers
+    const int nq = e->D.n_quad, A = e->D.n_atoms;
+    const int64_t esz = s->dtype == 0 ? 8 : 4, total = std::max(pair_capacity * nq, B);
+    const int64_t fixed = ecp_force_bytes(s, B, A, pair_capacity, nq, 0), per = ecp_force_bytes(s, B, A, pair_capacity, nq, 1) - fixed;
+    const int64_t ng = std::min(groups_per_pass(total, esz, PassSize{0, (size_t)(per / esz)}, workspace_budget()), OB_MAX_GROUPS);
+    return ecp_force_bytes(s, B, A, pair_capacity, nq, ng);
+}
+
+int ds_ecp_forces(ds_system* s, const ds_ecp* e, const void* params, const void* x, int64_t B, uint64_t philox_seed, uint64_t philox_offset,
+                  const double* rotations, int64_t pair_capacity, const double* base, double* out_force, double* sums, int64_t* n_bad,
+                  int64_t* out_pairs, double* out_rotation, void* ws, int64_t ws_bytes, void* stream) {
+    if (s) ++s->call_seq;
+    if (!s || !e || !params || !x || !ws) return fail("null argument");
+    if (!out_force && !sums) return fail("ds_ecp_forces: out_force and sums are both null, nothing to write");
+    if (int rc = ecp_check(s, e, B, pair_capacity)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    return DS_BY_DTYPE(s->dtype, ecp_forces_impl, s, e, params, x, B, philox_seed, philox_offset, rotations, pair_capacity, base, out_force,
+                       sums, n_bad, out_pairs, out_rotation, ws, ws_bytes, st);
 }
 
 int ds_energy_stats(ds_system* s, const void* ke, const void* ewald, int64_t B, double* out_stats, void* stream) {

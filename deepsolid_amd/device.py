@@ -1024,6 +1024,62 @@ class DeviceSystem:
                     rotations=rot, pair_capacity=cap,
                     ratios=torch.view_as_complex(ratios)[:int(pairs.sum()) * ecp.n_quad] if want_ratios else None)
 
+    def ecp_forces(self, params, x, ecp, seed=0, offset=0, rotations=None, pair_capacity=None, base=None, sums=None, want_walker=True,
+                   max_bytes=None):
+        """`ds_ecp_forces` (csrc/ds_ecp_force.h): per walker and ion of the simulation cell minus the derivative
+        of the pseudopotential energy E_loc + E_nl of `ecp_energy` in the ion position, with psi held fixed as a function of the
+        electron coordinates.  `ecp`, `seed`, `offset`, `rotations`, `pair_capacity` and the capacity retry are those of `ecp_energy`:
+        the same (seed, offset) uses the same quadrature points.  `base` (B, A, 3) float64 is added per walker to form the total
+        (meant for `ion_forces(x)['hf']`, the Ewald force with Z_eff).  `sums`: float64 device tensor (12 A + 1,) that is ADDED to
+        = per (a, c) [sum pp, sum pp^2, sum tot, sum tot^2] over the good walkers, then their number; pp = loc + Re nl,
+        tot = pp + base.  A walker with a non-finite coordinate, an electron exactly on a pseudo-ion or a non-finite result is NaN,
+        left out and counted.  `max_bytes` caps the workspace: more chunks, bit-identical results.
+        LIMITS: the Hellmann-Feynman part only (no Pulay term: the bias is first order in the error of psi); the delta term of the
+        jump of a radial function at its cutoff is left out; one forward-Laplacian chain evaluation per quadrature configuration.
+        -> dict(loc (B, A, 3) float64 and nl (B, A, 3) complex128, or None without `want_walker`; n_bad (1,) int64 device tensor;
+        pairs (B,) int64; rotations (B, 3, 3) float64; pair_capacity: the capacity the call ran with; sums).
+        The call synchronises the stream once (the pair total) and cannot be captured into a graph."""
+        import re
+        x = self._check_x(x)
+        B = x.shape[0]
+        ecp = self._ecp_tables(ecp)
+        A = int(self.tables.atom_coords.shape[0])
+        p = self.pack_params(params)
+        if rotations is not None:
+            rotations = rotations.to(device=self.device, dtype=torch.float64).contiguous()
+            if tuple(rotations.shape) != (B, 3, 3):
+                raise ValueError(f'rotations must be ({B}, 3, 3), got {tuple(rotations.shape)}')
+        if base is not None:
+            if not (base.is_cuda and base.dtype == torch.float64 and tuple(base.shape) == (B, A, 3)):
+                raise ValueError(f'base must be a float64 device tensor of shape ({B}, {A}, 3)')
+            base = base.contiguous()
+        if sums is not None and not (sums.is_cuda and sums.dtype == torch.float64 and sums.is_contiguous()
+                                     and tuple(sums.shape) == (12 * A + 1,)):
+            raise ValueError(f'sums must be a contiguous float64 device tensor of shape ({12 * A + 1},)')
+        if not want_walker and sums is None:
+            raise ValueError('nothing to compute: neither the walker forces nor sums are asked for')
+        cap = B * self.n if pair_capacity is None else int(pair_capacity)
+        force = torch.empty(B, A, 3, 3, dtype=torch.float64, device=self.device) if want_walker else None
+        pairs = torch.empty(B, dtype=torch.int64, device=self.device)
+        rot = torch.empty(B, 3, 3, dtype=torch.float64, device=self.device)
+        n_bad = torch.zeros(1, dtype=torch.int64, device=self.device)
+        for attempt in range(2):
+            # (the library refuses B < 1 / pair_capacity < 1 / another cell itself, here already)
+            ws = self._workspace('ds_ecp_forces_workspace_bytes', ecp.handle, B, cap, max_bytes=max_bytes)
+            rc = self.lib.ds_ecp_forces(self.handle, ecp.handle, _ptr(p), _ptr(x), B, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
+                                        _ptr(rotations), cap, _ptr(base), _ptr(force), _ptr(sums), _ptr(n_bad), _ptr(pairs), _ptr(rot),
+                                        _ptr(ws), ws.numel(), _stream())
+            if rc != 0 and attempt == 0:
+                m = re.search(r'pair capacity exceeded: the walkers have (\d+) pairs', self.lib.ds_last_error().decode())
+                if m:
+                    cap = int(m.group(1))
+                    continue
+            _lib.check(rc, 'ds_ecp_forces')
+            break
+        return dict(loc=force[..., 0] if want_walker else None,
+                    nl=torch.complex(force[..., 1], force[..., 2]) if want_walker else None,
+                    n_bad=n_bad, pairs=pairs, rotations=rot, pair_capacity=cap, sums=sums)
+
     def energy_stats(self, ke, ew):
         """`ds_energy_stats`: (8,) float64 = [sum Re E_L, sum Im E_L, sum |E_L|^2, n, n_nonfinite, sum Re ke, sum Im ke, sum ew]."""
         out = torch.empty(8, dtype=torch.float64, device=self.device)

@@ -863,6 +863,173 @@ class IonForces:
             return cls.from_state_dict({k: f[k] for k in f.files})
 
 
+# ------------------------------------------------------------------ pseudopotential forces (csrc/ds_ecp_force.h)
+# The reference has neither pseudopotentials nor forces; the conventions are this project's own.
+_ECP_KEYS = ('atom_species', 'n_l', 'r_cut_loc', 'r_cut_nl', 'n_quad', 'term_offset', 'term_n', 'term_zeta', 'term_c')
+
+
+def _ecp_signature(ecp):
+    """The arrays that define a `pseudopotential.SemiLocalECP` beyond cell and atoms, as plain numpy (what `merge` compares)."""
+    sig = dict(atom_species=np.asarray(ecp.atom_species, np.int32), n_l=np.asarray(ecp.n_l, np.int32),
+               r_cut_loc=np.asarray(ecp.r_cut_loc, np.float64), r_cut_nl=np.asarray(ecp.r_cut_nl, np.float64),
+               n_quad=np.asarray(ecp.n_quad, np.int32))
+    sig.update(ecp.tables())
+    return sig
+
+
+class PseudopotentialForces(IonForces):
+    """Forces on the ions of a simulation cell with a semi-local pseudopotential, accumulated on the device over any number of walker
+    batches: an accumulator with the interface of `IonForces`, for `run_inference(accumulators=...)` (VMC) and
+    `run_dmc(accumulators=...)`.  Per ion a:
+
+        pp    = < F^loc_a + Re F^nl_a >        minus the derivative of E_loc + E_nl of `ds_ecp_energy` in R_a, with psi held fixed
+                                               as a function of the electron coordinates (`ds_ecp_forces`)
+        total = < pp + hf >                    hf = -d(E_ei + E_ii)/dR_a of the Ewald energy with Z_eff (`ds_ion_forces`' out_hf)
+
+    No zero-variance term is added: inside the core the 1/r^2 of the Z_eff Ewald force is cancelled by v'_loc of any published
+    potential, so the variance of the total is finite without one.
+    LIMITS, read them before using a number:
+      - Hellmann-Feynman part only.  The Pulay term 2 <(E_L - E) d log psi / dR_a> with E_pp inside E_L is not evaluated, so the
+        bias is FIRST ORDER in the error of psi, as `IonForces` is without `PrimitiveForces`.
+      - The radial functions are exactly 0 outside their cutoffs.  The jump at a cutoff is a delta term of the exact derivative and
+        is left out; its size is that of the function at its cutoff, `find_cutoff`'s `tol`.
+      - A walker with an electron exactly on a pseudo-ion (r = 0: no direction) is bad: it is left out and counted in n_bad, like a
+        walker with a non-finite coordinate or result.
+      - Under `run_dmc` the numbers are MIXED estimates (psi_T psi_0), taken on comb blocks; not the pure estimate.
+      - Cost: one forward-Laplacian chain evaluation per quadrature configuration, N_q per (electron, ion) pair inside r_cut_nl.
+
+    Every `update` is ONE `ds_ion_forces` call for out_hf (no drift needed) and ONE `ds_ecp_forces` call with that as `base`, which
+    adds to 12 A + 1 float64 numbers in the library's fixed order; the rotation offset advances by one per update (`key` is the
+    Philox seed).  The `ds_ecp_forces` call synchronises the stream once (the pair total)."""
+
+    def __init__(self, net, params, pseudopotential, key=0):
+        if pseudopotential is None:
+            raise ValueError('PseudopotentialForces needs a pseudopotential (all-electron ions: IonForces)')
+        self.apply = getattr(net, 'apply', net)
+        self.params = params
+        self.pseudopotential = pseudopotential
+        cell = self.apply.simulation_cell
+        atoms, latvec = np.asarray(cell.atom_coords(), np.float64).reshape(-1, 3), np.asarray(cell.a, np.float64).reshape(3, 3)
+        if atoms.shape != pseudopotential.atoms.shape or not (np.allclose(atoms, pseudopotential.atoms, rtol=0, atol=1e-10) and
+                                                              np.allclose(latvec, pseudopotential.a, rtol=0, atol=1e-10)):
+            raise ValueError('PseudopotentialForces: the pseudopotential was built for another simulation cell')
+        self._setup(atoms, np.asarray(cell.atom_charges(), np.float64), latvec, int(sum(cell.nelec)),
+                    _ecp_signature(pseudopotential), key)
+
+    def _setup(self, atoms, charges, latvec, n_elec, ecp, key):
+        self.atoms = np.asarray(atoms, np.float64).reshape(-1, 3)
+        self.charges = np.asarray(charges, np.float64).reshape(-1)
+        self.latvec = np.asarray(latvec, np.float64).reshape(3, 3)
+        self.n_elec = int(n_elec)
+        self.ecp = {k: np.asarray(ecp[k]) for k in _ECP_KEYS}
+        self.seed, self.offset = int(key), 0
+        self.n_atoms = self.atoms.shape[0]
+        self.sums = torch.zeros(12 * self.n_atoms + 1, dtype=torch.float64)     # moved to the walkers' device by the first update
+        self.n_bad = torch.zeros(1, dtype=torch.int64)
+        self.n_walkers = 0
+        self.reduced = False
+
+    def update(self, data):
+        """Add the forces of every walker of `data` (B, 3N) to the sums: one `ds_ion_forces` and one `ds_ecp_forces` call."""
+        if self.apply is None:
+            raise RuntimeError('PseudopotentialForces.update: a loaded accumulator has no network; merge it into one that has')
+        if self.reduced:
+            raise RuntimeError('PseudopotentialForces.update after reduce(): the sums are already summed over the ranks')
+        if data.shape[-1] != 3 * self.n_elec:
+            raise ValueError(f'walkers have {data.shape[-1]} coordinates, the cell has {self.n_elec} electrons')
+        x = data.reshape(-1, 3 * self.n_elec)
+        if x.shape[0] == 0:
+            return
+        if self.sums.device != x.device:
+            self.sums, self.n_bad = self.sums.to(x.device), self.n_bad.to(x.device)
+        system = self.apply.system
+        hf = system.ion_forces(x)['hf']
+        out = system.ecp_forces(self.params, x, self.pseudopotential, seed=self.seed, offset=self.offset, base=hf, sums=self.sums,
+                                want_walker=False)
+        self.offset += 1
+        self.n_bad += out['n_bad']
+        self.n_walkers += int(x.shape[0])           # only now: a call that raised leaves the count with the sums
+
+    def _same_setup(self, other):
+        return (isinstance(other, PseudopotentialForces) and self.atoms.shape == other.atoms.shape and
+                np.array_equal(self.atoms, other.atoms) and np.array_equal(self.charges, other.charges) and
+                np.array_equal(self.latvec, other.latvec) and self.n_elec == other.n_elec and
+                all(np.array_equal(self.ecp[k], other.ecp[k]) for k in _ECP_KEYS))
+
+    def merge(self, other):
+        """Add the sums, the bad count and the walker number of another accumulator of the same ions, lattice and pseudopotential.
+        Both sides must be in the same state (rank-local or summed over the ranks)."""
+        if not self._same_setup(other):
+            raise ValueError('PseudopotentialForces.merge: the two accumulators differ in ions, lattice, electron number or pseudopotential')
+        if self.reduced != other.reduced and constants.world_size() > 1:
+            raise ValueError('PseudopotentialForces.merge: one side is summed over the ranks and the other is rank-local')
+        self.sums = self.sums + other.sums.to(self.sums.device)
+        self.n_bad = self.n_bad + other.n_bad.to(self.n_bad.device)
+        self.n_walkers += other.n_walkers
+        return self
+
+    def forces(self):
+        """-> dict(pp, pp_error, total, total_error (each (A, 3) float64, Ha/bohr), n_walkers, n_bad, atoms (A, 3)): the means over the
+        n_good walkers whose forces were finite, and error = sqrt((sum f^2 / n_good - mean^2) / (n_good - 1)): the NAIVE standard
+        error of `IonForces.forces` (walkers taken as independent; NaN below two good walkers).  NaN everywhere without a good
+        walker.  The limits of the class apply: Hellmann-Feynman only, no cutoff delta term, mixed estimate under DMC."""
+        s = self.sums.detach().cpu().numpy()
+        A = self.n_atoms
+        n = float(s[12 * A])
+        q = s[:12 * A].reshape(A, 3, 4)
+        out = dict(n_walkers=self.n_walkers, n_bad=int(self.n_bad.sum()), atoms=self.atoms.copy())
+        for name, k in (('pp', 0), ('total', 2)):
+            if n < 1:
+                out[name] = np.full((A, 3), np.nan)
+                out[name + '_error'] = np.full((A, 3), np.nan)
+                continue
+            mean = q[:, :, k] / n
+            var = np.maximum(q[:, :, k + 1] / n - mean * mean, 0.0)
+            out[name] = mean
+            out[name + '_error'] = np.sqrt(var / (n - 1)) if n > 1 else np.full((A, 3), np.nan)
+        return out
+
+    def state_dict(self):
+        """Plain numpy arrays: the sums and counts and the setup they belong to (the pseudopotential's tables as `ecp_<name>`)."""
+        sd = {'sums': self.sums.detach().cpu().numpy().copy(), 'n_bad': self.n_bad.detach().cpu().numpy().copy(),
+              'n_walkers': np.int64(self.n_walkers), 'atoms': self.atoms.copy(), 'charges': self.charges.copy(),
+              'latvec': self.latvec.copy(), 'n_elec': np.int64(self.n_elec), 'seed': np.int64(self.seed),
+              'offset': np.int64(self.offset), 'reduced': np.bool_(self.reduced)}
+        sd.update({'ecp_' + k: self.ecp[k].copy() for k in _ECP_KEYS})
+        return sd
+
+    def load_state_dict(self, sd):
+        """Replace the sums and counts by those of `sd` (same ions, lattice and pseudopotential); the rotation offset continues
+        behind the larger of the two, and the accumulator is rank-local and open for `update` afterwards."""
+        other = PseudopotentialForces.from_state_dict(sd)
+        if not self._same_setup(other):
+            raise ValueError('PseudopotentialForces.load_state_dict: the state belongs to other ions, another lattice or another pseudopotential')
+        self.sums, self.n_bad = other.sums.to(self.sums.device), other.n_bad.to(self.n_bad.device)
+        self.n_walkers, self.reduced, self.offset = other.n_walkers, False, max(self.offset, other.offset)
+        return self
+
+    @classmethod
+    def from_state_dict(cls, sd):
+        """An accumulator without a network: it can be merged, normalised and saved, not updated."""
+        acc = cls.__new__(cls)
+        acc.apply = acc.params = acc.pseudopotential = None
+        acc._setup(sd['atoms'], sd['charges'], sd['latvec'], int(sd['n_elec']), {k: sd['ecp_' + k] for k in _ECP_KEYS}, int(sd['seed']))
+        acc.offset = int(sd['offset'])
+        acc.sums = torch.as_tensor(np.array(sd['sums'], dtype=np.float64).reshape(12 * acc.n_atoms + 1))
+        acc.n_bad = torch.as_tensor(np.array(sd['n_bad'], dtype=np.int64).reshape(1))
+        acc.n_walkers = int(sd['n_walkers'])
+        return acc                          # reduced stays False: the loaded sums are this rank's contribution from here on
+
+    def save(self, path, results=True):
+        """One .npz of `state_dict()`; `results`: also pp, pp_error, total and total_error of `forces()`."""
+        sd = self.state_dict()
+        if results:
+            r = self.forces()
+            sd.update({k: r[k] for k in ('pp', 'pp_error', 'total', 'total_error')})
+        with open(path, 'wb') as f:
+            np.savez(f, **sd)
+
+
 # ------------------------------------------------------------------ stress tensor and pressure (csrc/ds_stress.h)
 # The reference has no stress estimator; the conventions of this section are this project's own (DESIGN.md section 23).
 STRESS_ROWS = ('kin', 'ee', 'ei', 'total')

@@ -25,6 +25,11 @@ so both are the force only for an exact wave function (bias first order in its e
 --forces-total: the TOTAL force per atom of the primitive cell (zero-variance force + Pulay term), through
 deepsolid_amd.estimator.PrimitiveForces, written to forces_total.npz; one block per evaluation step, errors by reblocking the block
 series; honours --forces-cutoff; all-electron only: not with --ecp;
+--forces-ecp: with --ecp, the forces on the two ions of the pseudopotential cell over the evaluation, through
+deepsolid_amd.estimator.PseudopotentialForces, written to forces_ecp.npz: pp = minus the derivative of E_loc + E_nl in the ion
+position, total = pp + the Hellmann-Feynman force of the Ewald energy with Z_eff.  Hellmann-Feynman part only (no Pulay term: bias
+first order in the error of psi), the delta term of the cutoffs is left out, and it costs one forward-Laplacian chain evaluation
+per quadrature configuration;
 --stress: the stress tensor and the pressure of the cell over the evaluation, through deepsolid_amd.estimator.StressTensor, written to
 stress.npz: the integrated-by-parts kinetic tensor plus the strain derivative of the Ewald sums over the volume, naive errors.  The
 change of psi with the cell at fixed parameters is NOT evaluated, so it is the stress only for an exact wave function; all-electron
@@ -109,6 +114,9 @@ if '--forces-cutoff' in sys.argv:
 if '--forces' in sys.argv:
     forces = True
     sys.argv.remove('--forces')
+forces_ecp = '--forces-ecp' in sys.argv
+if forces_ecp:
+    sys.argv.remove('--forces-ecp')
 stress_total = '--stress-total' in sys.argv
 if stress_total:
     sys.argv.remove('--stress-total')
@@ -139,6 +147,8 @@ if '--ecp' in sys.argv:
     del sys.argv[i:i + 2]
 if (forces or forces_total) and ecp_file is not None:
     sys.exit('--forces / --forces-total is all-electron only: the force terms of a pseudopotential are not implemented')
+if forces_ecp and ecp_file is None:
+    sys.exit('--forces-ecp needs --ecp FILE.npz')
 if (stress or stress_total) and ecp_file is not None:
     sys.exit('--stress / --stress-total is all-electron only: the strain derivative of a pseudopotential is not implemented')
 if dmc_pure is not None and dmc_blocks <= 0:
@@ -194,6 +204,11 @@ if forces_total:
     from deepsolid_amd import estimator
     total_acc = estimator.PrimitiveForces(logdet, params, cutoff=force_cutoff)
     accumulators += (total_acc,)
+ecp_force_acc = None
+if forces_ecp:
+    from deepsolid_amd import estimator
+    ecp_force_acc = estimator.PseudopotentialForces(logdet, params, ecp)
+    accumulators += (ecp_force_acc,)
 stress_acc = None
 if stress:
     from deepsolid_amd import estimator
@@ -235,6 +250,15 @@ for acc in accumulators:
         for a in range(len(f['atoms'])):
             print('            %-2s total (%9.4f %9.4f %9.4f) +- (%.4f %.4f %.4f)   ZV (%9.4f %9.4f %9.4f)   Pulay (%9.4f %9.4f %9.4f) Ha/Bohr'
                   % ((prim.atom_symbol(a),) + tuple(f['total'][a]) + tuple(f['total_error'][a]) + tuple(f['zv'][a]) + tuple(f['pulay'][a])))
+        continue
+    if acc is ecp_force_acc:
+        acc.save('forces_ecp.npz', results=True)
+        f = acc.forces()
+        print('pseudopotential forces: naive errors over %d walkers (%d left out); Hellmann-Feynman part only, no cutoff delta term'
+              % (f['n_walkers'], f['n_bad']))
+        for a in range(len(f['atoms'])):
+            print('            %-2s pp (%9.4f %9.4f %9.4f) +- (%.4f %.4f %.4f)   total (%9.4f %9.4f %9.4f) +- (%.4f %.4f %.4f) Ha/Bohr'
+                  % ((cell.atom_symbol(a),) + tuple(f['pp'][a]) + tuple(f['pp_error'][a]) + tuple(f['total'][a]) + tuple(f['total_error'][a])))
         continue
     if acc is stress_acc:
         acc.save('stress.npz', results=True)

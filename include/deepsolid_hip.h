@@ -690,6 +690,69 @@ int ds_ecp_energy(ds_system* sys, const ds_ecp* ecp, const void* params, const v
                   uint64_t philox_offset, const double* rotations, int64_t pair_capacity, double* out_energy, int64_t* out_pairs,
                   void* out_ratio, double* out_rotation, void* ws, int64_t ws_bytes, void* stream);
 
+/* Ionic forces of the semi-local pseudopotential (csrc/ds_ecp_force.h): minus the derivative of the
+ * E_loc + E_nl of ds_ecp_energy in the position of every ion of the simulation cell, per walker.  Every convention of ds_ecp_energy
+ * holds: the potential, the cutoffs, the minimum image, the two rules, the pair order.
+ *
+ * Estimator.  Per pair p = (w, i, I) inside r_cut_nl:
+ *       d = the minimum image of r_i - R_I,  r = |d|,  dhat = d / r;   U_q = Rot_w u_q;   c_q = U_q . dhat;
+ *       W_q = sum_l (2l + 1) v_l(r) P_l(c_q);   R'_q = R with r_i replaced by r_i - d + r U_q;   rho_q = psi(R'_q) / psi(R);
+ *       g_q = the three complex components of electron i of grad log psi at R'_q (Re = grad log|psi|, Im = grad arg psi, as
+ *             ds_logpsi_grad writes them).
+ *   The derivative is taken with psi held fixed as a function of the electron coordinates; the rotation of the call, the electron
+ *   positions and the image choice are held fixed too.  With d d / d R_I = -1 and d r'_a / d R_b = delta_ab - U_qa dhat_b:
+ *       F^loc_I(w) = sum_i [r_iI < r_cut_loc,I]  v'_loc,I(r) dhat
+ *       F^nl_I(w)  = sum_{i: r_iI < r_cut_nl,I} sum_q (1 / N_q) rho_q { sum_l (2l + 1) [ v'_l(r) P_l(c_q) dhat
+ *                                                                                       + v_l(r) P'_l(c_q) (U_q - c_q dhat) / r ]
+ *                                                                     - W_q ( g_q - (g_q . U_q) dhat ) }
+ *       v'(r) = sum_k c_k [ (n_k - 2) r^(n_k - 3) - 2 zeta_k r^(n_k - 1) ] exp(-zeta_k r^2)
+ *   - F^loc is real, F^nl complex.  An estimator uses F^pp = F^loc + Re F^nl; Im F^nl vanishes in expectation for a psi of fixed
+ *     phase.
+ *   - The radial functions are exactly 0 outside their cutoffs.  The jump at a cutoff is a delta term of the exact derivative and is
+ *     LEFT OUT; its size is that of the function at its cutoff.
+ *   - This is the Hellmann-Feynman part only: no Pulay term (E_pp is not part of the E_L of ds_logpsi_ion_vjp's estimator), no
+ *     zero-variance term.  Its bias is first order in the error of psi.  The Ewald force of the Z_eff ions is ds_ion_forces' out_hf.
+ *
+ * Rotation.  Philox stream 4 with the offset rule of ds_ecp_energy, or caller-supplied rotations: a force call and an energy call
+ * with the same (philox_seed, philox_offset) use the same points.
+ *
+ * ds_ecp_forces, one call:
+ *   1. steps 1-3 of ds_ecp_energy with its kernels: rotation, counts, offsets, pair records, and the pair total read back: ONE 8-byte
+ *      copy and ONE stream synchronisation, the only one of the call.  The call therefore CANNOT be captured into a graph.  A total
+ *      above pair_capacity fails the call before any chain pass, with ds_ecp_energy's message ("... the walkers have <n> pairs ...");
+ *   2. per walker F^loc: for every ion the electrons added in order i = 0 .. N-1; per pair the second record v'_l(r);
+ *   3. log psi(R): ONE pass of the forward-Laplacian chain with the gradient output (that of ds_logpsi_grad) over the B walkers (none
+ *      when there is no pair).  The ratios take this log|psi(R)| and phase(R), not the value chain's, so that numerator and
+ *      denominator come from the same arithmetic;
+ *   4. per chunk of a whole number of 80-configuration groups -- the chunk length follows from ws_bytes with the chain's per-walker
+ *      layout, at most 65535 configurations -- propose (ds_ecp_energy's rows), the same chain, and per configuration the complex
+ *      3-vector (rho_q / N_q) { ... } in float64 into the workspace.  A walker without a pair costs no chain work beyond step 3;
+ *   5. per walker one workgroup: for every ion, lane l of a wave adds the terms of the walker's configurations l, l + 64, ... in
+ *      order whose pair belongs to the ion, then the 64 lane results through the fixed tree (l += l + s, s = 32 .. 1);
+ *   6. with sums: k_force_part / k_force_final of ds_ion_forces on the rows (F^pp, F^tot): the tree over the 256 walkers of a group,
+ *      the groups in order onto sums.  Groups are cut at multiples of 256 walkers of the batch whatever the workspace.
+ *   - base (B, A, 3) float64, optional: added per walker, F^tot = F^pp + base; without it F^tot = F^pp.  It is meant for out_hf of
+ *     ds_ion_forces (the Ewald force with Z_eff, ion-ion force included); a base of another meaning cannot be detected and is the
+ *     caller's responsibility.
+ *   - out_force (B, A, 3, 3) float64, optional: last index = (F^loc, Re F^nl, Im F^nl).
+ *   - sums: device float64 [12 A + 1], ADDED to and never zeroed, optional: the layout of ds_ion_forces: per (a, c), at 4 (3 a + c),
+ *       [ sum F^pp, sum (F^pp)^2, sum F^tot, sum (F^tot)^2 ]  over the good walkers of the call, then their number.
+ *   - A walker with a non-finite coordinate, with a pair at r = 0 inside a cutoff (it has no dhat), or with a non-finite result
+ *     (base included) is bad: NaN in all its outputs, left out of sums, counted in n_bad (device (1,) int64, ADDED to; optional).
+ *   - out_pairs (B,) int64 and out_rotation (B, 3, 3) float64 as in ds_ecp_energy, optional.
+ * The chain is per-walker bit-independent of the batch it runs in and the order of every addition is a function of the walker's pair
+ * list (and, for sums, of B) alone: results are bit-identical from run to run and for ANY workspace size.  No floating-point
+ * atomics, no allocation, 64-bit indices.  Geometry, radial functions and Legendre polynomials are float64 for either dtype; products
+ * and sums are rounded one by one.
+ * Cost: one forward-Laplacian chain evaluation per quadrature configuration (EXPERIMENTS.md has the measured ratio to ds_ecp_energy).
+ * Refused with a ds_last_error message before any launch: a null handle, descriptor, params, x or ws; out_force and sums both NULL
+ * (nothing to write); everything ds_ecp_energy refuses of (B, pair_capacity, descriptor); a workspace below one group ("workspace too
+ * small"), with or without sums. */
+int64_t ds_ecp_forces_workspace_bytes(const ds_system* sys, const ds_ecp* ecp, int64_t B, int64_t pair_capacity);
+int ds_ecp_forces(ds_system* sys, const ds_ecp* ecp, const void* params, const void* x, int64_t B, uint64_t philox_seed,
+                  uint64_t philox_offset, const double* rotations, int64_t pair_capacity, const double* base, double* out_force,
+                  double* sums, int64_t* n_bad, int64_t* out_pairs, double* out_rotation, void* ws, int64_t ws_bytes, void* stream);
+
 /* Fixed-phase diffusion Monte Carlo (csrc/ds_dmc.h): all-electron drift-diffusion move, Metropolis
  * acceptance, symmetric branching weights, energy cut-off, fixed-population comb.  The reference has no DMC: the conventions are
  * this library's own.  One call runs a block of `steps` steps with no host synchronisation and no allocation.
